@@ -17,8 +17,10 @@ Workloads (``--config``; BASELINE.json ``configs``):
   4             evalHpatch-shaped stream: 960x720 pairs, minSize 720, 5 scales x2, coarseIter 50 000, multi-H on.
   5             evalKITTI-shaped stream: 1242x376 pairs, coarseSize 800, 3 scales x1.2, coarseIter 50 000, fineSize 650,
                 two-resolution fine pass, cycle-checked matchability, cc-filter on the device (evaluation/evalKITTI/evaluation.py).
-The default run also times a quick_start leg (``extra.quick_start``: 10 steps, own rooflines and parity block) and, on rank
-0 at N = 1, the CPU legs below.
+A plain run sets up, warms up, times ``--steps`` steps (``value`` / ``ms_per_step``), writes the last timed step's outputs if
+``--dump-outputs DIR`` is given, and prints the line.  ``--full`` adds everything else the line can carry: the rooflines (for
+configs 2 / 3 / 4 a second pass of the same steps under the per-launch events), a quick_start leg (``extra.quick_start``: 10 steps,
+own rooflines and parity block), the other exact modes and the fp32-MFMA-only build (config 3), and, on rank 0, the CPU legs below.
 
 N > 1: ``python bench.py --gpus N`` re-launches itself under ``torch.distributed.run`` (one rank per GPU, RCCL); when the
 driver launches it that way itself, RANK / LOCAL_RANK / WORLD_SIZE come from the environment.  Every rank aligns its own
@@ -26,7 +28,7 @@ shard of the pair stream (pair i -> rank i mod N: weak scaling, no data-path col
 -- nbH | status | rank | H[11] | flowDown8[11] | matchDown8[11], 0.85 MB per 480x640 pair, what
 evaluation/evalHpatch/evaluation.py:254-260 saves -- are collected with ONE all_gather per step.
 
-Prints one JSON line on rank 0 (the driver's contract): value = pairs/s over all ranks, plus
+Prints one JSON line on rank 0 (the driver's contract): value = pairs/s over all ranks, plus (``--full``)
   roofline      -- the conv-class kernel instance with the most GPU time (fp32 MFMA bound): algorithmic FLOP per launch /
                    average launch duration, HIP events on the launch stream inside the timed region (ops.Profiler);
   roofline_corr -- the same for the HBM-bound 7x7 correlation kernel, SURVEY 8d algorithmic bytes;
@@ -223,8 +225,16 @@ def parse_args():
                     help="how the mutual-NN scores are summed (ops.resolve_score_chunk): 'host' (default here: the K blocking of this host's "
                          "sgemm, probed ONCE on rank 0 before the workload is built and broadcast -- the parity legs compare with this host's "
                          "CPU run of the reference), 'default' (fixed 256 products) or a number of products per chunk")
-    ap.add_argument("--no-exact-leg", action="store_true", help="default run: skip extra.exact_mode (throughput of the exact modes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline + parity sweep)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: rooflines (configs 2 / 3 / 4: a second, profiled pass of the same steps), "
+                         "the quick_start / exact-mode / fp32-MFMA-only legs (config 3, N = 1), the CPU baseline and the parity sweeps; "
+                         "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): "
+                         "records.npy = the gathered per-pair record block, pair_ids.npy = the pair of every row; a fixed, seeded sample "
+                         "of the rows where the block exceeds 64 MB")
+    ap.add_argument("--no-exact-leg", action="store_true", help="--full run: skip extra.exact_mode (throughput of the exact modes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full run: skip the CPU legs (cpu_baseline + parity sweep)")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--parity-pairs", type=int, default=None, help="pairs of the batch covered by the parity sweep (default: all)")
     ap.add_argument("--parity-budget", type=float, default=95.0, help="wall-clock bound of the headline's parity sweep, seconds")
@@ -233,7 +243,7 @@ def parse_args():
     ap.add_argument("--qs-parity-budget", type=float, default=50.0, help="wall-clock bound of the quick_start leg's parity sweep")
     ap.add_argument("--stability-budget", type=float, default=55.0, help="wall-clock bound of the reference-vs-reference sweep")
     ap.add_argument("--no-qs-leg", "--no-config3-leg", dest="no_qs_leg", action="store_true",
-                    help="default run: skip the quick_start leg (extra.quick_start)")
+                    help="--full run: skip the quick_start leg (extra.quick_start)")
     ap.add_argument("--host-prep", action="store_true",
                     help="build the LANCZOS pyramid with PIL on the host before the timed region (default: raw uint8 images "
                          "resident in HBM, pyramid + ToTensor + Normalize on the device inside the timed step)")
@@ -658,6 +668,22 @@ def rooflines(prof, elapsed, rank, cfg="3", dev=None):
     return roof, corr
 
 
+def dump_outputs(d, rec, pair_ids, limit=64 * 10 ** 6 - 4096):
+    """--dump-outputs: the last timed step's gathered record block as ``d/records.npy`` (float32) and the pair id of every row as
+    ``d/pair_ids.npy`` (float64).  A block over ``limit`` bytes keeps a fixed, seeded sample of its rows (in order)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rec = rec.detach().float().cpu().numpy()
+    ids = np.asarray(pair_ids, dtype=np.float64)
+    rows = np.arange(rec.shape[0])
+    per_row = rec.shape[1] * 4 + 8
+    if rec.shape[0] * per_row > limit:
+        rows = np.sort(np.random.default_rng(0).choice(rec.shape[0], max(1, limit // per_row), replace=False))
+    np.save(os.path.join(d, "records.npy"), np.ascontiguousarray(rec[rows]))
+    np.save(os.path.join(d, "pair_ids.npy"), ids[rows])
+    log("outputs of the last timed step written to %s (%d of %d rows)" % (d, len(rows), rec.shape[0]))
+
+
 class _NoProf:
     conv, corr, corr_bidir = [], [], []
 
@@ -722,18 +748,24 @@ def main():
         prof_factory = ops.Profiler
         torch.manual_seed(123 + rank)
     log("workload built (config %s, rank %d/%d)" % (args.config, rank, world))
-    unprofiled = None
+    unprofiled, prof, out = None, None, None
     if not args.dry_run and args.config in ("2", "3", "4") and not (args.single_stream and args.config != "2"):
         # config 2: single-pair latency is launch-bound: the product path replays the trunk as ONE HIP graph, which cannot carry the
         # profiler's per-launch events.  configs 3 / 4: the multi-homography rounds run as two lock-step groups on two HIP streams
         # (multi_h_batched split=2) whose kernels overlap -- a per-launch event interval would charge a kernel with its neighbour's
-        # time.  -> the product path is timed WITHOUT the profiler (value), then the same steps once more with it (one group, eager
-        # launches, per-launch events) for the rooflines
+        # time.  -> the product path is timed WITHOUT the profiler (value), then (--full) the same steps once more with it (one
+        # group, eager launches, per-launch events) for the rooflines
         e_np, out, _ = timed_loop(step, args, dist, sync, _NoProf)
         unprofiled = e_np
         log("%d timed steps without the profiler (the product path): %.3f s" % (args.steps, e_np))
-    elapsed, out, prof = timed_loop(step, args, dist, sync, prof_factory)
-    log("%d timed steps: %.3f s" % (args.steps, elapsed))
+    timed_out = out
+    if unprofiled is None or args.full:
+        elapsed, out, prof = timed_loop(step, args, dist, sync, prof_factory)
+        log("%d timed steps: %.3f s" % (args.steps, elapsed))
+        if timed_out is None:
+            timed_out = out
+    else:
+        elapsed = unprofiled
     profiled_elapsed = elapsed
     if unprofiled is not None:
         elapsed = unprofiled
@@ -746,6 +778,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     B = args.batch
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_out, [r + world * i for r in range(world) for i in range(B)])
     if args.dump_records and rank == 0:
         # rank-major gathered order: row r*B + i = pair (r + world*i) of the stream (pair i -> rank i mod world)
         torch.save({"records": out.cpu(), "pair_ids": [r + world * i for r in range(world) for i in range(B)], "world": world},
@@ -790,11 +824,11 @@ def main():
         line["config"]["pcie_inclusive"] = ("NOT the headline: raw uint8 images uploaded from pinned host memory and the result records copied "
                                             "back to pinned host memory inside every timed step (%.1f + %.1f MB per step)"
                                             % (2.0 * B * args.height * args.width * 3 / 1e6, out.shape[0] / world * out.shape[1] * 4 / 1e6))
-    if not args.dry_run:
-        if col["nbh"] is not None:
-            nbh = out[:, col["nbh"]]
-            line["config"]["homographies_per_pair_last_step"] = {"mean": round(float(nbh.mean()), 2), "min": int(nbh.min()), "max": int(nbh.max())}
-            line["config"]["homographies_per_s"] = round(float(nbh.sum()) * args.steps / elapsed, 1)
+    if not args.dry_run and col["nbh"] is not None:
+        nbh = out[:, col["nbh"]]
+        line["config"]["homographies_per_pair_last_step"] = {"mean": round(float(nbh.mean()), 2), "min": int(nbh.min()), "max": int(nbh.max())}
+        line["config"]["homographies_per_s"] = round(float(nbh.sum()) * args.steps / elapsed, 1)
+    if not args.dry_run and args.full:
         roof, corr = rooflines(prof, profiled_elapsed, rank, args.config, dev)
         if unprofiled is not None and args.config == "2":
             roof["note"] = ("value / ms_per_step: HIP-graph trunk, no profiler (%.2f ms per pair); this roofline: a second pass of %d steps "
@@ -811,7 +845,7 @@ def main():
             line["roofline_corr"] = corr
 
     extras = {}
-    if rank == 0 and not args.dry_run and args.config == "3" and world == 1:
+    if rank == 0 and not args.dry_run and args.full and args.config == "3" and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         # ---- quick_start semantics, driver-timed next to the headline: rounds 1-2's headline workload ----
         if not args.no_qs_leg:
@@ -934,7 +968,7 @@ def main():
                         q = extras["quick_start"]["parity"]
                         q["flipped_pairs_device_vs_reference_per_pair"] = round(q["pairs_with_flips"] / max(q["pairs"], 1), 3)
                         q["flipped_pairs_reference_vs_reference_per_pair"] = round(ovo["pairs_with_flips"] / ovo["pairs"], 3)
-    elif rank == 0 and not args.dry_run and args.config == "qs" and world == 1 and not args.no_cpu_baseline:
+    elif rank == 0 and not args.dry_run and args.full and args.config == "qs" and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         line["cpu_baseline"] = cpu_baseline_subprocess(args)
         if not args.no_parity:
@@ -948,7 +982,7 @@ def main():
         # all collectives are done: leave the group BEFORE rank 0's CPU leg, so that no rank waits in a communicator for it
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.dry_run and args.config in ("3", "qs") and not args.no_cpu_baseline:
+    if rank == 0 and world > 1 and not args.dry_run and args.full and args.config in ("3", "qs") and not args.no_cpu_baseline:
         # N > 1: the line still carries the host baseline (bounded, ~1 min); the parity sweeps stay with the N = 1 run
         log("rank 0: timing the CPU reference (bounded sample, child process)")
         line["cpu_baseline"] = cpu_baseline_subprocess(args)

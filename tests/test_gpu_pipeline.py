@@ -472,7 +472,7 @@ def test_rccl_transport_with_a_world_of_one_rank(dev):
     env = dict(os.environ, RFX_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29641")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "8",
                           "--no-cpu-baseline", "--no-config3-leg"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
