@@ -503,8 +503,10 @@ int rfx_multih_accept_f32(const float* match, float* mask, const float* bg, cons
  *     out[n,m,p] = act(scale[m] * S + shift[m] + residual),
  *     S = sum_k (wh xh) + sum_k (wh xm + wm xh + wm xm + wh xl + wl xh)                 (every product exact in float32; the two
  *         sums in two float32 accumulators that round once per 16 k, added once at the end; the three dropped terms are below
- *         2^-32 |w x|).  Error against the float64 sum: 0.4x the fp32 kernel's fma chain (profiles/r06_bf16_split_study.json).
- * NOT bit-identical to rfx_conv2d_f32 (closer to the exact sum); +-inf inputs give NaN.  Cin % 16 == 0.
+ *         2^-24 (1 + 2^-10) |w x|, a bound nearly attained).  RMS error against the float64 sum: 0.4x the fp32 kernel's fma chain
+ *         (profiles/r06_bf16_split_study.json); the max error at K >= 2304 is 1.2x - 2.9x the chunked fp32 kernels'
+ *         (profiles/split_max_error_ratio.json).
+ * NOT bit-identical to rfx_conv2d_f32 (closer to the exact sum in rms); +-inf inputs give NaN.  Cin % 16 == 0.
  * wS: the weights split on the host and packed in fragment order, bf16 bit patterns (uint16):
  *     wS[kb = k / 16][piece (hi, mid, lo)][h = (k % 16) / 8][m (Mpad = Cout rounded up to 128, rows >= Cout zero)][k % 8]
  * in (N,Cin,HW), out / residual (N,Cout,HW) float32.
@@ -519,7 +521,7 @@ int rfx_conv1x1_split_strided_f32(const float* in, const void* wS, const float* 
  * model/resnet50.py:75; the FeatureExtractor's BasicBlock convolutions, model/model.py:32-35; conv2 / conv3 of the NetFlowCoarse /
  * NetMatchability stacks, model/model.py:170-181): nine shifted 1x1 products over one staged, split halo patch.  Cin % 16 == 0.
  * wS3: bf16 bit patterns, [kb = c / 16][tap = kh * 3 + kw][piece][h = (c % 16) / 8][m (Mpad)][c % 8] = piece of W[m][c][kh][kw].
- * in (N,Cin,H,W), out / residual (N,Cout,H,W) float32.  NOT bit-identical to rfx_conv3x3_f32 / rfx_conv2d_f32 (closer to the exact sum). */
+ * in (N,Cin,H,W), out / residual (N,Cout,H,W) float32.  NOT bit-identical to rfx_conv3x3_f32 / rfx_conv2d_f32 (closer to the exact sum in rms). */
 int rfx_conv3x3_split_f32(const float* in, const void* wS3, const float* scale, const float* shift, const float* residual,
                           float* out, int N, int Cin, int H, int W, int Cout, int act, void* stream);
 /* ... stride 2 (pad 1): ResNet-50 layer2.0 / layer3.0 conv2 (model/resnet50.py:75), the FeatureExtractor's strided conv1

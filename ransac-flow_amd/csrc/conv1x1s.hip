@@ -4,13 +4,16 @@
 // A float32 x has a 24-bit significand = three bf16 pieces of 8 bits:  x = hi + mid + lo  EXACTLY, with hi = bf16(x) (round to
 // nearest even), mid = bf16(x - hi), lo = bf16(x - hi - mid) (both differences are exact in float32).  A product of two pieces
 // (8 x 8 bits) is exact in float32, so
-//     w * x = (wh + wm + wl)(xh + xm + xl) = wh xh + [wh xm + wm xh] + [wm xm + wh xl + wl xh] + (three terms below 2^-32 |w x|)
+//     w * x = (wh + wm + wl)(xh + xm + xl) = wh xh + [wh xm + wm xh] + [wm xm + wh xl + wl xh] + (three terms below 2^-24 (1 + 2^-10) |w x|)
 // and six v_mfma_f32_32x32x16_bf16 per 16 k give the float32 sum with EVERY product exact -- what differs from an fp32 fma chain is
 // only where the float32 accumulator rounds: the matrix core adds the 16 products of an instruction before it rounds, and the hi*hi
 // products run in their own accumulator (the five small terms in a second one, added once at the end).  Measured on convolution-
 // shaped data (scripts/ubench/bf16x_emul.hip, profiles/r06_bf16_split_study.json): rms error against the float64 sum 2.3e-7 of the
 // output rms at K = 2304, against 6.1e-7 for the fp32 MFMA's single fma chain and 3.0e-7 for the chunked chain the fp32 kernels use
-// -- CLOSER to the exact sum than the float32 kernels it replaces, at 2.1x their matrix-pipe rate (6 x 32 cycles against 8 x 64 per 16 k).
+// -- CLOSER to the exact sum IN RMS than the float32 kernels it replaces, at 2.1x their matrix-pipe rate (6 x 32 cycles against 8 x 64
+// per 16 k).  Not in the max error at long K: against the chunked fp32 kernels the worst element is 1.2x - 2.9x further off at
+// K = 2304 / 4608 (the hi*hi accumulator is one chain of K / 16 roundings; profiles/split_max_error_ratio.json; the tests bound the
+// ratio and hold every element to a rigorous bound).  The dropped terms: at most 2^-24 (1 + 2^-10) |w x|, nearly attained (tests/test_split_numerics_cpu.py).
 // Not bit-identical to the fp32 kernels (conv1x1.hip stays: rfx_conv2d_f32 never routes here; the caller asks for this entry point).
 //
 // Operands.  Weights: split ONCE on the host into the three pieces and packed in fragment order (rfx_api.h: "wS"):

@@ -115,33 +115,50 @@ class launch_group:
     as ONE launch per kernel instance (rfx_group_begin / rfx_group_end: blockIdx.y selects the problem).  For the same layer
     of several independent inputs of different sizes (the 8 images of a single pair's trunk pass); the calls inside must not
     depend on each other, and their tensors must stay referenced until the block ends (the returned outputs do).  Not used
-    under a Profiler (per-launch events are meaningless for a recorded launch)."""
+    under a Profiler (per-launch events are meaningless for a recorded launch).  Temporaries an op makes for a recorded launch
+    (ConvPlan's zero-padded input of a ragged-Cin split convolution) are held by the block (``keep``) until the launch is issued:
+    the side streams join the caller's stream before rfx_group_end returns, so releasing them then is stream-ordered."""
+    _tls = threading.local()
 
     def __init__(self, device, side_streams=True):
         # side_streams=False: the group's kernel instances stay on the caller's stream (rfx_group_side_streams) -- for callers that
         # run several grouped chains on streams of their own
         self.dev, self.side = torch.device(device), bool(side_streams)
+        self._held = []
+
+    @staticmethod
+    def keep(t):
+        """Hold ``t`` until the active group (if any) has launched: a recorded launch reads its operands at the block's end."""
+        g = getattr(launch_group._tls, "active", None)
+        if g is not None:
+            g._held.append(t)
 
     def __enter__(self):
         _lib.check(_lib.load().rfx_group_begin(), "rfx_group_begin")
+        self._prev = getattr(launch_group._tls, "active", None)
+        launch_group._tls.active = self
         return self
 
     def __exit__(self, et, ev, tb):
         lib = _lib.load()
-        if et is not None:
-            lib.rfx_group_abort()
-            return False
-        prev = lib.rfx_group_side_streams(1 if self.side else 0)
+        launch_group._tls.active = self._prev
         try:
-            if self.dev.index is not None and self.dev.index != torch.cuda.current_device():
-                with torch.cuda.device(self.dev):
-                    rc = lib.rfx_group_end(_stream(self.dev))
-            else:
-                rc = lib.rfx_group_end(_stream())
+            if et is not None:
+                lib.rfx_group_abort()
+                return False
+            prev = lib.rfx_group_side_streams(1 if self.side else 0)
+            try:
+                if self.dev.index is not None and self.dev.index != torch.cuda.current_device():
+                    with torch.cuda.device(self.dev):
+                        rc = lib.rfx_group_end(_stream(self.dev))
+                else:
+                    rc = lib.rfx_group_end(_stream())
+            finally:
+                lib.rfx_group_side_streams(prev)
+            _lib.check(rc, "rfx_group_end")
+            return False
         finally:
-            lib.rfx_group_side_streams(prev)
-        _lib.check(rc, "rfx_group_end")
-        return False
+            self._held = []
 
 
 def _dev(t, name="tensor", dtype=torch.float32):
@@ -151,7 +168,11 @@ def _dev(t, name="tensor", dtype=torch.float32):
         raise RuntimeError("%s is on %s: rfx ops run only on a HIP device (no CPU fallback)" % (name, t.device))
     if t.dtype != dtype:
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t if t.is_contiguous() else t.contiguous()
+    if t.is_contiguous():
+        return t
+    t = t.contiguous()
+    launch_group.keep(t)          # a recorded launch reads the copy at the group's end
+    return t
 
 
 def _p(t):
@@ -285,6 +306,7 @@ class ConvPlan:
                 Cp = (C + 15) // 16 * 16
                 xin = torch.zeros((N, Cp, H, W), dtype=torch.float32, device=x.device)
                 xin[:, :C].copy_(x)
+                launch_group.keep(xin)              # inside a group the kernel reads it at the block's end, after this call returns
             _call("rfx_conv3x3_split_f32" if self.stride == 1 else "rfx_conv3x3_split_s2_f32", _one_device(xin, res, self.wS), _p(xin),
                   _p(self.wS), _p(self.scale), _p(self.shift), _p(res), _p(out), N, Cp, H, W, self.Cout, self.act if act is None else act)
             if e0 is not None:
