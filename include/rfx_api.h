@@ -40,9 +40,10 @@ const char* rfx_version(void);
 
 /* ABI revision of this header: bumped whenever an entry point changes its signature or its operand layout (round 2:
  * rfx_compose_flow_f32 gained Hc/Wc, 3x3/s1/p1 geometries moved to rfx_conv3x3_f32's packed weights; round 3: multi-homography
- * round kernels, two-direction correlation, grouped launches; round 4: rfx_draw_samples_i64 keyed by pair id).  A binding
+ * round kernels, two-direction correlation, grouped launches; round 4: rfx_draw_samples_i64 keyed by pair id; 11: the ragged-batch
+ * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 10
+#define RFX_ABI_VERSION 11
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -186,6 +187,12 @@ int rfx_stem_conv7x7_maxpool_f32(const float* in, const float* wT, const float* 
  * (quick_start/coarseAlignFeatMatch.py:108,115).  In-place allowed for the dense case. */
 int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, int HW, long long out_batch_stride,
                         long long out_chan_stride, void* stream);
+/* (ABI 11) The same norm, sums bit for bit, for the N images of one shape bucket of a ragged batch (quick_start/
+ * coarseAlignFeatMatch.py:106,124 per image): image n of in (N,C,HW) goes to out + dst_off[n] with channel stride out_chan_stride
+ * (>= HW); dst_off (N) int64 element offsets, e.g. its pair's column offset in the padded (batch,C,ldA) match matrix.  One
+ * launch per bucket instead of one per image.  Requires C % 4 == 0 and C >= 32. */
+int rfx_l2norm_nchw_scatter_f32(const float* in, float* out, int N, int C, int HW, const long long* dst_off,
+                                long long out_chan_stride, void* stream);
 
 /* NetFlowCoarse tail (model/model.py:228-233): softmax over the K*K logits, expectation of the tap
  * offsets; flow[n,0] = sum_q p_q * gx_q / cols * 2, flow[n,1] = sum_q p_q * gy_q / rows * 2 with
@@ -348,6 +355,18 @@ int rfx_mutual_nn_batched_f32(const float* featA, int ldA, int nA, long long str
                               int nB, long long strideB, int C, const float* maskB, int64_t* idx1, int64_t* idx2,
                               int32_t* count, void* ws, int batch, int score_chunk, void* stream);
 
+/* (ABI 11) Ragged batch: `batch` pairs of DIFFERENT sizes in one tile -> reduce -> compact launch chain (utils/outil.py:32-45 and the
+ * mask multiply of quick_start/coarseAlignFeatMatch.py:143, per pair).  nA, nB: (batch) int32 DEVICE arrays, pair b's own sizes,
+ * at most maxNA <= ldA / maxNB <= ldB (the host's maxima: they size the grid).  Features on a common padded layout: pair b reads
+ * the first nA[b] columns of featA + b*C*ldA (C,ldA) and the first nB[b] of featB + b*C*ldB (C,ldB); maskB (batch,ldB) or NULL.
+ * Pair b writes idx1/idx2 + b*cap ((batch,cap) int64, cap >= min(nA[b], nB[b])) and count[b], and uses the workspace slot
+ * ws + b*rfx_mutual_nn_ws_bytes(maxNA, maxNB).  Tiles past a pair's own grid exit at once; a pair with sizes out of range gets
+ * count 0.  Same k order, score_chunk chunking and tie rule as rfx_mutual_nn_f32: a pair's indices and count equal, bit for
+ * bit, a single-pair call on its own features.  Requires C % 32 == 0 and C >= 64. */
+int rfx_mutual_nn_ragged_f32(const float* featA, int ldA, const float* featB, int ldB, const int32_t* nA, const int32_t* nB,
+                             int maxNA, int maxNB, int C, const float* maskB, int64_t* idx1, int64_t* idx2, int cap,
+                             int32_t* count, void* ws, int batch, int score_chunk, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * RANSAC over 4-point DLT homographies (utils/outil.py:68-164).
  * match1/match2: (n,3) source / target points (x,y,1); samples: (N,4) int64 indices into them.
@@ -437,6 +456,13 @@ int rfx_dlt4_homography_flags(const float* X, const float* Y, int N, float* Hout
 int rfx_gather_matches_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* n, int cap, const float* xa,
                            const float* ya, const float* xb, const float* yb, float* match1, float* match2, int batch,
                            void* stream);
+
+/* (ABI 11) The same for a ragged batch, pairs of different sizes (quick_start/coarseAlignFeatMatch.py:150-155 per pair): pair b's
+ * cell coordinates are its own slice of packed tables, xa/ya + offA[b] and xb/yb + offB[b] (offA, offB: (batch) int64 element
+ * offsets); idx1/idx2 (batch,cap) int64 as written by rfx_mutual_nn_ragged_f32; rows at or past n[b] are zero. */
+int rfx_gather_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* n, int cap, const float* xa,
+                                  const float* ya, const long long* offA, const float* xb, const float* yb, const long long* offB,
+                                  float* match1, float* match2, int batch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The rounds of the multi-homography drivers without host glue (evaluation/evalHpatch/evaluation.py:211-243,

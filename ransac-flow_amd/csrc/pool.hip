@@ -333,6 +333,60 @@ __global__ __launch_bounds__(256) void l2norm_nchw_q4_kernel(const float* __rest
     for (; c < C; c += 4) dst[(size_t)c * ocs] = __fdiv_rn(src[(size_t)c * HW], d);
 }
 
+// The norm of l2norm_nchw_q4_kernel for the N images of one shape bucket of a ragged batch, image n written to out + dst_off[n]
+// (its pair's columns of the padded featA / featB): one launch per bucket instead of one per image.  Same loads, same chain, same
+// division as the kernel above -- only the destination differs -- so the sums are its sums bit for bit.
+__global__ __launch_bounds__(256) void l2norm_nchw_scatter_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                  const long long* __restrict__ dst_off, long long NP, int C, int HW,
+                                                                  long long ocs) {
+    constexpr int CB = 128;                        // channels per LDS block
+    __shared__ float tile[CB][64];
+    __shared__ float nrm_s[64];
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const long long p = (long long)blockIdx.x * 64 + lane;
+    const bool pv = p < NP;
+    const long long pc = pv ? p : 0;
+    const long long n = pc / HW;
+    const int px = (int)(pc - n * HW);
+    const float* src = in + (size_t)n * C * HW + px;
+    float* dst = out + dst_off[n] + px;
+    float s = 0.f;                                 // wavefront 0: the chain
+    for (int c0 = 0; c0 < C; c0 += CB) {
+        const int nb = C - c0 < CB ? C - c0 : CB;  // a multiple of 4 (launch precondition C % 4 == 0)
+        float v[CB / 4];
+#pragma unroll
+        for (int u = 0; u < CB / 4; ++u) v[u] = (q + 4 * u < nb) ? src[(size_t)(c0 + q + 4 * u) * HW] : 0.f;
+#pragma unroll
+        for (int u = 0; u < CB / 4; ++u) tile[q + 4 * u][lane] = v[u];
+        __syncthreads();
+        if (q == 0) {
+            for (int k = 0; k < nb; ++k) { const float a0 = tile[k][lane]; s = fmaf(a0, a0, s); }
+        }
+        __syncthreads();
+    }
+    if (q == 0) nrm_s[lane] = s;
+    __syncthreads();
+    const float nrm = sqrtf(nrm_s[lane]);
+    const float d = nrm > 1e-12f ? nrm : 1e-12f;
+    if (!pv) return;
+    int c = q;
+    for (; c + 124 < C; c += 128) {
+        float v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) v[u] = src[(size_t)(c + 4 * u) * HW];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) dst[(size_t)(c + 4 * u) * ocs] = __fdiv_rn(v[u], d);
+    }
+    for (; c + 28 < C; c += 32) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(c + 4 * u) * HW];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) dst[(size_t)(c + 4 * u) * ocs] = __fdiv_rn(v[u], d);
+    }
+    for (; c < C; c += 4) dst[(size_t)c * ocs] = __fdiv_rn(src[(size_t)c * HW], d);
+}
+
 extern "C" int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, int HW, long long out_batch_stride,
                                    long long out_chan_stride, void* stream) {
     if (!in || !out || N <= 0 || C <= 0 || HW <= 0 || out_batch_stride < 0 || out_chan_stride < 0) return RFX_E_ARG;
@@ -347,6 +401,18 @@ extern "C" int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, in
     }
     hipLaunchKernelGGL(l2norm_nchw_kernel, dim3(grid_for(NP, 64)), dim3(64), 0, rfx_stream(stream), in, out, NP, C, HW,
                        obs, ocs);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+extern "C" int rfx_l2norm_nchw_scatter_f32(const float* in, float* out, int N, int C, int HW, const long long* dst_off,
+                                           long long out_chan_stride, void* stream) {
+    if (!in || !out || !dst_off || N <= 0 || HW <= 0 || out_chan_stride < HW) return RFX_E_ARG;
+    if (C % 4 != 0 || C < 32) return RFX_E_ARG;              // the four-wavefront form (rfx_l2norm_nchw_f32 takes it for these C)
+    const long long NP = (long long)N * HW;
+    if ((NP + 63) / 64 > 0x7fffffffLL) return RFX_E_LIMIT;
+    hipLaunchKernelGGL(l2norm_nchw_scatter_kernel, dim3((unsigned)((NP + 63) / 64)), dim3(256), 0, rfx_stream(stream), in, out,
+                       dst_off, NP, C, HW, out_chan_stride);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

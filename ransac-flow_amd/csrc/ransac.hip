@@ -576,7 +576,39 @@ __global__ __launch_bounds__(256) void gather_matches_kernel(const int64_t* __re
         m2[o] = m2[o + 1] = m2[o + 2] = 0.0f;
     }
 }
+
+// Ragged batch: pair b's cell coordinates are its own slice of the packed tables, xa/ya + offA[b] and xb/yb + offB[b].
+__global__ __launch_bounds__(256) void gather_matches_ragged_kernel(const int64_t* __restrict__ idx1, const int64_t* __restrict__ idx2,
+                                                                    const int32_t* __restrict__ narr, int cap,
+                                                                    const float* __restrict__ xa, const float* __restrict__ ya,
+                                                                    const long long* __restrict__ offA, const float* __restrict__ xb,
+                                                                    const float* __restrict__ yb, const long long* __restrict__ offB,
+                                                                    float* __restrict__ m1, float* __restrict__ m2) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const size_t o = ((size_t)b * cap + i) * 3;
+    if (i < narr[b]) {
+        const int64_t a = offA[b] + idx1[(size_t)b * cap + i], t = offB[b] + idx2[(size_t)b * cap + i];
+        m1[o] = xa[a]; m1[o + 1] = ya[a]; m1[o + 2] = 1.0f;
+        m2[o] = xb[t]; m2[o + 1] = yb[t]; m2[o + 2] = 1.0f;
+    } else {
+        m1[o] = m1[o + 1] = m1[o + 2] = 0.0f;
+        m2[o] = m2[o + 1] = m2[o + 2] = 0.0f;
+    }
+}
 }  // namespace
+
+extern "C" int rfx_gather_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* n, int cap, const float* xa,
+                                             const float* ya, const long long* offA, const float* xb, const float* yb,
+                                             const long long* offB, float* match1, float* match2, int batch, void* stream) {
+    if (!idx1 || !idx2 || !n || !xa || !ya || !offA || !xb || !yb || !offB || !match1 || !match2 || cap <= 0 || batch <= 0)
+        return RFX_E_ARG;
+    if (batch > 65535) return RFX_E_LIMIT;
+    hipLaunchKernelGGL(gather_matches_ragged_kernel, dim3((cap + 255) / 256, batch), dim3(256), 0, rfx_stream(stream), idx1, idx2,
+                       n, cap, xa, ya, offA, xb, yb, offB, match1, match2);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
 
 extern "C" int rfx_gather_matches_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* n, int cap, const float* xa,
                                       const float* ya, const float* xb, const float* yb, float* match1, float* match2,

@@ -41,6 +41,7 @@ SIGNATURES = {
     "rfx_stem_conv3x3_maxblur_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "rfx_stem_conv7x7_maxpool_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "rfx_l2norm_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_longlong, c_void_p]),
+    "rfx_l2norm_nchw_scatter_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p]),
     "rfx_flow_head_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "rfx_resize_bilinear_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "rfx_lanczos_pass_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p]),
@@ -64,6 +65,8 @@ SIGNATURES = {
     "rfx_mutual_nn_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
     "rfx_mutual_nn_batched_f32": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int]
                                   + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    "rfx_mutual_nn_ragged_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rfx_dlt4_homography": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "rfx_prediction_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "rfx_score_hypotheses": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_void_p] * 5),
@@ -80,6 +83,7 @@ SIGNATURES = {
     "rfx_ransac_h4_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_void_p] * 4
                               + [c_int, c_void_p]),
     "rfx_gather_matches_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_void_p]),
+    "rfx_gather_matches_ragged_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_void_p]),
     "rfx_draw_samples_i64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rfx_filter_matches_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4
                                + [c_void_p] * 9),
@@ -89,7 +93,7 @@ SIGNATURES = {
                               + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong] + [c_int] * 5 + [c_void_p]),
 }
 
-ABI_VERSION = 10    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 11    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

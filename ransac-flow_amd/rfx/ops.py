@@ -515,6 +515,22 @@ def l2norm(x, out=None, out_batch_stride=0, out_chan_stride=0):
     return out
 
 
+
+def l2norm_scatter(x, out, dst_off, out_chan_stride):
+    """F.normalize(x, dim=1) of the N images of one shape bucket x (N,C,H,W), image n written to ``out`` at element offset
+    dst_off[n] with channel stride ``out_chan_stride`` (e.g. its pair's columns of a padded (B,C,ld) match matrix).  Sums bit-equal to
+    l2norm.  dst_off: (N,) int64 device tensor."""
+    x = _dev(x, "l2norm input")
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+        raise TypeError("l2norm_scatter out must be a float32 device tensor")
+    dst_off = _dev(dst_off, "dst_off", torch.int64)
+    N, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (N * C)
+    if dst_off.numel() != N:
+        raise ValueError("dst_off must hold one offset per image")
+    _call("rfx_l2norm_nchw_scatter_f32", _one_device(x, out, dst_off), _p(x), _p(out), N, C, HW, _p(dst_off), int(out_chan_stride))
+    return out
+
 def flow_head(logits, K=7):
     logits = _dev(logits, "flow logits")
     N, C, R, Cc = logits.shape
@@ -861,6 +877,35 @@ def mutual_nn(featA, featB, maskB=None, ldA=None, ldB=None, nA=None, nB=None, sc
     return idx1[:n], idx2[:n]
 
 
+
+def mutual_nn_ragged(featA, featB, nA, nB, maxNA=None, maxNB=None, maskB=None, score_chunk=0, cap=None):
+    """featA (B,C,ldA), featB (B,C,ldB) on a common padded layout, nA / nB (B,) int32 device tensors (pair b's own sizes) ->
+    idx1, idx2 (B,cap) int64, count (B,) int32.  ``maxNA`` / ``maxNB``: host maxima of nA / nB (they size the grid; default ldA /
+    ldB); ``cap``: max_b min(nA[b], nB[b]) (default min(maxNA, maxNB)); maskB (B,ldB) or None.  Pair b's indices and count equal mutual_nn on its own
+    features bit for bit.  No host sync."""
+    featA, featB = _dev(featA, "featA"), _dev(featB, "featB")
+    nA, nB = _dev(nA, "nA", torch.int32), _dev(nB, "nB", torch.int32)
+    if featA.dim() != 3 or featB.dim() != 3 or featA.shape[:2] != featB.shape[:2]:
+        raise ValueError("featA / featB must be (B,C,ldA) / (B,C,ldB)")
+    B, C, ldA = featA.shape
+    ldB = featB.shape[2]
+    if nA.numel() != B or nB.numel() != B:
+        raise ValueError("nA / nB must hold one size per pair")
+    maxNA = int(maxNA or ldA)
+    maxNB = int(maxNB or ldB)
+    m = _dev(maskB, "maskB") if maskB is not None else None
+    if m is not None and tuple(m.shape) != (B, ldB):
+        raise ValueError("maskB must be (B, ldB)")
+    lib = _lib.load()
+    ws = torch.empty(B * lib.rfx_mutual_nn_ws_bytes(maxNA, maxNB), dtype=torch.uint8, device=featA.device)
+    cap = int(cap or min(maxNA, maxNB))
+    idx1 = torch.empty((B, cap), dtype=torch.int64, device=featA.device)
+    idx2 = torch.empty((B, cap), dtype=torch.int64, device=featA.device)
+    count = torch.zeros(B, dtype=torch.int32, device=featA.device)
+    _call("rfx_mutual_nn_ragged_f32", _one_device(featA, featB, nA, nB, m), _p(featA), ldA, _p(featB), ldB, _p(nA), _p(nB), maxNA,
+          maxNB, C, _p(m), _p(idx1), _p(idx2), cap, _p(count), _p(ws), B, int(score_chunk))
+    return idx1, idx2, count
+
 def lapack_dlt(X, Y):
     """The reference's own solve (utils/outil.py:68-87: float32 products stored into a float64 8x9 system, numpy's LAPACK SVD,
     Vh[8], float32) for the FEW hypotheses the device flags as rank deficient.  For those systems the null space is two-
@@ -960,6 +1005,22 @@ def gather_matches(idx1, idx2, n, xa, ya, xb, yb):
                                                  _p(_dev(xb, "xb")), _p(_dev(yb, "yb")), _p(m1), _p(m2), B)
     return m1, m2
 
+
+
+def gather_matches_ragged(idx1, idx2, n, xa, ya, offA, xb, yb, offB):
+    """gather_matches for a ragged batch: pair b's cell coordinates are xa/ya[offA[b]:], xb/yb[offB[b]:] of the packed tables
+    (offA, offB: (B,) int64 device tensors) -> match1, match2 (B,cap,3) float32 (rows >= n[b] are zero)."""
+    idx1, idx2 = _dev(idx1, "idx1", torch.int64), _dev(idx2, "idx2", torch.int64)
+    n = _dev(n, "n", torch.int32)
+    offA, offB = _dev(offA, "offA", torch.int64), _dev(offB, "offB", torch.int64)
+    B, cap = idx1.shape
+    if n.numel() != B or offA.numel() != B or offB.numel() != B:
+        raise ValueError("n / offA / offB must hold one entry per pair")
+    m1 = torch.empty((B, cap, 3), dtype=torch.float32, device=idx1.device)
+    m2 = torch.empty((B, cap, 3), dtype=torch.float32, device=idx1.device)
+    _call("rfx_gather_matches_ragged_f32", _one_device(idx1, idx2, n, xa, ya, offA, xb, yb, offB), _p(idx1), _p(idx2), _p(n), cap,
+          _p(_dev(xa, "xa")), _p(_dev(ya, "ya")), _p(offA), _p(_dev(xb, "xb")), _p(_dev(yb, "yb")), _p(offB), _p(m1), _p(m2), B)
+    return m1, m2
 
 def ransac_h4_batched(match1, match2, n, samples, tol, degenerate="device", info=None):
     """match1/match2 (B,cap,3), n (B,) int32 device, samples (B,N,4) int64 -> bestH (B,3,3), inlier (B,cap) bool,

@@ -81,6 +81,46 @@ def cell_coords(n_rows, n_cols, device):
     return ((W - 0.5) * 2).to(device), ((Hh - 0.5) * 2).to(device)
 
 
+
+def ragged_plan(src_sizes, tgt_sizes, min_size, scales, mode="max"):
+    """Bucket / offset plan of a ragged batch: pair b's source of size src_sizes[b] = (w, h) gives len(scales) pyramid levels and its
+    target of size tgt_sizes[b] one more image, each resized by resize_dims exactly as the one-pair path does (multiples of 16).
+    Images of EQUAL shape -- any level, any pair, sources and targets alike -- form one bucket: one dense problem of the grouped trunk
+    pass.  Level index len(scales) stands for the target.  Pure function of the sizes (no tensors).
+    Returns dict(levels[b][i] = (h, w) of image i of pair b, cells[b][i] = (h // 16, w // 16), nA[b], nB[b], offs[b][i] = column
+    of level i in pair b's (C, nA) block, ldA / ldB = the largest nA / nB padded to a multiple of 4, cap = max_b min(nA, nB),
+    buckets = {(h, w): [(b, i), ...]} in order of first appearance, members ordered sources first (by pair, level), then targets)."""
+    nS = len(scales)
+    levels, cells, nA, nB, offs = [], [], [], [], []
+    for (sw, sh), (tw, th) in zip(src_sizes, tgt_sizes):
+        lv = []
+        for sc in scales:
+            nw, nh = resize_dims(sw, sh, int(min_size * sc), mode)
+            lv.append((nh, nw))
+        nw, nh = resize_dims(tw, th, min_size, mode)
+        lv.append((nh, nw))
+        cl = [(h // 16, w // 16) for h, w in lv]
+        o, off = [], 0
+        for r, c in cl[:nS]:
+            o.append(off)
+            off += r * c
+        levels.append(lv)
+        cells.append(cl)
+        offs.append(o)
+        nA.append(off)
+        nB.append(cl[nS][0] * cl[nS][1])
+    buckets = collections.OrderedDict()
+    for b, lv in enumerate(levels):
+        for i, shp in enumerate(lv):
+            buckets.setdefault(shp, [])
+    for shp in buckets:
+        mem = [(b, i) for b, lv in enumerate(levels) for i, x in enumerate(lv) if x == shp]
+        buckets[shp] = sorted(mem, key=lambda m: (m[1] == nS, m[0], m[1]))
+    pad4 = lambda n: (n + 3) // 4 * 4
+    return dict(levels=levels, cells=cells, nA=nA, nB=nB, offs=offs, ldA=pad4(max(nA)), ldB=pad4(max(nB)),
+                cap=max(min(a, b) for a, b in zip(nA, nB)), buckets=buckets, nS=nS, B=len(levels))
+
+
 class AlignPipeline:
     def __init__(self, sds, nbScale=7, nbIter=1000, tolerance=0.05, minSize=640, scaleR=1.2, variant="A",
                  device="cuda", kernelSize=7, draw="device", seed=0, degenerate="lapack", score_chunk=None):
@@ -216,6 +256,130 @@ class AlignPipeline:
         nw, nh = resize_dims(tw, th, self.minSize, mode)
         return ops.u8_to_f32(ops.lanczos_resize_u8(tgt_u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD)
 
+    # ---------------------------------------------------------------- ragged batches (pairs of different sizes)
+    def _ragged_prep(self, plan, norm, IsT, ItT):
+        """norm[(b, i)]: (1,3,h,w) normalised image i of pair b (i = nS: the target) -> the ragged prep: one (N,3,h,w) tensor per
+        bucket of the plan (members in the plan's order), the per-pair raw IsTensor / ItTensor (1,3,h,w) of the fine stage."""
+        xs = [torch.cat([norm[m] for m in mem], dim=0) for mem in plan["buckets"].values()]
+        return dict(ragged=True, plan=plan, B=plan["B"], bucket_x=xs, IsTensor=IsT, ItTensor=ItT)
+
+    def _ragged_plan(self, src_sizes, tgt_sizes):
+        return ragged_plan(src_sizes, tgt_sizes, self.minSize, self.scaleList, "max" if self.variant == "A" else "min")
+
+    def prepare_ragged(self, pairs):
+        """prepare() for pairs of different sizes (PIL path).  Every image is resized, converted and normalised exactly as prepare()
+        does it for its pair alone; images of one shape are stacked into one bucket (ragged_plan).  Returns a ragged prep, which
+        features / coarse / fine_quickstart / align_prepared accept."""
+        plan = self._ragged_plan([p[0].size for p in pairs], [p[1].size for p in pairs])
+        nS, mid = plan["nS"], plan["nS"] // 2
+        mean, std = self.mean, self.std
+        norm, IsT, ItT = {}, [], []
+        for b, (Is_org, It_org) in enumerate(pairs):
+            for i, s in enumerate(self.scaleList):
+                t = pil_to_tensor(self._resize(Is_org, int(self.minSize * s)))[None]
+                norm[(b, i)] = ((t - mean) / std).to(self.dev)
+                if i == mid:
+                    IsT.append(t.to(self.dev))
+            t = pil_to_tensor(self._resize(It_org, self.minSize))[None]
+            norm[(b, nS)] = ((t - mean) / std).to(self.dev)
+            ItT.append(t.to(self.dev))
+        return self._ragged_prep(plan, norm, IsT, ItT)
+
+    def prepare_ragged_device(self, src_list, tgt_list):
+        """prepare_device() for pairs of different sizes: src_list / tgt_list = uint8 (H,W,3) device tensors, one per pair.  The
+        LANCZOS pyramid and the float conversions run per (input shape, output shape) bucket -- one rfx_lanczos_pass_u8 /
+        rfx_u8_to_f32_chw chain for all images that share both -- and equal prepare_ragged() bit for bit."""
+        plan = self._ragged_plan([(x.shape[1], x.shape[0]) for x in src_list], [(x.shape[1], x.shape[0]) for x in tgt_list])
+        nS, mid = plan["nS"], plan["nS"] // 2
+        norm, IsT, ItT = {}, [None] * plan["B"], [None] * plan["B"]
+        groups = collections.OrderedDict()
+        for b, x in enumerate(src_list):
+            groups.setdefault(("src", tuple(x.shape)), []).append(b)
+        for b, x in enumerate(tgt_list):
+            groups.setdefault(("tgt", tuple(x.shape)), []).append(b)
+        for (kind, _), bs in groups.items():
+            u8 = torch.stack([(src_list if kind == "src" else tgt_list)[b] for b in bs])
+            lv = range(nS) if kind == "src" else [nS]
+            for i in lv:
+                nh, nw = plan["levels"][bs[0]][i]
+                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD,
+                                         want_raw=(i == mid or i == nS))
+                for k, b in enumerate(bs):
+                    norm[(b, i)] = nrm[k:k + 1]
+                    if i == mid and kind == "src":
+                        IsT[b] = raw[k:k + 1]
+                    elif i == nS:
+                        ItT[b] = raw[k:k + 1]
+        return self._ragged_prep(plan, norm, IsT, ItT)
+
+    def _features_ragged(self, prep):
+        """features() of a ragged prep: ONE grouped trunk pass over all buckets (nets.forward_group: one launch per kernel instance
+        and layer for up to RFX_MAX_GROUP buckets), then one rfx_l2norm_nchw_scatter_f32 per bucket and destination (sources into
+        the padded featA (B,1024,ldA), targets into featB (B,1024,ldB)).  Cell coordinates: per pair, the tables of the one-pair
+        path, packed pair after pair (offA / offB = where pair b's begin)."""
+        plan, B, dev = prep["plan"], prep["B"], self.dev
+        nS, ldA, ldB = plan["nS"], plan["ldA"], plan["ldB"]
+        featA = torch.zeros((B, 1024, ldA), dtype=torch.float32, device=dev)
+        featB = torch.zeros((B, 1024, ldB), dtype=torch.float32, device=dev)
+        fs = self.trunk.forward_group(prep["bucket_x"])
+        # all destination tables in one upload
+        offs_host, spans = [], []
+        for mem in plan["buckets"].values():
+            k = sum(1 for m in mem if m[1] < nS)
+            src = [b * 1024 * ldA + plan["offs"][b][i] for b, i in mem[:k]]
+            tgt = [b * 1024 * ldB for b, _ in mem[k:]]
+            spans.append((k, len(offs_host), len(mem)))
+            offs_host += src + tgt
+        offA = np.cumsum([0] + plan["nA"][:-1]).tolist()
+        offB = np.cumsum([0] + plan["nB"][:-1]).tolist()
+        tab = torch.tensor(offs_host + offA + offB, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        for f, (k, o, n) in zip(fs, spans):
+            if k:
+                ops.l2norm_scatter(f[:k], featA, tab[o:o + k], ldA)
+            if k < n:
+                ops.l2norm_scatter(f[k:], featB, tab[o + k:o + n], ldB)
+        WA, HA, Wt, Ht = [], [], [], []
+        for b in range(B):
+            for i, (r, c) in enumerate(plan["cells"][b]):
+                W, Hh = cell_coords_cached(r, c, dev)
+                (WA if i < nS else Wt).append(W)
+                (HA if i < nS else Ht).append(Hh)
+        no = len(offs_host)
+        sizes = torch.tensor(plan["nA"] + plan["nB"], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        return dict(ragged=True, featA=featA, featB=featB, ldA=ldA, ldB=ldB, nA=plan["nA"], nB=plan["nB"], cap=plan["cap"],
+                    nA_dev=sizes[:B], nB_dev=sizes[B:], WA=torch.cat(WA), HA=torch.cat(HA), Wt=torch.cat(Wt), Ht=torch.cat(Ht),
+                    offA=tab[no:no + B], offB=tab[no + B:no + 2 * B], offA_host=offA, offB_host=offB, _refs=(fs, tab))
+
+    def _mutual_ragged(self, feats, maskB=None):
+        mask = None
+        if maskB is not None:
+            mask = (torch.stack(list(maskB)) if not isinstance(maskB, torch.Tensor) else maskB).float().contiguous()
+        return ops.mutual_nn_ragged(feats["featA"], feats["featB"], feats["nA_dev"], feats["nB_dev"], max(feats["nA"]),
+                                    max(feats["nB"]), maskB=mask, score_chunk=self.score_chunk, cap=feats["cap"])
+
+    def _ragged_pair_feats(self, feats):
+        """Per-pair views of a ragged feats dict's cell-coordinate tables (the keys _coarse_per_pair reads)."""
+        out = []
+        for b, (oA, oB) in enumerate(zip(feats["offA_host"], feats["offB_host"])):
+            nA, nB = feats["nA"][b], feats["nB"][b]
+            out.append(dict(HA=feats["HA"][oA:oA + nA], WA=feats["WA"][oA:oA + nA], Ht=feats["Ht"][oB:oB + nB],
+                            Wt=feats["Wt"][oB:oB + nB]))
+        return out
+
+    def _fine_ragged(self, prep, Hs):
+        """fine_quickstart of a ragged prep: the pairs grouped by (source, target) image shape, each group through today's dense
+        batch kernels.  Returns one dict per pair, every tensor with a leading batch dimension of 1."""
+        groups = collections.OrderedDict()
+        for b in range(prep["B"]):
+            groups.setdefault((tuple(prep["IsTensor"][b].shape), tuple(prep["ItTensor"][b].shape)), []).append(b)
+        out = [None] * prep["B"]
+        for bs in groups.values():
+            sub = dict(IsTensor=torch.cat([prep["IsTensor"][b] for b in bs]), ItTensor=torch.cat([prep["ItTensor"][b] for b in bs]))
+            f = self.fine_quickstart(sub, Hs[bs])
+            for k, b in enumerate(bs):
+                out[b] = {key: v[k:k + 1] for key, v in f.items()}
+        return out
+
     def _trunk(self, x):
         """self.trunk(x), optionally in sub-batches of RFX_TRUNK_CHUNK images (experiment knob, round 6: does a working set that fits
         the 256 MB Infinity Cache make the layer-to-layer re-reads cheaper than the smaller launches cost?).  Every sample is
@@ -235,6 +399,8 @@ class AlignPipeline:
         shape into a HIP graph (``torch.cuda.CUDAGraph``: our ctypes launches go to torch's current stream, which is the
         capture stream) and replayed: one graph launch instead of ~900 (RFX_GRAPH=0 disables; never under ops.Profiler,
         whose per-launch events cannot be recorded into a graph)."""
+        if prep.get("ragged"):
+            return self._features_ragged(prep)
         B = prep["B"]
         if B <= 4 and os.environ.get("RFX_GRAPH", "1") != "0" and ops.Profiler.active() is None:
             return self._features_graphed(prep)
@@ -475,8 +641,9 @@ class AlignPipeline:
         feats = feats or self.features(prep)
         B = prep["B"]
         lib_out = []
+        ragged = bool(feats.get("ragged"))
         # ONE batched mutual-NN launch chain for all pairs
-        idx1, idx2, cnt = self._mutual_batched(feats, B, maskB)
+        idx1, idx2, cnt = self._mutual_ragged(feats, maskB) if ragged else self._mutual_batched(feats, B, maskB)
         host_draw = not (samples is None and sample_fn is None and self.draw == "device")
         self._last_degenerate = {}
         if not host_draw:
@@ -494,9 +661,14 @@ class AlignPipeline:
                 else:
                     draws.append(torch.zeros((self.nbIter, 4), dtype=torch.int64))
             if len({tuple(d.shape) for d in draws}) != 1:       # explicit draws of different lengths: one launch chain per pair
-                return self._coarse_per_pair(feats, idx1, idx2, counts, draws, self._degenerate_mode(True))
+                return self._coarse_per_pair(self._ragged_pair_feats(feats) if ragged else feats, idx1, idx2, counts, draws,
+                                             self._degenerate_mode(True))
             smp = torch.stack(draws).to(self.dev, non_blocking=True)
-        M1, M2 = ops.gather_matches(idx1, idx2, cnt, feats["HA"], feats["WA"], feats["Ht"], feats["Wt"])
+        if ragged:
+            M1, M2 = ops.gather_matches_ragged(idx1, idx2, cnt, feats["HA"], feats["WA"], feats["offA"], feats["Ht"], feats["Wt"],
+                                               feats["offB"])
+        else:
+            M1, M2 = ops.gather_matches(idx1, idx2, cnt, feats["HA"], feats["WA"], feats["Ht"], feats["Wt"])
         bestH, inl, resd = ops.ransac_h4_batched(M1, M2, cnt, smp, self.tol, degenerate=self._degenerate_mode(host_draw),
                                                  info=self._last_degenerate)
         host = torch.cat((cnt[:, None], resd), dim=1).cpu().tolist()  # <- sync: result records (+ the match counts)
@@ -517,9 +689,10 @@ class AlignPipeline:
             i1, i2 = idx1[b, :n], idx2[b, :n]
             res = dict(index1=i1, index2=i2, H=None, inlier=None, samples=None, n=n)
             if n >= 4:
+                fb = feats[b] if isinstance(feats, list) else feats          # a list: per-pair tables of a ragged batch
                 ones = torch.ones(n, dtype=torch.float32, device=self.dev)
-                m1 = torch.stack((feats["HA"][i1], feats["WA"][i1], ones), dim=1)
-                m2 = torch.stack((feats["Ht"][i2], feats["Wt"][i2], ones), dim=1)
+                m1 = torch.stack((fb["HA"][i1], fb["WA"][i1], ones), dim=1)
+                m2 = torch.stack((fb["Ht"][i2], fb["Wt"][i2], ones), dim=1)
                 bestH, inl, r = ops.ransac_h4(m1, m2, draws[b].to(self.dev), self.tol, degenerate=degenerate)
                 status, c, widx, nuniq = r.cpu().tolist()
                 res.update(match1=m1, match2=m2, samples=draws[b], status=status, count=c, winner=widx, nUnique=nuniq)
@@ -1178,10 +1351,18 @@ class AlignPipeline:
 
     # ---------------------------------------------------------------- whole path
     def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0):
+        """coarse() + fine_quickstart() of a prep from prepare / prepare_device or, for pairs of different sizes, prepare_ragged /
+        prepare_ragged_device.  A ragged batch gives every pair, bit for bit, what it gives alone (same ``pair_ids`` / draws); it
+        runs eagerly (no HIP-graph capture).  Not covered for ragged preps: multi_h_batched, multi_h_kitti_batched and
+        multi_h_variant_c, and the drop-in modules."""
         res = self.coarse(prep, feats=feats, samples=samples, pair_ids=pair_ids, draw_epoch=draw_epoch)
         if fine:
             eye = torch.eye(3, device=self.dev)
             Hs = torch.stack([r["H"] if r["H"] is not None else eye for r in res])
+            if prep.get("ragged"):
+                for r, f in zip(res, self._fine_ragged(prep, Hs)):
+                    r["flow12"], r["img1_fine"], r["flowDown"] = f["flow12"], f["img1_fine"], f["flowDown"]
+                return res
             f = self.fine_quickstart(prep, Hs)
             for b, r in enumerate(res):
                 r["flow12"] = f["flow12"][b:b + 1]
@@ -1189,5 +1370,9 @@ class AlignPipeline:
                 r["flowDown"] = f["flowDown"][b:b + 1]
         return res
 
-    def align_pairs(self, pairs, fine=True, samples=None):
-        return self.align_prepared(self.prepare(pairs), fine=fine, samples=samples)
+    def align_pairs(self, pairs, fine=True, samples=None, pair_ids=None):
+        """Pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense path.  Otherwise the
+        ragged path (prepare_ragged)."""
+        if len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1:
+            return self.align_prepared(self.prepare_ragged(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
+        return self.align_prepared(self.prepare(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
