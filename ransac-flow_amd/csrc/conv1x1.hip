@@ -21,12 +21,6 @@
 #include "conv_epilogue.h"
 #include "group.h"
 
-// experiments only (scripts/ubench/conv_bench.py, make c1dbgN): RFX_C1_DBG removes pieces of the main loop to price them
-//   1 no LDS stores in the loop   2 no global loads in the loop   3 neither   4 neither, no barrier   6 no output stores
-#ifndef RFX_C1_DBG
-#define RFX_C1_DBG 0
-#endif
-
 namespace {
 
 struct C1Args {
@@ -34,7 +28,6 @@ struct C1Args {
     int Cin, HW, Cout, act, Mpad;
     long long P;   // N*HW
     int tilesM, tilesP;
-    unsigned stagger;   // common.h: rfx_stagger
 };
 
 // Persistent form: gridDim.x (= 2 workgroups per CU, a multiple of 8) workgroups walk the output tiles v = blockIdx.x,
@@ -106,7 +99,6 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
         }
     };
 
-    rfx_stagger(a.stagger, bx, gsz);
     int v = (int)bx;
     int m0; long long n0;
     tile_origin(v, m0, n0);
@@ -178,26 +170,20 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (c + 1 < 4) read_chunk(c + 1, (c + 1) & 1);
-                constexpr bool ST = RFX_C1_DBG != 1 && RFX_C1_DBG != 3 && RFX_C1_DBG != 4;
-                constexpr bool LD = RFX_C1_DBG != 2 && RFX_C1_DBG != 3 && RFX_C1_DBG != 4;
+                const int oth = cur ^ 1;                      // the buffer K step s+1 is staged into
                 // a register is re-loaded right after it was stored, in chunks 0 / 1: the loads get the rest of the step to
                 // land (with the loads in chunks 2 / 3 the next step's first store waits for them: -5 % in
                 // scripts/ubench/mfma_mix.hip, variants g and g/1)
                 if (c == 0) {
 #pragma unroll
-                    for (int j = 0; j < NA; ++j) {
-                        if (ST) store_a(cur ^ 1, j); else if (LD) asm volatile("" ::"v"(ra[j]));
-                    }
+                    for (int j = 0; j < NA; ++j) store_a(oth, j);
 #pragma unroll
-                    for (int j = 0; j < NA; ++j) if (LD) load_a(wl, k2, j);
+                    for (int j = 0; j < NA; ++j) load_a(wl, k2, j);
                 } else if (c == 1) {
 #pragma unroll
-                    for (int j = 0; j < NB; ++j) {
-                        if (ST) store_b(cur ^ 1, j);
-                        else if (LD) { if (VEC) asm volatile("" ::"v"(rv[VEC ? j : 0])); else asm volatile("" ::"v"(rb[VEC ? 0 : j])); }
-                    }
+                    for (int j = 0; j < NB; ++j) store_b(oth, j);
 #pragma unroll
-                    for (int j = 0; j < NB; ++j) if (LD) load_b(bl, k2, j);
+                    for (int j = 0; j < NB; ++j) load_b(bl, k2, j);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -219,20 +205,11 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
                             for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
                 }
             }
-            if (RFX_C1_DBG != 4) __syncthreads();   // step s+1 is complete in the other buffer; everyone is done reading this one
+            __syncthreads();   // step s+1 is complete in the other buffer; everyone is done reading this one
         }
         put_scale((it + 1) & 1, m0n);             // the next tile's BN vectors (read after >= nk barriers)
-        if (RFX_C1_DBG == 6) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-            if (sacc == 123.456f) a.out[t] = sacc;
-        } else {
-            // ---- epilogue (conv_epilogue.h); the loads of the next tile's K step 1 are in flight meanwhile ----
+        // ---- epilogue (conv_epilogue.h); the loads of the next tile's K step 1 are in flight meanwhile ----
+        {
             size_t pix_off[2];
             bool pix_ok[2];
 #pragma unroll
@@ -282,8 +259,6 @@ int launch_1x1(C1Args& a, hipStream_t st) {
         slots = (2 * cus + 7) / 8 * 8;
     }
     const unsigned grid = (unsigned)(nwg < slots ? (nwg + 7) / 8 * 8 : slots);
-    static const unsigned stagger = rfx_stagger_env("RFX_C1_STAGGER", "RFX_C1_STAGGER_MODE");
-    a.stagger = (rfx_group_recording() || (int)grid < slots) ? 0u : stagger;      // only when every CU holds its two workgroups
     if (rfx_group_recording()) return rfx_group_record(&c1_group_launch<TM, VEC, KCH>, &a, sizeof(a), grid);
     hipLaunchKernelGGL((conv1x1_kmajor_kernel<TM, VEC, KCH>), dim3(grid), dim3(256), 0, st, a);
     RFX_LAUNCH_CHECK();

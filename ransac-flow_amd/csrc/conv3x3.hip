@@ -16,7 +16,7 @@
 // 16-byte-per-lane copy: coalesced global loads, conflict-free ds_write_b128, no register transposes.
 // The global loads of step s+1 are not issued as one burst: they are dealt out two at a time between the 16-MFMA
 // chunks of step s, where they issue in the shadow of the matrix pipe (a burst in front of the MFMAs cost 13 % of
-// the kernel, the bank-conflicting transposed stores another 8 %: scripts/ubench/conv_bench.py, make c3dbgN).
+// the kernel, the bank-conflicting transposed stores another 8 %: scripts/ubench/conv_bench.py).
 // B patch rows are 48 floats apart so that the two 16-pixel rows a 32-lane half reads fall on disjoint banks.
 // Numerics: k runs channel-major, taps row-major -- the same order as conv.hip / the packed weight matrix, so the
 // result is bit-identical to the implicit-GEMM kernel.
@@ -59,16 +59,10 @@ struct C3Args {
     // FUSE: the 1x1 expansion that follows (Bottleneck conv3 + bn3 + residual + ReLU, model/resnet50.py:77-79,99-103)
     const float* wT3; const float* scale3; const float* shift3;
     int Cexp, Mpad3, act3;
-    unsigned stagger;   // common.h: rfx_stagger
 #ifdef RFX_TRACE
     long long* trace;
 #endif
 };
-// experiments only (scripts/ubench/conv_bench.py): RFX_C3_DBG removes pieces of the main loop to price them
-//   1 no LDS stores in the loop   2 no global loads in the loop   3 neither   4 neither, no barriers   6 no output stores
-#ifndef RFX_C3_DBG
-#define RFX_C3_DBG 0
-#endif
 // 1: the fused tail drains the epilogue of expansion pass p inside the K loop of pass p + 1 (round 5, VERDICT r4 #6: "the one structural
 // conv idea still on the table"); 0 (default): the burst form.  MEASURED NEGATIVE on one box, same library otherwise
 // (profiles/r05_conv_ab.jsonl, 128 / 64 images): 64-channel tail 101.4 -> 98.2 TFLOP/s at 120x160, 101.9 -> 98.4 at 240x320, 86.8 -> 82.4 at
@@ -130,7 +124,6 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
     const int tilesP = a.tilesH * a.tilesW;     // tilesH counts patch rows of the whole stack
     const int nwg = a.tilesM * tilesP;
     int bid = (int)bx;
-    rfx_stagger(a.stagger, bx, 512u);
     RFX_STAMP(0);
     {   // XCD-aware bijective remap, m-tile fastest: the workgroups sharing one input patch sit on one L2
         const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
@@ -280,10 +273,8 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
         for (int q = 0; q < 9; ++q) {
             const int cur = q & 1;
             if (q + 1 < 9) read_chunk(q + 1, cur ^ 1);
-            if (RFX_C3_DBG != 2 && RFX_C3_DBG != 3 && RFX_C3_DBG != 4) {
 #pragma unroll
-                for (int i = 0; i < LPC; ++i) load_one(q * LPC + i, wstep, base, lastn);   // tile s+1, in the MFMA shadow
-            }
+            for (int i = 0; i < LPC; ++i) load_one(q * LPC + i, wstep, base, lastn);   // tile s+1, in the MFMA shadow
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -304,27 +295,9 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
                         for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
             }
         }
-        if (RFX_C3_DBG != 4) __syncthreads();   // everyone is done reading the tile
-        if (RFX_C3_DBG != 1 && RFX_C3_DBG != 3 && RFX_C3_DBG != 4)
-            store_lds(lastn);   // tile s+1
-        else if (RFX_C3_DBG == 1) {   // keep the loads alive (and waited for) without the LDS stores
-#pragma unroll
-            for (int j = 0; j < NA; ++j) asm volatile("" ::"v"(ra[j]));
-#pragma unroll
-            for (int u = 0; u < NB; ++u) asm volatile("" ::"v"(rb[u]));
-        }
-        if (RFX_C3_DBG != 4) __syncthreads();
-    }
-    if (RFX_C3_DBG == 6) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (sacc == 123.456f) a.out[t] = sacc;
-        return;
+        __syncthreads();   // everyone is done reading the tile
+        store_lds(lastn);   // tile s+1
+        __syncthreads();
     }
 
     RFX_STAMP(2);
@@ -826,9 +799,6 @@ static int launch_direct(C3Args& a, hipStream_t st) {
     // 32-bit byte offsets inside the images one input patch can touch
     const long long span = (G::PR + a.H) / (a.H + 1) + 1;
     if (span * a.Cin * a.H * a.W * 4 > 0xffffffffLL) return RFX_E_LIMIT;
-    static const unsigned stagger = FUSE ? rfx_stagger_env("RFX_C3F_STAGGER", "RFX_C3F_STAGGER_MODE")
-                                         : rfx_stagger_env("RFX_C3_STAGGER", "RFX_C3_STAGGER_MODE");
-    a.stagger = (rfx_group_recording() || nwg < 1024) ? 0u : stagger;
     if constexpr (TN == 2 && !RAG) {
         if (rfx_group_recording()) return rfx_group_record(&c3_group_launch<TM, PTC, FUSE, KCH>, &a, sizeof(a), (unsigned)nwg);
     }
@@ -888,7 +858,7 @@ int rfx_conv3x3_s2_launch(const float* in, const float* wP, const float* scale, 
     C3Args a;
     a.in = in; a.wT = wP; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.act = act; a.Mpad = (Cout + 127) / 128 * 128;
-    a.wT3 = a.scale3 = a.shift3 = nullptr; a.Cexp = a.Mpad3 = a.act3 = 0; a.stagger = 0;
+    a.wT3 = a.scale3 = a.shift3 = nullptr; a.Cexp = a.Mpad3 = a.act3 = 0;
 #ifdef RFX_TRACE
     a.trace = nullptr;
 #endif

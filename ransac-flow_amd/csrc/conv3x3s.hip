@@ -232,9 +232,6 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
                     b1[j] = as_frag(bimg[2 * PP + b_base[j] + toff]);
                 }
             }
-#ifndef RFX_C3S_DBG          // experiments only (WRONG RESULTS): 1 = no weight DMA in the loop, 2 = no activation requests in the loop
-#define RFX_C3S_DBG 0
-#endif
             if (!ADMA) {
                 if (q + 1 < nq) store_a((q + 1) & 1);       // stage q+1's weights: registers -> the other buffer
                 if (q + 2 < nq) load_a(q + 2);
@@ -258,7 +255,7 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
             if (tap == 8 && kb + 2 < nk) { b_next = 0; b_kb = kb + 2; }
             const bool b_req = b_next >= 0;
             // the DMA BEHIND the stage's ds_writes (store_b): the compiler drains the counter in front of an LDS write that follows an LDS-DMA
-            if (ADMA && q + 1 < nq && RFX_C3S_DBG != 1) dma_a(q + 1, (q + 1) & 1);      // its readers (stage q - 1) passed the last barrier
+            if (ADMA && q + 1 < nq) dma_a(q + 1, (q + 1) & 1);      // its readers (stage q - 1) passed the last barrier
             if (!ADMA && b_req) { if (b_next == 0) load_b(b_kb, 0); else if (b_next == 1) load_b(b_kb, 1); else load_b(b_kb, NBI - 1); }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (ADMA) {
@@ -289,7 +286,7 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
 #pragma unroll
                 for (int j = 0; j < 2; ++j) b1[j] = as_frag(bimg[4 * PP + b_base[j] + toff]);
             }
-            if (ADMA && b_req && RFX_C3S_DBG != 2) {
+            if (ADMA && b_req) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (b_next == 0) load_b(b_kb, 0); else if (b_next == 1) load_b(b_kb, 1); else load_b(b_kb, NBI - 1);
                 __builtin_amdgcn_sched_barrier(0);

@@ -59,12 +59,10 @@ constexpr int TC = 16;           // columns per wavefront
 
 // Kernel configuration: tile TR x 16*NCB, CK channels per chunk, NS-deep LDS ring, NG groups of window rows (one
 // wavefront per 16x16 block and group), PF = software-pipeline distance of the LDS reads in (channel, window row)
-// steps (0 = compiler-scheduled reads), DBG: 0 product; experiments with wrong results: 1 DMA only, 2 compute only,
-// 5 no LDS reads, 6 no FMAs;
-// SB: sched_barrier pinning of the step order, OPT: bit set of BAL / ZM / XPAD / PRIO below.
-template <int TR_, int NCB_, int CK_, int NS_, int NG_ = 2, int PF_ = 0, int DBG_ = 0, int SB_ = 0, int OPT_ = 0>
+// steps (0 = compiler-scheduled reads), SB: sched_barrier pinning of the step order, OPT: bit set of BAL / ZM / XPAD / PRIO below.
+template <int TR_, int NCB_, int CK_, int NS_, int NG_ = 2, int PF_ = 0, int SB_ = 0, int OPT_ = 0>
 struct Cfg {
-    static constexpr int TR = TR_, NCB = NCB_, CK = CK_, NS = NS_, NG = NG_, PF = PF_, DBG = DBG_, SB = SB_;
+    static constexpr int TR = TR_, NCB = NCB_, CK = CK_, NS = NS_, NG = NG_, PF = PF_, SB = SB_;
     static constexpr bool BAL = OPT_ & 1;   // wave -> (block, tap group) map that equalises the FMA count per SIMD
     static constexpr bool ZM = OPT_ & 2;    // halo / padding slots zeroed ONCE, DMA lanes that would fetch zeros masked off
     static constexpr bool XPAD = OPT_ & 4;  // x rows padded to the y row stride (conflict-free ds_read_b128 of x)
@@ -141,93 +139,62 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // is then drained together with the newest ones and the prefetch distance collapses to zero.  The reads and their
 // COUNTED waits are therefore written by hand: ds_read_b128 with a compile-time byte offset, and s_waitcnt lgkmcnt(K)
 // carrying the registers it makes valid as in/out operands so that no use can be scheduled above it.
-template <int OFF, bool REAL = true>
+template <int OFF>
 __device__ __forceinline__ void lds_read128(f32x4& d, unsigned addr) {
-    if constexpr (REAL) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-    else asm volatile("; (experiment: LDS read removed)" : "=v"(d) : "v"(addr));
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
 }
-template <int K, bool REAL = true>
+template <int K>
 __device__ __forceinline__ void lds_wait(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {
-    if constexpr (REAL) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(K));
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(K));
 }
 
 // One (channel, window row) step of a chunk, ST = 0 .. CK*NI-1, recursively unrolled (the offsets must be immediates).
 template <class G, int I0, int I1, int ST>
 __device__ __forceinline__ void corr7_steps(f32x4 (&wq)[G::CK * (I1 - I0)][3], f32x4 (&xq)[G::CK], float (&acc)[4][(I1 - I0) * 7],
-                                            unsigned ya, unsigned xa, f32x4 (&macc)[I1 - I0][4], float (&xm)[G::CK][4]) {
+                                            unsigned ya, unsigned xa) {
     constexpr int NI = I1 - I0, NSTEP = G::CK * NI, PF = G::PF;
-    constexpr bool RD = G::DBG != 5, FMA = G::DBG != 6;   // experiments 5 / 6: the LDS reads / the FMAs removed (DMA kept)
-    // experiments 7 / 8 (round 6, VERDICT r5 #2 -- WRONG RESULTS, instruction mix only): the 16 products of a step whose window
-    // element lies in the MIDDLE quad (x quad (x) y quad: every one of them is a tap) leave the VALU for the idle matrix pipe as
-    // four v_mfma_f32_4x4x1_16b_f32 (16 blocks of 4x4x1 each = 64 (quad, row) blocks per wave and step), the VALU keeps the 12
-    // edge products.  7: operands = registers the step already holds (optimistic: no extra LDS traffic); 8: the middle quad is
-    // not read as a b128, the MFMA operands come from 4 + 4 extra ds_read_b32 per step (x: per channel) -- the lane layout an
-    // MFMA block needs (lane 4b+k = element k of block b) is not the quad-per-lane layout of the VALU part
-    constexpr bool HY = G::DBG == 7 || G::DBG == 8;
-    constexpr bool HY8 = G::DBG == 8;
     constexpr int YROW = G::YQ * 16, YCH = G::YR * G::YQ * 16, XCH = G::TR * G::XQ * 16;
     if constexpr (ST == 0) {          // pipeline fill: steps 0 .. PF-1 (+ the x quad of channel 0)
-        lds_read128<0, RD>(xq[0], xa);
-        lds_read128<I0 * YROW, RD>(wq[0][0], ya);
-        lds_read128<I0 * YROW + 16, RD && !HY8>(wq[0][1], ya);
-        lds_read128<I0 * YROW + 32, RD>(wq[0][2], ya);
+        lds_read128<0>(xq[0], xa);
+        lds_read128<I0 * YROW>(wq[0][0], ya);
+        lds_read128<I0 * YROW + 16>(wq[0][1], ya);
+        lds_read128<I0 * YROW + 32>(wq[0][2], ya);
         if constexpr (PF >= 2 && NSTEP > 1) {
             constexpr int o = (1 / NI) * YCH + (I0 + 1 % NI) * YROW;
-            if constexpr (1 % NI == 0) lds_read128<(1 / NI) * XCH, RD>(xq[1 / NI], xa);
-            lds_read128<o, RD>(wq[1][0], ya); lds_read128<o + 16, RD && !HY8>(wq[1][1], ya); lds_read128<o + 32, RD>(wq[1][2], ya);
+            if constexpr (1 % NI == 0) lds_read128<(1 / NI) * XCH>(xq[1 / NI], xa);
+            lds_read128<o>(wq[1][0], ya); lds_read128<o + 16>(wq[1][1], ya); lds_read128<o + 32>(wq[1][2], ya);
         }
         if constexpr (PF >= 3 && NSTEP > 2) {
             constexpr int o = (2 / NI) * YCH + (I0 + 2 % NI) * YROW;
-            if constexpr (2 % NI == 0) lds_read128<(2 / NI) * XCH, RD>(xq[2 / NI], xa);
-            lds_read128<o, RD>(wq[2][0], ya); lds_read128<o + 16, RD && !HY8>(wq[2][1], ya); lds_read128<o + 32, RD>(wq[2][2], ya);
+            if constexpr (2 % NI == 0) lds_read128<(2 / NI) * XCH>(xq[2 / NI], xa);
+            lds_read128<o>(wq[2][0], ya); lds_read128<o + 16>(wq[2][1], ya); lds_read128<o + 32>(wq[2][2], ya);
         }
     }
     constexpr int S2 = ST + PF;       // the step whose reads are issued now
     if constexpr (S2 < NSTEP) {
         constexpr int o = (S2 / NI) * YCH + (I0 + S2 % NI) * YROW;
-        if constexpr (S2 % NI == 0) lds_read128<(S2 / NI) * XCH, RD>(xq[S2 / NI], xa);
-        lds_read128<o, RD>(wq[S2][0], ya); lds_read128<o + 16, RD && !HY8>(wq[S2][1], ya); lds_read128<o + 32, RD>(wq[S2][2], ya);
+        if constexpr (S2 % NI == 0) lds_read128<(S2 / NI) * XCH>(xq[S2 / NI], xa);
+        lds_read128<o>(wq[S2][0], ya); lds_read128<o + 16>(wq[S2][1], ya); lds_read128<o + 32>(wq[S2][2], ya);
     }
     // reads issued after those of step ST: steps ST+1 .. min(ST+PF, NSTEP-1), 3 each + 1 for a step that opens a channel
     constexpr int LAST = S2 < NSTEP ? S2 : NSTEP - 1;
-    constexpr int NEWER = (HY8 ? 2 : 3) * (LAST - ST) + (LAST / NI - ST / NI);
+    constexpr int NEWER = 3 * (LAST - ST) + (LAST / NI - ST / NI);
     constexpr int ch = ST / NI, r = ST % NI;
-    lds_wait<NEWER, RD>(wq[ST][0], wq[ST][1], wq[ST][2], xq[ch]);
+    lds_wait<NEWER>(wq[ST][0], wq[ST][1], wq[ST][2], xq[ch]);
     const f32x4 w0 = wq[ST][0], w1 = wq[ST][1], w2 = wq[ST][2], xv = xq[ch];
-    if constexpr (HY) {
-        float bm[4];
-        if constexpr (HY8) {
-            // operands in block layout from LDS: 4 x floats per channel (read at the channel's first window row), 4 y floats per step
-            constexpr int o = ch * YCH + (I0 + r) * YROW;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(bm[m]) : "v"(ya), "n"(o + 16 + 256 * m));
-            if constexpr (r == 0) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(xm[ch][m]) : "v"(xa), "n"(ch * XCH + 256 * m));
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xm[ch][0]), "+v"(xm[ch][1]), "+v"(xm[ch][2]), "+v"(xm[ch][3]));
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bm[0]), "+v"(bm[1]), "+v"(bm[2]), "+v"(bm[3]));
-        } else {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) bm[m] = w1[m];
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m) macc[r][m] = __builtin_amdgcn_mfma_f32_4x4x1f32(HY8 ? xm[ch][m] : xv[m], bm[m], macc[r][m], 0, 0, 0);
-    }
     // element e = d+j+1 of the 12-float window, picked straight out of the three quads (an intermediate float[12] makes
     // the optimiser re-load the window from the wq array with overlapping 48-byte loads, which pins wq in scratch)
 #pragma unroll
-    for (int d = 0; d < 4 && FMA; ++d)
+    for (int d = 0; d < 4; ++d)
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
             const int e = d + j + 1;
-            if (HY && e >= 4 && e < 8) continue;          // the matrix pipe's share
             const float yv = e < 4 ? w0[e & 3] : (e < 8 ? w1[e & 3] : w2[e & 3]);
             float& a = acc[G::ROT ? (d + j) & 3 : d][r * 7 + j];
             a = fmaf(xv[d], yv, a);
         }
     if constexpr (G::SB) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (ST + 1 < NSTEP) corr7_steps<G, I0, I1, ST + 1>(wq, xq, acc, ya, xa, macc, xm);
+    if constexpr (ST + 1 < NSTEP) corr7_steps<G, I0, I1, ST + 1>(wq, xq, acc, ya, xa);
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform n (the immediate must be a constant): n = DMA instructions of this wave that may
@@ -250,7 +217,7 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
                                             int strip, int cb, int lane, int nchunks, size_t HW,
                                             float* __restrict__ out, float* __restrict__ out21, int n, int row0, int c0, int H,
                                             int W, int trv) {
-    constexpr int NI = I1 - I0, NS = G::NS, CK = G::CK, PF = G::PF, DBG = G::DBG, TR = G::TR;
+    constexpr int NI = I1 - I0, NS = G::NS, CK = G::CK, PF = G::PF, TR = G::TR;
     auto issue = [&](int chunk, int buf) {
         const size_t cbase = (size_t)chunk * CK * HW;
 #pragma unroll
@@ -278,11 +245,6 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
     for (int d = 0; d < 4; ++d)
 #pragma unroll
         for (int q = 0; q < NI * 7; ++q) acc[d][q] = 0.f;
-    f32x4 macc[NI][4];                          // experiments 7 / 8 only (dead otherwise): the matrix pipe's accumulators
-#pragma unroll
-    for (int q = 0; q < NI; ++q)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) macc[q][m] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int tc = lane >> 4;
     const int tr = strip * 16 + (lane & 15);
     const int yoff = tr * G::YQ + cb * 4 + tc;        // slot of (row tr, this lane's first window quad) in a channel's y tile
@@ -296,19 +258,17 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
     int buf = 0;
     for (int s = 0; s < nchunks; ++s) {
         // chunk s must have landed; the (up to NS-2) younger chunks of this wave may stay in flight across the barrier
-        const int younger = DBG == 2 ? (s < NS - 1 ? NS - 2 - s : 0) : (nchunks - 1 - s < NS - 2 ? nchunks - 1 - s : NS - 2);
+        const int younger = nchunks - 1 - s < NS - 2 ? nchunks - 1 - s : NS - 2;
         wait_vm(younger * npieces);
         __builtin_amdgcn_s_barrier();  // all waves: chunk s visible, and everyone is done reading buffer (s-1)%NS
-        if (DBG != 2 && s + NS - 1 < nchunks) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);  // (s+NS-1)%NS == (s-1)%NS
-        if (DBG == 1) { buf = buf == NS - 1 ? 0 : buf + 1; continue; }   // experiments: DMA only
+        if (s + NS - 1 < nchunks) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);  // (s+NS-1)%NS == (s-1)%NS
         if constexpr (PF > 0) {
             // hand-pipelined LDS reads (see lds_read128): byte addresses of this lane's first window quad / x quad
             const unsigned ya = lds_base + (unsigned)(buf * G::BUF_SLOTS + yoff) * 16u;
             const unsigned xa = lds_base + (unsigned)(buf * G::BUF_SLOTS + G::Y_PIECES * 64 + xoff) * 16u;
             f32x4 wq[CK * NI][3];
             f32x4 xq[CK];
-            float xm[CK][4];
-            corr7_steps<G, I0, I1, 0>(wq, xq, acc, ya, xa, macc, xm);
+            corr7_steps<G, I0, I1, 0>(wq, xq, acc, ya, xa);
         } else {
             const f32x4* yb = smem + buf * G::BUF_SLOTS + yoff;
             const f32x4* xb = smem + buf * G::BUF_SLOTS + G::Y_PIECES * 64 + xoff;
@@ -347,14 +307,6 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
             const float t0 = acc[(0 + j) & 3][q], t1 = acc[(1 + j) & 3][q], t2 = acc[(2 + j) & 3][q], t3 = acc[(3 + j) & 3][q];
             acc[0][q] = t0; acc[1][q] = t1; acc[2][q] = t2; acc[3][q] = t3;
         }
-    }
-    if constexpr (DBG == 7 || DBG == 8) {      // keep the matrix pipe's sums alive: they take the 16 slots per row the VALU left at zero
-#pragma unroll
-        for (int q = 0; q < NI; ++q)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k][q * 7 + (m + 3 - k)] = macc[q][m][k];       // (pixel k, middle element m) -> tap column m+3-k
     }
     const int gr = row0 + tr, gc = c0 + cb * TC + 4 * tc;
     if (tr < trv && gr < H && gc < W) {
@@ -789,20 +741,20 @@ __global__ __launch_bounds__(256) void corr7_plain_kernel(const float* __restric
 //   6: as 5 with 2 tap groups (10 waves)      7 / 8: the tuned kernel with 48- / 64-column tiles      9: 32x32 (plain)
 //   21 / 22 / 23 / 24: variant 5 with the compute / the DMA / the LDS reads / the FMAs removed -- WRONG RESULTS, for the
 //            roofline decomposition in scripts/ubench/corr_bench.py only (how long does each side take alone?)
-using CfgTuned = Cfg<16, 5, 2, 4, 3, 1, 0, 0, 15>;
-using CfgTuned4 = Cfg<16, 4, 2, 4, 3, 1, 0, 0, 14>;   // 64-column tiles: 12 waves, one of each tap group per SIMD by construction
-using CfgTuned3 = Cfg<16, 3, 2, 4, 3, 1, 0, 0, 14>;   // 48-column tiles: 9 waves
+using CfgTuned = Cfg<16, 5, 2, 4, 3, 1, 0, 15>;
+using CfgTuned4 = Cfg<16, 4, 2, 4, 3, 1, 0, 14>;   // 64-column tiles: 12 waves, one of each tap group per SIMD by construction
+using CfgTuned3 = Cfg<16, 3, 2, 4, 3, 1, 0, 14>;   // 48-column tiles: 9 waves
 // BIDIR forms (OPT bit 16) of the tile shapes the automatic choice can return: same main loop, second store in the epilogue
-using CfgTunedB = Cfg<16, 5, 2, 4, 3, 1, 0, 0, 15 | 16>;
-using CfgTuned4B = Cfg<16, 4, 2, 4, 3, 1, 0, 0, 14 | 16>;
-using CfgTuned3B = Cfg<16, 3, 2, 4, 3, 1, 0, 0, 14 | 16>;
+using CfgTunedB = Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 16>;
+using CfgTuned4B = Cfg<16, 4, 2, 4, 3, 1, 0, 14 | 16>;
+using CfgTuned3B = Cfg<16, 3, 2, 4, 3, 1, 0, 14 | 16>;
 static int launch_variant(int v, const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W,
                           hipStream_t st) {
     if (out21) {
         switch (v) {
-            case 1: launch_corr<Cfg<64, 1, 2, 3, 2, 0, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
-            case 2: launch_corr<Cfg<32, 1, 2, 3, 2, 0, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
-            case 3: launch_corr<Cfg<16, 1, 2, 3, 2, 0, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
+            case 1: launch_corr<Cfg<64, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
+            case 2: launch_corr<Cfg<32, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
+            case 3: launch_corr<Cfg<16, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
             case 5: launch_corr<CfgTunedB>(x, y, out, N, C, H, W, st, true, out21); break;
             case 7: launch_corr<CfgTuned3B>(x, y, out, N, C, H, W, st, true, out21); break;
             case 8: launch_corr<CfgTuned4B>(x, y, out, N, C, H, W, st, true, out21); break;
@@ -817,27 +769,16 @@ static int launch_variant(int v, const float* x, const float* y, float* out, flo
         case 3: launch_corr<Cfg<16, 1, 2, 3>>(x, y, out, N, C, H, W, st); break;
         case 4: launch_corr<Cfg<16, 5, 2, 4>>(x, y, out, N, C, H, W, st); break;
         case 5: launch_corr<CfgTuned>(x, y, out, N, C, H, W, st, true); break;
-        case 6: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 0, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
+        case 6: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
         case 7: launch_corr<CfgTuned3>(x, y, out, N, C, H, W, st, true); break;
         case 8: launch_corr<CfgTuned4>(x, y, out, N, C, H, W, st, true); break;
         case 9: launch_corr<Cfg<32, 2, 2, 3>>(x, y, out, N, C, H, W, st); break;
-        case 10: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 5 + DMA on the light waves
-        case 11: launch_corr<Cfg<16, 5, 2, 5, 3, 1, 0, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 10 with a ring of 5
-        case 12: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 0, 15 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 5 + accumulator bank rotation
-        case 13: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 0, 15 | 32 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 12 + DMA on the light waves
+        case 10: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 5 + DMA on the light waves
+        case 11: launch_corr<Cfg<16, 5, 2, 5, 3, 1, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 10 with a ring of 5
+        case 12: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 5 + accumulator bank rotation
+        case 13: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 32 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 12 + DMA on the light waves
         case 14: if (W > 80) return RFX_E_ARG; launch_corr_dpp<CfgD<16, 5, 2, 4, 2>>(x, y, out, N, C, H, W, st); break;   // DPP form, 80-column tiles, 2 tap groups
         case 15: if (W > 80) return RFX_E_ARG; launch_corr_dpp<CfgD<16, 5, 2, 3, 2>>(x, y, out, N, C, H, W, st); break;   // 14 with a ring of 3
-#ifdef RFX_CORR_EXPERIMENTS   // `make exp NAME=correxp SRC=corr DEFS=-DRFX_CORR_EXPERIMENTS`: never in the product library
-        case 21: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 1, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
-        case 22: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 2, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
-        case 23: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 5, 0, 15>>(x, y, out, N, C, H, W, st, true); break;   // DMA + FMAs, no LDS reads
-        case 24: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 6, 0, 15>>(x, y, out, N, C, H, W, st, true); break;   // DMA + LDS reads, no FMAs
-        case 25: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 7, 0, 15>>(x, y, out, N, C, H, W, st, true); break;   // hybrid: 12 of 28 FMAs on the VALU + 4 v_mfma_f32_4x4x1 per step, register operands
-        case 26: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 8, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
-        case 27: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 7, 0, 15>>(x, y, out, N, C, H, W, st, true); break;   // 25 / 26 on the 10-wave map (2 tap groups, 168 registers: no spills)
-        case 28: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 8, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
-        case 29: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 6, 0, 15>>(x, y, out, N, C, H, W, st, true); break;   // 10-wave map, no FMAs (its DMA + LDS-read floor)   // 25 with the MFMA operands read from LDS in block layout (2 b128 + 8 b32 per step)
-#endif
         default: return RFX_E_ARG;
     }
     return RFX_OK;

@@ -22,15 +22,7 @@ constexpr int TH = 4, TW = 16;                 // pooled outputs per workgroup
 constexpr int CR = 2 * TH + 2, CC = 2 * TW + 2; // conv outputs under the tile: 10 x 34
 constexpr int PRW = CR + 2, PCL = CC + 2;       // input patch 12 x 36
 constexpr int CST = CC + 1;                     // row stride of the conv tile in LDS (35: odd -> rows on different banks)
-// experiments only (scripts/ubench/stem_bench.py; WRONG RESULTS): RFX_STEM3_DBG removes one phase of the 3x3 stem to price it
-//   1 no pooling pass / output stores   2 pooling arithmetic but no interior stores   3 no MFMA phase / C-tile stores
-#ifndef RFX_STEM3_DBG
-#define RFX_STEM3_DBG 0
-#endif
-#ifndef RFX_STEM3_PLANE_PAD
-#define RFX_STEM3_PLANE_PAD 1                   // 0: round 5's 350-word planes (A/B runs)
-#endif
-constexpr int CPS = CR * CST + RFX_STEM3_PLANE_PAD;   // channel-plane stride 351: ODD, so the four channels a wavefront of the pooling pass covers
+constexpr int CPS = CR * CST + 1;               // channel-plane stride 351: ODD, so the four channels a wavefront of the pooling pass covers
                                                 // (8 blocks x 2 block rows x 4 channels, block columns 4 words apart) fall into the four bank
                                                 // classes mod 4 -- every bank twice, the minimum for 64 lanes; 350 gave two classes: 4-way
                                                 // conflicts on each of the 36 window reads (SQ_LDS_BANK_CONFLICT 0.20 per instruction, round 6)
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
 
     // ---- 2./3. conv on the MFMA, BN + ReLU, tile -> LDS
     const float* pf = &P[0][0][0];
-    for (int s = wave; s < NSUB && RFX_STEM3_DBG != 3; s += 4) {
+    for (int s = wave; s < NSUB; s += 4) {
         const int p = s * 32 + lcol;
         const bool pv = p < NPX;
         const int pc = pv ? p : 0;
@@ -139,7 +131,7 @@ __global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
     // ---- 4. max 2x2 (stride 1) + blur/2 with reflection on the max-pooled map; 2x2 output blocks
     const float w3[3] = {0.25f, 0.5f, 0.25f};
     const int Hm = a.H - 1, Wm = a.W - 1;
-    for (int b = t; b < MCH * (TH / 2) * (TW / 2) && RFX_STEM3_DBG != 1; b += 256) {
+    for (int b = t; b < MCH * (TH / 2) * (TW / 2); b += 256) {
         const int bx = b % (TW / 2), by = (b / (TW / 2)) % (TH / 2), ch = b / ((TW / 2) * (TH / 2));
         const int oh = oh0 + 2 * by, ow = ow0 + 2 * bx;        // first output of the block
         if (oh >= a.Ho || ow >= a.Wo) continue;
@@ -172,7 +164,7 @@ __global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
                     for (int i = 0; i < 3; ++i)
 #pragma unroll
                         for (int j = 0; j < 3; ++j) acc = fmaf(M[2 * dy + i][2 * dx + j], w3[i] * w3[j], acc);
-                    if (RFX_STEM3_DBG != 2 || acc == 12345.678f) dst[(size_t)(oh + dy) * a.Wo + ow + dx] = acc;
+                    dst[(size_t)(oh + dy) * a.Wo + ow + dx] = acc;
                 }
             continue;
         }
@@ -210,30 +202,12 @@ __global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
 //   TH = 4 pooled rows (9 x 33 conv outputs = 10 MFMA sub-tiles on 4 waves: 3 + 3 + 2 + 2), BN vectors in registers   54-55 (round 5)
 //   TH = 4, BN vectors in LDS (32 registers less)                                                                      50-55
 //   TH = 5 (11 x 33 conv outputs = 12 sub-tiles: 3 per wave, 83 % instead of 67 % useful MFMA slots)                   56-62  <- default
-//   one workgroup walking both 32-channel groups over the staged patch (RFX_STEM7_CGLOOP=1: half the patch loads)      40-50: the
-//     two inlined group bodies keep 150 registers spilled around the barriers (rolled sub-tile loops); kept for experiments only
-#ifndef RFX_STEM7_CGLOOP
-#define RFX_STEM7_CGLOOP 0
-#endif
-// experiments only (scripts/ubench/stem_bench.py; WRONG RESULTS): RFX_STEM7_DBG removes one phase to price it
-//   1 no pooling / output stores   2 no patch loads from global memory   3 no MFMA phase   4 no weight (A fragment) loads
-#ifndef RFX_STEM7_DBG
-#define RFX_STEM7_DBG 0
-#endif
-// RFX_STEM7_ROWSTAGE=1 (experiment, round 6): patch staging by wave-uniform rows -- 690 fewer vector-ALU instructions per wave (444
-// instead of 1135 before the first barrier), bit-identical, and NO change in the kernel's time (62.1 vs 62.1 TFLOP/s): the staging
-// phase's VALU work does not hold the other workgroup's MFMA phase back.  Off: the element-wise form stays the product path.
-#ifndef RFX_STEM7_ROWSTAGE
-#define RFX_STEM7_ROWSTAGE 0
-#endif
-#ifndef RFX_STEM7_UNROLL
-#define RFX_STEM7_UNROLL 0
-#endif
-#ifndef RFX_STEM7_TH
-#define RFX_STEM7_TH 5      // experiments: make exp NAME=stem4 SRC=stem DEFS=-DRFX_STEM7_TH=4
-#endif
+//   one workgroup walking both 32-channel groups over the staged patch (half the patch loads)                          40-50: the
+//     two inlined group bodies keep 150 registers spilled around the barriers (rolled sub-tile loops)
+//   patch staging by wave-uniform rows (444 instead of 1135 vector-ALU instructions before the first barrier)          62.1 vs 62.1:
+//     the staging phase's VALU work does not hold the other workgroup's MFMA phase back; the element-wise form stayed
 namespace r50 {
-constexpr int TH = RFX_STEM7_TH, TW = 16;
+constexpr int TH = 5, TW = 16;
 constexpr int CR = 2 * TH + 1, CC = 2 * TW + 1;    // 9 x 33 conv outputs
 constexpr int PR = 2 * CR + 5, PCW = 2 * CC + 5;   // 23 x 71 input patch
 constexpr int PHALF = 36, PST = 2 * PHALF + 2;     // de-interleaved row: 36 even + 36 odd columns (+2: the 9 lanes of the column
@@ -241,10 +215,7 @@ constexpr int PHALF = 36, PST = 2 * PHALF + 2;     // de-interleaved row: 36 eve
 // conv-output tile in LDS, rows de-interleaved by column parity as well ([17 even | 17 odd at +17], row stride 40): the
 // pooling pass reads columns 2*ow + j of 16 consecutive pooled outputs as CONSECUTIVE words, and the four pooled rows of a
 // wavefront lie 2*CST = 80 words = 16 banks apart -> every bank is hit exactly twice by the 64 lanes (the minimum).
-#ifndef RFX_STEM7_CST
-#define RFX_STEM7_CST 40
-#endif
-constexpr int CHALF = 17, CST = RFX_STEM7_CST;
+constexpr int CHALF = 17, CST = 40;
 // MFMA sub-tiles are ROW-ALIGNED (round 4): sub-tile s < 9 = conv row s, columns 0..31 (32 consecutive LDS words per tap: no
 // bank conflict); sub-tile 9 = column 32 of the nine rows (9 live lanes).  The old numbering p = s*32 + lcol over the 9 x 33
 // map made most sub-tiles straddle two rows that land 2*PST = 16 banks apart on overlapping banks: 2-way conflicts on the B
@@ -281,11 +252,9 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int lrow = lane >> 5, lcol = lane & 31;
     int bid = (int)bx;
-    // RFX_STEM7_CGLOOP (default since round 6): ONE workgroup per pooled tile walks the Cout / 32 channel groups over the SAME staged
-    // input patch (the patch load + its barrier were paid once per channel group before: 2x for the 64-channel stem)
-    const int cg_first = RFX_STEM7_CGLOOP ? 0 : bid % a.chGroups;
-    const int cg_last = RFX_STEM7_CGLOOP ? a.chGroups : cg_first + 1;
-    if (!RFX_STEM7_CGLOOP) bid /= a.chGroups;
+    // one workgroup per (pooled tile, 32-channel group): the patch is staged once per channel group (2x for the 64-channel stem)
+    const int cg_first = bid % a.chGroups;
+    bid /= a.chGroups;
     const int tw = bid % a.tilesW; bid /= a.tilesW;
     const int th = bid % a.tilesH;
     const int n = bid / a.tilesH;
@@ -295,32 +264,8 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
     const size_t HW = (size_t)a.H * a.W;
 
     RFX_STAMP7(0);
-    // ---- input patch -> registers.  RFX_STEM7_ROWSTAGE (round 6): by ROWS -- wave w takes patch rows w, w+4, .. (3 x PR rows of PCW <= 71
-    // columns: lane = column, lanes 0..PCW-65 a second one), so that the row's base address, its validity and its LDS row are
-    // wave-uniform (scalar ALU) and a load costs ONE vector instruction besides itself (the border select).  The element-wise form
-    // (element t + 256u of the patch) spent ~20 vector-ALU instructions per element on index arithmetic, bounds and 64-bit addresses;
-    // every fp32 VALU instruction takes ~4 cycles out of the matrix pipe's time (profiles/r06_mfma_forms_and_pipe_concurrency.txt, C).
+    // ---- input patch -> registers
     const float* inn = a.in + (size_t)n * 3 * HW;
-#if RFX_STEM7_ROWSTAGE
-    constexpr int NROW = (3 * PR + 3) / 4;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int gx0 = ix0 + lane, gx1 = ix0 + lane + 64;
-    const bool cok0 = (unsigned)gx0 < (unsigned)a.W;
-    const bool has1 = lane + 64 < PCW;
-    const bool cok1 = has1 && (unsigned)gx1 < (unsigned)a.W;
-    const int gxc0 = cok0 ? gx0 : 0, gxc1 = cok1 ? gx1 : 0;
-    const int lc0 = (lane & 1) * PHALF + (lane >> 1), lc1 = (lane & 1) * PHALF + ((lane + 64) >> 1);
-    float pv0[NROW], pv1[NROW];
-#pragma unroll
-    for (int j = 0; j < NROW; ++j) {
-        const int row = wave_u + 4 * j;                       // = c * PR + pr, wave-uniform
-        const int c = row / PR, pr = row - c * PR, gy = iy0 + pr;
-        const bool rok = row < 3 * PR && (unsigned)gy < (unsigned)a.H;
-        const float* rp = inn + (size_t)(row < 3 * PR ? c : 0) * HW + (size_t)(rok ? gy : 0) * a.W;
-        pv0[j] = RFX_STEM7_DBG == 2 ? (float)j : rp[gxc0];
-        pv1[j] = RFX_STEM7_DBG == 2 ? (float)j : rp[gxc1];
-    }
-#else
     constexpr int NP = (3 * PR * PCW + 255) / 256;
     float pv_[NP];
     unsigned pok = 0;
@@ -333,16 +278,14 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
             const int gy = iy0 + pr, gx = ix0 + pc;
             const bool ok = c < 3 && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
             pok |= ok ? (1u << u) : 0u;
-            pv_[u] = RFX_STEM7_DBG == 2 ? (float)u : inn[ok ? (size_t)c * HW + (size_t)gy * a.W + gx : 0];
+            pv_[u] = inn[ok ? (size_t)c * HW + (size_t)gy * a.W + gx : 0];
             pc += 256 % PCW; pr += 256 / PCW;
             if (pc >= PCW) { pc -= PCW; ++pr; }
             if (pr >= PR) { pr -= PR; ++c; }
         }
     }
-#endif
     float af[KKS];
-    // folded-BN vectors of every channel group in LDS (round 6: 32 registers less across the MFMA loop -- with the channel-group
-    // loop the kernel sat at the 256-register cap and spilled 112)
+    // folded-BN vectors in LDS (round 6: 32 registers less across the MFMA loop)
     __shared__ float s_bn[2][128];
     for (int c = t; c < a.Cout && c < 128; c += 256) {
         s_bn[0][c] = a.scale ? a.scale[c] : 1.0f;
@@ -350,34 +293,11 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
     }
     auto load_weights = [&](int m0) {
         const float* wl = a.wT;
-        asm volatile("" : "+s"(wl) :: "memory");     // opaque per call: the loads of the NEXT channel group must not be hoisted into this one
+        asm volatile("" : "+s"(wl) :: "memory");     // opaque base pointer: part of the code the kernel was measured with
 #pragma unroll
-        for (int kk = 0; kk < KKS; ++kk) af[kk] = RFX_STEM7_DBG == 4 ? (float)(kk + lcol) : wl[(size_t)(2 * kk + lrow) * a.Mpad + m0 + lcol];
+        for (int kk = 0; kk < KKS; ++kk) af[kk] = wl[(size_t)(2 * kk + lrow) * a.Mpad + m0 + lcol];
     };
-    if (!RFX_STEM7_CGLOOP) load_weights(cg_first * MCH);          // in flight while the patch goes to LDS
-#if RFX_STEM7_ROWSTAGE
-    {
-        float* pflat = &P[0][0][0];
-#pragma unroll
-        for (int j = 0; j < NROW; ++j) {
-            const int row = wave_u + 4 * j;
-            if (row < 3 * PR) {                                // wave-uniform
-                const bool rok = (unsigned)(iy0 + row - (row / PR) * PR) < (unsigned)a.H;
-                pflat[row * PST + lc0] = (rok && cok0) ? pv0[j] : 0.0f;
-            }
-        }
-        if (has1) {                                            // ONE exec-mask region for the few lanes that own a second column
-#pragma unroll
-            for (int j = 0; j < NROW; ++j) {
-                const int row = wave_u + 4 * j;
-                if (row < 3 * PR) {
-                    const bool rok = (unsigned)(iy0 + row - (row / PR) * PR) < (unsigned)a.H;
-                    pflat[row * PST + lc1] = (rok && cok1) ? pv1[j] : 0.0f;
-                }
-            }
-        }
-    }
-#else
+    load_weights(cg_first * MCH);          // in flight while the patch goes to LDS
     {
         int c = c_0, pr = pr_0, pc = pc_0;
 #pragma unroll
@@ -388,27 +308,18 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
             if (pr >= PR) { pr -= PR; ++c; }
         }
     }
-#endif
     RFX_STAMP7(1);
     __syncthreads();
     RFX_STAMP7(2);
 
-    // One channel group (32 channels) from the staged patch: MFMA phase -> C tile -> pooling -> global.  A generic lambda inlined
-    // once per group (two groups for the 64-channel stem) rather than a run-time loop: as a loop the three sub-tile passes stay
-    // rolled, the scheduler hoists their 74 operand reads on top of the 74 weight registers and the kernel spills ~100 registers.
-    auto channel_group = [&](const int cg, const bool first) {
+    // The channel group's work stays a lambda called from a one-trip loop: that is the form the kernel was tuned and measured in.
+    // Written straight into the body the compiler knows the range of the thread index in the pooling pass and picks other
+    // instructions for its index arithmetic (16-bit multiplies, one more SGPR spill); a change for whoever re-measures the kernel.
+    auto channel_group = [&](const int cg) {
     const int m0 = cg * MCH;
     const float* pf = &P[0][0][0];
-    if (RFX_STEM7_CGLOOP) {
-        if (!first) __syncthreads();                           // everyone is done pooling from C
-        load_weights(m0);
-        asm volatile("" : "+v"(pf));                           // the patch is invariant across groups: keep its reads in THIS group
-    }
     // ---- conv on the MFMA, BN + ReLU -> LDS
-#if RFX_STEM7_UNROLL
-#pragma unroll
-#endif
-    for (int s = wave; s < NSUB && RFX_STEM7_DBG != 3; s += 4) {
+    for (int s = wave; s < NSUB; s += 4) {
         const bool pv = s < CR || lcol < CR;
         const int py = s < CR ? s : (lcol < CR ? lcol : 0), px = s < CR ? lcol : CC - 1;
         const int pbase = 2 * py * PST + px;
@@ -418,7 +329,7 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
 #pragma unroll
         for (int kk = 0; kk < KKS; ++kk) {
             const int off = lrow ? koff(2 * kk + 1) : koff(2 * kk);
-            float b = RFX_STEM7_DBG == 5 ? af[(kk + 1) % KKS] : pf[pbase + off];      // 5: no LDS operand reads
+            float b = pf[pbase + off];
             if (kk == KKS - 1) b = lrow ? 0.0f : b;   // k = 147: padded tap
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], b, acc, 0, 0, 0);
         }
@@ -438,7 +349,7 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
 
     // ---- MaxPool2d(3, stride 2, pad 1): -inf padding = positions outside the conv map are skipped; the values are ReLU
     // outputs, so the unsigned-integer max is the NaN-propagating float max and 0 its identity (see umaxf above)
-    for (int o = t; o < MCH * TH * TW && RFX_STEM7_DBG != 1; o += 256) {
+    for (int o = t; o < MCH * TH * TW; o += 256) {
         const int owl = o % TW, ohl = (o / TW) % TH, ch = o / (TW * TH);
         const int oh = oh0 + ohl, ow = ow0 + owl;
         if (oh >= a.Hp || ow >= a.Wp) continue;
@@ -457,14 +368,9 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
         a.out[(((size_t)n * a.Cout + m0 + ch) * a.Hp + oh) * a.Wp + ow] = m;
     }
     RFX_STAMP7(5);
-    };   // channel_group
-    if (RFX_STEM7_CGLOOP && a.chGroups == 2) {
-        channel_group(0, true);
-        channel_group(1, false);
-    } else {
+    };
 #pragma unroll 1
-        for (int cg = cg_first; cg < cg_last; ++cg) channel_group(cg, cg == cg_first);
-    }
+    for (int cg = cg_first; cg < cg_first + 1; ++cg) channel_group(cg);
 }
 
 __global__ __launch_bounds__(256, 2) void stem7_conv_maxpool_kernel(Stem7Args a) {
@@ -511,7 +417,7 @@ extern "C" int rfx_stem_conv7x7_maxpool_f32(const float* in, const float* wT, co
     a.Hc = (H + 6 - 7) / 2 + 1; a.Wc = (W + 6 - 7) / 2 + 1;
     a.Hp = (a.Hc + 2 - 3) / 2 + 1; a.Wp = (a.Wc + 2 - 3) / 2 + 1;
     a.tilesH = (a.Hp + r50::TH - 1) / r50::TH; a.tilesW = (a.Wp + r50::TW - 1) / r50::TW; a.chGroups = Cout / r50::MCH;
-    const long long nwg = (long long)N * a.tilesH * a.tilesW * (RFX_STEM7_CGLOOP ? 1 : a.chGroups);
+    const long long nwg = (long long)N * a.tilesH * a.tilesW * a.chGroups;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();

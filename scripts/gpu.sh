@@ -32,13 +32,11 @@ for step in "$@"; do
                 timeout 1200 python tests/run_parity_sweep.py ev ${EV_N:-160} 2>&1 | tail -1 | cut -c1-1200; cp gpurun_out/parity_sweep_ev_${EV_N:-160}.json $OUT/parity_sweep_ev_${EV_N:-160}pairs.json
                 timeout 900 python oracle/parity_sweep.py --config qs --stability --threads 8 --budget 500 --seeds $(seq 0 $((${QS_N:-128}-1))) --records $OUT/oracle_vs_oracle_qs_${QS_N:-128}pairs.json 2>&1 | tail -1 | cut -c1-900
                 timeout 1200 python oracle/parity_sweep.py --config ev --stability --threads 8 --budget 800 --seeds $(seq 0 $((${EV_N:-160}-1))) --records $OUT/oracle_vs_oracle_ev_${EV_N:-160}pairs.json 2>&1 | tail -1 | cut -c1-900 ;;
-    kernels_ab) # round 5 kernel A/B on ONE box: fused tails (chunked + interleaved epilogue vs the burst form vs round 4's chains), the
+    kernels_ab) # round 5 kernel A/B on ONE box: fused tails, the
                 # implicit-GEMM kernel with the k-major A image vs the transposed one
                 T="tail64_120x160 tail128_60x80 tail64_240x320 tail64_100x132 tail128_50x66"
                 G="ds_256_512_s2_120x160 s2_128_128_120x160 head49_512_60x80"
                 timeout 300 python scripts/ubench/conv_bench.py --shapes $T $G pw256_1024_30x40_res fe64_240x320 --out $OUT/conv_ab_r5.json 2>&1 | tail -14
-                RFX_LIB=$PWD/ransac-flow_amd/librfx_noint.so timeout 300 python scripts/ubench/conv_bench.py --shapes $T --out $OUT/conv_ab_burst_epilogue.json 2>&1 | tail -6
-                RFX_C3_TAIL_CHUNK=0 RFX_LIB=$PWD/ransac-flow_amd/librfx_noint.so timeout 300 python scripts/ubench/conv_bench.py --shapes $T --out $OUT/conv_ab_r4_tails.json 2>&1 | tail -6
                 RFX_LIB=$PWD/ransac-flow_amd/librfx_oldconv.so timeout 300 python scripts/ubench/conv_bench.py --shapes $G --out $OUT/conv_ab_transposed_A.json 2>&1 | tail -4 ;;
     sweeps_more) # further seeds for the flip statistics (qs 128..383, ev 160..319): device vs reference, then reference vs reference
                 timeout 1200 python tests/run_parity_sweep.py qs 256 128 2>&1 | tail -1 | cut -c1-1200; cp gpurun_out/parity_sweep_qs_256_from128.json $OUT/parity_sweep_qs_seeds128_383.json

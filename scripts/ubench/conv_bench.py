@@ -5,7 +5,6 @@ fraction of the 157.3 TFLOP/s fp32 MFMA peak, and a checksum of the output (vari
 bit-identical are compared through it).
 
     python scripts/ubench/conv_bench.py [--shapes name ...] [--iters 20] [--out file.json]
-    RFX_LIB=ransac-flow_amd/librfx_c3dbg1.so python scripts/ubench/conv_bench.py     # experiments (make c3dbg1)
 """
 import argparse
 import json

@@ -21,7 +21,7 @@ from rfx import ops  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[64, 128])
-    ap.add_argument("--variants", type=int, nargs="+", default=[3, 1, 2, 4, 5, 6, 21, 22])
+    ap.add_argument("--variants", type=int, nargs="+", default=[3, 1, 2, 4, 5, 6])
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--shape", type=int, nargs=3, default=[256, 60, 80])
     ap.add_argument("--sets", type=int, default=3)

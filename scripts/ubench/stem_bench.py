@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Micro-benchmark of the two fused stem kernels on the config-3 shapes (64 images per pyramid level), back-to-back launches between
-one HIP event pair; checks every library variant (RFX_LIB=...) bit for bit against the un-fused convolution + pooling ops.
+one HIP event pair; checks the library bit for bit against the un-fused convolution + pooling ops.
     python scripts/ubench/stem_bench.py [--n 64] [--out gpurun_out/r06/stem_bench.json]"""
 import argparse
 import json
