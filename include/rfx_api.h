@@ -41,9 +41,10 @@ const char* rfx_version(void);
 /* ABI revision of this header: bumped whenever an entry point changes its signature or its operand layout (round 2:
  * rfx_compose_flow_f32 gained Hc/Wc, 3x3/s1/p1 geometries moved to rfx_conv3x3_f32's packed weights; round 3: multi-homography
  * round kernels, two-direction correlation, grouped launches; round 4: rfx_draw_samples_i64 keyed by pair id; 11: the ragged-batch
- * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes).  A binding
+ * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes; 12: the ragged forms of the
+ * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 11
+#define RFX_ABI_VERSION 12
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -521,6 +522,41 @@ int rfx_multih_accept_f32(const float* match, float* mask, const float* bg, cons
                           const float* match12Down8, const float* match21Down8, int h8, int w8, const float* flowD2, int hd2,
                           int wd2, float* rec, long long rec_stride, int max_h, int off_H, int off_flow, int off_match,
                           int off_d2, void* stream);
+
+/* (ABI 12) The two round kernels above for ACTIVE PAIRS OF DIFFERENT SIZES (a ragged batch; the loop of
+ * evaluation/evalHpatch/evaluation.py:184-243 runs per pair, so a dataset of mixed image sizes is the normal case).  Per-pair state
+ * is packed: pair b's explained-region mask (and background map) are h_b * w_b floats at element offset moff[b] (batch int64) of
+ * ONE float buffer, and row b of the device table geom (batch,6) int32 holds its geometry: h, w (target image), rt, ct (target
+ * feature map), h8, w8 (the /8 maps of the fine stage).  Each kernel runs the dense kernel's body on the pair's own values, so a
+ * pair's outputs are bit for bit those of the dense entry point called on that pair alone.
+ *
+ * rfx_filter_matches_ragged_f32 (evaluation/evalHpatch/coarseAlignFeatMatch.py:156-170 per pair): idx1/idx2 (batch,cap) + count
+ * as written by rfx_mutual_nn_ragged_f32; pair b's cell-coordinate tables are the slices xa/ya + offA[b], xb/yb + offB[b] of packed
+ * tables (offA, offB: batch int64, as for rfx_gather_matches_ragged_f32); the resize scales are h_b / rt_b and w_b / ct_b rounded to
+ * float32 exactly as rfx_filter_matches_f32 forms them.  Outputs as the dense kernel's: match1/match2 (n_active,cap,3), n_out
+ * (n_active), kept (n_active,cap) or NULL -- what rfx_ransac_h4_batched and rfx_draw_samples_i64 consume. */
+int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* count, int cap, const int32_t* active,
+                                  int n_active, const float* mask, const float* bg, const long long* moff, const int32_t* geom,
+                                  const float* xa, const float* ya, const long long* offA, const float* xb, const float* yb,
+                                  const long long* offB, float* match1, float* match2, int32_t* n_out, int32_t* kept,
+                                  void* stream);
+
+/* rfx_multih_accept_ragged_f32 (evalHpatch/evaluation.py:225,238-239; mode 1: evalKITTI/evaluation.py:322,332-333): the accept rule,
+ * mask update and record store of rfx_multih_accept_f32.  The round's per-pair inputs are packed PER ACTIVE PAIR (offsets per k, the
+ * order the fine stage of the round produced them in): match of pair k = h_b * w_b floats at match_off[k] (n_active int64);
+ * flowDown8 of pair k at 2 * off8[k], match12Down8 / match21Down8 at off8[k] (n_active int64; required when one of the three
+ * is given).  mask / bg are packed per PAIR (moff[b]).  gain: pair k's own HW is cut into the same 64 slices of ceil(HW / 64)
+ * pixels, summed in the same order in double, as the dense kernel does for that pair.  max_hw = the largest h * w among the active
+ * pairs (sizes the mask-update grid only).  Records: one row of rec_stride floats per pair, header and H slots as in the dense
+ * layout (off_H, off_flow), flowDown8 slots of 2 h8_b w8_b floats from off_flow, matchDown8 slots from off_flow + 2 h8_b w8_b max_h
+ * (rfx.ops.MultiHRecordsRagged); there is no flowD2 part.  ws: rfx_multih_accept_ragged_ws_bytes(n_active). */
+size_t rfx_multih_accept_ragged_ws_bytes(int n_active);
+int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off, float* mask, const float* bg,
+                                 const long long* moff, const int32_t* geom, const int32_t* active, int n_active, long long max_hw,
+                                 const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH, double th, int mode,
+                                 int32_t* accept, float* gain, void* ws, const float* bestH, const float* flowDown8,
+                                 const float* match12Down8, const float* match21Down8, const long long* off8, float* rec,
+                                 long long rec_stride, int max_h, int off_H, int off_flow, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * rfx_conv1x1_split_f32 (ABI 10): the 1x1 / stride 1 / pad 0 convolution of rfx_conv2d_f32 (the Bottleneck conv1 / conv3 layers,

@@ -91,46 +91,7 @@ __global__ __launch_bounds__(1024) void filter_matches_kernel(
     idx1 += (size_t)b * cap; idx2 += (size_t)b * cap;
     m1 += (size_t)k * cap * 3; m2 += (size_t)k * cap * 3;
     if (kept) kept += (size_t)k * cap;
-    __shared__ int wsum[16];
-    __shared__ int base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base = 0;
-    __syncthreads();
-    for (int s = 0; s < n; s += 1024) {
-        const int i = s + t;
-        bool keep = false;
-        int64_t a = 0, cell = 0;
-        if (i < n) {
-            a = idx1[i]; cell = idx2[i];
-            const int r = (int)(cell / ct), c = (int)(cell - (int64_t)r * ct);
-            keep = keep_cell(mask, bg, h, w, sh, sw, r, c);
-        }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const int cq = wsum[q]; if (q < wave) woff += cq; tot += cq; }
-        const int b0 = base;
-        if (keep) {
-            const size_t o = (size_t)(b0 + woff + before) * 3;
-            m1[o] = xa[a]; m1[o + 1] = ya[a]; m1[o + 2] = 1.0f;
-            m2[o] = xb[cell]; m2[o + 1] = yb[cell]; m2[o + 2] = 1.0f;
-            if (kept) kept[b0 + woff + before] = i;
-        }
-        __syncthreads();
-        if (t == 0) base = b0 + tot;
-        __syncthreads();
-    }
-    const int ntot = base;
-    for (int i = ntot + t; i < cap; i += 1024) {
-        const size_t o = (size_t)i * 3;
-        m1[o] = m1[o + 1] = m1[o + 2] = 0.0f;
-        m2[o] = m2[o + 1] = m2[o + 2] = 0.0f;
-        if (kept) kept[i] = -1;
-    }
-    if (t == 0) n_out[k] = ntot;
+#include "multih_filter_body.inc"
 }
 
 // The whole keep map of the active pairs: what CoarseAlign.getCoarse of variants A / C multiplies the target features with before
@@ -162,24 +123,9 @@ __global__ __launch_bounds__(256) void accept_partial_kernel(const float* __rest
                                                              const float* __restrict__ bg, const int32_t* __restrict__ active,
                                                              long long HW, int mode, double* __restrict__ part) {
     const int k = blockIdx.y, b = active ? active[k] : k;
-    match += (size_t)k * HW; mask += (size_t)b * HW;
-    if (bg) bg += (size_t)b * HW;
-    const long long per = (HW + NPART - 1) / NPART;
-    const long long p0 = blockIdx.x * per, p1 = p0 + per < HW ? p0 + per : HW;
-    double s = 0.0;
-    for (long long p = p0 + threadIdx.x; p < p1; p += 256) {
-        const float nf = __fsub_rn(1.0f, fg_px(mask, bg, (size_t)p));
-        const float m = match[p];
-        s += (double)__fmul_rn(mode ? (m > 0.9999f ? 1.0f : 0.0f) : m, nf);
-    }
-    __shared__ double red[256];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(size_t)k * NPART + blockIdx.x] = red[0];
+#define MH_MATCH_OFF ((size_t)k * HW)
+#define MH_MASK_OFF ((size_t)b * HW)
+#include "multih_accept_partial_body.inc"
 }
 
 __global__ __launch_bounds__(256) void accept_update_kernel(const float* __restrict__ match, float* __restrict__ mask,
@@ -189,26 +135,9 @@ __global__ __launch_bounds__(256) void accept_update_kernel(const float* __restr
                                                             const int32_t* __restrict__ nbH, double th,
                                                             int32_t* __restrict__ accept, float* __restrict__ gain) {
     const int k = blockIdx.y, b = active ? active[k] : k;
-    __shared__ int s_acc;
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int q = 0; q < NPART; ++q) s += part[(size_t)k * NPART + q];     // fixed order: every block gets the same sum
-        const float g = (float)(s / (double)HW);
-        const bool ok = n_match[k] >= 4 && res[k * 4] == 0 && ((double)g > th || nbH[b] == 0);
-        s_acc = ok ? 1 : 0;
-        if (blockIdx.x == 0) { accept[k] = ok ? 1 : 0; gain[k] = g; }
-    }
-    __syncthreads();
-    if (!s_acc) return;
-    match += (size_t)k * HW; mask += (size_t)b * HW;
-    if (bg) bg += (size_t)b * HW;
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
-        const float mk = mask[p];
-        const float bgv = bg ? bg[p] : 1.0f;
-        const float fg = __fadd_rn(mk, __fsub_rn(1.0f, bgv)) > 0.5f ? 1.0f : 0.0f;
-        const float v = __fadd_rn(mk, __fmul_rn(match[p], __fsub_rn(1.0f, fg)));
-        mask[p] = (mode ? v > 0.9999f : v >= 1.0f) ? 1.0f : 0.0f;
-    }
+#include "multih_accept_update_body.inc"
+#undef MH_MATCH_OFF
+#undef MH_MASK_OFF
 }
 
 // The per-pair result record (what evaluation/evalHpatch/evaluation.py:254-260 saves per pair): slot nbH[b] of
@@ -220,32 +149,92 @@ __global__ __launch_bounds__(1024) void accept_store_kernel(const int32_t* __res
                                                             int hwd2, float* __restrict__ rec, long long rec_stride, int max_h,
                                                             int off_H, int off_flow, int off_match, int off_d2) {
     const int k = blockIdx.x, b = active ? active[k] : k;
-    if (!accept[k]) return;
-    const int slot = nbH[b];
-    const int t = threadIdx.x;
-    if (rec && slot < max_h) {
-        float* r = rec + (size_t)b * rec_stride;
-        if (t < 9) r[off_H + slot * 9 + t] = bestH[k * 9 + t];
-        if (flow8)
-            for (int i = t; i < 2 * hw8; i += 1024) r[off_flow + (size_t)slot * 2 * hw8 + i] = flow8[(size_t)k * 2 * hw8 + i];
-        if (m12 && m21)
-            for (int i = t; i < hw8; i += 1024) {
-                r[off_match + (size_t)slot * 2 * hw8 + i] = m12[(size_t)k * hw8 + i];
-                r[off_match + (size_t)slot * 2 * hw8 + hw8 + i] = m21[(size_t)k * hw8 + i];
-            }
-        if (flowd2)
-            for (int i = t; i < 2 * hwd2; i += 1024) r[off_d2 + (size_t)slot * 2 * hwd2 + i] = flowd2[(size_t)k * 2 * hwd2 + i];
-    }
-    __syncthreads();
-    if (t == 0) {
-        nbH[b] = slot + 1;
-        // the record's nbH field never exceeds the slots it holds; a pair that accepted more (only the unbounded KITTI loop
-        // can) is flagged with status 3, and the device counter nbH[] keeps the true number
-        if (rec) {
-            rec[(size_t)b * rec_stride] = (float)(slot + 1 < max_h ? slot + 1 : max_h);
-            rec[(size_t)b * rec_stride + 1] = slot + 1 > max_h ? 3.0f : 0.0f;
-        }
-    }
+#define MH_F8_OFF ((size_t)k * 2 * hw8)
+#define MH_M8_OFF ((size_t)k * hw8)
+#define MH_D2_OFF ((size_t)k * 2 * hwd2)
+#include "multih_accept_store_body.inc"
+#undef MH_F8_OFF
+#undef MH_M8_OFF
+#undef MH_D2_OFF
+}
+
+// ---- ragged batches: the active pairs of one launch differ in size ----------------------------------------------------------------
+// Pair b's explained-region mask (and background map) lives at element offset moff[b] of ONE packed float buffer; its geometry is row b
+// of a device table geom (batch, RG) int32 = h, w, rt, ct, h8, w8.  Every kernel below sets the per-pair values the dense kernel takes
+// as launch arguments and then runs the dense kernel's body text (the multih_*_body.inc files): same ballots, same partition of the
+// pair's own HW pixels into NPART partial sums, same order of the double additions.
+constexpr int RG = 6;
+
+__global__ __launch_bounds__(1024) void filter_matches_ragged_kernel(
+    const int64_t* __restrict__ idx1, const int64_t* __restrict__ idx2, const int32_t* __restrict__ count, int cap,
+    const int32_t* __restrict__ active, const float* __restrict__ mask, const float* __restrict__ bg,
+    const long long* __restrict__ moff, const int32_t* __restrict__ geom, const float* __restrict__ xa,
+    const float* __restrict__ ya, const long long* __restrict__ offA, const float* __restrict__ xb, const float* __restrict__ yb,
+    const long long* __restrict__ offB, float* __restrict__ m1, float* __restrict__ m2, int32_t* __restrict__ n_out,
+    int32_t* __restrict__ kept) {
+    const int k = blockIdx.x;
+    const int b = active ? active[k] : k;
+    const int h = geom[b * RG], w = geom[b * RG + 1], rt = geom[b * RG + 2], ct = geom[b * RG + 3];
+    const bool sane = h > 0 && w > 0 && rt > 0 && ct > 0;            // a pair with a broken table row keeps no match
+    const int n = sane ? (count[b] < cap ? count[b] : cap) : 0;
+    // the dense entry point's host-side (float)h / (float)rt: the double quotient of two 24-bit integers rounds to the same float
+    const float sh = (float)((double)h / (double)(sane ? rt : 1)), sw = (float)((double)w / (double)(sane ? ct : 1));
+    mask += moff[b];
+    if (bg) bg += moff[b];
+    xa += offA[b]; ya += offA[b]; xb += offB[b]; yb += offB[b];
+    idx1 += (size_t)b * cap; idx2 += (size_t)b * cap;
+    m1 += (size_t)k * cap * 3; m2 += (size_t)k * cap * 3;
+    if (kept) kept += (size_t)k * cap;
+#include "multih_filter_body.inc"
+}
+
+// match: packed per ACTIVE pair, pair k of the round at element offset match_off[k]; mask / bg: pair b at moff[b]
+#define MH_MATCH_OFF ((size_t)match_off[k])
+#define MH_MASK_OFF ((size_t)moff[b])
+__global__ __launch_bounds__(256) void accept_partial_ragged_kernel(const float* __restrict__ match,
+                                                                    const long long* __restrict__ match_off,
+                                                                    const float* __restrict__ mask, const float* __restrict__ bg,
+                                                                    const long long* __restrict__ moff, const int32_t* __restrict__ geom,
+                                                                    const int32_t* __restrict__ active, int mode,
+                                                                    double* __restrict__ part) {
+    const int k = blockIdx.y, b = active ? active[k] : k;
+    const long long HW = (long long)geom[b * RG] * geom[b * RG + 1];
+#include "multih_accept_partial_body.inc"
+}
+
+__global__ __launch_bounds__(256) void accept_update_ragged_kernel(const float* __restrict__ match, const long long* __restrict__ match_off,
+                                                                   float* __restrict__ mask, const float* __restrict__ bg,
+                                                                   const long long* __restrict__ moff, const int32_t* __restrict__ geom,
+                                                                   const int32_t* __restrict__ active, int mode,
+                                                                   const double* __restrict__ part, const int32_t* __restrict__ res,
+                                                                   const int32_t* __restrict__ n_match, const int32_t* __restrict__ nbH,
+                                                                   double th, int32_t* __restrict__ accept, float* __restrict__ gain) {
+    const int k = blockIdx.y, b = active ? active[k] : k;
+    const long long HW = (long long)geom[b * RG] * geom[b * RG + 1];
+#include "multih_accept_update_body.inc"
+}
+#undef MH_MATCH_OFF
+#undef MH_MASK_OFF
+
+// The record row of pair b is laid out with the pair's OWN h8 * w8 (ops.MultiHRecordsRagged); the /8 maps of the round are packed per
+// active pair: flowDown8 of pair k at 2 * off8[k], match12Down8 / match21Down8 at off8[k].
+__global__ __launch_bounds__(1024) void accept_store_ragged_kernel(const int32_t* __restrict__ active, const int32_t* __restrict__ accept,
+                                                                   int32_t* __restrict__ nbH, const float* __restrict__ bestH,
+                                                                   const float* __restrict__ flow8, const float* __restrict__ m12,
+                                                                   const float* __restrict__ m21, const long long* __restrict__ off8,
+                                                                   const int32_t* __restrict__ geom, float* __restrict__ rec,
+                                                                   long long rec_stride, int max_h, int off_H, int off_flow) {
+    const int k = blockIdx.x, b = active ? active[k] : k;
+    const int hw8 = geom[b * RG + 4] * geom[b * RG + 5], hwd2 = 0;
+    const int off_match = off_flow + 2 * hw8 * max_h, off_d2 = 0;
+    const float* flowd2 = nullptr;
+#define MH_F8_OFF ((size_t)2 * off8[k])
+#define MH_M8_OFF ((size_t)off8[k])
+#define MH_D2_OFF ((size_t)0)
+#include "multih_accept_store_body.inc"
+#undef MH_F8_OFF
+#undef MH_M8_OFF
+#undef MH_D2_OFF
 }
 
 }  // namespace
@@ -317,6 +306,52 @@ extern "C" int rfx_multih_accept_f32(const float* match, float* mask, const floa
     RFX_LAUNCH_CHECK();
     hipLaunchKernelGGL(accept_store_kernel, dim3(n_active), dim3(1024), 0, st, active, accept, nbH, bestH, flowDown8, match12Down8,
                        match21Down8, h8 * w8, flowD2, hd2 * wd2, rec, rec_stride, max_h, off_H, off_flow, off_match, off_d2);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+extern "C" int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, const int32_t* count, int cap,
+                                             const int32_t* active, int n_active, const float* mask, const float* bg,
+                                             const long long* moff, const int32_t* geom, const float* xa, const float* ya,
+                                             const long long* offA, const float* xb, const float* yb, const long long* offB,
+                                             float* match1, float* match2, int32_t* n_out, int32_t* kept, void* stream) {
+    if (!idx1 || !idx2 || !count || !mask || !moff || !geom || !xa || !ya || !offA || !xb || !yb || !offB || !match1 || !match2 ||
+        !n_out || cap <= 0 || n_active <= 0)
+        return RFX_E_ARG;
+    hipLaunchKernelGGL(filter_matches_ragged_kernel, dim3(n_active), dim3(1024), 0, rfx_stream(stream), idx1, idx2, count, cap, active,
+                       mask, bg, moff, geom, xa, ya, offA, xb, yb, offB, match1, match2, n_out, kept);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+extern "C" size_t rfx_multih_accept_ragged_ws_bytes(int n_active) { return rfx_multih_accept_ws_bytes(n_active); }
+
+extern "C" int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off, float* mask, const float* bg,
+                                            const long long* moff, const int32_t* geom, const int32_t* active, int n_active,
+                                            long long max_hw, const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH,
+                                            double th, int mode, int32_t* accept, float* gain, void* ws, const float* bestH,
+                                            const float* flowDown8, const float* match12Down8, const float* match21Down8,
+                                            const long long* off8, float* rec, long long rec_stride, int max_h, int off_H,
+                                            int off_flow, void* stream) {
+    if (!match || !match_off || !mask || !moff || !geom || !ransac_result || !n_match || !nbH || !accept || !gain || !ws ||
+        n_active <= 0 || max_hw <= 0 || (mode != 0 && mode != 1))
+        return RFX_E_ARG;
+    if (rec && (!bestH || max_h <= 0 || rec_stride <= 0)) return RFX_E_ARG;
+    if ((flowDown8 || match12Down8 || match21Down8) && !off8) return RFX_E_ARG;
+    if (n_active > 65535) return RFX_E_LIMIT;
+    hipStream_t st = rfx_stream(stream);
+    double* part = static_cast<double*>(ws);
+    hipLaunchKernelGGL(accept_partial_ragged_kernel, dim3(NPART, n_active), dim3(256), 0, st, match, match_off, mask, bg, moff, geom,
+                       active, mode, part);
+    RFX_LAUNCH_CHECK();
+    // the update's grid follows the LARGEST pair (max_hw = its h * w): a smaller pair's surplus workgroups find no pixel and leave
+    long long g = (max_hw + 255) / 256;
+    if (g > 256) g = 256;
+    hipLaunchKernelGGL(accept_update_ragged_kernel, dim3((unsigned)g, n_active), dim3(256), 0, st, match, match_off, mask, bg, moff,
+                       geom, active, mode, part, ransac_result, n_match, nbH, th, accept, gain);
+    RFX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(accept_store_ragged_kernel, dim3(n_active), dim3(1024), 0, st, active, accept, nbH, bestH, flowDown8,
+                       match12Down8, match21Down8, off8, geom, rec, rec_stride, max_h, off_H, off_flow);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

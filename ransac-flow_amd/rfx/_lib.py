@@ -91,9 +91,13 @@ SIGNATURES = {
     "rfx_multih_accept_ws_bytes": (c_size_t, [c_int]),
     "rfx_multih_accept_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3 + [c_double, c_int] + [c_void_p] * 7
                               + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong] + [c_int] * 5 + [c_void_p]),
+    "rfx_filter_matches_ragged_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 15),
+    "rfx_multih_accept_ragged_ws_bytes": (c_size_t, [c_int]),
+    "rfx_multih_accept_ragged_f32": (c_int, [c_void_p] * 7 + [c_int, c_longlong] + [c_void_p] * 3 + [c_double, c_int]
+                                     + [c_void_p] * 9 + [c_longlong] + [c_int] * 3 + [c_void_p]),
 }
 
-ABI_VERSION = 11    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 12    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

@@ -1193,6 +1193,36 @@ def filter_matches(idx1, idx2, count, active, mask, bg, rt, ct, xa, ya, xb, yb, 
     return (m1, m2, n, kept) if want_kept else (m1, m2, n)
 
 
+def filter_matches_ragged(idx1, idx2, count, active, mask, bg, moff, geom, xa, ya, offA, xb, yb, offB, want_kept=False):
+    """filter_matches for active pairs of DIFFERENT sizes (rfx_filter_matches_ragged_f32, one launch): ``mask`` / ``bg`` are packed
+    1-D float32 buffers, pair b's h*w values at element ``moff[b]`` ((B,) int64); ``geom`` (B,6) int32 = h, w, rt, ct, h8, w8 per
+    pair; the cell-coordinate tables are packed pair after pair (offA / offB (B,) int64, as for gather_matches_ragged); idx1 / idx2
+    (B,cap) + count as mutual_nn_ragged returns them.  Per pair the result is filter_matches' on that pair's own tensors:
+    -> match1, match2 (a,cap,3) float32, n (a,) int32[, kept (a,cap) int32]."""
+    idx1, idx2 = _dev(idx1, "idx1", torch.int64), _dev(idx2, "idx2", torch.int64)
+    count = _dev(count, "count", torch.int32)
+    mask = _dev(mask, "mask")
+    bg = _dev(bg, "bg") if bg is not None else None
+    act = _dev(active, "active", torch.int32) if active is not None else None
+    moff, offA, offB = _dev(moff, "moff", torch.int64), _dev(offA, "offA", torch.int64), _dev(offB, "offB", torch.int64)
+    geom = _dev(geom, "geom", torch.int32)
+    B, cap = idx1.shape
+    if mask.dim() != 1 or (bg is not None and bg.shape != mask.shape):
+        raise ValueError("mask / bg of a ragged batch are packed 1-D buffers of one size")
+    if geom.shape != (B, 6) or moff.numel() != B or offA.numel() != B or offB.numel() != B or count.numel() != B:
+        raise ValueError("geom must be (B,6) and moff / offA / offB / count hold one entry per pair")
+    a = B if act is None else act.shape[0]
+    dev = idx1.device
+    m1 = torch.empty((a, cap, 3), dtype=torch.float32, device=dev)
+    m2 = torch.empty((a, cap, 3), dtype=torch.float32, device=dev)
+    n = torch.empty(a, dtype=torch.int32, device=dev)
+    kept = torch.empty((a, cap), dtype=torch.int32, device=dev) if want_kept else None
+    _call("rfx_filter_matches_ragged_f32", _one_device(idx1, idx2, count, act, mask, bg, moff, geom, xa, ya, offA, xb, yb, offB),
+          _p(idx1), _p(idx2), _p(count), cap, _p(act), a, _p(mask), _p(bg), _p(moff), _p(geom), _p(_dev(xa, "xa")), _p(_dev(ya, "ya")),
+          _p(offA), _p(_dev(xb, "xb")), _p(_dev(yb, "yb")), _p(offB), _p(m1), _p(m2), _p(n), _p(kept))
+    return (m1, m2, n, kept) if want_kept else (m1, m2, n)
+
+
 def keep_mask(mask, bg, active, rt, ct, n=None, hw=None, device=None):
     """The (a, rt*ct) 0/1 keep map of variant A / C's getCoarse for the active pairs (rfx_keep_mask_f32): what the per-call
     mutual matching takes as its column mask.  ``mask`` (B,h,w) float32 or None (nothing explained yet: a zero mask is used when
@@ -1251,6 +1281,50 @@ class MultiHRecords:
                 r[:, self.off_match:self.off_match + n8 * m].view(B, m, 2, self.h8, self.w8), d2)
 
 
+    @staticmethod
+    def ragged(h8_list, w8_list, device, max_h=11):
+        """The records of a batch whose pairs differ in size: a MultiHRecordsRagged (the dense layout above is unchanged)."""
+        return MultiHRecordsRagged(h8_list, w8_list, device, max_h=max_h)
+
+
+class MultiHRecordsRagged:
+    """MultiHRecords for pairs of DIFFERENT sizes: still one fixed-width float32 row per pair (one all_gather moves a batch), the
+    width set by the batch's largest h8 * w8.  Row b: [0] nbH | [1] status (the dense codes) | [2] h8 | [3] w8 of the pair |
+    H (max_h,9) from off_H = 4 | flowDown8 (max_h,2,h8,w8) from off_flow | matchDown8 (max_h,2,h8,w8) from off_flow + 2 h8 w8 max_h,
+    both laid out with the pair's OWN h8 * w8 (a row of one pair = the dense row of MultiHRecords(1, h8, w8)); the rest of the row
+    is zero.  A pure function of the size lists.  Filled on the device by multih_accept_ragged."""
+
+    def __init__(self, h8_list, w8_list, device, max_h=11):
+        if len(h8_list) != len(w8_list) or not h8_list:
+            raise ValueError("one (h8, w8) per pair")
+        self.h8, self.w8 = [int(x) for x in h8_list], [int(x) for x in w8_list]
+        self.B, self.max_h = len(self.h8), max_h
+        r4 = lambda x: (x + 3) // 4 * 4
+        self.off_H = 4
+        self.off_flow = self.off_H + r4(9 * max_h)
+        self.off_match = [self.off_flow + 2 * a * b * max_h for a, b in zip(self.h8, self.w8)]
+        self.width = r4(max(o + 2 * a * b * max_h for o, a, b in zip(self.off_match, self.h8, self.w8)))
+        self.rec = torch.zeros((self.B, self.width), dtype=torch.float32, device=device)
+        self.rec[:, 1] = 1.0
+        self.rec[:, 2] = torch.tensor(self.h8, dtype=torch.float32).to(device)
+        self.rec[:, 3] = torch.tensor(self.w8, dtype=torch.float32).to(device)
+
+    def rows(self, lo, hi):
+        """The records of pairs [lo, hi) as a MultiHRecordsRagged of their own over the SAME storage (a lock-step group)."""
+        import copy
+        r = copy.copy(self)
+        r.B, r.rec = hi - lo, self.rec[lo:hi]
+        r.h8, r.w8, r.off_match = self.h8[lo:hi], self.w8[lo:hi], self.off_match[lo:hi]
+        return r
+
+    def views(self, b):
+        """Pair b's (nbH, status, H (max_h,3,3), flowDown8 (max_h,2,h8,w8), matchDown8 (max_h,2,h8,w8))."""
+        r, m, h8, w8 = self.rec[b], self.max_h, self.h8[b], self.w8[b]
+        n8 = 2 * h8 * w8
+        return (r[0], r[1], r[self.off_H:self.off_H + 9 * m].view(m, 3, 3), r[self.off_flow:self.off_flow + n8 * m].view(m, 2, h8, w8),
+                r[self.off_match[b]:self.off_match[b] + n8 * m].view(m, 2, h8, w8))
+
+
 def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode, bestH=None, flowDown8=None, match12Down8=None,
                   match21Down8=None, flowD2=None, records=None):
     """Accept rule + mask update + record store of one round (rfx_multih_accept_f32) -> (accept (a,) int32, gain (a,) f32),
@@ -1289,4 +1363,48 @@ def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode
           _p(m21), h8, w8, _p(fd2), hd2, wd2, _p(R.rec) if R is not None else ctypes.c_void_p(0), R.width if R is not None else 0,
           R.max_h if R is not None else 0, R.off_H if R is not None else 0, R.off_flow if R is not None else 0,
           R.off_match if R is not None else 0, R.off_d2 if R is not None else 0)
+    return accept, gain
+
+
+def multih_accept_ragged(match, match_off, mask, bg, moff, geom, active, ransac_result, n_match, nbH, th, mode, max_hw, bestH=None,
+                         flowDown8=None, match12Down8=None, match21Down8=None, off8=None, records=None):
+    """multih_accept for active pairs of DIFFERENT sizes (rfx_multih_accept_ragged_f32) -> (accept (a,) int32, gain (a,) f32).
+    ``mask`` / ``bg``: packed 1-D buffers, pair b at ``moff[b]``; ``geom`` (B,6) int32 (see filter_matches_ragged).  The round's
+    tensors are packed per ACTIVE pair: ``match`` 1-D, pair k's h*w values at ``match_off[k]``; ``flowDown8`` 1-D, pair k at
+    2 * off8[k]; ``match12Down8`` / ``match21Down8`` 1-D, pair k at off8[k] (match_off, off8: (a,) int64).  ``max_hw``: the largest
+    h * w among the active pairs.  ``records``: a MultiHRecordsRagged.  ``mask`` and ``nbH`` (B,) int32 are updated in place."""
+    for t, name in ((mask, "mask"), (nbH, "nbH")):          # updated IN PLACE: a silent .contiguous() copy would lose the update
+        if isinstance(t, torch.Tensor) and not t.is_contiguous():
+            raise ValueError("%s must be contiguous (updated in place)" % name)
+    match, mask = _dev(match, "match"), _dev(mask, "mask")
+    bg = _dev(bg, "bg") if bg is not None else None
+    act = _dev(active, "active", torch.int32) if active is not None else None
+    res, n_match, nbH = _dev(ransac_result, "ransac result", torch.int32), _dev(n_match, "n", torch.int32), _dev(nbH, "nbH", torch.int32)
+    match_off, moff, geom = _dev(match_off, "match_off", torch.int64), _dev(moff, "moff", torch.int64), _dev(geom, "geom", torch.int32)
+    a, B = match_off.numel(), moff.numel()
+    if mask.dim() != 1 or match.dim() != 1 or (bg is not None and bg.shape != mask.shape):
+        raise ValueError("match / mask / bg of a ragged batch are packed 1-D buffers")
+    if geom.shape != (B, 6) or nbH.numel() != B or res.shape != (a, 4) or n_match.numel() != a or (act is None and a != B) or \
+            (act is not None and act.numel() != a):
+        raise ValueError("geom (B,6), nbH (B,), ransac result (a,4), n / match_off / active (a,) expected")
+    dev = match.device
+    accept = torch.empty(a, dtype=torch.int32, device=dev)
+    gain = torch.empty(a, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(lib.rfx_multih_accept_ragged_ws_bytes(a), dtype=torch.uint8, device=dev)
+    f8 = m12 = m21 = o8 = None
+    if flowDown8 is not None:
+        f8, m12, m21 = _dev(flowDown8, "flowDown8"), _dev(match12Down8, "match12Down8"), _dev(match21Down8, "match21Down8")
+        o8 = _dev(off8, "off8", torch.int64)
+        if o8.numel() != a:
+            raise ValueError("off8 must hold one offset per active pair")
+    R = records
+    if R is not None and (not isinstance(R, MultiHRecordsRagged) or R.B != B):
+        raise ValueError("records of a ragged batch: a MultiHRecordsRagged with one row per pair")
+    bh = _dev(bestH, "bestH") if bestH is not None else None
+    _call("rfx_multih_accept_ragged_f32", _one_device(match, match_off, mask, bg, moff, geom, act, res, n_match, nbH, bh, f8, m12, m21, o8),
+          _p(match), _p(match_off), _p(mask), _p(bg), _p(moff), _p(geom), _p(act), a, int(max_hw), _p(res), _p(n_match), _p(nbH),
+          float(th), int(mode), _p(accept), _p(gain), _p(ws), _p(bh), _p(f8), _p(m12), _p(m21), _p(o8),
+          _p(R.rec) if R is not None else ctypes.c_void_p(0), R.width if R is not None else 0, R.max_h if R is not None else 0,
+          R.off_H if R is not None else 0, R.off_flow if R is not None else 0)
     return accept, gain

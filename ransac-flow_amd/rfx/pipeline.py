@@ -121,6 +121,22 @@ def ragged_plan(src_sizes, tgt_sizes, min_size, scales, mode="max"):
                 cap=max(min(a, b) for a, b in zip(nA, nB)), buckets=buckets, nS=nS, B=len(levels))
 
 
+def ragged_multih_tables(plan):
+    """The packed-mask tables of a ragged batch's multi-homography rounds, a pure function of the plan: pair b's explained-region mask
+    (and background map) are the h*w floats at element ``moff[b]`` of one buffer of ``total`` floats, pair after pair without gaps,
+    and ``geom[b]`` = (h, w, rt, ct, h8, w8): the resized target image (plan["levels"][b][nS]), its feature map
+    (plan["cells"][b][nS]) and the /8 maps of the fine stage.  What rfx_filter_matches_ragged_f32 / rfx_multih_accept_ragged_f32 read."""
+    nS = plan["nS"]
+    moff, geom, pos = [], [], 0
+    for b in range(plan["B"]):
+        h, w = plan["levels"][b][nS]
+        rt, ct = plan["cells"][b][nS]
+        moff.append(pos)
+        geom.append((h, w, rt, ct, h // 8, w // 8))
+        pos += h * w
+    return dict(moff=moff, geom=geom, total=pos)
+
+
 class AlignPipeline:
     def __init__(self, sds, nbScale=7, nbIter=1000, tolerance=0.05, minSize=640, scaleR=1.2, variant="A",
                  device="cuda", kernelSize=7, draw="device", seed=0, degenerate="lapack", score_chunk=None):
@@ -878,7 +894,13 @@ class AlignPipeline:
         per-pair Python lists (throughput drivers that only ship the records).  ``trace``: a list that receives one dict per
         round with the round's state (mask before the round, counts, H, PredFlowMask outputs, accept flags) -- the parity
         sweeps replay every round on the oracle from it.
+        A ragged prep (prepare_ragged / prepare_ragged_device: pairs of different sizes) takes the same rounds with packed masks
+        (_multi_h_batched_ragged): per pair the results are, bit for bit, the pair's alone; ``It_bg`` is then a list of per-pair
+        (h_b, w_b) tensors (None entries = all ones) and ``records`` an ops.MultiHRecordsRagged.
         Returns a list of dicts like multi_h() (H / flowDown8 / matchDown8 lists are views of per-round tensors)."""
+        if prep.get("ragged"):
+            return self._multi_h_batched_ragged(prep, maxCoarse, maskRegionTh, It_bg, feats, sample_fn, records, want_lists, trace,
+                                                pair_ids, draw_epoch, split)
         feats = feats or self.features(prep)
         dev = self.dev
         B = prep["B"]
@@ -1038,6 +1060,194 @@ class AlignPipeline:
                     # truncated pair is distinguishable from one that ended on the accept test)
                     st["records"].rec[b, 1] = 4.0
                 else:
+                    nxt.append(m)
+            active = nxt
+
+    # ---------------------------------------------------------------- multi-homography rounds of a ragged batch
+    def _multi_h_batched_ragged(self, prep, maxCoarse, maskRegionTh, It_bg, feats, sample_fn, records, want_lists, trace, pair_ids,
+                                draw_epoch, split):
+        """multi_h_batched for a ragged prep.  One grouped trunk pass (_features_ragged), one ragged mutual matching, then the
+        lock-step rounds of _multi_h_rounds_ragged under the dense driver's coroutine / stream machinery (_drive_rounds, ``split``).
+        The explained-region masks (and background maps) of all pairs live in ONE packed buffer (ragged_multih_tables: offsets and
+        geometry uploaded once), so a round is one filter launch, one draw, one RANSAC search and one accept launch for all active
+        pairs of a group whatever their sizes, and one host readback.  Only the fine stage of a round (warp_grid, PredFlowMask)
+        runs per group of active pairs that share (source shape, target shape), on the dense kernels."""
+        feats = feats or self.features(prep)
+        dev, B, plan = self.dev, prep["B"], prep["plan"]
+        tabs = ragged_multih_tables(plan)
+        idx1, idx2, cnt = self._mutual_ragged(feats)
+        host_draw = sample_fn is not None or self.draw == "host"
+        if split is None:
+            split = int(os.environ.get("RFX_MULTIH_SPLIT", "0")) or (4 if B >= 32 else (3 if B >= 12 else (2 if B >= 8 else 1)))
+        if host_draw or trace is not None or ops.Profiler.active() is not None and os.environ.get("RFX_MULTIH_SPLIT_PROFILED", "0") != "1":
+            split = 1
+        split = max(1, min(int(split), B))
+        ids, epoch = self._draw_epoch(pair_ids, "multi_h", draw_epoch)
+        if ids is None and split > 1:
+            ids = torch.arange(B, dtype=torch.int32, device=dev)       # the key of pair b stays its batch position b
+        if records is not None and (not isinstance(records, ops.MultiHRecordsRagged) or
+                                    list(zip(records.h8, records.w8)) != [g[4:6] for g in tabs["geom"]]):
+            raise ValueError("a ragged batch fills an ops.MultiHRecordsRagged built from its pairs' own /8 sizes")
+        tab = torch.tensor(tabs["moff"] + [v for g in tabs["geom"] for v in g], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        bg = None
+        if It_bg is not None:
+            if len(It_bg) != B:
+                raise ValueError("It_bg of a ragged batch: one (h, w) tensor (or None) per pair")
+            parts = []
+            for x, g in zip(It_bg, tabs["geom"]):
+                if x is not None and tuple(x.shape) != g[:2]:
+                    raise ValueError("It_bg entry of shape %s for a target of %s" % (tuple(x.shape), g[:2]))
+                parts.append(torch.ones(g[0] * g[1], dtype=torch.float32, device=dev) if x is None else x.to(dev).float().reshape(-1))
+            bg = torch.cat(parts)
+        st = dict(prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, B=B, ids=ids, epoch=epoch, bg=bg, tabs=tabs,
+                  moff=tab[:B], geom=tab[B:].to(torch.int32).view(B, 6),
+                  Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
+                  outs=[dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], nb=[0] * B, records=records,
+                  eye=torch.eye(3, device=dev), degenerate=self._degenerate_mode(host_draw))
+        bounds = [(B * k // split, B * (k + 1) // split) for k in range(split)]
+        gens = [self._multi_h_rounds_ragged(st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace) for lo, hi in bounds]
+        self._drive_rounds(gens)
+        outs = st["outs"]
+        for b in range(B):
+            o, (h, w) = tabs["moff"][b], tabs["geom"][b][:2]
+            outs[b]["mask"] = st["Mask"][o:o + h * w].view(h, w)
+            outs[b]["nbH"] = st["nb"][b]
+            outs[b]["matches"] = (idx1[b], idx2[b], cnt[b:b + 1])      # the cached mutual matches (rows beyond the count: undefined)
+        return outs
+
+    def _multi_h_rounds_ragged(self, st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace):
+        """_multi_h_rounds for pairs [lo, hi) of a ragged batch (same yields: the exact mode's gather event, the accept flags).
+        Pairs of the slice that share (source shape, target shape) form a fine group: their raw images are stacked once, the target
+        features are computed once per target shape, and every round runs warp_grid + PredFlowMask once per fine group over its
+        active members.  The round's matchability and /8 maps are packed in fine-group order (one torch.cat each) and handed to
+        rfx_multih_accept_ragged_f32 with per-active-pair offsets; those offsets and the groups' gather indices go up in ONE
+        pinned table per round."""
+        dev = self.dev
+        prep, feats, tabs = st["prep"], st["feats"], st["tabs"]
+        G = hi - lo
+        cut = lambda t: None if t is None else t[lo:hi]
+        idx1, idx2, cnt = cut(st["idx1"]), cut(st["idx2"]), cut(st["cnt"])
+        nbH, ids, moff, geom = cut(st["nbH"]), cut(st["ids"]), cut(st["moff"]), cut(st["geom"])
+        offA, offB = cut(feats["offA"]), cut(feats["offB"])
+        Mask, bg = st["Mask"], st["bg"]                                  # packed: the offsets are absolute
+        gm = tabs["geom"][lo:hi]
+        IsT, ItT = prep["IsTensor"][lo:hi], prep["ItTensor"][lo:hi]
+        R = st["records"]
+        if R is not None:
+            R = R.rows(lo, hi)
+        # fine groups: members in ascending order; target-shape groups for the FeatureExtractor pass of the targets
+        fine, tgroups = collections.OrderedDict(), collections.OrderedDict()
+        for m in range(G):
+            fine.setdefault((tuple(IsT[m].shape), tuple(ItT[m].shape)), []).append(m)
+            tgroups.setdefault(tuple(ItT[m].shape), []).append(m)
+        fine = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=gm[mem[0]][:2],
+                     Is=torch.cat([IsT[m] for m in mem]) if len(mem) > 1 else IsT[mem[0]]) for mem in fine.values()]
+
+        def target_features():
+            ft = {}
+            for shp, mem in tgroups.items():
+                f = ops.l2norm(self.feat(torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]]))
+                for j, m in enumerate(mem):
+                    ft[m] = f[j:j + 1]
+            for g in fine:
+                g["featt"] = torch.cat([ft[m] for m in g["members"]]) if len(g["members"]) > 1 else ft[g["members"][0]]
+
+        outs, nb, eye, degen, epoch = st["outs"], st["nb"], st["eye"], st["degenerate"], st["epoch"]
+        acc_host = torch.empty(G, dtype=torch.int32).pin_memory()
+        have_featt = False
+        active = list(range(G))
+        rnd = 0
+        while active:
+            a = len(active)
+            full = a == G
+            A = None if full else torch.tensor(active, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            # the round's layout: fine groups in order, each with its active members; pair k of the active list sits at
+            # match_off[k] of the packed matchability and at off8[k] of the packed /8 maps
+            kpos = {m: k for k, m in enumerate(active)}
+            rg, table, m_off, o8 = [], [0] * (2 * a), 0, 0
+            for g in fine:
+                mem = [m for m in g["members"] if m in kpos]
+                if not mem:
+                    continue
+                h, w = g["hw"]
+                for m in mem:
+                    table[kpos[m]], table[a + kpos[m]] = m_off, o8
+                    m_off += h * w
+                    o8 += (h // 8) * (w // 8)
+                ent = dict(g=g, mem=mem, kidx=None, sel=None)
+                if len(mem) != a or [kpos[m] for m in mem] != list(range(a)):
+                    ent["kidx"] = (len(table), len(mem))
+                    table += [kpos[m] for m in mem]
+                if len(mem) != len(g["members"]):
+                    ent["sel"] = (len(table), len(mem))
+                    table += [g["pos"][m] for m in mem]
+                rg.append(ent)
+            T = torch.tensor(table, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            M1, M2, n_dev = ops.filter_matches_ragged(idx1, idx2, cnt, A, Mask, bg, moff, geom, feats["HA"], feats["WA"], offA,
+                                                      feats["Ht"], feats["Wt"], offB)
+            smp = self._round_draws([lo + k for k in active], n_dev, sample_fn, A, ids, epoch, rnd)
+            rnd += 1
+            if degen == "lapack":
+                # the exact mode (see _multi_h_rounds): the targets' FeatureExtractor passes of the first round go BEHIND the gather
+                search = ops.ransac_h4_batched_begin(M1, M2, n_dev, smp, self.tol)
+                if not have_featt:
+                    target_features()
+                    have_featt = True
+                yield search.event
+                info = {} if getattr(self, "exact_log", None) is not None else None
+                bestH, inl, res = ops.ransac_h4_batched_finish(search, info=info)
+                if info is not None:
+                    self.exact_log.append(dict(info, round=rnd - 1, lo=lo, active=a))
+            else:
+                if not have_featt:
+                    target_features()
+                    have_featt = True
+                bestH, inl, res = ops.ransac_h4_batched(M1, M2, n_dev, smp, self.tol, degenerate=degen)
+            Hs = torch.where((res[:, 0] == 0)[:, None, None], bestH, eye)                # failed pairs: any finite warp
+            mask_before = None
+            if trace is not None:
+                mask_before = [Mask[tabs["moff"][lo + m]:tabs["moff"][lo + m] + gm[m][0] * gm[m][1]].view(gm[m][:2]).clone() for m in active]
+            # fine stage: per fine group, today's dense kernels
+            for ent in rg:
+                g = ent["g"]
+                take = lambda t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
+                h, w = g["hw"]
+                ent["pm"] = self.pred_flow_mask(take(g["Is"], "sel"), take(g["featt"], "sel"), ops.warp_grid(take(Hs, "kidx"), h, w))
+            pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
+            match = pack("match")
+            accept, gain = ops.multih_accept_ragged(match, T[:a], Mask, bg, moff, geom, A, res, n_dev, nbH, maskRegionTh, 0,
+                                                    max(gm[m][0] * gm[m][1] for m in active), bestH=bestH, flowDown8=pack("flowDown8"),
+                                                    match12Down8=pack("match12Down8"), match21Down8=pack("match21Down8"),
+                                                    off8=T[a:2 * a], records=R)
+            where = {}                                                                  # pair m -> (its fine group's outputs, row)
+            for ent in rg:
+                if want_lists:
+                    ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
+                for j, m in enumerate(ent["mem"]):
+                    where[m] = (ent, j)
+            if trace is not None:
+                trace.append(dict(active=[lo + m for m in active], mask_before=mask_before, n=n_dev, H=bestH, res=res, inlier=inl,
+                                  pm=[{key: v[where[m][1]:where[m][1] + 1] for key, v in where[m][0]["pm"].items()} for m in active],
+                                  accept=accept, gain=gain, samples=smp, round=rnd - 1,
+                                  mask_after=[Mask[tabs["moff"][lo + m]:tabs["moff"][lo + m] + gm[m][0] * gm[m][1]].view(gm[m][:2]).clone()
+                                              for m in active]))
+            acc_host[:a].copy_(accept, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            yield ev                                                                    # the round's host readback: accept flags
+            acc = acc_host[:a].tolist()
+            nxt = []
+            for k, m in enumerate(active):
+                if not acc[k]:
+                    continue
+                b = lo + m
+                if want_lists:
+                    ent, j = where[m]
+                    outs[b]["H"].append(bestH[k])
+                    outs[b]["flowDown8"].append(ent["pm"]["flowDown8"][j:j + 1])
+                    outs[b]["matchDown8"].append(ent["md2"][j:j + 1])
+                nb[b] += 1
+                if nb[b] <= maxCoarse:
                     nxt.append(m)
             active = nxt
 
@@ -1353,8 +1563,8 @@ class AlignPipeline:
     def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0):
         """coarse() + fine_quickstart() of a prep from prepare / prepare_device or, for pairs of different sizes, prepare_ragged /
         prepare_ragged_device.  A ragged batch gives every pair, bit for bit, what it gives alone (same ``pair_ids`` / draws); it
-        runs eagerly (no HIP-graph capture).  Not covered for ragged preps: multi_h_batched, multi_h_kitti_batched and
-        multi_h_variant_c, and the drop-in modules."""
+        runs eagerly (no HIP-graph capture).  multi_h_batched takes ragged preps too (multi_h_pairs).  Not covered for ragged
+        preps: multi_h_kitti_batched and multi_h_variant_c, and the drop-in modules."""
         res = self.coarse(prep, feats=feats, samples=samples, pair_ids=pair_ids, draw_epoch=draw_epoch)
         if fine:
             eye = torch.eye(3, device=self.dev)
@@ -1376,3 +1586,14 @@ class AlignPipeline:
         if len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1:
             return self.align_prepared(self.prepare_ragged(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
         return self.align_prepared(self.prepare(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
+
+    def multi_h_pairs(self, pairs, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None, want_lists=True,
+                      trace=None, pair_ids=None, draw_epoch=0, split=None):
+        """multi_h_batched on pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense
+        path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise prepare_ragged() and the ragged path (``It_bg`` a
+        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged)."""
+        ragged = len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1
+        prep = self.prepare_ragged(pairs) if ragged else self.prepare(pairs)
+        return self.multi_h_batched(prep, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
+                                    records=records, want_lists=want_lists, trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch,
+                                    split=split)
