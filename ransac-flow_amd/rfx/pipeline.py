@@ -11,13 +11,14 @@ Host-side work that stays on the CPU: PIL LANCZOS pyramid + ToTe
 ``prepare()`` does it and uploads; everything after runs on the device.
 """
 import collections
+import functools
 import os
 
 import numpy as np
 import torch
 import PIL.Image as Image
 
-from . import ops
+from . import ops, rounds
 from .nets import ResNet50Trunk, FeatureExtractorNet, NetFlowCoarseNet, NetMatchabilityNet
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -879,14 +880,13 @@ class AlignPipeline:
         wait per round: the flagged 4-point samples, re-solved by the host's LAPACK).  Semantics per pair =
         evaluation/evalHpatch/evaluation.py:184-243.
         ``split``: the rounds of the batch as this many independent lock-step groups (contiguous slices of the batch), each on its
-        own HIP stream, driven from this one host thread as coroutines (_multi_h_rounds yields at its host waits; _drive_rounds
-        resumes the group whose event is due): while one group waits for the host -- accept flags, the LAPACK stage -- the other
-        groups' kernels keep the GPU busy, and the small launches of one group's late rounds share the chip with another's.
-        Per pair the arithmetic is unchanged (every kernel computes a pair independently; device draws are keyed by absolute
-        pair position / id).  None = RFX_MULTIH_SPLIT or, for device draws, 3 groups from 12 pairs on, 2 from 8 (measured,
-        profiles/r06_stream_sweep.txt: config 3, 64 pairs: 1 / 2 / 3 / 4 / 6 groups = 110.2 / 112.7 / 115.3 / 115.4 / 115.6 pairs/s;
-        config 4, 16 pairs, 50 000 hypotheses: 2 / 3 / 4 groups = 56.1 / 57.4 / 56.2), else 1; forced to 1 with host draws /
-        ``sample_fn`` (the CPU generator is consumed in pair order), with ``trace`` and under an ops.Profiler (per-launch events).
+        own HIP stream, driven from this one host thread as coroutines (rounds.lockstep_rounds yields at its host waits;
+        rounds.drive_rounds resumes the group whose event is due): while one group waits for the host -- accept flags, the LAPACK
+        stage -- the other groups' kernels keep the GPU busy, and the small launches of one group's late rounds share the chip with
+        another's.  Per pair the arithmetic is unchanged (every kernel computes a pair independently; device draws are keyed by
+        absolute pair position / id).  None = RFX_MULTIH_SPLIT or, for device draws, 4 groups from 32 pairs on, 3 from 12, 2 from 8
+        (rounds.HPATCH_SPLIT), else 1; forced to 1 with host draws / ``sample_fn`` (the CPU generator is consumed in pair order),
+        with ``trace`` and under an ops.Profiler (per-launch events): rounds.split_policy.
         ``sample_fn(b, n, nbIter)`` -> (nbIter,4) int64 CPU tensor: explicit draws (parity mode; costs a second sync per round).
         ``pair_ids``: absolute ids of the batch's pairs for the device draw (see _draw_epoch): with them a pair's homographies
         are the same alone, in any batch and under any sharding.
@@ -906,168 +906,22 @@ class AlignPipeline:
         B = prep["B"]
         h, w = prep["ItTensor"].shape[2], prep["ItTensor"].shape[3]
         idx1, idx2, cnt = self._mutual_batched(feats, B)
-        host_draw = sample_fn is not None or self.draw == "host"
-        if split is None:
-            split = int(os.environ.get("RFX_MULTIH_SPLIT", "0")) or (4 if B >= 32 else (3 if B >= 12 else (2 if B >= 8 else 1)))
-        if host_draw or trace is not None or ops.Profiler.active() is not None and os.environ.get("RFX_MULTIH_SPLIT_PROFILED", "0") != "1":
-            split = 1
-        split = max(1, min(int(split), B))
-        ids, epoch = self._draw_epoch(pair_ids, "multi_h", draw_epoch)
-        if ids is None and split > 1:
-            ids = torch.arange(B, dtype=torch.int32, device=dev)       # the key of pair b stays its batch position b
-        st = dict(prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, h=h, w=w, B=B, ids=ids, epoch=epoch,
-                  bg=None if It_bg is None else It_bg.to(dev).float().contiguous(),
-                  Mask=torch.zeros((B, h, w), dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
-                  outs=[dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], nb=[0] * B, records=records,
-                  eye=torch.eye(3, device=dev), degenerate=self._degenerate_mode(host_draw),
-                  featt=None if split > 1 or self._degenerate_mode(host_draw) == "lapack" else ops.l2norm(self.feat(prep["ItTensor"])))
-        bounds = [(B * k // split, B * (k + 1) // split) for k in range(split)]
-        gens = [self._multi_h_rounds(st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace) for lo, hi in bounds]
-        self._drive_rounds(gens)
-        outs, Mask = st["outs"], st["Mask"]
-        for b in range(B):
-            outs[b]["mask"] = Mask[b]
-            outs[b]["nbH"] = st["nb"][b]
-            outs[b]["matches"] = (idx1[b], idx2[b], cnt[b:b + 1])      # the cached mutual matches (rows beyond the count: undefined)
-        return outs
-
-    def _drive_rounds(self, gens):
-        """Run lock-step round generators to completion from this host thread: generator k runs under stream k (the caller's
-        stream for k = 0, pipeline-owned side streams after), yields a HIP event whenever it needs the host to see device results,
-        and is resumed once that event has completed -- whichever group is ready first.  One generator: the plain sequential loop."""
-        main = torch.cuda.current_stream(self.dev)
-        if len(gens) > 1:
-            pool = self.__dict__.setdefault("_round_streams", [])
-            while len(pool) < len(gens) - 1:
-                pool.append(torch.cuda.Stream(device=self.dev))
-            streams = [main] + pool[:len(gens) - 1]
-            for s in streams[1:]:
-                s.wait_stream(main)
-        else:
-            streams = [main]
-        live = [(g, s, None) for g, s in zip(gens, streams)]
-        while live:
-            # the group whose event has already completed goes first (its host work -- the LAPACK stage, the next round's
-            # launches -- then runs under the other groups' queued kernels); none ready: wait for the one that yielded first
-            k = next((i for i, (_, _, ev) in enumerate(live) if ev is None or ev.query()), 0)
-            g, s, ev = live.pop(k)
-            if ev is not None:
-                ev.synchronize()
-            with torch.cuda.stream(s):
-                try:
-                    ev = next(g)
-                except StopIteration:
-                    continue
-            live.append((g, s, ev))
-        for s in streams[1:]:
-            main.wait_stream(s)
-
-    def _multi_h_rounds(self, st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace):
-        """The rounds of pairs [lo, hi) of a batch as a generator (see multi_h_batched / _drive_rounds): yields a recorded HIP event
-        at every host wait.  All launches go to the stream that is current while the generator runs."""
-        dev = self.dev
-        prep, feats, B, h, w = st["prep"], st["feats"], st["B"], st["h"], st["w"]
-        G = hi - lo
-        whole = lo == 0 and hi == B
-        cut = (lambda t: t) if whole else (lambda t: None if t is None else t[lo:hi])
-        idx1, idx2, cnt = cut(st["idx1"]), cut(st["idx2"]), cut(st["cnt"])
-        Mask, nbH, bg, ids = cut(st["Mask"]), cut(st["nbH"]), cut(st["bg"]), cut(st["ids"])
-        IsT, ItT = cut(prep.get("IsTensor")), cut(prep.get("ItTensor"))
-        rt, ct = feats["rt"], feats["ct"]
-        R = st["records"]
-        if R is not None and not whole:
-            R = R.rows(lo, hi)
-        featt = cut(st["featt"])
-        kitti = st.get("kitti")
-        if kitti is not None:
-            kitti = dict(kitti, tensor_s=cut(kitti["tensor_s"]), tensor_d2=cut(kitti["tensor_d2"]), tensor_resize=cut(kitti["tensor_resize"]))
-        outs, nb, eye, degen, epoch = st["outs"], st["nb"], st["eye"], st["degenerate"], st["epoch"]
-        acc_host = torch.empty(G, dtype=torch.int32).pin_memory()
-        active = list(range(G))
-        rnd = 0
-        while active:
-            full = len(active) == G
-            A = None if full else torch.tensor(active, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-            M1, M2, n_dev = ops.filter_matches(idx1, idx2, cnt, A, Mask, bg, rt, ct, feats["HA"], feats["WA"], feats["Ht"],
-                                               feats["Wt"])
-            smp = self._round_draws([lo + k for k in active], n_dev, sample_fn, A, ids, epoch, rnd)
-            rnd += 1
-            if degen == "lapack":
-                # the exact mode: stage 1 + the flagged samples into pinned memory, then -- first round only -- the target's
-                # FeatureExtractor pass (independent of the search) BEHIND the gather, so that the host's LAPACK stage runs
-                # while the GPU works; the other rounds hide it under another group's kernels (split > 1)
-                search = ops.ransac_h4_batched_begin(M1, M2, n_dev, smp, self.tol)
-                if featt is None and kitti is None:
-                    featt = ops.l2norm(self.feat(ItT))
-                yield search.event
-                info = {} if getattr(self, "exact_log", None) is not None else None
-                bestH, inl, res = ops.ransac_h4_batched_finish(search, info=info)
-                if info is not None:
-                    self.exact_log.append(dict(info, round=rnd - 1, lo=lo, active=len(active)))
-            else:
-                if featt is None and kitti is None:
-                    featt = ops.l2norm(self.feat(ItT))
-                bestH, inl, res = ops.ransac_h4_batched(M1, M2, n_dev, smp, self.tol, degenerate=degen)
-            Hs = torch.where((res[:, 0] == 0)[:, None, None], bestH, eye)                # failed pairs: any finite warp
-            mask_before = (Mask if full else Mask.index_select(0, A)).clone() if trace is not None else None
-            if kitti is None:
-                flowCoarse = ops.warp_grid(Hs, h, w)
-                Is = IsT if full else IsT.index_select(0, A)
-                pm = self.pred_flow_mask(Is, featt if full else featt.index_select(0, A), flowCoarse)
-                match, flow_d2 = pm["match"][:, 0], None
-                accept, gain = ops.multih_accept(pm["match"], Mask, bg, A, res, n_dev, nbH, maskRegionTh, 0, bestH=bestH,
-                                                 flowDown8=pm["flowDown8"], match12Down8=pm["match12Down8"],
-                                                 match21Down8=pm["match21Down8"], records=R)
-            else:
-                # evaluation/evalKITTI/evaluation.py:279-336: the two-resolution fine pass, the small-component filter, accept mode 1
-                selk = (lambda t: t) if full else (lambda t: t.index_select(0, A))
-                flow_d2, pm, match = self.kitti_fine_round(Hs, selk(kitti["tensor_s"]), selk(kitti["tensor_d2"]), selk(kitti["tensor_resize"]),
-                                                           (h, w), kitti["cc_th"], kitti["remove_small_cc"])
-                accept, gain = ops.multih_accept(match, Mask, bg, A, res, n_dev, nbH, maskRegionTh, 1, bestH=bestH,
-                                                 flowDown8=pm["flowDown8"], match12Down8=pm["match12Down8"],
-                                                 match21Down8=pm["match21Down8"], flowD2=flow_d2, records=R)
-            if trace is not None:
-                tr = dict(active=[lo + k for k in active], mask_before=mask_before, n=n_dev, H=bestH, res=res, inlier=inl, pm=pm,
-                          match=match, accept=accept, gain=gain, mask_after=(Mask if full else Mask.index_select(0, A)).clone(),
-                          samples=smp, round=rnd - 1)
-                if flow_d2 is not None:
-                    tr["flowD2"] = flow_d2
-                trace.append(tr)
-            md2 = torch.cat((pm["match12Down8"], pm["match21Down8"]), dim=1) if want_lists else None
-            acc_host[:len(active)].copy_(accept, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            yield ev                                                                    # the round's host readback: accept flags
-            acc = acc_host[:len(active)].tolist()
-            nxt = []
-            for k, m in enumerate(active):
-                if not acc[k]:
-                    continue
-                b = lo + m
-                if want_lists:
-                    outs[b]["H"].append(bestH[k])
-                    if flow_d2 is not None:
-                        outs[b]["flowD2"].append(flow_d2[k:k + 1])
-                    outs[b]["flowDown8"].append(pm["flowDown8"][k:k + 1])
-                    outs[b]["matchDown8"].append(md2[k:k + 1])
-                nb[b] += 1
-                if kitti is None:
-                    if nb[b] <= maxCoarse:
-                        nxt.append(m)
-                elif st["records"] is not None and nb[b] >= st["records"].max_h:
-                    # the reference's ``while True`` has no round limit; a fixed-size record has: the pair stops at the record's
-                    # capacity and its record says so (status 4 = "capped by the driver": the reference might have gone on; a
-                    # truncated pair is distinguishable from one that ended on the accept test)
-                    st["records"].rec[b, 1] = 4.0
-                else:
-                    nxt.append(m)
-            active = nxt
+        st = rounds.RoundState(self, [dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "multi_h", rounds.HPATCH_SPLIT, split,
+                               sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
+        batch = dict(feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, IsTensor=prep["IsTensor"], ItTensor=prep["ItTensor"],
+                     bg=None if It_bg is None else It_bg.to(dev).float().contiguous(),
+                     Mask=torch.zeros((B, h, w), dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev))
+        groups = [rounds.DenseGroup(st, batch, lo, hi) for lo, hi in st.bounds]
+        if st.split == 1 and st.degenerate != "lapack":
+            groups[0].target_features()       # one group and no host stage to put it behind: ahead of the rounds
+        rounds.drive_rounds(self, [rounds.lockstep_rounds(g) for g in groups])
+        return st.close(lambda b: batch["Mask"][b], (idx1, idx2, cnt))
 
     # ---------------------------------------------------------------- multi-homography rounds of a ragged batch
     def _multi_h_batched_ragged(self, prep, maxCoarse, maskRegionTh, It_bg, feats, sample_fn, records, want_lists, trace, pair_ids,
                                 draw_epoch, split):
         """multi_h_batched for a ragged prep.  One grouped trunk pass (_features_ragged), one ragged mutual matching, then the
-        lock-step rounds of _multi_h_rounds_ragged under the dense driver's coroutine / stream machinery (_drive_rounds, ``split``).
+        lock-step rounds of rounds.RaggedGroup under the dense driver's coroutine / stream machinery (rounds.drive_rounds, ``split``).
         The explained-region masks (and background maps) of all pairs live in ONE packed buffer (ragged_multih_tables: offsets and
         geometry uploaded once), so a round is one filter launch, one draw, one RANSAC search and one accept launch for all active
         pairs of a group whatever their sizes, and one host readback.  Only the fine stage of a round (warp_grid, PredFlowMask)
@@ -1076,15 +930,8 @@ class AlignPipeline:
         dev, B, plan = self.dev, prep["B"], prep["plan"]
         tabs = ragged_multih_tables(plan)
         idx1, idx2, cnt = self._mutual_ragged(feats)
-        host_draw = sample_fn is not None or self.draw == "host"
-        if split is None:
-            split = int(os.environ.get("RFX_MULTIH_SPLIT", "0")) or (4 if B >= 32 else (3 if B >= 12 else (2 if B >= 8 else 1)))
-        if host_draw or trace is not None or ops.Profiler.active() is not None and os.environ.get("RFX_MULTIH_SPLIT_PROFILED", "0") != "1":
-            split = 1
-        split = max(1, min(int(split), B))
-        ids, epoch = self._draw_epoch(pair_ids, "multi_h", draw_epoch)
-        if ids is None and split > 1:
-            ids = torch.arange(B, dtype=torch.int32, device=dev)       # the key of pair b stays its batch position b
+        st = rounds.RoundState(self, [dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "multi_h", rounds.HPATCH_SPLIT, split,
+                               sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
         if records is not None and (not isinstance(records, ops.MultiHRecordsRagged) or
                                     list(zip(records.h8, records.w8)) != [g[4:6] for g in tabs["geom"]]):
             raise ValueError("a ragged batch fills an ops.MultiHRecordsRagged built from its pairs' own /8 sizes")
@@ -1099,157 +946,15 @@ class AlignPipeline:
                     raise ValueError("It_bg entry of shape %s for a target of %s" % (tuple(x.shape), g[:2]))
                 parts.append(torch.ones(g[0] * g[1], dtype=torch.float32, device=dev) if x is None else x.to(dev).float().reshape(-1))
             bg = torch.cat(parts)
-        st = dict(prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, B=B, ids=ids, epoch=epoch, bg=bg, tabs=tabs,
-                  moff=tab[:B], geom=tab[B:].to(torch.int32).view(B, 6),
-                  Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
-                  outs=[dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], nb=[0] * B, records=records,
-                  eye=torch.eye(3, device=dev), degenerate=self._degenerate_mode(host_draw))
-        bounds = [(B * k // split, B * (k + 1) // split) for k in range(split)]
-        gens = [self._multi_h_rounds_ragged(st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace) for lo, hi in bounds]
-        self._drive_rounds(gens)
-        outs = st["outs"]
-        for b in range(B):
+        batch = dict(prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, bg=bg, tabs=tabs, moff=tab[:B],
+                     geom=tab[B:].to(torch.int32).view(B, 6), Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev),
+                     nbH=torch.zeros(B, dtype=torch.int32, device=dev))
+        rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
+
+        def mask_of(b):
             o, (h, w) = tabs["moff"][b], tabs["geom"][b][:2]
-            outs[b]["mask"] = st["Mask"][o:o + h * w].view(h, w)
-            outs[b]["nbH"] = st["nb"][b]
-            outs[b]["matches"] = (idx1[b], idx2[b], cnt[b:b + 1])      # the cached mutual matches (rows beyond the count: undefined)
-        return outs
-
-    def _multi_h_rounds_ragged(self, st, lo, hi, maxCoarse, maskRegionTh, sample_fn, want_lists, trace):
-        """_multi_h_rounds for pairs [lo, hi) of a ragged batch (same yields: the exact mode's gather event, the accept flags).
-        Pairs of the slice that share (source shape, target shape) form a fine group: their raw images are stacked once, the target
-        features are computed once per target shape, and every round runs warp_grid + PredFlowMask once per fine group over its
-        active members.  The round's matchability and /8 maps are packed in fine-group order (one torch.cat each) and handed to
-        rfx_multih_accept_ragged_f32 with per-active-pair offsets; those offsets and the groups' gather indices go up in ONE
-        pinned table per round."""
-        dev = self.dev
-        prep, feats, tabs = st["prep"], st["feats"], st["tabs"]
-        G = hi - lo
-        cut = lambda t: None if t is None else t[lo:hi]
-        idx1, idx2, cnt = cut(st["idx1"]), cut(st["idx2"]), cut(st["cnt"])
-        nbH, ids, moff, geom = cut(st["nbH"]), cut(st["ids"]), cut(st["moff"]), cut(st["geom"])
-        offA, offB = cut(feats["offA"]), cut(feats["offB"])
-        Mask, bg = st["Mask"], st["bg"]                                  # packed: the offsets are absolute
-        gm = tabs["geom"][lo:hi]
-        IsT, ItT = prep["IsTensor"][lo:hi], prep["ItTensor"][lo:hi]
-        R = st["records"]
-        if R is not None:
-            R = R.rows(lo, hi)
-        # fine groups: members in ascending order; target-shape groups for the FeatureExtractor pass of the targets
-        fine, tgroups = collections.OrderedDict(), collections.OrderedDict()
-        for m in range(G):
-            fine.setdefault((tuple(IsT[m].shape), tuple(ItT[m].shape)), []).append(m)
-            tgroups.setdefault(tuple(ItT[m].shape), []).append(m)
-        fine = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=gm[mem[0]][:2],
-                     Is=torch.cat([IsT[m] for m in mem]) if len(mem) > 1 else IsT[mem[0]]) for mem in fine.values()]
-
-        def target_features():
-            ft = {}
-            for shp, mem in tgroups.items():
-                f = ops.l2norm(self.feat(torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]]))
-                for j, m in enumerate(mem):
-                    ft[m] = f[j:j + 1]
-            for g in fine:
-                g["featt"] = torch.cat([ft[m] for m in g["members"]]) if len(g["members"]) > 1 else ft[g["members"][0]]
-
-        outs, nb, eye, degen, epoch = st["outs"], st["nb"], st["eye"], st["degenerate"], st["epoch"]
-        acc_host = torch.empty(G, dtype=torch.int32).pin_memory()
-        have_featt = False
-        active = list(range(G))
-        rnd = 0
-        while active:
-            a = len(active)
-            full = a == G
-            A = None if full else torch.tensor(active, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-            # the round's layout: fine groups in order, each with its active members; pair k of the active list sits at
-            # match_off[k] of the packed matchability and at off8[k] of the packed /8 maps
-            kpos = {m: k for k, m in enumerate(active)}
-            rg, table, m_off, o8 = [], [0] * (2 * a), 0, 0
-            for g in fine:
-                mem = [m for m in g["members"] if m in kpos]
-                if not mem:
-                    continue
-                h, w = g["hw"]
-                for m in mem:
-                    table[kpos[m]], table[a + kpos[m]] = m_off, o8
-                    m_off += h * w
-                    o8 += (h // 8) * (w // 8)
-                ent = dict(g=g, mem=mem, kidx=None, sel=None)
-                if len(mem) != a or [kpos[m] for m in mem] != list(range(a)):
-                    ent["kidx"] = (len(table), len(mem))
-                    table += [kpos[m] for m in mem]
-                if len(mem) != len(g["members"]):
-                    ent["sel"] = (len(table), len(mem))
-                    table += [g["pos"][m] for m in mem]
-                rg.append(ent)
-            T = torch.tensor(table, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-            M1, M2, n_dev = ops.filter_matches_ragged(idx1, idx2, cnt, A, Mask, bg, moff, geom, feats["HA"], feats["WA"], offA,
-                                                      feats["Ht"], feats["Wt"], offB)
-            smp = self._round_draws([lo + k for k in active], n_dev, sample_fn, A, ids, epoch, rnd)
-            rnd += 1
-            if degen == "lapack":
-                # the exact mode (see _multi_h_rounds): the targets' FeatureExtractor passes of the first round go BEHIND the gather
-                search = ops.ransac_h4_batched_begin(M1, M2, n_dev, smp, self.tol)
-                if not have_featt:
-                    target_features()
-                    have_featt = True
-                yield search.event
-                info = {} if getattr(self, "exact_log", None) is not None else None
-                bestH, inl, res = ops.ransac_h4_batched_finish(search, info=info)
-                if info is not None:
-                    self.exact_log.append(dict(info, round=rnd - 1, lo=lo, active=a))
-            else:
-                if not have_featt:
-                    target_features()
-                    have_featt = True
-                bestH, inl, res = ops.ransac_h4_batched(M1, M2, n_dev, smp, self.tol, degenerate=degen)
-            Hs = torch.where((res[:, 0] == 0)[:, None, None], bestH, eye)                # failed pairs: any finite warp
-            mask_before = None
-            if trace is not None:
-                mask_before = [Mask[tabs["moff"][lo + m]:tabs["moff"][lo + m] + gm[m][0] * gm[m][1]].view(gm[m][:2]).clone() for m in active]
-            # fine stage: per fine group, today's dense kernels
-            for ent in rg:
-                g = ent["g"]
-                take = lambda t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
-                h, w = g["hw"]
-                ent["pm"] = self.pred_flow_mask(take(g["Is"], "sel"), take(g["featt"], "sel"), ops.warp_grid(take(Hs, "kidx"), h, w))
-            pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
-            match = pack("match")
-            accept, gain = ops.multih_accept_ragged(match, T[:a], Mask, bg, moff, geom, A, res, n_dev, nbH, maskRegionTh, 0,
-                                                    max(gm[m][0] * gm[m][1] for m in active), bestH=bestH, flowDown8=pack("flowDown8"),
-                                                    match12Down8=pack("match12Down8"), match21Down8=pack("match21Down8"),
-                                                    off8=T[a:2 * a], records=R)
-            where = {}                                                                  # pair m -> (its fine group's outputs, row)
-            for ent in rg:
-                if want_lists:
-                    ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
-                for j, m in enumerate(ent["mem"]):
-                    where[m] = (ent, j)
-            if trace is not None:
-                trace.append(dict(active=[lo + m for m in active], mask_before=mask_before, n=n_dev, H=bestH, res=res, inlier=inl,
-                                  pm=[{key: v[where[m][1]:where[m][1] + 1] for key, v in where[m][0]["pm"].items()} for m in active],
-                                  accept=accept, gain=gain, samples=smp, round=rnd - 1,
-                                  mask_after=[Mask[tabs["moff"][lo + m]:tabs["moff"][lo + m] + gm[m][0] * gm[m][1]].view(gm[m][:2]).clone()
-                                              for m in active]))
-            acc_host[:a].copy_(accept, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            yield ev                                                                    # the round's host readback: accept flags
-            acc = acc_host[:a].tolist()
-            nxt = []
-            for k, m in enumerate(active):
-                if not acc[k]:
-                    continue
-                b = lo + m
-                if want_lists:
-                    ent, j = where[m]
-                    outs[b]["H"].append(bestH[k])
-                    outs[b]["flowDown8"].append(ent["pm"]["flowDown8"][j:j + 1])
-                    outs[b]["matchDown8"].append(ent["md2"][j:j + 1])
-                nb[b] += 1
-                if nb[b] <= maxCoarse:
-                    nxt.append(m)
-            active = nxt
+            return batch["Mask"][o:o + h * w].view(h, w)
+        return st.close(mask_of, (idx1, idx2, cnt))
 
     # ---------------------------------------------------------------- YFCC / Corr driver shape (variant C; VERDICT r4 #4)
     def pred_flow_mask_cycle(self, IsTensor, featt, flowCoarse):
@@ -1309,24 +1014,21 @@ class AlignPipeline:
             cand.append(dict(ItT=ItT, featB=fB, rt=rt, ct=ct, Wt=Wt, Ht=Ht,
                              bg=None if It_bg is None or It_bg[k] is None else It_bg[k].to(dev).float().contiguous()))
 
-        def search(c, fA, maskB, n_pairs, draw_fn):
-            """variant C's getCoarse for a batch: masked mutual matching -> matches -> draw -> RANSAC."""
-            f = dict(featA=fA, featB=c["featB_sel"], nA=nA, ldA=ldA, nB=c["rt"] * c["ct"])
+        def matches(c, fA, fB, maskB, n_pairs):
+            """The matching half of variant C's getCoarse for a batch: masked mutual matching -> matches."""
+            f = dict(featA=fA, featB=fB, nA=nA, ldA=ldA, nB=c["rt"] * c["ct"])
             idx1, idx2, cnt = self._mutual_batched(f, n_pairs, maskB)
             M1, M2 = ops.gather_matches(idx1, idx2, cnt, feats["HA"], feats["WA"], c["Ht"], c["Wt"])
-            smp = draw_fn(cnt)
-            bestH, inl, res = ops.ransac_h4_batched(M1, M2, cnt, smp, self.tol, degenerate=degen)
-            return cnt, bestH, res
+            return M1, M2, cnt
 
         ids, ep_sel = self._draw_epoch(pair_ids, "variant_c_select", draw_epoch)
-        ep_loop = self._draw_epoch(pair_ids, "variant_c", draw_epoch)[1]
         all_b = list(range(B))
         counts = []
         for k, c in enumerate(cand):
-            c["featB_sel"] = c["featB"]
-            h, w = c["ItT"].shape[2], c["ItT"].shape[3]
             keep = None if c["bg"] is None else ops.keep_mask(None, c["bg"], None, c["rt"], c["ct"])
-            n_k, _, res = search(c, featA, keep, B, lambda cnt, k=k: self._round_draws(all_b, cnt, sample_fn, None, ids, ep_sel, k))
+            M1, M2, n_k = matches(c, featA, c["featB"], keep, B)
+            smp = self._round_draws(all_b, n_k, sample_fn, None, ids, ep_sel, k)
+            _, _, res = ops.ransac_h4_batched(M1, M2, n_k, smp, self.tol, degenerate=degen)
             counts.append(torch.where((res[:, 0] == 0) & (n_k >= 4), res[:, 1], torch.zeros_like(res[:, 1])))
         table = torch.stack(counts, dim=1).cpu()                          # the ONE sync of the search: (B,K) inlier counts
         chosen = [int(max(range(K), key=lambda k: (int(table[b, k]), -k))) for b in range(B)]     # first maximum (np.argmax)
@@ -1336,70 +1038,31 @@ class AlignPipeline:
         groups = {}
         for b in range(B):
             groups.setdefault(tuple(cand[chosen[b]]["ItT"].shape[2:]), []).append(b)
-        IsT_all = prep["IsTensor"]
-        eye = torch.eye(3, device=dev)
-        for shape, members in groups.items():
-            # the group's tensors: pair m of the group = pair members[m] of the batch with ITS chosen candidate
-            G = len(members)
-            gi = torch.tensor(members, dtype=torch.int64, device=dev)
-            h, w = shape
-            ref_c = cand[chosen[members[0]]]
-            rt, ct = ref_c["rt"], ref_c["ct"]
-            pick = lambda key: torch.stack([cand[chosen[b]][key][b] for b in members])
-            ItT, fB = pick("ItT"), pick("featB")
-            bg = None if all(cand[chosen[b]]["bg"] is None for b in members) else torch.stack(
-                [cand[chosen[b]]["bg"][b] if cand[chosen[b]]["bg"] is not None else torch.ones((h, w), device=dev) for b in members])
-            fA, IsT = featA.index_select(0, gi), IsT_all.index_select(0, gi)
-            gids = gi.int() if ids is None else ids.index_select(0, gi)     # absolute batch positions when no ids were given
-            featt = ops.l2norm(self.feat(ItT))
-            Mask = torch.zeros((G, h, w), dtype=torch.float32, device=dev)
-            nbH = torch.zeros(G, dtype=torch.int32, device=dev)
-            R = None
-            if records is not None:
-                if (records.h8, records.w8) != (h // 8, w // 8):
-                    raise ValueError("records were built for /8 maps of %dx%d, this group's targets give %dx%d (one MultiHRecords per "
-                                     "shape group)" % (records.h8, records.w8, h // 8, w // 8))
-                R = ops.MultiHRecords(G, records.h8, records.w8, dev, max_h=records.max_h)
-                R.rec[:, 2:4] = records.rec.index_select(0, gi)[:, 2:4]
-            nb = [0] * G
-            active = list(range(G))
-            rnd = 0
-            gc = dict(ref_c)
-            while active:
-                full = len(active) == G
-                A = None if full else torch.tensor(active, dtype=torch.int32).to(dev, non_blocking=True)
-                sel = (lambda t: t) if full else (lambda t: t.index_select(0, A.long()))
-                keep = ops.keep_mask(Mask, bg, A, rt, ct)
-                gc["featB_sel"] = sel(fB)
-                act_pairs = [members[m] for m in active]
-                n_dev, bestH, res = search(gc, sel(fA), keep, len(active), lambda cnt: self._round_draws(
-                    act_pairs, cnt, sample_fn, None, sel(gids), ep_loop, rnd))
-                rnd += 1
-                Hs = torch.where((res[:, 0] == 0)[:, None, None], bestH, eye)                # failed pairs: any finite warp
-                pm = self.pred_flow_mask_cycle(sel(IsT), sel(featt), ops.warp_grid(Hs, h, w))
-                accept, _ = ops.multih_accept(pm["match"], Mask, bg, A, res, n_dev, nbH, maskRegionTh, 0, bestH=bestH,
-                                              flowDown8=pm["flowDown8"], match12Down8=pm["match12Down8"],
-                                              match21Down8=pm["match21Down8"], records=R)
-                md2 = torch.cat((pm["match12Down8"], pm["match21Down8"]), dim=1) if want_lists else None
-                acc = accept.cpu().tolist()                                                 # the round's ONE sync
-                nxt = []
-                for k, m in enumerate(active):
-                    if not acc[k]:
-                        continue
-                    if want_lists:
-                        o = outs[members[m]]
-                        o["H"].append(bestH[k])
-                        o["flowDown8"].append(pm["flowDown8"][k:k + 1])
-                        o["matchDown8"].append(md2[k:k + 1])
-                    nb[m] += 1
-                    if nb[m] <= maxCoarse:
-                        nxt.append(m)
-                active = nxt
-            for m, b in enumerate(members):
-                outs[b]["mask"], outs[b]["nbH"] = Mask[m], nb[m]
-            if R is not None:
-                records.rec.index_copy_(0, gi, R.rec)
-        return outs
+        # the shape groups one after the other, each as ONE lock-step group of its own (no split, no trace)
+        st = rounds.RoundState(self, outs, "variant_c", (), 1, sample_fn, records, want_lists, None, pair_ids, draw_epoch, maskRegionTh,
+                               maxCoarse)
+        masks = {}
+
+        def shape_groups():
+            for (h, w), members in groups.items():
+                # the group's tensors: pair m of the group = pair members[m] of the batch with ITS chosen candidate
+                G = len(members)
+                gi = torch.tensor(members, dtype=torch.int64, device=dev)
+                ref_c = cand[chosen[members[0]]]
+                pick = lambda key: torch.stack([cand[chosen[b]][key][b] for b in members])
+                bg = None if all(cand[chosen[b]]["bg"] is None for b in members) else torch.stack(
+                    [cand[chosen[b]]["bg"][b] if cand[chosen[b]]["bg"] is not None else torch.ones((h, w), device=dev) for b in members])
+                batch = dict(ItTensor=pick("ItT"), featB=pick("featB"), bg=bg, featA=featA.index_select(0, gi),
+                             IsTensor=prep["IsTensor"].index_select(0, gi), rt=ref_c["rt"], ct=ref_c["ct"], gi=gi,
+                             Mask=torch.zeros((G, h, w), dtype=torch.float32, device=dev), nbH=torch.zeros(G, dtype=torch.int32, device=dev))
+                g = rounds.VariantCGroup(st, batch, members, functools.partial(matches, ref_c))
+                for m, b in enumerate(members):
+                    masks[b] = g.Mask[m]
+                yield from rounds.lockstep_rounds(g)
+                g.store_records()
+
+        rounds.drive_rounds(self, [shape_groups()])
+        return st.close(lambda b: masks[b])
 
     # ---------------------------------------------------------------- KITTI two-resolution driver (BASELINE config 5)
     @staticmethod
@@ -1530,34 +1193,17 @@ class AlignPipeline:
         tensor_resize, _ = ops.u8_to_f32(ops.lanczos_resize_u8(tgt_u8, w_r, h_r))
         tensor_d2, _ = ops.u8_to_f32(ops.lanczos_resize_u8(tgt_u8, w_d2, h_d2))
         idx1, idx2, cnt = self._mutual_batched(feats, B)
-        host_draw = sample_fn is not None or self.draw == "host"
-        if split is None:
-            # measured at config 5 (B = 8): two groups of 4 hide the exact mode's host stage but run the fine passes at batch 4
-            # instead of 8 -- a wash (21.0 vs 21.1 pairs/s, profiles/r06_stream_sweep.txt); groups pay from 8 pairs per group on
-            split = int(os.environ.get("RFX_MULTIH_SPLIT", "0")) or (2 if B >= 16 else 1)
-        if host_draw or trace is not None or remove_small_cc is not None or (
-                ops.Profiler.active() is not None and os.environ.get("RFX_MULTIH_SPLIT_PROFILED", "0") != "1"):
-            split = 1                         # (an injected host filter is called in pair order: one group)
-        split = max(1, min(int(split), B))
-        ids, epoch = self._draw_epoch(pair_ids, "kitti", draw_epoch)
-        if ids is None and split > 1:
-            ids = torch.arange(B, dtype=torch.int32, device=dev)
-        # the rounds are _multi_h_rounds' (the Hpatch driver's generator) with the KITTI fine pass / accept mode / stop rule: lock-step
+        # (an injected host filter is called in pair order: one group)
+        st = rounds.RoundState(self, [dict(H=[], flowD2=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "kitti", rounds.KITTI_SPLIT,
+                               split, sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh,
+                               host_filter=remove_small_cc is not None)
+        # the rounds are the Hpatch driver's with the KITTI fine pass / accept mode / stop rule (rounds.KittiGroup): lock-step
         # groups on streams, ready-first scheduling, the exact mode's host stage hidden under the other groups' kernels
-        st = dict(prep=dict(prep, IsTensor=None, ItTensor=None), feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, h=h_org, w=w_org, B=B, ids=ids,
-                  epoch=epoch, bg=None if It_bg is None else It_bg.to(dev).float().contiguous(),
-                  Mask=torch.zeros((B, h_org, w_org), dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
-                  outs=[dict(H=[], flowD2=[], flowDown8=[], matchDown8=[]) for _ in range(B)], nb=[0] * B, records=records,
-                  eye=torch.eye(3, device=dev), degenerate=self._degenerate_mode(host_draw), featt=None,
-                  kitti=dict(tensor_s=tensor_s, tensor_d2=tensor_d2, tensor_resize=tensor_resize, cc_th=cc_th, remove_small_cc=remove_small_cc))
-        bounds = [(B * k // split, B * (k + 1) // split) for k in range(split)]
-        self._drive_rounds([self._multi_h_rounds(st, lo, hi, None, maskRegionTh, sample_fn, want_lists, trace) for lo, hi in bounds])
-        outs = st["outs"]
-        for b in range(B):
-            outs[b]["mask"] = st["Mask"][b]
-            outs[b]["nbH"] = st["nb"][b]
-            outs[b]["matches"] = (idx1[b], idx2[b], cnt[b:b + 1])      # the cached mutual matches (rows beyond the count: undefined)
-        return outs
+        batch = dict(feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, bg=None if It_bg is None else It_bg.to(dev).float().contiguous(),
+                     Mask=torch.zeros((B, h_org, w_org), dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
+                     tensor_s=tensor_s, tensor_d2=tensor_d2, tensor_resize=tensor_resize, cc_th=cc_th, remove_small_cc=remove_small_cc)
+        rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.KittiGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
+        return st.close(lambda b: batch["Mask"][b], (idx1, idx2, cnt))
 
     # ---------------------------------------------------------------- whole path
     def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0):
