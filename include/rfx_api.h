@@ -42,9 +42,10 @@ const char* rfx_version(void);
  * rfx_compose_flow_f32 gained Hc/Wc, 3x3/s1/p1 geometries moved to rfx_conv3x3_f32's packed weights; round 3: multi-homography
  * round kernels, two-direction correlation, grouped launches; round 4: rfx_draw_samples_i64 keyed by pair id; 11: the ragged-batch
  * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes; 12: the ragged forms of the
- * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32).  A binding
+ * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32; 13:
+ * rfx_conv1x1_split_tile_channels).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 12
+#define RFX_ABI_VERSION 13
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -579,6 +580,12 @@ int rfx_conv1x1_split_f32(const float* in, const void* wS, const float* scale, c
  * Ho = (Hin - 1) / stride + 1, reads input pixel (y * stride, x * stride). */
 int rfx_conv1x1_split_strided_f32(const float* in, const void* wS, const float* scale, const float* shift, const float* residual,
                                   float* out, int N, int Cin, int Hin, int Win, int Cout, int stride, int act, void* stream);
+/* Output channels per workgroup tile of the two launches above at N images of HWout OUTPUT pixels: 64 (Cout <= 64), 128, or 256 --
+ * the 8-wavefront instance that stages a 128-pixel activation image once for 256 channels, taken where Cout >= 256, Cin >= 512 and
+ * the launch's rounds over the CUs come out shorter than the 128-channel tile's (the measured rule in csrc/conv1x1s.hip).  Every
+ * instance returns the same bits (same k order, same products, same epilogue).
+ * RFX_C1S_WIDE (environment, read once): 0 = never 256; 1 = 256 wherever Cout >= 256. */
+int rfx_conv1x1_split_tile_channels(int N, int Cin, int HWout, int Cout);
 /* rfx_conv3x3_split_f32 (ABI 10): the same scheme for the 3x3 / stride 1 / pad 1 convolution (ResNet-50 layer3 conv2,
  * model/resnet50.py:75; the FeatureExtractor's BasicBlock convolutions, model/model.py:32-35; conv2 / conv3 of the NetFlowCoarse /
  * NetMatchability stacks, model/model.py:170-181): nine shifted 1x1 products over one staged, split halo patch.  Cin % 16 == 0.

@@ -23,8 +23,16 @@
 // (4.5 vector-ALU instructions per element, once per workgroup) and store three 16-byte words into the LDS image
 //     Bs[piece][h][pixel (128)][8 bf16]
 // so that both fragments of an MFMA are single conflict-free ds_read_b128 (consecutive lanes, consecutive words).
-// Tile 64*TM channels x 128 pixels, 2 x 2 wavefronts, one 16-k block per stage, LDS double buffered, one barrier per stage:
-// registers hold block s+1 while block s runs on the matrix pipe and block s+2 is in flight.
+// One 16-k block per stage, LDS double buffered, one barrier per stage: registers hold block s+1 while block s runs on the matrix
+// pipe and block s+2 is in flight.  Every wavefront owns 32 TM channels x 64 pixels; two tiles:
+//   * 64 TM channels x 128 pixels, 2 x 2 wavefronts (conv1x1_split_kernel<TM>): TM = 1 for Cout <= 64, TM = 2 otherwise;
+//   * 256 channels x 128 pixels, 4 x 2 wavefronts on 512 threads (conv1x1_split_wide_kernel): the SAME 128-pixel activation image per
+//     stage under twice the matrix work -- the activation loads, the split and the Bs writes per MFMA halve (each thread stages 4 k
+//     of a pixel instead of 8), a layer with Cout <= 256 reads and splits its input exactly once, a 1024-channel layer 4 times
+//     instead of 8.  74 KB of LDS: one workgroup per CU, the same 2 wavefronts per SIMD as two 128-channel workgroups.  Taken where
+//     Cout >= 256, Cin >= 512 and the launch's rounds over the CUs come out shorter (c1s_tile_channels; RFX_C1S_WIDE=0: never).
+// Only the assignment of tiles to wavefronts differs: every output element sees the same 16-k blocks in the same order, the same six
+// products per block into the same two accumulators, one acc += low and the same epilogue -- the tiles agree bit for bit.
 // Infinities: x = +-inf gives hi = inf, x - hi = NaN -> NaN where the fp32 kernel returns +-inf (NaN inputs give NaN in both).
 #include "common.h"
 #include "conv_epilogue.h"
@@ -36,6 +44,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct C1SArgs {
     const float* in; const u32x4* wS; const float* scale; const float* shift; const float* res; float* out;
@@ -65,11 +74,14 @@ __device__ __forceinline__ bf16x8 as_frag(const u32x4& w) {
     return f;
 }
 
-template <int TM>
+// WM wavefronts along the channels x 2 along the pixels, each with a 32 TM x 64 output: <1, 2> / <2, 2> = 64 / 128 channels on 256
+// threads, <2, 4> = the wide tile, 256 channels on 512 threads over the SAME 128-pixel activation image.
+template <int TM, int WM>
 __device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsigned bx) {
-    constexpr int BM = 64 * TM, BN = 128, KB = 16;
-    constexpr int A_WORDS = 3 * 2 * BM;                 // 16-byte words of a stage's weight image: 768 / 384
-    constexpr int NA = (A_WORDS + 255) / 256;           // per thread: 3 / 2 (the second one only for t < 128)
+    constexpr int BM = 32 * TM * WM, BN = 128, KB = 16, NT = 128 * WM;
+    constexpr int A_WORDS = 3 * 2 * BM;                 // 16-byte words of a stage's weight image: 384 / 768 / 1536
+    constexpr int NA = (A_WORDS + NT - 1) / NT;         // per thread: 2 (the second one only for t < 128) / 3 / 3
+    constexpr bool WIDE = WM == 4;
     __shared__ u32x4 As[2][3][2][BM];
     __shared__ u32x4 Bs[2][3][2][BN];
     __shared__ float s_scale[BM], s_shift[BM];
@@ -89,13 +101,18 @@ __device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsig
         m0 = (bid % a.tilesM) * BM;
         n0 = (long long)(bid / a.tilesM) * BN;
     }
-    // staging roles.  A: words t + 256 j of the stage image [piece][h][BM] <- wS[kb][piece][h][m0 + m]
-    constexpr int A_ROWS = 256 / BM;                                                  // word t + 256 j sits A_ROWS * j [piece][h] rows below word t
+    // staging roles.  A: words t + NT j of the stage image [piece][h][BM] <- wS[kb][piece][h][m0 + m]
+    constexpr int A_ROWS = NT / BM;                                                   // word t + NT j sits A_ROWS * j [piece][h] rows below word t
+    // Mpad is a multiple of 128: the last wide tile of a Cout in (256 j, 256 j + 128] ends 128 rows past it -- those lanes read the
+    // last row instead (any valid word: their outputs are channels >= Cout, which the epilogue does not store)
     const u32x4* wsrc = a.wS + (size_t)(t / BM) * a.Mpad + m0 + t % BM;              // + (kb * 6 + A_ROWS * j) * Mpad
+    if (WIDE && m0 + t % BM >= a.Mpad) wsrc = a.wS + (size_t)(t / BM) * a.Mpad + a.Mpad - 1;
     // piece j exists for every thread (compile time) or for the first wavefronts only (TM = 1: 384 words): no per-lane branches around
     // the loads -- a divergent region makes the compiler drain the vector-memory counter between two loads
-    auto a_on = [&](int j) { return (j + 1) * 256 <= A_WORDS || t + 256 * j < A_WORDS; };
-    // B: thread = (h = t >> 7, pixel t & 127): rows k0 + 8 h .. + 7 of that pixel
+    auto a_on = [&](int j) { return (j + 1) * NT <= A_WORDS || t + NT * j < A_WORDS; };
+    // B: thread = (q = t >> 7, pixel t & 127): rows k0 + NB q .. + NB - 1 of that pixel, NB = 8 (256 threads: one 16-byte word of
+    // each piece) or 4 (512 threads: one half of it -- every wavefront loads and splits the same share, no branch around the loads)
+    constexpr int NB = 2048 / NT;
     const int bh = t >> 7, bp = t & 127;
     const float* bsrc;
     {
@@ -104,31 +121,45 @@ __device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsig
         const long long n = p / a.HW;
         int off = (int)(p - n * a.HW);
         if (a.stride != 1) { const int y = off / a.Wo, x = off - y * a.Wo; off = y * a.stride * a.Win + x * a.stride; }
-        bsrc = a.in + ((size_t)n * a.Cin + 8 * bh) * HWin + (size_t)off;                          // + k0 * HWin
+        bsrc = a.in + ((size_t)n * a.Cin + NB * bh) * HWin + (size_t)off;                         // + k0 * HWin
     }
     u32x4 ra[NA];
-    float rb[8];
+    float rb[NB];
     auto load_stage = [&](int kb) {
 #pragma unroll
         for (int j = 0; j < NA; ++j)
             ra[j] = wsrc[((size_t)kb * 6 + (a_on(j) ? A_ROWS * j : 0)) * a.Mpad];              // off lanes: any valid word
 #pragma unroll
-        for (int i = 0; i < 8; ++i) rb[i] = bsrc[(size_t)(kb * KB + i) * HWin];
+        for (int i = 0; i < NB; ++i) rb[i] = bsrc[(size_t)(kb * KB + i) * HWin];
     };
     auto store_stage = [&](int buf) {
 #pragma unroll
         for (int j = 0; j < NA; ++j)
-            if (a_on(j)) (&As[buf][0][0][0])[t + 256 * j] = ra[j];
-        u32x4 hi, mid, lo;
+            if (a_on(j)) (&As[buf][0][0][0])[t + NT * j] = ra[j];
+        if constexpr (NB == 8) {
+            u32x4 hi, mid, lo;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            unsigned h_, m_, l_;
-            split_pair(rb[2 * i], rb[2 * i + 1], h_, m_, l_);
-            hi[i] = h_; mid[i] = m_; lo[i] = l_;
+            for (int i = 0; i < 4; ++i) {
+                unsigned h_, m_, l_;
+                split_pair(rb[2 * i], rb[2 * i + 1], h_, m_, l_);
+                hi[i] = h_; mid[i] = m_; lo[i] = l_;
+            }
+            Bs[buf][0][bh][bp] = hi;
+            Bs[buf][1][bh][bp] = mid;
+            Bs[buf][2][bh][bp] = lo;
+        } else {                                            // k half bh >> 1, 8-byte half bh & 1 of its word
+            u32x2 hi, mid, lo;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                unsigned h_, m_, l_;
+                split_pair(rb[2 * i], rb[2 * i + 1], h_, m_, l_);
+                hi[i] = h_; mid[i] = m_; lo[i] = l_;
+            }
+            u32x2* w = reinterpret_cast<u32x2*>(&Bs[buf][0][bh >> 1][bp]) + (bh & 1);
+            w[0] = hi;
+            w[4 * BN] = mid;                                // one piece = 2 * BN words of two halves
+            w[8 * BN] = lo;
         }
-        Bs[buf][0][bh][bp] = hi;
-        Bs[buf][1][bh][bp] = mid;
-        Bs[buf][2][bh][bp] = lo;
     };
     if (t < BM) {
         const int m = m0 + t;
@@ -204,14 +235,25 @@ __device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsig
 
 template <int TM>
 __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(C1SArgs a) {
-    conv1x1_split_body<TM>(a, blockIdx.x);
+    conv1x1_split_body<TM, 2>(a, blockIdx.x);
 }
 
 template <int TM>
 __global__ __launch_bounds__(256, 2) void conv1x1_split_group_kernel(RfxGroupArgs<C1SArgs> g) {
     const unsigned y = blockIdx.y;
     if (blockIdx.x >= g.gx[y]) return;
-    conv1x1_split_body<TM>(g.p[y], blockIdx.x);
+    conv1x1_split_body<TM, 2>(g.p[y], blockIdx.x);
+}
+
+// the wide tile: 74 KB of LDS, one workgroup of 8 wavefronts per CU -- 2 wavefronts per SIMD, as two 256-thread workgroups have
+__global__ __launch_bounds__(512, 1) void conv1x1_split_wide_kernel(C1SArgs a) {
+    conv1x1_split_body<2, 4>(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(512, 1) void conv1x1_split_wide_group_kernel(RfxGroupArgs<C1SArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    conv1x1_split_body<2, 4>(g.p[y], blockIdx.x);
 }
 
 template <int TM>
@@ -219,14 +261,53 @@ static int c1s_group_launch(const void* blob, const unsigned* gx, int n, hipStre
     return rfx_group_launch_impl<C1SArgs>(conv1x1_split_group_kernel<TM>, 256, blob, gx, n, st);
 }
 
-template <int TM>
+static int c1s_wide_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<C1SArgs>(conv1x1_split_wide_group_kernel, 512, blob, gx, n, st);
+}
+
+// Channels per workgroup tile of a launch: 64 (Cout <= 64), 128, or 256 where the wide tile is the faster one.  Measured (MI355X,
+// scripts/ubench/split_bench.py --c1s-ab, profiles/c1s_wide_ab.json):
+//   * a wide workgroup has its CU to itself, so its epilogue (residual loads, stores) overlaps no other workgroup's K loop: with
+//     Cin <= 256 the wide tile is level with or behind the 128-channel one (256 -> 1024 + residual 1.01x / 0.95x / 0.92x at 60x80 /
+//     25x33 / 15x20, 128 -> 512 0.97x), from Cin = 512 on it is 4 - 11 % faster on full launches -> Cin >= 512 only;
+//   * workgroup times at K = 512 (K = 1024 alike): one 128-channel workgroup alone on its CU 0.031 ms, two of them sharing it
+//     0.053 ms, one wide one 0.043 ms = 0.58 : 1 : 0.81.  A launch takes its rounds over the CUs: W wide workgroups
+//     ceil(W / CUs) * 0.81; the 2 W 128-channel ones 1 per full round of 2 CUs workgroups, plus 0.58 for a rest of at most one per
+//     CU or 1 for a larger rest.  The rule takes the cheaper side; it reproduces every measured winner (W = 150, 207, 413, >= 1200
+//     wide; W = 38, 75, 300 not).  Large launches always come out wide; the small pyramid levels and late multi-homography rounds
+//     mostly stay on 128 channels.
+// RFX_C1S_WIDE (read once): 0 = never the wide tile, 1 = wherever Cout >= 256 (A/B runs and tests).
+int c1s_tile_channels(long long P, int Cin, int Cout) {
+    static const int mode = [] { const char* e = getenv("RFX_C1S_WIDE"); return e ? (atoi(e) == 0 ? 0 : 1) : -1; }();
+    static const long long cus = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return (long long)(n > 0 ? n : 256);
+    }();
+    if (Cout <= 64) return 64;
+    if (Cout < 256 || mode == 0) return 128;
+    if (mode == 1) return 256;
+    if (Cin < 512) return 128;
+    const long long tp = (P + 127) / 128, w = (Cout + 255) / 256 * tp, n = (Cout + 127) / 128 * tp;
+    const long long rest = n % (2 * cus);
+    const long long cost_wide = (w + cus - 1) / cus * 81, cost_128 = n / (2 * cus) * 100 + (rest == 0 ? 0 : rest <= cus ? 58 : 100);
+    return cost_wide < cost_128 ? 256 : 128;
+}
+
+template <int TM, int WM>
 int launch_split(C1SArgs& a, hipStream_t st) {
-    a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
+    constexpr int BM = 32 * TM * WM;
+    a.tilesM = (a.Cout + BM - 1) / BM;
     a.tilesP = (int)((a.P + 127) / 128);
     const long long nwg = (long long)a.tilesM * a.tilesP;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    if (rfx_group_recording()) return rfx_group_record(&c1s_group_launch<TM>, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL((conv1x1_split_kernel<TM>), dim3((unsigned)nwg), dim3(256), 0, st, a);
+    if constexpr (WM == 4) {
+        if (rfx_group_recording()) return rfx_group_record(&c1s_wide_group_launch, &a, sizeof(a), (unsigned)nwg);
+        hipLaunchKernelGGL(conv1x1_split_wide_kernel, dim3((unsigned)nwg), dim3(512), 0, st, a);
+    } else {
+        if (rfx_group_recording()) return rfx_group_record(&c1s_group_launch<TM>, &a, sizeof(a), (unsigned)nwg);
+        hipLaunchKernelGGL((conv1x1_split_kernel<TM>), dim3((unsigned)nwg), dim3(256), 0, st, a);
+    }
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -244,7 +325,16 @@ static int conv1x1_split_launch(const float* in, const void* wS, const float* sc
     a.Cin = Cin; a.HW = Ho * Wo; a.Cout = Cout; a.act = act; a.Mpad = (Cout + 127) / 128 * 128;
     a.P = (long long)N * a.HW;
     a.stride = stride; a.Win = Win; a.Wo = Wo; a.HWin = Hin * Win;
-    return Cout > 64 ? launch_split<2>(a, rfx_stream(stream)) : launch_split<1>(a, rfx_stream(stream));
+    switch (c1s_tile_channels(a.P, Cin, Cout)) {
+        case 256: return launch_split<2, 4>(a, rfx_stream(stream));
+        case 128: return launch_split<2, 2>(a, rfx_stream(stream));
+        default: return launch_split<1, 2>(a, rfx_stream(stream));
+    }
+}
+
+extern "C" int rfx_conv1x1_split_tile_channels(int N, int Cin, int HWout, int Cout) {
+    if (N <= 0 || Cin <= 0 || HWout <= 0 || Cout <= 0) return RFX_E_ARG;
+    return c1s_tile_channels((long long)N * HWout, Cin, Cout);
 }
 
 extern "C" int rfx_conv1x1_split_f32(const float* in, const void* wS, const float* scale, const float* shift, const float* residual,
