@@ -569,7 +569,7 @@ def lanczos_resize_u8(img, out_w, out_h):
         _LANCZOS_TABLES[key] = tabs
         while len(_LANCZOS_TABLES) > _LANCZOS_MAX:
             # the evicted tensors stay alive for as long as a kernel that reads them is queued (stream-ordered allocator); a captured
-            # HIP graph that baked their addresses in holds its own references (pipeline._features_graphed keeps `prep`)
+            # HIP graph that baked their addresses in holds its own references (trunk_pass.graphed keeps `prep` in the cache entry)
             _LANCZOS_TABLES.popitem(last=False)
     else:
         _LANCZOS_TABLES.move_to_end(key)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import PIL.Image as Image
 
-from . import ops, rounds
+from . import ops, rounds, trunk_pass
 from .nets import ResNet50Trunk, FeatureExtractorNet, NetFlowCoarseNet, NetMatchabilityNet
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -54,7 +54,7 @@ _CELL_COORDS_MAX = 64
 def cell_coords_cached(n_rows, n_cols, device):
     """cell_coords() memoised per (shape, device): the grids are constants of the map size (a dozen tiny ATen launches per
     pyramid level and step otherwise).  LRU-bounded (64 shapes: a stream of variable-size pairs must not grow it for ever).
-    Captured HIP graphs (_features_graphed, prepare_and_features) bake these tensors' addresses into their kernels: the feature
+    Captured HIP graphs (trunk_pass.graphed) bake these tensors' addresses into their kernels: the feature
     dict a capture returns carries the tensors it read (``_coord_refs``), so an evicted entry stays alive for as long as a graph
     that replays against it does."""
     key = (n_rows, n_cols, str(device))
@@ -176,6 +176,8 @@ class AlignPipeline:
         self.scaleList = scale_list(nbScale, scaleR)
         self.mean = torch.tensor(IMAGENET_MEAN).view(1, 3, 1, 1)
         self.std = torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
+        self._capture = trunk_pass.CapturePolicy(self.MAX_GRAPHS)       # which trunk-pass shapes replay a HIP graph
+        self._graphs = self._capture.entries
 
     def _degenerate_mode(self, host_draw):
         if self.degenerate == "auto":
@@ -397,15 +399,6 @@ class AlignPipeline:
                 out[b] = {key: v[k:k + 1] for key, v in f.items()}
         return out
 
-    def _trunk(self, x):
-        """self.trunk(x), optionally in sub-batches of RFX_TRUNK_CHUNK images (experiment knob, round 6: does a working set that fits
-        the 256 MB Infinity Cache make the layer-to-layer re-reads cheaper than the smaller launches cost?).  Every sample is
-        computed independently: bit-identical."""
-        ch = int(os.environ.get("RFX_TRUNK_CHUNK", "0"))
-        if ch <= 0 or x.shape[0] <= ch:
-            return self.trunk(x)
-        return torch.cat([self.trunk(x[i:i + ch]) for i in range(0, x.shape[0], ch)], dim=0)
-
     # ---------------------------------------------------------------- coarse stage
     def features(self, prep):
         """ResNet-50 conv4 features of every pyramid level and of the target, L2-normalised, written into
@@ -418,236 +411,41 @@ class AlignPipeline:
         whose per-launch events cannot be recorded into a graph)."""
         if prep.get("ragged"):
             return self._features_ragged(prep)
-        B = prep["B"]
-        if B <= 4 and os.environ.get("RFX_GRAPH", "1") != "0" and ops.Profiler.active() is None:
+        if trunk_pass.graph_eligible(prep["B"]):
             return self._features_graphed(prep)
         return self._features_eager(prep)
 
     MAX_GRAPHS = 4      # captured shapes kept (LRU): each pins a private memory pool + static input / output buffers
 
+    def _cell_coords(self, n_rows, n_cols):
+        return cell_coords_cached(n_rows, n_cols, self.dev)
+
+    def _features_eager(self, prep):
+        return trunk_pass.features_eager(self, prep)
+
     def _features_graphed(self, prep):
-        """HIP-graph replay of the trunk pass.  A shape is captured at its SECOND sighting (a stream of variable-size pairs
-        never pays warm-up + capture for shapes it sees once) and at most MAX_GRAPHS captures are kept (LRU; an evicted
-        entry releases its graph, pool and static buffers).  Warm-up, capture and replay run under the pipeline's own
-        device: ``torch.cuda.graph`` captures the CURRENT device's stream, while the kernels launch on self.dev's."""
-        import collections
+        """HIP-graph replay of the trunk pass over the pyramid levels and the target (trunk_pass.graphed: captured at the SECOND
+        sighting of a shape, at most MAX_GRAPHS captures kept)."""
+        B = prep["B"]
         key = (tuple(tuple(x.shape) for x in prep["src"]), tuple(prep["tgt"].shape))
-        cache = self.__dict__.setdefault("_graphs", collections.OrderedDict())
-        seen = self.__dict__.setdefault("_graph_seen", collections.OrderedDict())
-        ent = cache.get(key)
-        if ent is None:
-            if key not in seen:
-                seen[key] = True
-                while len(seen) > 64:
-                    seen.popitem(last=False)
-                return self._features_eager(prep)
-            with torch.cuda.device(self.dev):
-                self._features_eager(prep)                  # warm-up: lazily built state (packed weights ...) must exist
-                torch.cuda.synchronize(self.dev)
-                static = dict(src=[x.clone() for x in prep["src"]], tgt=prep["tgt"].clone(), B=prep["B"])
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    out = self._features_eager(static)
-                # an empty capture (kernels launched outside the captured stream) would replay stale features for ever:
-                # check once that a replay really rewrites the outputs
-                out["featA"].zero_()
-                g.replay()
-                torch.cuda.synchronize(self.dev)
-                if not bool(out["featA"].abs().sum() > 0):
-                    raise RuntimeError("HIP-graph capture of the trunk pass is empty (kernels did not go to the capture stream)")
-            ent = cache[key] = (g, static, out)
-            while len(cache) > self.MAX_GRAPHS:
-                cache.popitem(last=False)
-        else:
-            cache.move_to_end(key)
-        g, static, out = ent
-        with torch.cuda.device(self.dev):
-            for d, x in zip(static["src"], prep["src"]):
-                d.copy_(x)
-            static["tgt"].copy_(prep["tgt"])
-            g.replay()
-            res = dict(out)
-            res["featA"], res["featB"] = out["featA"].clone(), out["featB"].clone()   # the graph's own buffers are reused by the next replay
-        return res
+        body = lambda t: (None, self._features_eager(dict(src=list(t[:-1]), tgt=t[-1], B=B)))
+        return trunk_pass.graphed(self, key, (*prep["src"], prep["tgt"]), body)[1]
 
     def prepare_and_features(self, src_u8, tgt_u8):
         """prepare_device + features -> (prep, feats).  Small batches (B <= 4): ONE HIP graph from the raw uint8 images to the
         normalised features -- the device pyramid (24 launches of tiny kernels per pair) is as launch-bound as the trunk pass, and
-        a graph that starts at the raw images needs 2 input copies instead of 8.  Same capture policy as _features_graphed (second
-        sighting, LRU of MAX_GRAPHS, non-empty check); the returned ``prep`` tensors belong to the graph and are valid until its
-        next replay.  Larger batches, RFX_GRAPH=0 or an active Profiler: the two eager calls."""
-        import collections
-        B = src_u8.shape[0]
-        if not (B <= 4 and os.environ.get("RFX_GRAPH", "1") != "0" and ops.Profiler.active() is None):
+        a graph that starts at the raw images needs 2 input copies instead of 8.  Same capture policy and cache as _features_graphed;
+        the returned ``prep`` tensors belong to the graph and are valid until its next replay.  Larger batches, RFX_GRAPH=0 or an
+        active Profiler: the two eager calls."""
+        if not trunk_pass.graph_eligible(src_u8.shape[0]):
             prep = self.prepare_device(src_u8, tgt_u8)
             return prep, self.features(prep)
         key = ("raw", tuple(src_u8.shape), tuple(tgt_u8.shape))
-        cache = self.__dict__.setdefault("_graphs", collections.OrderedDict())
-        seen = self.__dict__.setdefault("_graph_seen", collections.OrderedDict())
-        ent = cache.get(key)
-        if ent is None:
-            if key not in seen:
-                seen[key] = True
-                while len(seen) > 64:
-                    seen.popitem(last=False)
-                prep = self.prepare_device(src_u8, tgt_u8)
-                return prep, self._features_eager(prep)
-            with torch.cuda.device(self.dev):
-                self._features_eager(self.prepare_device(src_u8, tgt_u8))     # warm-up: lazily built state must exist
-                torch.cuda.synchronize(self.dev)
-                static = (src_u8.clone(), tgt_u8.clone())
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    prep = self.prepare_device(*static)
-                    out = self._features_eager(prep)
-                out["featA"].zero_()
-                g.replay()
-                torch.cuda.synchronize(self.dev)
-                if not bool(out["featA"].abs().sum() > 0):
-                    raise RuntimeError("HIP-graph capture of the pyramid + trunk pass is empty (kernels did not go to the capture stream)")
-            ent = cache[key] = (g, static, (prep, out))
-            while len(cache) > self.MAX_GRAPHS:
-                cache.popitem(last=False)
-        else:
-            cache.move_to_end(key)
-        g, static, (prep, out) = ent
-        with torch.cuda.device(self.dev):
-            static[0].copy_(src_u8)
-            static[1].copy_(tgt_u8)
-            g.replay()
-            res = dict(out)
-            res["featA"], res["featB"] = out["featA"].clone(), out["featB"].clone()   # the graph's own buffers are reused by the next replay
-        return prep, res
 
-    def _features_eager(self, prep):
-        B = prep["B"]
-        dims = [(x.shape[2] // 16, x.shape[3] // 16) for x in prep["src"]]
-        nA = sum(r * c for r, c in dims)
-        ldA = (nA + 3) // 4 * 4      # rows padded to 16 bytes: the mutual-NN kernel then stages with float4 loads
-        featA = torch.empty((B, 1024, ldA), dtype=torch.float32, device=self.dev)
-        Ws, Hs, offs = [], [], []
-        off = 0
-        for (r, c) in dims:
-            W, Hh = cell_coords_cached(r, c, self.dev)
-            Ws.append(W)
-            Hs.append(Hh)
-            offs.append(off)
-            off += r * c
-        tgt = prep["tgt"]
-        # The pyramid levels are independent trunk passes.  With S > 1 streams (RFX_TRUNK_STREAMS) they are dealt to S HIP streams
-        # (largest level first) so that the launch tails of one level -- the /16 maps of the small levels have few
-        # workgroups per layer -- overlap with the next level's kernels; every level still writes its own columns of featA.
-        # Default: one stream per level for small batches (B <= 4: a layer of one level has too few workgroups to fill 256 CUs
-        # -- a single 480x640 pair drops from 15.9 to 10.6 ms), four streams otherwise; ONE stream under an ops.Profiler
-        # (overlapping launches would distort the per-kernel event timing bench.py's rooflines are computed from).
-        # (measured, coarse stage of 480x640 pairs: B = 1 7.73 -> 6.83 ms, B = 2 10.15 -> 9.99 ms, B = 4 16.7 -> 18.3 ms: from four
-        # pairs on the per-level batches are large enough for the 8-stream form to win)
-        grouped = (B <= 2 and os.environ.get("RFX_GROUPED", "1") != "0" and ops.Profiler.active() is None
-                   and not os.environ.get("RFX_TRUNK_STREAMS"))
-        ft_raw = None
-        if grouped:
-            # Small batches: the 8 images of a pair (7 pyramid levels + target) have 8 different sizes, so a layer is 8 launches
-            # of 2-150 workgroups on 256 CUs and the pass is bound by one workgroup lifetime per layer AND level.  All levels
-            # go through the trunk layer by layer with ONE grouped launch per kernel instance and layer (nets.forward_group:
-            # blockIdx.y selects the image); bit-identical to the per-level passes.
-            xs, shared = [], None
-            for i, x in enumerate(prep["src"]):
-                if shared is None and x.shape == tgt.shape:
-                    xs.append(torch.cat((x, tgt), dim=0))           # the scale-1 level and the target: one problem of 2B images
-                    shared = i
-                else:
-                    xs.append(x)
-            if shared is None:
-                xs.append(tgt)
-            nch = max(1, int(os.environ.get("RFX_GROUP_CHAINS", "2")))
-            if nch == 1:
-                fs = self.trunk.forward_group(xs)
-                for i, (r, c) in enumerate(dims):
-                    f = fs[i][:B] if i == shared else fs[i]
-                    ops.l2norm(f, out=featA[:, :, offs[i]:], out_batch_stride=1024 * ldA, out_chan_stride=ldA)
-            else:
-                # The images split into k pixel-balanced subsets, each its own grouped chain on its own stream (captured as a fork /
-                # join of the graph): the launch tails of one chain overlap the other's kernels.  Single 480x640 pair: 6.08-6.35 -> 5.38-5.70 ms
-                # with two chains on the same box (three: 5.7-6.3, four: 5.8), two pairs 10.22 -> 9.54 ms; each chain keeps its kernel
-                # instances serial on its stream.  RFX_GROUP_CHAINS=1: one chain + the library's side streams (round 3's first form).
-                order = sorted(range(len(xs)), key=lambda i: -xs[i].numel())
-                chains, load = [[] for _ in range(nch)], [0] * nch
-                for i in order:                      # largest first to the lighter chain (measured against "the two largest levels
-                    k = load.index(min(load))        # vs the rest" 5.63 ms and alternating 5.99 ms: 5.38-5.43 ms)
-                    chains[k].append(i)
-                    load[k] += xs[i].numel()
-                if getattr(self, "_chain_streams", None) is None or len(self._chain_streams) != nch - 1:
-                    self._chain_streams = [torch.cuda.Stream(device=self.dev) for _ in range(nch - 1)]
-                main_s = torch.cuda.current_stream(self.dev)
-                ready_c = torch.cuda.Event()
-                ready_c.record(main_s)
-                fs, done_c = [None] * len(xs), []
-                for k, idxs in enumerate(chains):
-                    if not idxs:
-                        continue
-                    st = main_s if k == 0 else self._chain_streams[k - 1]
-                    with torch.cuda.stream(st):
-                        if k:
-                            st.wait_event(ready_c)
-                        # (side streams inside a chain, shared or one pool per chain, crash the process on ROCm 7.2: chains stay serial)
-                        out = self.trunk.forward_group([xs[i] for i in idxs], side_streams=False)
-                        for i, f in zip(idxs, out):
-                            fs[i] = f
-                            if i < len(dims):
-                                ops.l2norm(f[:B] if i == shared else f, out=featA[:, :, offs[i]:], out_batch_stride=1024 * ldA,
-                                           out_chan_stride=ldA)
-                        if k:
-                            ev = torch.cuda.Event()
-                            ev.record(st)
-                            done_c.append(ev)
-                for ev in done_c:
-                    main_s.wait_event(ev)
-                for f in fs:
-                    f.record_stream(main_s)
-            ft_raw = fs[shared][B:] if shared is not None else fs[-1]
-        env = os.environ.get("RFX_TRUNK_STREAMS")
-        # larger batches: 4 streams (round 6, profiles/r06_stream_sweep.txt: 1 / 2 / 4 / 8 streams = 113.6 / 113.0 / 114.6 / 114.8 pairs/s
-        # on config 3 with 3 lock-step groups) -- the tail of one level's layer overlaps another level's kernels
-        nstream = max(1, int(env)) if env else (len(prep["src"]) if B <= 4 else min(4, len(prep["src"])))
-        if ops.Profiler.active() is not None:
-            nstream = 1          # per-launch event timing: overlapping streams would charge one kernel with another's time
-        main = torch.cuda.current_stream(self.dev)
-        if not grouped and nstream > 1 and (getattr(self, "_streams", None) is None or len(self._streams) != nstream):
-            # (stream priorities for the largest levels -- the critical path of a small-batch pass -- were measured: 7.7 ->
-            # 9.1-9.2 ms with one or two high-priority queues; all queues stay equal)
-            self._streams = [torch.cuda.Stream(device=self.dev) for _ in range(nstream)]
-        ready = torch.cuda.Event()
-        if nstream > 1 and not grouped:
-            ready.record(main)
-        done = []
-        for i, (x, (r, c)) in enumerate(zip(prep["src"], dims)):
-            if grouped:
-                break
-            st = self._streams[i % nstream] if nstream > 1 else main
-            with torch.cuda.stream(st):
-                if nstream > 1:
-                    st.wait_event(ready)
-                if ft_raw is None and x.shape == tgt.shape:
-                    # the pyramid level of scale 1 has the target's size: one trunk pass over both (twice the batch, one
-                    # launch tail less per layer); every sample is computed independently, bit-identical to two passes
-                    f2 = self._trunk(torch.cat((x, tgt), dim=0))
-                    f, ft_raw = f2[:B], f2[B:]
-                else:
-                    f = self._trunk(x)
-                ops.l2norm(f, out=featA[:, :, offs[i]:], out_batch_stride=1024 * ldA, out_chan_stride=ldA)
-                if nstream > 1:
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    done.append(ev)
-        for ev in done:
-            main.wait_event(ev)
-        if ft_raw is not None and nstream > 1 and not grouped:
-            ft_raw.record_stream(main)
-        ft = ops.l2norm(ft_raw if ft_raw is not None else self.trunk(tgt))
-        rt, ct = ft.shape[2], ft.shape[3]
-        Wt, Ht = cell_coords_cached(rt, ct, self.dev)
-        return dict(featA=featA, featB=ft.view(B, 1024, rt * ct), nA=nA, ldA=ldA, nB=rt * ct, WA=torch.cat(Ws), HA=torch.cat(Hs),
-                    Wt=Wt, Ht=Ht, rt=rt, ct=ct, _coord_refs=(Ws, Hs))
+        def body(t):
+            prep = self.prepare_device(*t)
+            return prep, self._features_eager(prep)
+        return trunk_pass.graphed(self, key, (src_u8, tgt_u8), body, what="pyramid + trunk pass")
 
     def coarse(self, prep, feats=None, samples=None, maskB=None, sample_fn=None, pair_ids=None, draw_epoch=0):
         """Per pair: mutual NN -> matches -> RANSAC.  Index draw (utils/outil.py:120): ``samples`` = list of (nbIter,4) int64

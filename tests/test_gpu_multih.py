@@ -217,6 +217,61 @@ def test_graph_from_raw_images_equals_the_eager_calls(dev, monkeypatch):
     assert len(res) == 1
 
 
+TRUNK_SWITCHES = ("RFX_GRAPH", "RFX_GROUPED", "RFX_GROUP_CHAINS", "RFX_TRUNK_STREAMS")
+# (batch, calls, one environment per run): the launch forms of the trunk pass besides the default small-batch ones
+TRUNK_FORMS = {
+    "grouped_one_then_three_chains": (1, 1, [dict(RFX_GRAPH="0", RFX_GROUP_CHAINS="1"), dict(RFX_GRAPH="0", RFX_GROUP_CHAINS="3")]),
+    "two_levels_per_stream": (1, 1, [dict(RFX_GRAPH="0", RFX_GROUPED="0", RFX_TRUNK_STREAMS="2")]),
+    "graphed_stream_per_level": (3, 2, [dict(RFX_GRAPH="1")]),
+    "large_batch_defaults": (5, 1, [dict()]),
+}
+
+
+@pytest.fixture(scope="module")
+def trunk_forms(dev):
+    """One pipeline for all cases, and the plain form -- no graph, no grouped launches, one stream: one trunk pass per level and one
+    for the target (or one over the scale-1 level and the target together), back to back -- computed once per (batch, target height)."""
+    pipe = AlignPipeline(dict(trunk=weights.resnet50_trunk_sd(0)), nbScale=3, nbIter=10, tolerance=0.05, minSize=160, scaleR=1.2,
+                         device=dev)
+    cache = {}
+
+    def get(B, tgt_h):
+        if (B, tgt_h) not in cache:
+            prep = pipe.prepare([(synth.make_pair(128, 160, seed=s)[0], synth.make_pair(tgt_h, 160, seed=s)[1]) for s in range(B)])
+            with pytest.MonkeyPatch.context() as mp:
+                for k, v in dict(RFX_GRAPH="0", RFX_GROUPED="0", RFX_TRUNK_STREAMS="1").items():
+                    mp.setenv(k, v)
+                f = pipe.features(prep)
+            cache[(B, tgt_h)] = prep, f["featA"].clone(), f["featB"].clone()
+        return cache[(B, tgt_h)]
+    return pipe, get
+
+
+@pytest.mark.parametrize("tgt_h", [128, 96], ids=["level_paired_with_target", "target_alone"])
+@pytest.mark.parametrize("form", sorted(TRUNK_FORMS))
+def test_trunk_pass_forms_equal_the_plain_form(trunk_forms, monkeypatch, form, tgt_h):
+    """Every launch form of the trunk pass -- one grouped chain, three balanced chains on their own streams, per-level passes two to
+    a stream, the captured graph of the stream-per-level form (first sighting, then capture + replay), the large-batch default --
+    gives the plain form's features bit for bit, with a target of the scale-1 level's shape (one pass of 2B images over both) and
+    with a target of its own shape (tests/test_trunk_pass_cpu.py pins which is which)."""
+    from rfx.trunk_pass import pair_level_with_target
+    pipe, plain = trunk_forms
+    B, calls, envs = TRUNK_FORMS[form]
+    prep, featA, featB = plain(B, tgt_h)
+    paired = pair_level_with_target([x.shape for x in prep["src"]], prep["tgt"].shape)
+    assert paired == (1 if tgt_h == 128 else None)
+    for env in envs:
+        for k in TRUNK_SWITCHES:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        n_graphs = len(pipe._graphs)
+        for _ in range(calls):
+            f = pipe.features(prep)
+            assert torch.equal(f["featA"], featA) and torch.equal(f["featB"], featB), env
+        assert len(pipe._graphs) == n_graphs + (1 if form == "graphed_stream_per_level" else 0)
+
+
 def test_lock_step_driver_device_draw_records_and_determinism(dev):
     """The throughput form as bench.py runs it: device-side draw (no explicit samples), result records filled on the device.
     Same seed + same call sequence -> the same homographies; the records hold exactly what the per-pair lists hold; the
