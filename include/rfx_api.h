@@ -43,9 +43,10 @@ const char* rfx_version(void);
  * round kernels, two-direction correlation, grouped launches; round 4: rfx_draw_samples_i64 keyed by pair id; 11: the ragged-batch
  * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes; 12: the ragged forms of the
  * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32; 13:
- * rfx_conv1x1_split_tile_channels).  A binding
+ * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
+ * rfx_multih_accept_ragged_d2_f32).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 13
+#define RFX_ABI_VERSION 14
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -326,6 +327,19 @@ size_t rfx_remove_small_cc_ws_bytes(int N, int H, int W);
 int rfx_remove_small_cc_f32(const float* in, float* out, int N, int H, int W, float match_th, int max_area, void* ws,
                             void* stream);
 
+/* (ABI 14) The same filter for n_active maps of DIFFERENT sizes in one launch chain (a round of the KITTI driver on a ragged batch):
+ * map k is h_k * w_k floats at element offset match_off[k] (n_active int64) of ONE packed buffer of total_px floats -- the layout
+ * rfx_multih_accept_ragged_f32 consumes, so the filter runs in place between the fine stage and the accept kernel -- and row k of the
+ * device table dims (n_active,3) int32 holds h_k, w_k and the map's OWN max_area_k (the bound above formed with h_k * w_k).  Maps
+ * must not overlap; a table row that does not lie inside the buffer is skipped.  Every map is labelled on its own (segments, rows
+ * and unions are relative to the map's origin; "a component that is the whole image stays" uses h_k * w_k), so map k's output is,
+ * bit for bit, rfx_remove_small_cc_f32 on that map alone.  max_hw = the largest h_k * w_k (sizes the grid).  Limits: total_px <=
+ * 2^31 - 1, n_active <= 65535 (RFX_E_LIMIT).  ws: rfx_remove_small_cc_ragged_ws_bytes(total_px) = three int32 per packed pixel.
+ * in and out may be the same buffer; pixels of the buffer that belong to no map are neither read nor written. */
+size_t rfx_remove_small_cc_ragged_ws_bytes(long long total_px);
+int rfx_remove_small_cc_ragged_f32(const float* in, float* out, const long long* match_off, const int32_t* dims, int n_active,
+                                   long long total_px, long long max_hw, float match_th, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * All-pairs correlation + mutual nearest neighbours (utils/outil.py:32-45, mutualMatching).
  * featA: (C, nA) and featB: (C, nB), column = one cell ("K-major": element (k,i) at k*ld+i).
@@ -550,7 +564,8 @@ int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, cons
  * pixels, summed in the same order in double, as the dense kernel does for that pair.  max_hw = the largest h * w among the active
  * pairs (sizes the mask-update grid only).  Records: one row of rec_stride floats per pair, header and H slots as in the dense
  * layout (off_H, off_flow), flowDown8 slots of 2 h8_b w8_b floats from off_flow, matchDown8 slots from off_flow + 2 h8_b w8_b max_h
- * (rfx.ops.MultiHRecordsRagged); there is no flowD2 part.  ws: rfx_multih_accept_ragged_ws_bytes(n_active). */
+ * (rfx.ops.MultiHRecordsRagged); this entry point stores no flowD2 part (rfx_multih_accept_ragged_d2_f32 below does).
+ * ws: rfx_multih_accept_ragged_ws_bytes(n_active). */
 size_t rfx_multih_accept_ragged_ws_bytes(int n_active);
 int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off, float* mask, const float* bg,
                                  const long long* moff, const int32_t* geom, const int32_t* active, int n_active, long long max_hw,
@@ -558,6 +573,19 @@ int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off,
                                  int32_t* accept, float* gain, void* ws, const float* bestH, const float* flowDown8,
                                  const float* match12Down8, const float* match21Down8, const long long* off8, float* rec,
                                  long long rec_stride, int max_h, int off_H, int off_flow, void* stream);
+
+/* (ABI 14) rfx_multih_accept_ragged_f32 with the KITTI part of the record (evaluation/evalKITTI/evaluation.py:326: the half-resolution
+ * /8 flow saved per homography): flowD2 of active pair k = 2 * hd2_b * wd2_b floats at element 2 * offd2[k] (n_active int64) of a
+ * packed buffer, d2dims (batch,2) int32 = hd2_b, wd2_b per PAIR.  For an accepted pair slot s of its row also receives flowD2 at
+ * off_flow + 4 h8_b w8_b max_h + 2 hd2_b wd2_b s -- where the dense row of that pair alone (MultiHRecords(1, h8, w8, hd2, wd2)) has
+ * its off_d2.  flowD2, offd2 and d2dims are required; everything else is rfx_multih_accept_ragged_f32's. */
+int rfx_multih_accept_ragged_d2_f32(const float* match, const long long* match_off, float* mask, const float* bg,
+                                    const long long* moff, const int32_t* geom, const int32_t* active, int n_active,
+                                    long long max_hw, const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH, double th,
+                                    int mode, int32_t* accept, float* gain, void* ws, const float* bestH, const float* flowDown8,
+                                    const float* match12Down8, const float* match21Down8, const long long* off8,
+                                    const float* flowD2, const long long* offd2, const int32_t* d2dims, float* rec,
+                                    long long rec_stride, int max_h, int off_H, int off_flow, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * rfx_conv1x1_split_f32 (ABI 10): the 1x1 / stride 1 / pad 0 convolution of rfx_conv2d_f32 (the Bottleneck conv1 / conv3 layers,

@@ -217,20 +217,23 @@ __global__ __launch_bounds__(256) void accept_update_ragged_kernel(const float* 
 #undef MH_MASK_OFF
 
 // The record row of pair b is laid out with the pair's OWN h8 * w8 (ops.MultiHRecordsRagged); the /8 maps of the round are packed per
-// active pair: flowDown8 of pair k at 2 * off8[k], match12Down8 / match21Down8 at off8[k].
+// active pair: flowDown8 of pair k at 2 * off8[k], match12Down8 / match21Down8 at off8[k].  KITTI rounds (flowd2 given): the
+// half-resolution /8 flow of pair k, 2 * hd2_b * wd2_b floats (d2dims (batch,2) int32 = hd2, wd2 per pair) at 2 * offd2[k], goes to
+// the row's flowD2 part, which starts where the dense row of that pair alone has its off_d2: behind the two /8 parts.
 __global__ __launch_bounds__(1024) void accept_store_ragged_kernel(const int32_t* __restrict__ active, const int32_t* __restrict__ accept,
                                                                    int32_t* __restrict__ nbH, const float* __restrict__ bestH,
                                                                    const float* __restrict__ flow8, const float* __restrict__ m12,
                                                                    const float* __restrict__ m21, const long long* __restrict__ off8,
-                                                                   const int32_t* __restrict__ geom, float* __restrict__ rec,
+                                                                   const int32_t* __restrict__ geom, const float* __restrict__ flowd2,
+                                                                   const long long* __restrict__ offd2,
+                                                                   const int32_t* __restrict__ d2dims, float* __restrict__ rec,
                                                                    long long rec_stride, int max_h, int off_H, int off_flow) {
     const int k = blockIdx.x, b = active ? active[k] : k;
-    const int hw8 = geom[b * RG + 4] * geom[b * RG + 5], hwd2 = 0;
-    const int off_match = off_flow + 2 * hw8 * max_h, off_d2 = 0;
-    const float* flowd2 = nullptr;
+    const int hw8 = geom[b * RG + 4] * geom[b * RG + 5], hwd2 = flowd2 ? d2dims[2 * b] * d2dims[2 * b + 1] : 0;
+    const int off_match = off_flow + 2 * hw8 * max_h, off_d2 = off_match + 2 * hw8 * max_h;
 #define MH_F8_OFF ((size_t)2 * off8[k])
 #define MH_M8_OFF ((size_t)off8[k])
-#define MH_D2_OFF ((size_t)0)
+#define MH_D2_OFF ((size_t)2 * offd2[k])
 #include "multih_accept_store_body.inc"
 #undef MH_F8_OFF
 #undef MH_M8_OFF
@@ -326,18 +329,19 @@ extern "C" int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t*
 
 extern "C" size_t rfx_multih_accept_ragged_ws_bytes(int n_active) { return rfx_multih_accept_ws_bytes(n_active); }
 
-extern "C" int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off, float* mask, const float* bg,
-                                            const long long* moff, const int32_t* geom, const int32_t* active, int n_active,
-                                            long long max_hw, const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH,
-                                            double th, int mode, int32_t* accept, float* gain, void* ws, const float* bestH,
-                                            const float* flowDown8, const float* match12Down8, const float* match21Down8,
-                                            const long long* off8, float* rec, long long rec_stride, int max_h, int off_H,
-                                            int off_flow, void* stream) {
+namespace {
+int accept_ragged(const float* match, const long long* match_off, float* mask, const float* bg, const long long* moff,
+                  const int32_t* geom, const int32_t* active, int n_active, long long max_hw, const int32_t* ransac_result,
+                  const int32_t* n_match, int32_t* nbH, double th, int mode, int32_t* accept, float* gain, void* ws, const float* bestH,
+                  const float* flowDown8, const float* match12Down8, const float* match21Down8, const long long* off8,
+                  const float* flowD2, const long long* offd2, const int32_t* d2dims, float* rec, long long rec_stride, int max_h,
+                  int off_H, int off_flow, void* stream) {
     if (!match || !match_off || !mask || !moff || !geom || !ransac_result || !n_match || !nbH || !accept || !gain || !ws ||
         n_active <= 0 || max_hw <= 0 || (mode != 0 && mode != 1))
         return RFX_E_ARG;
     if (rec && (!bestH || max_h <= 0 || rec_stride <= 0)) return RFX_E_ARG;
     if ((flowDown8 || match12Down8 || match21Down8) && !off8) return RFX_E_ARG;
+    if (flowD2 && (!offd2 || !d2dims)) return RFX_E_ARG;
     if (n_active > 65535) return RFX_E_LIMIT;
     hipStream_t st = rfx_stream(stream);
     double* part = static_cast<double*>(ws);
@@ -351,7 +355,34 @@ extern "C" int rfx_multih_accept_ragged_f32(const float* match, const long long*
                        geom, active, mode, part, ransac_result, n_match, nbH, th, accept, gain);
     RFX_LAUNCH_CHECK();
     hipLaunchKernelGGL(accept_store_ragged_kernel, dim3(n_active), dim3(1024), 0, st, active, accept, nbH, bestH, flowDown8,
-                       match12Down8, match21Down8, off8, geom, rec, rec_stride, max_h, off_H, off_flow);
+                       match12Down8, match21Down8, off8, geom, flowD2, offd2, d2dims, rec, rec_stride, max_h, off_H, off_flow);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
+}
+}  // namespace
+
+extern "C" int rfx_multih_accept_ragged_f32(const float* match, const long long* match_off, float* mask, const float* bg,
+                                            const long long* moff, const int32_t* geom, const int32_t* active, int n_active,
+                                            long long max_hw, const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH,
+                                            double th, int mode, int32_t* accept, float* gain, void* ws, const float* bestH,
+                                            const float* flowDown8, const float* match12Down8, const float* match21Down8,
+                                            const long long* off8, float* rec, long long rec_stride, int max_h, int off_H,
+                                            int off_flow, void* stream) {
+    return accept_ragged(match, match_off, mask, bg, moff, geom, active, n_active, max_hw, ransac_result, n_match, nbH, th, mode, accept,
+                         gain, ws, bestH, flowDown8, match12Down8, match21Down8, off8, nullptr, nullptr, nullptr, rec, rec_stride, max_h,
+                         off_H, off_flow, stream);
+}
+
+extern "C" int rfx_multih_accept_ragged_d2_f32(const float* match, const long long* match_off, float* mask, const float* bg,
+                                               const long long* moff, const int32_t* geom, const int32_t* active, int n_active,
+                                               long long max_hw, const int32_t* ransac_result, const int32_t* n_match, int32_t* nbH,
+                                               double th, int mode, int32_t* accept, float* gain, void* ws, const float* bestH,
+                                               const float* flowDown8, const float* match12Down8, const float* match21Down8,
+                                               const long long* off8, const float* flowD2, const long long* offd2,
+                                               const int32_t* d2dims, float* rec, long long rec_stride, int max_h, int off_H,
+                                               int off_flow, void* stream) {
+    if (!flowD2) return RFX_E_ARG;
+    return accept_ragged(match, match_off, mask, bg, moff, geom, active, n_active, max_hw, ransac_result, n_match, nbH, th, mode, accept,
+                         gain, ws, bestH, flowDown8, match12Down8, match21Down8, off8, flowD2, offd2, d2dims, rec, rec_stride, max_h,
+                         off_H, off_flow, stream);
 }

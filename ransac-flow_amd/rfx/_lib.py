@@ -62,6 +62,8 @@ SIGNATURES = {
     "rfx_match_score_f32": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p]),
     "rfx_remove_small_cc_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_remove_small_cc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "rfx_remove_small_cc_ragged_ws_bytes": (c_size_t, [c_longlong]),
+    "rfx_remove_small_cc_ragged_f32": (c_int, [c_void_p] * 4 + [c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p]),
     "rfx_mutual_nn_ws_bytes": (c_size_t, [c_int, c_int]),
     "rfx_mutual_nn_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
     "rfx_mutual_nn_batched_f32": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int]
@@ -96,9 +98,11 @@ SIGNATURES = {
     "rfx_multih_accept_ragged_ws_bytes": (c_size_t, [c_int]),
     "rfx_multih_accept_ragged_f32": (c_int, [c_void_p] * 7 + [c_int, c_longlong] + [c_void_p] * 3 + [c_double, c_int]
                                      + [c_void_p] * 9 + [c_longlong] + [c_int] * 3 + [c_void_p]),
+    "rfx_multih_accept_ragged_d2_f32": (c_int, [c_void_p] * 7 + [c_int, c_longlong] + [c_void_p] * 3 + [c_double, c_int]
+                                        + [c_void_p] * 12 + [c_longlong] + [c_int] * 3 + [c_void_p]),
 }
 
-ABI_VERSION = 13    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 14    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

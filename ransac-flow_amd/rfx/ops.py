@@ -780,6 +780,50 @@ def remove_small_cc(match, cc_th, match_th=0.99):
     return out[0] if squeeze else out
 
 
+def cc_dims_table(hw_list, cc_th):
+    """Rows (h, w, max_area) of rfx_remove_small_cc_ragged_f32's table for maps of the sizes ``hw_list``: max_area is each map's own
+    cc_max_area(h * w, cc_th)."""
+    return [(int(h), int(w), cc_max_area(int(h) * int(w), float(cc_th))) for h, w in hw_list]
+
+
+def remove_small_cc_ragged(match, match_off, hw, cc_th, match_th=0.99, inplace=False, max_hw=None):
+    """remove_small_cc for maps of DIFFERENT sizes in one launch chain (rfx_remove_small_cc_ragged_f32): ``match`` is a packed 1-D
+    float32 buffer, map k's h_k * w_k values at element ``match_off[k]`` ((n,) int64 device tensor) -- the layout
+    multih_accept_ragged consumes.  ``hw``: a list of n (h, w) (the table is built with cc_dims_table and uploaded here), or the
+    (n,3) int32 device table itself (rows h, w, max_area; then ``max_hw`` = the largest h * w is required and ``cc_th`` only
+    decides whether anything runs).  Each map's area bound comes from its OWN size; map k's result equals remove_small_cc on that
+    map alone bit for bit.  Returns a new packed buffer, or ``match`` itself filtered in place (``inplace=True``).  cc_th == 0: the
+    identity."""
+    m = _dev(match, "match buffer")
+    if m.dim() != 1:
+        raise ValueError("match of a ragged round is a packed 1-D buffer")
+    if inplace and m is not match:
+        raise ValueError("match must be a contiguous float32 device tensor (filtered in place)")
+    if cc_th == 0:
+        return m
+    off = _dev(match_off, "match_off", torch.int64)
+    n = off.numel()
+    if isinstance(hw, torch.Tensor):
+        dims = _dev(hw, "dims", torch.int32)
+        if max_hw is None:
+            raise ValueError("a device table needs max_hw = the largest h * w of its maps")
+    else:
+        rows = cc_dims_table(hw, cc_th)
+        dims = torch.tensor(rows, dtype=torch.int32).to(m.device)
+        max_hw = max(h * w for h, w, _ in rows)
+    if dims.shape != (n, 3):
+        raise ValueError("one (h, w[, max_area]) per offset expected")
+    total = m.numel()
+    lib = _lib.load()
+    ws = torch.empty(lib.rfx_remove_small_cc_ragged_ws_bytes(total), dtype=torch.uint8, device=m.device)
+    out = m if inplace else torch.empty_like(m)
+    if not inplace:
+        out.copy_(m)                  # elements of the buffer that belong to no map pass through
+    _call("rfx_remove_small_cc_ragged_f32", _one_device(m, off, dims), _p(m), _p(out), _p(off), _p(dims), n, total, int(max_hw),
+          float(match_th), _p(ws))
+    return out
+
+
 _HOST_KC = None
 
 
@@ -1282,9 +1326,9 @@ class MultiHRecords:
 
 
     @staticmethod
-    def ragged(h8_list, w8_list, device, max_h=11):
+    def ragged(h8_list, w8_list, device, max_h=11, hd2_list=None, wd2_list=None):
         """The records of a batch whose pairs differ in size: a MultiHRecordsRagged (the dense layout above is unchanged)."""
-        return MultiHRecordsRagged(h8_list, w8_list, device, max_h=max_h)
+        return MultiHRecordsRagged(h8_list, w8_list, device, max_h=max_h, hd2_list=hd2_list, wd2_list=wd2_list)
 
 
 class MultiHRecordsRagged:
@@ -1292,18 +1336,30 @@ class MultiHRecordsRagged:
     width set by the batch's largest h8 * w8.  Row b: [0] nbH | [1] status (the dense codes) | [2] h8 | [3] w8 of the pair |
     H (max_h,9) from off_H = 4 | flowDown8 (max_h,2,h8,w8) from off_flow | matchDown8 (max_h,2,h8,w8) from off_flow + 2 h8 w8 max_h,
     both laid out with the pair's OWN h8 * w8 (a row of one pair = the dense row of MultiHRecords(1, h8, w8)); the rest of the row
-    is zero.  A pure function of the size lists.  Filled on the device by multih_accept_ragged."""
+    is zero.  With ``hd2_list`` / ``wd2_list`` (the KITTI driver: the half-resolution /8 sizes per pair) row b gains flowD2
+    (max_h,2,hd2,wd2) from off_d2[b] = off_match[b] + 2 h8 w8 max_h, again the dense row of MultiHRecords(1, h8, w8, hd2=, wd2=);
+    without them width, offsets and views are unchanged.  A pure function of the size lists.  Filled on the device by
+    multih_accept_ragged."""
 
-    def __init__(self, h8_list, w8_list, device, max_h=11):
+    def __init__(self, h8_list, w8_list, device, max_h=11, hd2_list=None, wd2_list=None):
         if len(h8_list) != len(w8_list) or not h8_list:
             raise ValueError("one (h8, w8) per pair")
+        if (hd2_list is None) != (wd2_list is None) or (hd2_list is not None and
+                                                        (len(hd2_list) != len(h8_list) or len(wd2_list) != len(h8_list))):
+            raise ValueError("hd2_list and wd2_list: both, one (hd2, wd2) per pair")
         self.h8, self.w8 = [int(x) for x in h8_list], [int(x) for x in w8_list]
         self.B, self.max_h = len(self.h8), max_h
         r4 = lambda x: (x + 3) // 4 * 4
         self.off_H = 4
         self.off_flow = self.off_H + r4(9 * max_h)
         self.off_match = [self.off_flow + 2 * a * b * max_h for a, b in zip(self.h8, self.w8)]
-        self.width = r4(max(o + 2 * a * b * max_h for o, a, b in zip(self.off_match, self.h8, self.w8)))
+        end = [o + 2 * a * b * max_h for o, a, b in zip(self.off_match, self.h8, self.w8)]
+        self.hd2 = self.wd2 = self.off_d2 = self.d2dims = None
+        if hd2_list is not None:
+            self.hd2, self.wd2, self.off_d2 = [int(x) for x in hd2_list], [int(x) for x in wd2_list], end
+            end = [o + 2 * a * b * max_h for o, a, b in zip(self.off_d2, self.hd2, self.wd2)]
+            self.d2dims = torch.tensor(list(zip(self.hd2, self.wd2)), dtype=torch.int32).to(device)      # (B,2): the store kernel's table
+        self.width = r4(max(end))
         self.rec = torch.zeros((self.B, self.width), dtype=torch.float32, device=device)
         self.rec[:, 1] = 1.0
         self.rec[:, 2] = torch.tensor(self.h8, dtype=torch.float32).to(device)
@@ -1315,14 +1371,21 @@ class MultiHRecordsRagged:
         r = copy.copy(self)
         r.B, r.rec = hi - lo, self.rec[lo:hi]
         r.h8, r.w8, r.off_match = self.h8[lo:hi], self.w8[lo:hi], self.off_match[lo:hi]
+        if self.hd2 is not None:
+            r.hd2, r.wd2, r.off_d2, r.d2dims = self.hd2[lo:hi], self.wd2[lo:hi], self.off_d2[lo:hi], self.d2dims[lo:hi]
         return r
 
     def views(self, b):
-        """Pair b's (nbH, status, H (max_h,3,3), flowDown8 (max_h,2,h8,w8), matchDown8 (max_h,2,h8,w8))."""
+        """Pair b's (nbH, status, H (max_h,3,3), flowDown8 (max_h,2,h8,w8), matchDown8 (max_h,2,h8,w8)[, flowD2 (max_h,2,hd2,wd2):
+        records built with the d2 lists])."""
         r, m, h8, w8 = self.rec[b], self.max_h, self.h8[b], self.w8[b]
         n8 = 2 * h8 * w8
-        return (r[0], r[1], r[self.off_H:self.off_H + 9 * m].view(m, 3, 3), r[self.off_flow:self.off_flow + n8 * m].view(m, 2, h8, w8),
-                r[self.off_match[b]:self.off_match[b] + n8 * m].view(m, 2, h8, w8))
+        v = (r[0], r[1], r[self.off_H:self.off_H + 9 * m].view(m, 3, 3), r[self.off_flow:self.off_flow + n8 * m].view(m, 2, h8, w8),
+             r[self.off_match[b]:self.off_match[b] + n8 * m].view(m, 2, h8, w8))
+        if self.hd2 is not None:
+            hd2, wd2 = self.hd2[b], self.wd2[b]
+            v += (r[self.off_d2[b]:self.off_d2[b] + 2 * hd2 * wd2 * m].view(m, 2, hd2, wd2),)
+        return v
 
 
 def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode, bestH=None, flowDown8=None, match12Down8=None,
@@ -1367,12 +1430,15 @@ def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode
 
 
 def multih_accept_ragged(match, match_off, mask, bg, moff, geom, active, ransac_result, n_match, nbH, th, mode, max_hw, bestH=None,
-                         flowDown8=None, match12Down8=None, match21Down8=None, off8=None, records=None):
+                         flowDown8=None, match12Down8=None, match21Down8=None, off8=None, records=None, flowD2=None, offd2=None,
+                         d2dims=None):
     """multih_accept for active pairs of DIFFERENT sizes (rfx_multih_accept_ragged_f32) -> (accept (a,) int32, gain (a,) f32).
     ``mask`` / ``bg``: packed 1-D buffers, pair b at ``moff[b]``; ``geom`` (B,6) int32 (see filter_matches_ragged).  The round's
     tensors are packed per ACTIVE pair: ``match`` 1-D, pair k's h*w values at ``match_off[k]``; ``flowDown8`` 1-D, pair k at
     2 * off8[k]; ``match12Down8`` / ``match21Down8`` 1-D, pair k at off8[k] (match_off, off8: (a,) int64).  ``max_hw``: the largest
-    h * w among the active pairs.  ``records``: a MultiHRecordsRagged.  ``mask`` and ``nbH`` (B,) int32 are updated in place."""
+    h * w among the active pairs.  ``records``: a MultiHRecordsRagged.  ``mask`` and ``nbH`` (B,) int32 are updated in place.
+    KITTI rounds (rfx_multih_accept_ragged_d2_f32): ``flowD2`` 1-D, pair k's (2,hd2,wd2) half-resolution /8 flow at 2 * offd2[k]
+    ((a,) int64); the per-pair sizes are ``d2dims`` (B,2) int32 or, by default, the records' own (built with the d2 lists)."""
     for t, name in ((mask, "mask"), (nbH, "nbH")):          # updated IN PLACE: a silent .contiguous() copy would lose the update
         if isinstance(t, torch.Tensor) and not t.is_contiguous():
             raise ValueError("%s must be contiguous (updated in place)" % name)
@@ -1402,9 +1468,25 @@ def multih_accept_ragged(match, match_off, mask, bg, moff, geom, active, ransac_
     if R is not None and (not isinstance(R, MultiHRecordsRagged) or R.B != B):
         raise ValueError("records of a ragged batch: a MultiHRecordsRagged with one row per pair")
     bh = _dev(bestH, "bestH") if bestH is not None else None
-    _call("rfx_multih_accept_ragged_f32", _one_device(match, match_off, mask, bg, moff, geom, act, res, n_match, nbH, bh, f8, m12, m21, o8),
+    rec_args = (_p(R.rec) if R is not None else ctypes.c_void_p(0), R.width if R is not None else 0, R.max_h if R is not None else 0,
+                R.off_H if R is not None else 0, R.off_flow if R is not None else 0)
+    if flowD2 is None:
+        if R is not None and R.hd2 is not None:
+            raise ValueError("records with a flowD2 part need the round's flowD2")
+        _call("rfx_multih_accept_ragged_f32", _one_device(match, match_off, mask, bg, moff, geom, act, res, n_match, nbH, bh, f8, m12, m21, o8),
+              _p(match), _p(match_off), _p(mask), _p(bg), _p(moff), _p(geom), _p(act), a, int(max_hw), _p(res), _p(n_match), _p(nbH),
+              float(th), int(mode), _p(accept), _p(gain), _p(ws), _p(bh), _p(f8), _p(m12), _p(m21), _p(o8), *rec_args)
+        return accept, gain
+    fd2, od2 = _dev(flowD2, "flowD2"), _dev(offd2, "offd2", torch.int64)
+    if R is not None and R.hd2 is None:
+        raise ValueError("flowD2 needs records built with hd2_list / wd2_list")
+    dd = _dev(d2dims if d2dims is not None else (R.d2dims if R is not None else None), "d2dims", torch.int32)
+    if fd2.dim() != 1 or od2.numel() != a or dd.shape != (B, 2):
+        raise ValueError("flowD2 packed 1-D, offd2 (a,), d2dims (B,2) expected")
+    if R is not None and d2dims is not None and not torch.equal(dd, R.d2dims):
+        raise ValueError("d2dims differ from the sizes the records were built with")
+    _call("rfx_multih_accept_ragged_d2_f32", _one_device(match, match_off, mask, bg, moff, geom, act, res, n_match, nbH, bh, f8, m12, m21,
+                                                          o8, fd2, od2, dd),
           _p(match), _p(match_off), _p(mask), _p(bg), _p(moff), _p(geom), _p(act), a, int(max_hw), _p(res), _p(n_match), _p(nbH),
-          float(th), int(mode), _p(accept), _p(gain), _p(ws), _p(bh), _p(f8), _p(m12), _p(m21), _p(o8),
-          _p(R.rec) if R is not None else ctypes.c_void_p(0), R.width if R is not None else 0, R.max_h if R is not None else 0,
-          R.off_H if R is not None else 0, R.off_flow if R is not None else 0)
+          float(th), int(mode), _p(accept), _p(gain), _p(ws), _p(bh), _p(f8), _p(m12), _p(m21), _p(o8), _p(fd2), _p(od2), _p(dd), *rec_args)
     return accept, gain

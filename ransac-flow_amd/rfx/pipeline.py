@@ -138,6 +138,38 @@ def ragged_multih_tables(plan):
     return dict(moff=moff, geom=geom, total=pos)
 
 
+def resize_img_dims(w, h, stride, min_size):
+    """outil.resizeImg (utils/outil.py:6-19): smaller side -> min_size, each side ROUNDED to a multiple of stride."""
+    ratio = min(w / min_size, h / min_size)
+    return int(round(w / ratio / stride) * stride), int(round(h / ratio / stride) * stride)
+
+
+def ragged_kitti_tables(plan, tgt_sizes, fineSize):
+    """The tables of a ragged batch's KITTI rounds, a pure function of the plan, the targets' ORIGINAL sizes ``tgt_sizes[b]`` = (w, h)
+    and ``fineSize``: per pair org[b] = (h_org, w_org), resize[b] = (h_r, w_r) and half[b] = (h_d2, w_d2) = resize_img_dims at fineSize
+    and fineSize // 2 (stride 8), d2[b] = (h_d2 // 8, w_d2 // 8) = the size of the half-resolution /8 flow.  The explained-region
+    masks (and background maps) live at the ORIGINAL target size: pair b's h_org * w_org floats at ``moff[b]`` of one buffer of
+    ``total`` floats, and geom[b] = (h_org, w_org, rt, ct, h_r // 8, w_r // 8) -- the mask's size, the coarse target feature map
+    (plan["cells"][b][nS]) and the /8 maps of the full-resolution pass: what rfx_filter_matches_ragged_f32 /
+    rfx_multih_accept_ragged_d2_f32 read."""
+    nS = plan["nS"]
+    out = dict(moff=[], geom=[], org=[], resize=[], half=[], d2=[])
+    pos = 0
+    for b, (w_org, h_org) in enumerate(tgt_sizes):
+        w_r, h_r = resize_img_dims(w_org, h_org, 8, fineSize)
+        w_d2, h_d2 = resize_img_dims(w_org, h_org, 8, fineSize // 2)
+        rt, ct = plan["cells"][b][nS]
+        out["moff"].append(pos)
+        out["geom"].append((h_org, w_org, rt, ct, h_r // 8, w_r // 8))
+        out["org"].append((h_org, w_org))
+        out["resize"].append((h_r, w_r))
+        out["half"].append((h_d2, w_d2))
+        out["d2"].append((h_d2 // 8, w_d2 // 8))
+        pos += h_org * w_org
+    out["total"] = pos
+    return out
+
+
 class AlignPipeline:
     def __init__(self, sds, nbScale=7, nbIter=1000, tolerance=0.05, minSize=640, scaleR=1.2, variant="A",
                  device="cuda", kernelSize=7, draw="device", seed=0, degenerate="lapack", score_chunk=None):
@@ -863,11 +895,7 @@ class AlignPipeline:
         return st.close(lambda b: masks[b])
 
     # ---------------------------------------------------------------- KITTI two-resolution driver (BASELINE config 5)
-    @staticmethod
-    def resize_img_dims(w, h, stride, min_size):
-        """outil.resizeImg (utils/outil.py:6-19): smaller side -> min_size, each side ROUNDED to a multiple of stride."""
-        ratio = min(w / min_size, h / min_size)
-        return int(round(w / ratio / stride) * stride), int(round(h / ratio / stride) * stride)
+    resize_img_dims = staticmethod(resize_img_dims)     # outil.resizeImg's sizes (module level: ragged_kitti_tables uses it too)
 
     def multi_h_kitti(self, src_u8, tgt_u8, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, feats=None, prep=None,
                       sample_fn=None, remove_small_cc=None):
@@ -970,7 +998,8 @@ class AlignPipeline:
 
     def multi_h_kitti_batched(self, src_u8, tgt_u8, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, sample_fn=None,
                               remove_small_cc=None, records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None):
-        """multi_h_kitti() for B pairs of ONE size in lock-step (src_u8 / tgt_u8: (B,H,W,3) uint8 on the device): round k
+        """multi_h_kitti() for B pairs in lock-step (src_u8 / tgt_u8: (B,H,W,3) uint8 on the device, or -- pairs of DIFFERENT sizes
+        -- per side a list of (H,W,3) / (1,H,W,3) uint8 device tensors, see below): round k
         computes the k-th homography of every pair that is still active -- one batched launch chain for the trunk features,
         the match filtering (rfx_filter_matches_f32), the index draw (device mode), RANSAC (rfx_ransac_h4_batched), the two
         warps and both PredFlowMask passes over the active pairs, the small-component filter on the device and the accept
@@ -980,8 +1009,24 @@ class AlignPipeline:
         (the 3x3 kernels run at 0.59 of the matrix peak at batch 1, 0.8 at batch 8).
         ``sample_fn(b, n, nbIter)`` -> (nbIter,4) int64 CPU tensor: explicit draws (parity mode; a second sync per round).
         ``records``: ops.MultiHRecords built with the half-resolution /8 size (hd2, wd2); ``trace``: as in multi_h_batched.
+        Lists of images: all sources of one shape and all targets of one shape are stacked and take the dense path unchanged;
+        otherwise the ragged path (_multi_h_kitti_batched_ragged: real KITTI lists mix 1242x375, 1241x376, 1238x374, 1226x370 and
+        1224x370 frames) -- per pair the results are, bit for bit, the pair's alone; ``It_bg`` is then a list with one (h_org, w_org)
+        tensor or None per pair and ``records`` an ops.MultiHRecordsRagged built with the d2 lists.
         Returns a list of dicts like multi_h_kitti()."""
         dev = self.dev
+        if isinstance(src_u8, (list, tuple)) or isinstance(tgt_u8, (list, tuple)):
+            one = lambda x: x[0] if x.dim() == 4 else x
+            src_l, tgt_l = [one(x) for x in src_u8], [one(x) for x in tgt_u8]
+            if len(src_l) != len(tgt_l) or not src_l:
+                raise ValueError("one source and one target per pair")
+            if len({tuple(x.shape) for x in src_l}) > 1 or len({tuple(x.shape) for x in tgt_l}) > 1:
+                return self._multi_h_kitti_batched_ragged(src_l, tgt_l, fineSize, maskRegionTh, cc_th, It_bg, sample_fn, remove_small_cc,
+                                                          records, want_lists, trace, pair_ids, draw_epoch, split)
+            src_u8, tgt_u8 = torch.stack(src_l), torch.stack(tgt_l)
+            if isinstance(It_bg, (list, tuple)):
+                It_bg = None if all(x is None for x in It_bg) else torch.stack(
+                    [torch.ones(tgt_u8.shape[1:3], device=dev) if x is None else x.to(dev).float() for x in It_bg])
         B, h_org, w_org = tgt_u8.shape[0], tgt_u8.shape[1], tgt_u8.shape[2]
         prep = self.prepare_device(src_u8, tgt_u8)
         feats = self.features(prep)
@@ -1003,12 +1048,89 @@ class AlignPipeline:
         rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.KittiGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
         return st.close(lambda b: batch["Mask"][b], (idx1, idx2, cnt))
 
+    def _multi_h_kitti_batched_ragged(self, src_l, tgt_l, fineSize, maskRegionTh, cc_th, It_bg, sample_fn, remove_small_cc, records,
+                                      want_lists, trace, pair_ids, draw_epoch, split):
+        """multi_h_kitti_batched for pairs of different sizes (src_l / tgt_l: per-pair (H,W,3) uint8 device tensors).  One grouped
+        trunk pass and one ragged mutual matching (prepare_ragged_device, _features_ragged, _mutual_ragged), the fine-stage images
+        from one LANCZOS / float-conversion chain per distinct shape, then the lock-step rounds of rounds.RaggedKittiGroup: per round
+        and group ONE filter launch, ONE draw, ONE RANSAC search, ONE small-component filter (rfx_remove_small_cc_ragged_f32) and ONE
+        accept launch (rfx_multih_accept_ragged_d2_f32) for all active pairs whatever their sizes, and one host readback; only the
+        two PredFlowMask passes run per group of active pairs that share (source original shape, target original shape)."""
+        dev, B = self.dev, len(src_l)
+        prep = self.prepare_ragged_device(src_l, tgt_l)
+        feats = self.features(prep)
+        tabs = ragged_kitti_tables(prep["plan"], [(x.shape[1], x.shape[0]) for x in tgt_l], fineSize)
+        if records is not None and (not isinstance(records, ops.MultiHRecordsRagged) or records.hd2 is None or
+                                    list(zip(records.h8, records.w8, records.hd2, records.wd2)) !=
+                                    [g[4:6] + d for g, d in zip(tabs["geom"], tabs["d2"])]):
+            raise ValueError("a ragged KITTI batch fills an ops.MultiHRecordsRagged built from its pairs' own sizes: h8_list / w8_list = "
+                             "the /8 sizes of the full-resolution pass, hd2_list / wd2_list = those of the half-resolution pass "
+                             "(pipeline.ragged_kitti_tables: geom[b][4:6] and d2[b])")
+        # the fine-stage images: sources at their ORIGINAL size, targets at fineSize and fineSize // 2 -- one chain per distinct shape
+        tensor_s, tensor_resize, tensor_d2 = [None] * B, [None] * B, [None] * B
+        groups = collections.OrderedDict()
+        for b in range(B):
+            groups.setdefault(("src", tuple(src_l[b].shape)), []).append(b)
+            groups.setdefault(("tgt", tuple(tgt_l[b].shape)), []).append(b)
+        for (kind, _), bs in groups.items():
+            u8 = torch.stack([(src_l if kind == "src" else tgt_l)[b] for b in bs])
+            if kind == "src":
+                outs = ((tensor_s, ops.u8_to_f32(u8)[0]),)
+            else:
+                (h_r, w_r), (h_d2, w_d2) = tabs["resize"][bs[0]], tabs["half"][bs[0]]
+                outs = ((tensor_resize, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_r, h_r))[0]),
+                        (tensor_d2, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_d2, h_d2))[0]))
+            for dst, t in outs:
+                for k, b in enumerate(bs):
+                    dst[b] = t[k:k + 1]
+        idx1, idx2, cnt = self._mutual_ragged(feats)
+        st = rounds.RoundState(self, [dict(H=[], flowD2=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "kitti", rounds.KITTI_SPLIT,
+                               split, sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh,
+                               host_filter=remove_small_cc is not None)
+        tab = torch.tensor(tabs["moff"] + [v for g in tabs["geom"] for v in g] + [v for d in tabs["d2"] for v in d],
+                           dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        bg = None
+        if It_bg is not None:
+            if len(It_bg) != B:
+                raise ValueError("It_bg of a ragged batch: one (h_org, w_org) tensor (or None) per pair")
+            parts = []
+            for x, hw in zip(It_bg, tabs["org"]):
+                if x is not None and tuple(x.shape) != hw:
+                    raise ValueError("It_bg entry of shape %s for a target of %s" % (tuple(x.shape), hw))
+                parts.append(torch.ones(hw[0] * hw[1], dtype=torch.float32, device=dev) if x is None else x.to(dev).float().reshape(-1))
+            bg = torch.cat(parts)
+        batch = dict(feats=feats, tabs=tabs, idx1=idx1, idx2=idx2, cnt=cnt, bg=bg, moff=tab[:B],
+                     geom=tab[B:7 * B].to(torch.int32).view(B, 6), d2dims=tab[7 * B:].to(torch.int32).view(B, 2), d2=tabs["d2"],
+                     Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
+                     tensor_s=tensor_s, tensor_d2=tensor_d2, tensor_resize=tensor_resize, cc_th=cc_th, remove_small_cc=remove_small_cc)
+        rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedKittiGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
+
+        def mask_of(b):
+            o, (h, w) = tabs["moff"][b], tabs["org"][b]
+            return batch["Mask"][o:o + h * w].view(h, w)
+        return st.close(mask_of, (idx1, idx2, cnt))
+
+    def multi_h_kitti_pairs(self, pairs, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, sample_fn=None, remove_small_cc=None,
+                            records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None):
+        """multi_h_kitti_batched on pairs of PIL images.  All sources of one size and all targets of one size: upload_raw(), today's
+        dense path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise per-pair uploads and the ragged path (``It_bg`` a
+        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged with the d2 lists)."""
+        if len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1:
+            up = lambda im: torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(self.dev)
+            src, tgt = [up(p[0]) for p in pairs], [up(p[1]) for p in pairs]
+        else:
+            src, tgt = self.upload_raw(pairs)
+        return self.multi_h_kitti_batched(src, tgt, fineSize=fineSize, maskRegionTh=maskRegionTh, cc_th=cc_th, It_bg=It_bg,
+                                          sample_fn=sample_fn, remove_small_cc=remove_small_cc, records=records, want_lists=want_lists,
+                                          trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
+
     # ---------------------------------------------------------------- whole path
     def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0):
         """coarse() + fine_quickstart() of a prep from prepare / prepare_device or, for pairs of different sizes, prepare_ragged /
         prepare_ragged_device.  A ragged batch gives every pair, bit for bit, what it gives alone (same ``pair_ids`` / draws); it
-        runs eagerly (no HIP-graph capture).  multi_h_batched takes ragged preps too (multi_h_pairs).  Not covered for ragged
-        preps: multi_h_kitti_batched and multi_h_variant_c, and the drop-in modules."""
+        runs eagerly (no HIP-graph capture).  multi_h_batched takes ragged preps too (multi_h_pairs), and multi_h_kitti_batched takes
+        lists of images of different sizes (multi_h_kitti_pairs).  Not covered for ragged batches: multi_h_variant_c and the drop-in
+        modules."""
         res = self.coarse(prep, feats=feats, samples=samples, pair_ids=pair_ids, draw_epoch=draw_epoch)
         if fine:
             eye = torch.eye(3, device=self.dev)

@@ -6,8 +6,8 @@ active list -> matches of the round -> index draws -> RANSAC search -> fine stag
 flags) -> per-pair outputs and stop rule.  It is a generator that yields a HIP event at every host wait; ``drive_rounds`` runs
 one generator per lock-step group, each under its own stream, and resumes the group whose event is due.  What the drivers differ
 in -- where a round's matches come from, the fine stage, how a pair's outputs are cut out of the round's tensors, when a pair
-stops -- is the group class: DenseGroup (Hpatch), KittiGroup, RaggedGroup (Hpatch, pairs of different sizes), VariantCGroup (one
-target-shape group of the YFCC driver).  ``split_policy`` decides how many groups a batch is cut into, RoundState holds what the
+stops -- is the group class: DenseGroup (Hpatch), KittiGroup, RaggedGroup (Hpatch, pairs of different sizes), RaggedKittiGroup
+(KITTI, pairs of different sizes), VariantCGroup (one target-shape group of the YFCC driver).  ``split_policy`` decides how many groups a batch is cut into, RoundState holds what the
 groups of one call share.
 """
 import collections
@@ -311,13 +311,17 @@ class RaggedGroup:
         self.Mask, self.bg = batch["Mask"], batch["bg"]                  # packed: the offsets are absolute
         self.gm, self.mo = tabs["geom"][lo:hi], tabs["moff"][lo:hi]
         self.R = None if st.records is None else st.records.rows(lo, hi)
+        self.fine_setup(batch, lo, hi)
+
+    def fine_setup(self, batch, lo, hi):
+        """The fine groups of the slice and their stacked images."""
         IsT, self.ItT = batch["prep"]["IsTensor"][lo:hi], batch["prep"]["ItTensor"][lo:hi]
         # fine groups: members in ascending order; target-shape groups for the FeatureExtractor pass of the targets
         fine, self.tgroups = collections.OrderedDict(), collections.OrderedDict()
         for m in range(hi - lo):
             fine.setdefault((tuple(IsT[m].shape), tuple(self.ItT[m].shape)), []).append(m)
             self.tgroups.setdefault(tuple(self.ItT[m].shape), []).append(m)
-        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2],
+        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2], hw8=self.gm[mem[0]][4:6],
                                  Is=torch.cat([IsT[m] for m in mem]) if len(mem) > 1 else IsT[mem[0]]) for mem in fine.values()]
         self.have_featt = False
 
@@ -331,11 +335,11 @@ class RaggedGroup:
             mem = [m for m in g["members"] if m in kpos]
             if not mem:
                 continue
-            h, w = g["hw"]
+            (h, w), (h8, w8) = g["hw"], g["hw8"]
             for m in mem:
                 table[kpos[m]], table[a + kpos[m]] = m_off, o8
                 m_off += h * w
-                o8 += (h // 8) * (w // 8)
+                o8 += h8 * w8
             ent = dict(g=g, mem=mem, kidx=None, sel=None)
             if len(mem) != a or [kpos[m] for m in mem] != list(range(a)):
                 ent["kidx"] = (len(table), len(mem))
@@ -344,10 +348,16 @@ class RaggedGroup:
                 ent["sel"] = (len(table), len(mem))
                 table += [g["pos"][m] for m in mem]
             rg.append(ent)
-        self.rg, self.T = rg, torch.tensor(table, dtype=torch.int64).pin_memory().to(self.st.pipe.dev, non_blocking=True)
+        self.x0 = len(table)
+        table += self.extra_table(rg, kpos, a)
+        self.rg, self.table, self.T = rg, table, torch.tensor(table, dtype=torch.int64).pin_memory().to(self.st.pipe.dev, non_blocking=True)
         f = self.feats
         return ops.filter_matches_ragged(self.idx1, self.idx2, self.cnt, A, self.Mask, self.bg, self.moff, self.geom, f["HA"], f["WA"],
                                          self.offA, f["Ht"], f["Wt"], self.offB)
+
+    def extra_table(self, rg, kpos, a):
+        """What a driver's round needs in the pinned table besides the offsets and gather indices (from self.x0 on)."""
+        return []
 
     def target_features(self):
         if self.have_featt:
@@ -396,3 +406,92 @@ class RaggedGroup:
 
     def goes_on(self, b):
         return self.st.nb[b] <= self.st.maxCoarse
+
+
+class RaggedKittiGroup(RaggedGroup):
+    """Pairs [lo, hi) of a ragged batch of the KITTI driver: RaggedGroup with the differences KittiGroup has over DenseGroup -- the
+    two-resolution fine pass, the small-component filter, accept mode 1, no cached target features, the reference's ``while True``
+    with the capacity stop, flowD2 collected and traced.  The packed masks live at the ORIGINAL target sizes
+    (pipeline.ragged_kitti_tables).  A fine group is the pairs of the slice that share (source ORIGINAL shape, target ORIGINAL shape):
+    the source is sampled at its original size and the outputs live at the original target size, so two pairs whose resized shapes
+    coincide but whose originals differ are two groups.  A round runs pipeline.kitti_fine_round (without its dense filter) once per
+    fine group over its active members, packs the matchability maps in fine-group order, then ONE rfx_remove_small_cc_ragged_f32 in
+    place for all active pairs and ONE ragged accept (mode 1) with the flowD2 store.  ``batch``: RaggedGroup's plus tensor_s /
+    tensor_d2 / tensor_resize (per-pair (1,3,.,.) lists), d2 (per-pair (hd2, wd2) of the half-resolution /8 flow), d2dims (B,2) on the
+    device, cc_th / remove_small_cc."""
+    accept_mode = 1
+    goes_on = KittiGroup.goes_on
+
+    def fine_setup(self, batch, lo, hi):
+        Ts, Td2, Tr = batch["tensor_s"][lo:hi], batch["tensor_d2"][lo:hi], batch["tensor_resize"][lo:hi]
+        self.cc_th, self.remove_small_cc = batch["cc_th"], batch["remove_small_cc"]
+        self.d2, self.d2dims = batch["d2"][lo:hi], batch["d2dims"][lo:hi]
+        fine = collections.OrderedDict()
+        for m in range(hi - lo):
+            fine.setdefault((tuple(Ts[m].shape), self.gm[m][:2]), []).append(m)
+        stack = lambda ts, mem: torch.cat([ts[m] for m in mem]) if len(mem) > 1 else ts[mem[0]]
+        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2], hw8=self.gm[mem[0]][4:6],
+                                 Is=stack(Ts, mem), d2=stack(Td2, mem), resize=stack(Tr, mem)) for mem in fine.values()]
+
+    def target_features(self):
+        pass                                             # both PredFlowMask passes of a round compute their own
+
+    def extra_table(self, rg, kpos, a):
+        # flowD2 offsets per active pair (packed in fine-group order like the other maps), then the filter's (h, w, max_area) rows
+        offd2, dims, pos = [0] * a, [0] * (3 * a), 0
+        for ent in rg:
+            for m in ent["mem"]:
+                k = kpos[m]
+                offd2[k] = pos
+                pos += self.d2[m][0] * self.d2[m][1]
+                h, w = self.gm[m][:2]
+                dims[3 * k:3 * k + 3] = h, w, ops.cc_max_area(h * w, self.cc_th) if self.cc_th > 0 else 0
+        return offd2 + dims
+
+    def fine(self, A, active, Hs, bestH, res, n_dev):
+        rg, T, a, gm, x0 = self.rg, self.T, len(active), self.gm, self.x0
+        pipe = self.st.pipe
+        for ent in rg:
+            g = ent["g"]
+            take = lambda t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
+            ent["flow_d2"], ent["pm"], ent["match"] = pipe.kitti_fine_round(take(Hs, "kidx"), take(g["Is"], "sel"), take(g["d2"], "sel"),
+                                                                            take(g["resize"], "sel"), g["hw"], cc_th=0)
+        cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]) if len(ts) > 1 else ts[0].reshape(-1)
+        pack = lambda key: cat([e["pm"][key] for e in rg])
+        max_hw = max(gm[m][0] * gm[m][1] for m in active)
+        match = cat([e["match"] for e in rg])
+        if self.cc_th > 0:                                                              # evalKITTI/evaluation.py:321
+            if self.remove_small_cc is None:
+                if len(rg) == 1:
+                    match = match.clone()            # a view of the fine group's own map: keep PredFlowMask's output (trace) as it is
+                ops.remove_small_cc_ragged(match, T[:a], T[x0 + a:x0 + 4 * a].to(torch.int32).view(a, 3), self.cc_th, 0.99,
+                                           inplace=True, max_hw=max_hw)
+            else:                                    # an injected host filter, called in pair order: one round trip
+                mh = match.cpu().numpy().copy()
+                for k, m in enumerate(active):
+                    o, (h, w) = self.table[k], gm[m][:2]
+                    mh[o:o + h * w] = self.remove_small_cc(mh[o:o + h * w].reshape(h, w), 0.99, self.cc_th).reshape(-1)
+                match = torch.from_numpy(mh).to(pipe.dev)
+        accept, gain = ops.multih_accept_ragged(match, T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
+                                                self.st.maskRegionTh, self.accept_mode, max_hw, bestH=bestH, flowDown8=pack("flowDown8"),
+                                                match12Down8=pack("match12Down8"), match21Down8=pack("match21Down8"), off8=T[a:2 * a],
+                                                records=self.R, flowD2=cat([e["flow_d2"] for e in rg]), offd2=T[x0:x0 + a],
+                                                d2dims=self.d2dims if self.R is None else None)
+        where = {}
+        for ent in rg:
+            if self.st.want_lists:
+                ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
+            for j, m in enumerate(ent["mem"]):
+                where[m] = (ent, j)
+        return dict(accept=accept, gain=gain, where=where, match=match)
+
+    def trace_entry(self, rd, active):
+        where, tab, gm = rd["where"], self.table, self.gm
+        cut = lambda k, m: rd["match"][tab[k]:tab[k] + gm[m][0] * gm[m][1]].view(gm[m][:2])
+        return dict(super().trace_entry(rd, active), flowD2=[where[m][0]["flow_d2"][where[m][1]:where[m][1] + 1] for m in active],
+                    match=[cut(k, m) for k, m in enumerate(active)])
+
+    def collect(self, out, rd, k, m):
+        super().collect(out, rd, k, m)
+        ent, j = rd["where"][m]
+        out["flowD2"].append(ent["flow_d2"][j:j + 1])
