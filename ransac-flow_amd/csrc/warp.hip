@@ -42,7 +42,9 @@ __device__ __forceinline__ Corners corners(float gx, float gy, int Hi, int Wi, i
     const float xw = floorf(ix), yn = floorf(iy);
     const float w = ix - xw, e = 1.0f - w, n = iy - yn, s = 1.0f - n;
     c.nw = s * e; c.ne = s * w; c.sw = n * e; c.se = n * w;
-    // NaN / huge coordinates: comparisons below are all false -> contributes 0 like ATen's masks
+    // NaN / +-inf / huge coordinates: the comparisons below are all false -> the pixel is 0, as in ATen's CUDA grid_sampler (its
+    // within-bounds masks); ATen's CPU kernel returns NaN for NaN / +-inf coordinates and is not followed.  The (int) conversion
+    // further down is applied only to a floor that passed a range test (tests/test_gpu_pointwise_exact.py pins all of this).
     const bool xin0 = xw >= 0.0f && xw <= (float)(Wi - 1), xin1 = xw + 1.0f >= 0.0f && xw + 1.0f <= (float)(Wi - 1);
     const bool yin0 = yn >= 0.0f && yn <= (float)(Hi - 1), yin1 = yn + 1.0f >= 0.0f && yn + 1.0f <= (float)(Hi - 1);
     c.m_nw = xin0 && yin0; c.m_ne = xin1 && yin0; c.m_sw = xin0 && yin1; c.m_se = xin1 && yin1;

@@ -3,7 +3,8 @@ inputs, plus the reference golden vectors.  Needs a real MI355X: run with ``-m g
 
 Tolerances: integer / index outputs bit exact; float32 outputs within round-off of the value range
 (stated per test).  Where a float near-tie could flip an arg-max the test verifies that every
-disagreement IS such a near-tie (margin check in float64) and bounds their rate."""
+disagreement IS such a near-tie (margin check in float64) and bounds their rate.
+The warp / pool / resize / seg kernels are held to float64 at their edges in tests/test_gpu_pointwise_exact.py."""
 import os
 
 import numpy as np
