@@ -10,6 +10,8 @@
 //            count: no host sync for nbMatch, no 10 000-50 000 x 4 CPU draw + upload per pair and homography
 //   accept   gain = mean(newly explained matchability) -> accept rule -> mask update -> result-record store, with ONE
 //            small readback (the accept flags) per round for the host's active list.
+// The filter and the three accept steps are device functions (filter_body, accept_*_body) with typed parameters: the kernel for
+// same-size batches and the one for mixed-size (ragged) batches both call them and differ only in where a pair's data lies.
 #include "common.h"
 #include <math.h>
 
@@ -45,10 +47,13 @@ __global__ __launch_bounds__(256) void draw_samples_kernel(const int32_t* __rest
 // ---- explained-region mask -> keep map at a feature cell ------------------------------------------------------------------
 // fg = ((Mask + (1 - bg)) > 0.5) (evaluation/evalHpatch/evaluation.py:212); MtExtend = 1 - fg, bilinear-resized to the target
 // feature map (align_corners=False) and thresholded at 0.5 (evaluation/evalHpatch/coarseAlignFeatMatch.py:158-160).
-__device__ __forceinline__ float keep_px(const float* __restrict__ mask, const float* __restrict__ bg, size_t o) {
+__device__ __forceinline__ float fg_px(float maskv, const float* __restrict__ bg, size_t o) {
     const float bgv = bg ? bg[o] : 1.0f;
-    const float fg = __fadd_rn(mask[o], __fsub_rn(1.0f, bgv)) > 0.5f ? 1.0f : 0.0f;
-    return __fsub_rn(1.0f, fg);
+    return __fadd_rn(maskv, __fsub_rn(1.0f, bgv)) > 0.5f ? 1.0f : 0.0f;
+}
+
+__device__ __forceinline__ float keep_px(const float* __restrict__ mask, const float* __restrict__ bg, size_t o) {
+    return __fsub_rn(1.0f, fg_px(mask[o], bg, o));
 }
 
 __device__ __forceinline__ float src_index_nc(float scale, int dst) {   // ATen upsample_bilinear2d, align_corners=False
@@ -75,6 +80,57 @@ __global__ __launch_bounds__(256) void fill_ones_kernel(float* __restrict__ p, s
     if (i < n) p[i] = 1.0f;
 }
 
+// Ordered ballot compaction of one pair's cached matches: the body both match-filter kernels run, one 1024-thread workgroup per pair.
+// Every pointer is already moved to the pair (mask / bg / idx1 / idx2 / xa / ya / xb / yb to pair b, m1 / m2 / kept to slot k); n_out
+// is the whole array, indexed with k.  Holds barriers: every thread of the workgroup calls it, as the LAST statement of its kernel.
+__device__ __forceinline__ void filter_body(const int64_t* __restrict__ idx1, const int64_t* __restrict__ idx2,
+                                            const float* __restrict__ mask, const float* __restrict__ bg,
+                                            const float* __restrict__ xa, const float* __restrict__ ya,
+                                            const float* __restrict__ xb, const float* __restrict__ yb, float* __restrict__ m1,
+                                            float* __restrict__ m2, int32_t* __restrict__ n_out, int32_t* __restrict__ kept, int k,
+                                            int n, int cap, int h, int w, int ct, float sh, float sw) {
+    __shared__ int wsum[16];
+    __shared__ int base;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) base = 0;
+    __syncthreads();
+    for (int s = 0; s < n; s += 1024) {
+        const int i = s + t;
+        bool keep = false;
+        int64_t a = 0, cell = 0;
+        if (i < n) {
+            a = idx1[i]; cell = idx2[i];
+            const int r = (int)(cell / ct), c = (int)(cell - (int64_t)r * ct);
+            keep = keep_cell(mask, bg, h, w, sh, sw, r, c);
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) { const int cq = wsum[q]; if (q < wave) woff += cq; tot += cq; }
+        const int b0 = base;
+        if (keep) {
+            const size_t o = (size_t)(b0 + woff + before) * 3;
+            m1[o] = xa[a]; m1[o + 1] = ya[a]; m1[o + 2] = 1.0f;
+            m2[o] = xb[cell]; m2[o + 1] = yb[cell]; m2[o + 2] = 1.0f;
+            if (kept) kept[b0 + woff + before] = i;
+        }
+        __syncthreads();
+        if (t == 0) base = b0 + tot;
+        __syncthreads();
+    }
+    const int ntot = base;
+    for (int i = ntot + t; i < cap; i += 1024) {
+        const size_t o = (size_t)i * 3;
+        m1[o] = m1[o + 1] = m1[o + 2] = 0.0f;
+        m2[o] = m2[o + 1] = m2[o + 2] = 0.0f;
+        if (kept) kept[i] = -1;
+    }
+    if (t == 0) n_out[k] = ntot;
+}
+
 // One workgroup per active pair: the cached matches of pair b that fall outside the explained region, in order.
 __global__ __launch_bounds__(1024) void filter_matches_kernel(
     const int64_t* __restrict__ idx1, const int64_t* __restrict__ idx2, const int32_t* __restrict__ count, int cap,
@@ -91,7 +147,7 @@ __global__ __launch_bounds__(1024) void filter_matches_kernel(
     idx1 += (size_t)b * cap; idx2 += (size_t)b * cap;
     m1 += (size_t)k * cap * 3; m2 += (size_t)k * cap * 3;
     if (kept) kept += (size_t)k * cap;
-#include "multih_filter_body.inc"
+    filter_body(idx1, idx2, mask, bg, xa, ya, xb, yb, m1, m2, n_out, kept, k, n, cap, h, w, ct, sh, sw);
 }
 
 // The whole keep map of the active pairs: what CoarseAlign.getCoarse of variants A / C multiplies the target features with before
@@ -114,18 +170,103 @@ constexpr int NPART = 64;     // partial sums per pair
 
 // mode 0 (evalHpatch/evaluation.py:225,238-239): stat = match * (1 - fg); mask <- (mask + match * (1 - fg)) >= 1
 // mode 1 (evalKITTI/evaluation.py:322,332-333):  stat = (match > 0.9999) * (1 - fg); mask <- (mask + match * (1 - fg)) > 0.9999
-__device__ __forceinline__ float fg_px(const float* __restrict__ mask, const float* __restrict__ bg, size_t o) {
-    const float bgv = bg ? bg[o] : 1.0f;
-    return __fadd_rn(mask[o], __fsub_rn(1.0f, bgv)) > 0.5f ? 1.0f : 0.0f;
+// The three accept bodies below are what the dense and the ragged kernel of each step both run; the kernels differ only in where a
+// pair's maps lie (the element offsets they pass).  Each holds barriers and some leave early behind one: every thread of the
+// workgroup calls the body, as the LAST statement of its kernel.
+
+// Accept statistic: partial blockIdx.x of NPART over pair k's HW pixels.  match_off / mask_off: element offsets of the pair's
+// matchability map and of its mask (and background map).
+__device__ __forceinline__ void accept_partial_body(const float* __restrict__ match, const float* __restrict__ mask,
+                                                    const float* __restrict__ bg, int mode, double* __restrict__ part, int k,
+                                                    long long HW, size_t match_off, size_t mask_off) {
+    match += match_off; mask += mask_off;
+    if (bg) bg += mask_off;
+    const long long per = (HW + NPART - 1) / NPART;
+    const long long p0 = blockIdx.x * per, p1 = p0 + per < HW ? p0 + per : HW;
+    double s = 0.0;
+    for (long long p = p0 + threadIdx.x; p < p1; p += 256) {
+        const float nf = keep_px(mask, bg, (size_t)p);
+        const float m = match[p];
+        s += (double)__fmul_rn(mode ? (m > 0.9999f ? 1.0f : 0.0f) : m, nf);
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(size_t)k * NPART + blockIdx.x] = red[0];
+}
+
+// Accept rule and mask update of pair k (batch row b); offsets as in accept_partial_body.
+__device__ __forceinline__ void accept_update_body(const float* __restrict__ match, float* __restrict__ mask,
+                                                   const float* __restrict__ bg, int mode, const double* __restrict__ part,
+                                                   const int32_t* __restrict__ res, const int32_t* __restrict__ n_match,
+                                                   const int32_t* __restrict__ nbH, double th, int32_t* __restrict__ accept,
+                                                   float* __restrict__ gain, int k, int b, long long HW, size_t match_off,
+                                                   size_t mask_off) {
+    __shared__ int s_acc;
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int q = 0; q < NPART; ++q) s += part[(size_t)k * NPART + q];     // fixed order: every block gets the same sum
+        const float g = (float)(s / (double)HW);
+        const bool ok = n_match[k] >= 4 && res[k * 4] == 0 && ((double)g > th || nbH[b] == 0);
+        s_acc = ok ? 1 : 0;
+        if (blockIdx.x == 0) { accept[k] = ok ? 1 : 0; gain[k] = g; }
+    }
+    __syncthreads();
+    if (!s_acc) return;
+    match += match_off; mask += mask_off;
+    if (bg) bg += mask_off;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
+        const float mk = mask[p];
+        const float v = __fadd_rn(mk, __fmul_rn(match[p], __fsub_rn(1.0f, fg_px(mk, bg, (size_t)p))));
+        mask[p] = (mode ? v > 0.9999f : v >= 1.0f) ? 1.0f : 0.0f;
+    }
+}
+
+// Record store of pair k (batch row b): hw8 / hwd2 are the pair's /8 and half-resolution /8 pixel counts, off_* the parts of its
+// record row, f8_off / m8_off / d2_off the element offsets of pair k's /8 flow, /8 matchability maps and half-resolution flow.
+__device__ __forceinline__ void accept_store_body(const int32_t* __restrict__ accept, int32_t* __restrict__ nbH,
+                                                  const float* __restrict__ bestH, const float* __restrict__ flow8,
+                                                  const float* __restrict__ m12, const float* __restrict__ m21,
+                                                  const float* __restrict__ flowd2, float* __restrict__ rec, long long rec_stride,
+                                                  int max_h, int k, int b, int hw8, int hwd2, int off_H, int off_flow, int off_match,
+                                                  int off_d2, size_t f8_off, size_t m8_off, size_t d2_off) {
+    if (!accept[k]) return;
+    const int slot = nbH[b];
+    const int t = threadIdx.x;
+    if (rec && slot < max_h) {
+        float* r = rec + (size_t)b * rec_stride;
+        if (t < 9) r[off_H + slot * 9 + t] = bestH[k * 9 + t];
+        if (flow8)
+            for (int i = t; i < 2 * hw8; i += 1024) r[off_flow + (size_t)slot * 2 * hw8 + i] = flow8[f8_off + i];
+        if (m12 && m21)
+            for (int i = t; i < hw8; i += 1024) {
+                r[off_match + (size_t)slot * 2 * hw8 + i] = m12[m8_off + i];
+                r[off_match + (size_t)slot * 2 * hw8 + hw8 + i] = m21[m8_off + i];
+            }
+        if (flowd2)
+            for (int i = t; i < 2 * hwd2; i += 1024) r[off_d2 + (size_t)slot * 2 * hwd2 + i] = flowd2[d2_off + i];
+    }
+    __syncthreads();
+    if (t == 0) {
+        nbH[b] = slot + 1;
+        // the record's nbH field never exceeds the slots it holds; a pair that accepted more (only the unbounded KITTI loop
+        // can) is flagged with status 3, and the device counter nbH[] keeps the true number
+        if (rec) {
+            rec[(size_t)b * rec_stride] = (float)(slot + 1 < max_h ? slot + 1 : max_h);
+            rec[(size_t)b * rec_stride + 1] = slot + 1 > max_h ? 3.0f : 0.0f;
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void accept_partial_kernel(const float* __restrict__ match, const float* __restrict__ mask,
                                                              const float* __restrict__ bg, const int32_t* __restrict__ active,
                                                              long long HW, int mode, double* __restrict__ part) {
     const int k = blockIdx.y, b = active ? active[k] : k;
-#define MH_MATCH_OFF ((size_t)k * HW)
-#define MH_MASK_OFF ((size_t)b * HW)
-#include "multih_accept_partial_body.inc"
+    accept_partial_body(match, mask, bg, mode, part, k, HW, (size_t)k * HW, (size_t)b * HW);
 }
 
 __global__ __launch_bounds__(256) void accept_update_kernel(const float* __restrict__ match, float* __restrict__ mask,
@@ -135,9 +276,7 @@ __global__ __launch_bounds__(256) void accept_update_kernel(const float* __restr
                                                             const int32_t* __restrict__ nbH, double th,
                                                             int32_t* __restrict__ accept, float* __restrict__ gain) {
     const int k = blockIdx.y, b = active ? active[k] : k;
-#include "multih_accept_update_body.inc"
-#undef MH_MATCH_OFF
-#undef MH_MASK_OFF
+    accept_update_body(match, mask, bg, mode, part, res, n_match, nbH, th, accept, gain, k, b, HW, (size_t)k * HW, (size_t)b * HW);
 }
 
 // The per-pair result record (what evaluation/evalHpatch/evaluation.py:254-260 saves per pair): slot nbH[b] of
@@ -149,19 +288,14 @@ __global__ __launch_bounds__(1024) void accept_store_kernel(const int32_t* __res
                                                             int hwd2, float* __restrict__ rec, long long rec_stride, int max_h,
                                                             int off_H, int off_flow, int off_match, int off_d2) {
     const int k = blockIdx.x, b = active ? active[k] : k;
-#define MH_F8_OFF ((size_t)k * 2 * hw8)
-#define MH_M8_OFF ((size_t)k * hw8)
-#define MH_D2_OFF ((size_t)k * 2 * hwd2)
-#include "multih_accept_store_body.inc"
-#undef MH_F8_OFF
-#undef MH_M8_OFF
-#undef MH_D2_OFF
+    accept_store_body(accept, nbH, bestH, flow8, m12, m21, flowd2, rec, rec_stride, max_h, k, b, hw8, hwd2, off_H, off_flow, off_match,
+                      off_d2, (size_t)k * 2 * hw8, (size_t)k * hw8, (size_t)k * 2 * hwd2);
 }
 
 // ---- ragged batches: the active pairs of one launch differ in size ----------------------------------------------------------------
 // Pair b's explained-region mask (and background map) lives at element offset moff[b] of ONE packed float buffer; its geometry is row b
 // of a device table geom (batch, RG) int32 = h, w, rt, ct, h8, w8.  Every kernel below sets the per-pair values the dense kernel takes
-// as launch arguments and then runs the dense kernel's body text (the multih_*_body.inc files): same ballots, same partition of the
+// as launch arguments and then calls the dense kernel's body function (filter_body, accept_*_body): same ballots, same partition of the
 // pair's own HW pixels into NPART partial sums, same order of the double additions.
 constexpr int RG = 6;
 
@@ -185,12 +319,10 @@ __global__ __launch_bounds__(1024) void filter_matches_ragged_kernel(
     idx1 += (size_t)b * cap; idx2 += (size_t)b * cap;
     m1 += (size_t)k * cap * 3; m2 += (size_t)k * cap * 3;
     if (kept) kept += (size_t)k * cap;
-#include "multih_filter_body.inc"
+    filter_body(idx1, idx2, mask, bg, xa, ya, xb, yb, m1, m2, n_out, kept, k, n, cap, h, w, ct, sh, sw);
 }
 
 // match: packed per ACTIVE pair, pair k of the round at element offset match_off[k]; mask / bg: pair b at moff[b]
-#define MH_MATCH_OFF ((size_t)match_off[k])
-#define MH_MASK_OFF ((size_t)moff[b])
 __global__ __launch_bounds__(256) void accept_partial_ragged_kernel(const float* __restrict__ match,
                                                                     const long long* __restrict__ match_off,
                                                                     const float* __restrict__ mask, const float* __restrict__ bg,
@@ -199,7 +331,7 @@ __global__ __launch_bounds__(256) void accept_partial_ragged_kernel(const float*
                                                                     double* __restrict__ part) {
     const int k = blockIdx.y, b = active ? active[k] : k;
     const long long HW = (long long)geom[b * RG] * geom[b * RG + 1];
-#include "multih_accept_partial_body.inc"
+    accept_partial_body(match, mask, bg, mode, part, k, HW, (size_t)match_off[k], (size_t)moff[b]);
 }
 
 __global__ __launch_bounds__(256) void accept_update_ragged_kernel(const float* __restrict__ match, const long long* __restrict__ match_off,
@@ -211,10 +343,9 @@ __global__ __launch_bounds__(256) void accept_update_ragged_kernel(const float* 
                                                                    double th, int32_t* __restrict__ accept, float* __restrict__ gain) {
     const int k = blockIdx.y, b = active ? active[k] : k;
     const long long HW = (long long)geom[b * RG] * geom[b * RG + 1];
-#include "multih_accept_update_body.inc"
+    accept_update_body(match, mask, bg, mode, part, res, n_match, nbH, th, accept, gain, k, b, HW, (size_t)match_off[k],
+                       (size_t)moff[b]);
 }
-#undef MH_MATCH_OFF
-#undef MH_MASK_OFF
 
 // The record row of pair b is laid out with the pair's OWN h8 * w8 (ops.MultiHRecordsRagged); the /8 maps of the round are packed per
 // active pair: flowDown8 of pair k at 2 * off8[k], match12Down8 / match21Down8 at off8[k].  KITTI rounds (flowd2 given): the
@@ -231,13 +362,10 @@ __global__ __launch_bounds__(1024) void accept_store_ragged_kernel(const int32_t
     const int k = blockIdx.x, b = active ? active[k] : k;
     const int hw8 = geom[b * RG + 4] * geom[b * RG + 5], hwd2 = flowd2 ? d2dims[2 * b] * d2dims[2 * b + 1] : 0;
     const int off_match = off_flow + 2 * hw8 * max_h, off_d2 = off_match + 2 * hw8 * max_h;
-#define MH_F8_OFF ((size_t)2 * off8[k])
-#define MH_M8_OFF ((size_t)off8[k])
-#define MH_D2_OFF ((size_t)2 * offd2[k])
-#include "multih_accept_store_body.inc"
-#undef MH_F8_OFF
-#undef MH_M8_OFF
-#undef MH_D2_OFF
+    // off8 / offd2 may be null where the maps they index are not given
+    const size_t o8 = off8 ? (size_t)off8[k] : 0, od2 = flowd2 ? (size_t)offd2[k] : 0;
+    accept_store_body(accept, nbH, bestH, flow8, m12, m21, flowd2, rec, rec_stride, max_h, k, b, hw8, hwd2, off_H, off_flow, off_match,
+                      off_d2, 2 * o8, o8, 2 * od2);
 }
 
 }  // namespace

@@ -317,19 +317,232 @@ __global__ __launch_bounds__(256, 2) void mnn_tile_kernel(MnnArgs a) {
 // quick_start's, 104.2 -> 98.5 at config 5's (8 x 25 747 x 8 250).  The tile kernel is therefore NOT bound by operand bytes per MFMA
 // (nor, a fortiori, by the 4.6x panel re-fetch traffic the counters show: it is served by L2 / the Infinity Cache at ~1 TB/s): one
 // barrier per K step across EIGHT wavefronts costs more than two independent 4-wave workgroups lose to each other.  128 x 128 stays.
+//
+// The three steps are device functions that the single-pair / dense kernels call with their launch arguments and the ragged kernels
+// (below) with a copy narrowed to the workgroup's own pair.  The tile and the compaction body hold barriers: every thread of the
+// workgroup calls the body, as the LAST statement of its kernel.
+template <bool VEC, int WA>
+__device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
+    constexpr int BMA = BM * WA, NT = 256 * WA;
+    constexpr int A_TPR = VEC ? BMA / 4 : BMA;     // threads per A row
+    constexpr int A_RPR = NT / A_TPR;              // A rows per round of all threads: 8 (VEC) / 2 (scalar)
+    constexpr int NLA = BK / A_RPR;                // A loads per thread and K step: 4 / 16
+    constexpr int B_TPR = VEC ? BN / 4 : BN;
+    constexpr int B_RPR = NT / B_TPR;              // 8 * WA / 2 * WA
+    constexpr int NLB = BK / B_RPR;                // 4 / WA, 16 / WA
+    __shared__ __attribute__((aligned(16))) float As[2][BK][BMA];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int lrow = lane >> 5, lcol = lane & 31;
+    const int pair = blockIdx.y;
+    const float* Ab = a.A + (size_t)pair * a.strideA;
+    const float* Bb = a.B + (size_t)pair * a.strideB;
+    char* ws = a.ws + (size_t)pair * a.wsStride;
+    float* rowPartVal = reinterpret_cast<float*>(ws + a.oRowPartVal);
+    int* rowPartIdx = reinterpret_cast<int*>(ws + a.oRowPartIdx);
+    float* colPartVal = reinterpret_cast<float*>(ws + a.oColPartVal);
+    int* colPartIdx = reinterpret_cast<int*>(ws + a.oColPartIdx);
+    const int nwg = a.tilesA * a.tilesB;
+    int bid = blockIdx.x;
+    {   // XCD-aware bijective remap; column tile fastest so an XCD's L2 keeps one A panel hot
+        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+    }
+    const int tb = bid % a.tilesB, ta = bid / a.tilesB;
+    const int i0 = ta * BMA, j0 = tb * BN;
+    // staging roles: row t / TPR (+ RPR per round), cells (t % TPR) * (VEC ? 4 : 1) ..
+    const int arow_s = t / A_TPR, acol_s = (t % A_TPR) * (VEC ? 4 : 1);
+    const int brow_s = t / B_TPR, bcol_s = (t % B_TPR) * (VEC ? 4 : 1);
+    int ca = i0 + acol_s, cb = j0 + bcol_s;
+    if (VEC) { if (ca + 4 > a.ldA) ca = a.ldA - 4; if (cb + 4 > a.ldB) cb = a.ldB - 4; }
+    else     { if (ca >= a.nA) ca = a.nA - 1;     if (cb >= a.nB) cb = a.nB - 1; }
+    const float* asrc = Ab + (size_t)arow_s * a.ldA + ca;
+    const float* bsrc = Bb + (size_t)brow_s * a.ldB + cb;
+    f32x4 va[VEC ? NLA : 1], vb[VEC ? NLB : 1];
+    float ra[VEC ? 1 : NLA], rb[VEC ? 1 : NLB];
+    auto load_a = [&](int k0, int j) {
+        if (VEC) va[j] = *reinterpret_cast<const f32x4*>(asrc + (size_t)(k0 + A_RPR * j) * a.ldA);
+        else     ra[j] = asrc[(size_t)(k0 + A_RPR * j) * a.ldA];
+    };
+    auto load_b = [&](int k0, int j) {
+        if (VEC) vb[j] = *reinterpret_cast<const f32x4*>(bsrc + (size_t)(k0 + B_RPR * j) * a.ldB);
+        else     rb[j] = bsrc[(size_t)(k0 + B_RPR * j) * a.ldB];
+    };
+    auto store_a = [&](int buf, int j) {
+        if (VEC) *reinterpret_cast<f32x4*>(&As[buf][arow_s + A_RPR * j][acol_s]) = va[j];
+        else     As[buf][arow_s + A_RPR * j][acol_s] = ra[j];
+    };
+    auto store_b = [&](int buf, int j) {
+        if (VEC) *reinterpret_cast<f32x4*>(&Bs[buf][brow_s + B_RPR * j][bcol_s]) = vb[j];
+        else     Bs[buf][brow_s + B_RPR * j][bcol_s] = rb[j];
+    };
+    const int nk = a.C / BK;
+#pragma unroll
+    for (int j = 0; j < NLA; ++j) load_a(0, j);
+#pragma unroll
+    for (int j = 0; j < NLB; ++j) load_b(0, j);
+#pragma unroll
+    for (int j = 0; j < NLA; ++j) store_a(0, j);
+#pragma unroll
+    for (int j = 0; j < NLB; ++j) store_b(0, j);
+#pragma unroll
+    for (int j = 0; j < NLA; ++j) load_a(BK, j);
+#pragma unroll
+    for (int j = 0; j < NLB; ++j) load_b(BK, j);
+    __syncthreads();
+
+    f32x16 acc[2][2], tot[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.0f;
+    const float* arow = &As[0][lrow][wm * 64 + lcol];
+    const float* brow = &Bs[0][lrow][wn * 64 + lcol];
+    for (int s = 0; s < nk; ++s) {
+        const int cur = s & 1;
+        const float* ap = arow + cur * (BK * BMA);
+        const float* bp = brow + cur * (BK * BN);
+        const int k2 = (s + 2 < nk ? s + 2 : nk - 1) * BK;      // past the end: re-load the last step (never consumed)
+        float af[2][4][2], bf[2][4][2];
+        auto read_chunk = [&](int c, int slot) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int kk = c * 4 + e;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) af[slot][e][i] = ap[2 * kk * BMA + i * 32];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bf[slot][e][j] = bp[2 * kk * BN + j * 32];
+            }
+        };
+        read_chunk(0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c + 1 < 4) read_chunk(c + 1, (c + 1) & 1);
+            // the registers hold K step s+1: stored into the other buffer and re-loaded with step s+2 right behind the store
+            if (c == 0) {
+#pragma unroll
+                for (int j = 0; j < NLA; ++j) store_a(cur ^ 1, j);
+#pragma unroll
+                for (int j = 0; j < NLA; ++j) load_a(k2, j);
+            } else if (c == 1) {
+#pragma unroll
+                for (int j = 0; j < NLB; ++j) store_b(cur ^ 1, j);
+#pragma unroll
+                for (int j = 0; j < NLB; ++j) load_b(k2, j);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c & 1][e][i], bf[c & 1][e][j], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (s + 1 == nk || (a.kch && (s + 1) % a.kch == 0)) mnn_close_chunk(tot, acc);
+        __syncthreads();
+    }
+    if (a.maskB) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int gj = j0 + (wn * 2 + j) * 32 + lcol;
+            const float mk = gj < a.nB ? a.maskB[(size_t)pair * a.strideMask + gj] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] *= mk;
+        }
+    }
+    mnn_tile_epilogue<WA>(tot, a, &As[0][0][0], reinterpret_cast<int*>(&Bs[0][0][0]), i0, j0, ta, tb, rowPartVal, rowPartIdx, colPartVal,
+                          colPartIdx);
+}
+
 template <bool VEC, int WA = 1>
 __global__ __launch_bounds__(256 * WA, WA == 1 ? 2 : 1) void mnn_tile_kmajor_kernel(MnnArgs a) {
-#include "mnn_tile_kmajor_body.inc"
+    mnn_tile_kmajor_body<VEC, WA>(a);
 }
 
-__global__ __launch_bounds__(256) void mnn_reduce_kernel(MnnArgs a) {
-#include "mnn_reduce_body.inc"
+// blockIdx.y = the pair; one thread per row of A, then per row of B
+__device__ __forceinline__ void mnn_reduce_body(const MnnArgs& a) {
+    char* ws = a.ws + (size_t)blockIdx.y * a.wsStride;
+    const float* rowPartVal = reinterpret_cast<const float*>(ws + a.oRowPartVal);
+    const int* rowPartIdx = reinterpret_cast<const int*>(ws + a.oRowPartIdx);
+    const float* colPartVal = reinterpret_cast<const float*>(ws + a.oColPartVal);
+    const int* colPartIdx = reinterpret_cast<const int*>(ws + a.oColPartIdx);
+    float* rowVal = reinterpret_cast<float*>(ws + a.oRowVal);
+    int* rowIdx = reinterpret_cast<int*>(ws + a.oRowIdx);
+    int* colIdx = reinterpret_cast<int*>(ws + a.oColIdx);
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < a.nA) {
+        float bv = -INFINITY;
+        int bj = 0x7fffffff;
+        for (int tb = 0; tb < a.tilesB; ++tb)
+            take_min_idx(bv, bj, rowPartVal[(size_t)tb * a.nA + g], rowPartIdx[(size_t)tb * a.nA + g]);
+        rowVal[g] = bv;
+        rowIdx[g] = bj;
+    } else if (g - a.nA < a.nB) {
+        const int j = g - a.nA;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int ta = 0; ta < a.tilesA; ++ta)
+            take_min_idx(bv, bi, colPartVal[(size_t)ta * a.nB + j], colPartIdx[(size_t)ta * a.nB + j]);
+        colIdx[j] = bi;
+    }
 }
 
-// single workgroup, ordered compaction by ascending source index
-__global__ __launch_bounds__(1024) void mnn_compact_kernel(MnnArgs a) {
-#include "mnn_compact_body.inc"
+__global__ __launch_bounds__(256) void mnn_reduce_kernel(MnnArgs a) { mnn_reduce_body(a); }
+
+// single workgroup per pair (blockIdx.x), ordered compaction by ascending source index
+__device__ __forceinline__ void mnn_compact_body(const MnnArgs& a) {
+    char* ws = a.ws + (size_t)blockIdx.x * a.wsStride;
+    const float* rowVal = reinterpret_cast<const float*>(ws + a.oRowVal);
+    const int* rowIdx = reinterpret_cast<const int*>(ws + a.oRowIdx);
+    const int* colIdx = reinterpret_cast<const int*>(ws + a.oColIdx);
+    const int nA = a.nA, nB = a.nB;
+    int64_t* idx1 = a.idx1 + (size_t)blockIdx.x * a.idxStride;
+    int64_t* idx2 = a.idx2 + (size_t)blockIdx.x * a.idxStride;
+    int32_t* count = a.count + blockIdx.x;
+    __shared__ int wsum[16];
+    __shared__ int base;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) base = 0;
+    __syncthreads();
+    for (int s = 0; s < nA; s += 1024) {
+        const int i = s + t;
+        bool keep = false;
+        int j = 0;
+        if (i < nA) {
+            j = rowIdx[i];
+            const float v = rowVal[i];
+            keep = ((unsigned)j < (unsigned)nB) && (colIdx[j] == i) && (v * v > 0.0f);
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int woff = 0, tot = 0;
+        for (int w = 0; w < 16; ++w) {
+            const int c = wsum[w];
+            if (w < wave) woff += c;
+            tot += c;
+        }
+        const int b = base;
+        if (keep) {
+            idx1[b + woff + before] = i;
+            idx2[b + woff + before] = j;
+        }
+        __syncthreads();
+        if (t == 0) base = b + tot;
+        __syncthreads();
+    }
+    if (t == 0) count[0] = base;
 }
+
+__global__ __launch_bounds__(1024) void mnn_compact_kernel(MnnArgs a) { mnn_compact_body(a); }
 
 struct WsLayout {
     size_t rowPartVal, rowPartIdx, colPartVal, colPartIdx, rowVal, rowIdx, colIdx, total;
@@ -353,7 +566,7 @@ inline WsLayout layout(int nA, int nB) {
 // ---------------------------------------------------------------------------------------------------------------
 // Ragged batches: B pairs of different sizes in one tile -> reduce -> compact chain.  The launch's MnnArgs carry the batch
 // MAXIMA (nA, nB: the grids, the uniform workspace layout and slot stride); each workgroup narrows them to its own pair's
-// nA[b], nB[b] and runs the single-pair kernels' body text (the *_body.inc files) unchanged -- same tiles, same k order, same chunking, same tie rule, so a pair's
+// nA[b], nB[b] and calls the single-pair kernels' body functions -- same tiles, same k order, same chunking, same tie rule, so a pair's
 // match list is the one rfx_mutual_nn_f32 finds on its own features.  Tiles and reduce threads past a pair's own grid exit at once.
 // A pair whose sizes are out of range (<= 0, above the maxima, or more possible matches than `cap`) gets count 0 and no work.
 struct MnnRagged {
@@ -372,13 +585,12 @@ __device__ __forceinline__ bool mnn_ragged_pair(MnnArgs& a, const MnnRagged& r, 
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void mnn_tile_ragged_kernel(MnnArgs a, MnnRagged r) {
     if (!mnn_ragged_pair(a, r, blockIdx.y) || (int)blockIdx.x >= a.tilesA * a.tilesB) return;
-    constexpr int WA = 1;
-#include "mnn_tile_kmajor_body.inc"
+    mnn_tile_kmajor_body<VEC, 1>(a);
 }
 
 __global__ __launch_bounds__(256) void mnn_reduce_ragged_kernel(MnnArgs a, MnnRagged r) {
     if (!mnn_ragged_pair(a, r, blockIdx.y) || (int)(blockIdx.x * blockDim.x) >= a.nA + a.nB) return;
-#include "mnn_reduce_body.inc"
+    mnn_reduce_body(a);
 }
 
 __global__ __launch_bounds__(1024) void mnn_compact_ragged_kernel(MnnArgs a, MnnRagged r) {
@@ -386,7 +598,7 @@ __global__ __launch_bounds__(1024) void mnn_compact_ragged_kernel(MnnArgs a, Mnn
         if (threadIdx.x == 0) a.count[blockIdx.x] = 0;
         return;
     }
-#include "mnn_compact_body.inc"
+    mnn_compact_body(a);
 }
 
 }  // namespace
@@ -408,14 +620,20 @@ static int mnn_chunk_steps(int score_chunk, int* kch) {
     return RFX_OK;
 }
 
-static int mnn_launch(MnnArgs& a, int batch, hipStream_t st) {
+// Tile counts and per-pair workspace layout for a.nA x a.nB (a ragged batch: its maxima); RFX_E_LIMIT where a grid cannot hold them.
+static int mnn_plan(MnnArgs& a, int batch, long long* nwg) {
     const WsLayout L = layout(a.nA, a.nB);
     a.tilesA = (a.nA + BM - 1) / BM; a.tilesB = (a.nB + BN - 1) / BN;
     a.wsStride = L.total;
     a.oRowPartVal = L.rowPartVal; a.oRowPartIdx = L.rowPartIdx; a.oColPartVal = L.colPartVal; a.oColPartIdx = L.colPartIdx;
     a.oRowVal = L.rowVal; a.oRowIdx = L.rowIdx; a.oColIdx = L.colIdx;
-    const long long nwg = (long long)a.tilesA * a.tilesB;
-    if (nwg > 0x7fffffffLL || batch > 65535) return RFX_E_LIMIT;
+    *nwg = (long long)a.tilesA * a.tilesB;
+    return (*nwg > 0x7fffffffLL || batch > 65535) ? RFX_E_LIMIT : RFX_OK;
+}
+
+static int mnn_launch(MnnArgs& a, int batch, hipStream_t st) {
+    long long nwg;
+    if (mnn_plan(a, batch, &nwg) != RFX_OK) return RFX_E_LIMIT;
     const bool vec = a.ldA % 4 == 0 && a.ldB % 4 == 0 && a.strideA % 4 == 0 && a.strideB % 4 == 0 &&
                      ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.B)) & 15) == 0;
     const char* fe = getenv("RFX_MNN_FORM");                  // 1: force the transposed-image kernel (tests, A/B timing)
@@ -480,16 +698,12 @@ extern "C" int rfx_mutual_nn_ragged_f32(const float* featA, int ldA, const float
     if (C % BK != 0 || C < 2 * BK) return RFX_E_ARG;
     MnnArgs a;
     if (mnn_chunk_steps(score_chunk, &a.kch) != RFX_OK) return RFX_E_ARG;
-    const WsLayout L = layout(maxNA, maxNB);
     a.A = featA; a.B = featB; a.maskB = maskB; a.ldA = ldA; a.ldB = ldB; a.nA = maxNA; a.nB = maxNB; a.C = C;
-    a.tilesA = (maxNA + BM - 1) / BM; a.tilesB = (maxNB + BN - 1) / BN;
     a.strideA = (long long)C * ldA; a.strideB = (long long)C * ldB; a.strideMask = ldB;
-    a.ws = static_cast<char*>(ws); a.wsStride = L.total;
-    a.oRowPartVal = L.rowPartVal; a.oRowPartIdx = L.rowPartIdx; a.oColPartVal = L.colPartVal; a.oColPartIdx = L.colPartIdx;
-    a.oRowVal = L.rowVal; a.oRowIdx = L.rowIdx; a.oColIdx = L.colIdx;
+    a.ws = static_cast<char*>(ws);
     a.idx1 = idx1; a.idx2 = idx2; a.count = count; a.idxStride = cap;
-    const long long nwg = (long long)a.tilesA * a.tilesB;
-    if (nwg > 0x7fffffffLL || batch > 65535) return RFX_E_LIMIT;
+    long long nwg;
+    if (mnn_plan(a, batch, &nwg) != RFX_OK) return RFX_E_LIMIT;
     MnnRagged r;
     r.nA = nA; r.nB = nB; r.cap = cap;
     const bool vec = ldA % 4 == 0 && ldB % 4 == 0 &&
