@@ -28,31 +28,33 @@ class ResNet50Trunk:
             for b in range(nblk):
                 p = "%s.%d" % (layer, b)
                 s = stride if b == 0 else 1
-                # split=True (round 6): the long-K 1x1 layers -- conv1 of every block but the first (K = 256 ... 1024) and layer3's
-                # conv3 (K = 256, + residual) -- run on rfx_conv1x1_split_f32: float32 sums from exact bf16 operand pieces, closer to
-                # the exact sum than the fp32-MFMA kernel and 1.3-1.5x faster (profiles/r06_split_conv_bench.json).  The conv3 of a
-                # block whose tail can fuse (layer1 / layer2) stays on the fp32 kernels: fused and two-kernel forms stay bit-identical.
-                w1 = sd[p + ".conv1.weight"]
+                w1, w2, w3 = (sd["%s.conv%d.weight" % (p, i)] for i in (1, 2, 3))
+                # Which convolutions ask for the split kernels (float32 sums from exact bf16 operand pieces, closer to the exact sum
+                # than the fp32-MFMA kernels and 1.3-1.5x faster: profiles/r06_split_conv_bench.json) is decided here, from the
+                # layer's shapes, before anything is packed.  c1 and the projection shortcut: the long-K 1x1 layers (K >= 128).
+                # (scale: bottleneck_tail_shape only asks whether one is folded -- every convolution here has its BatchNorm)
+                tail = ops.bottleneck_tail_shape(ops.ConvGeometry(*w2.shape, stride=s, pad=1, act=ACT_RELU, scale="bn2"),
+                                                 ops.ConvGeometry(*w3.shape, stride=1, pad=0, act=ACT_RELU, scale="bn3"))
+                if not tail:
+                    # layer3 (256 -> 256 3x3, K = 2304; conv3 with K = 256, + residual) and the stride-2 3x3 of a layer's first block
+                    split2 = split3 = True
+                elif ops.conv_split_enabled() and os.environ.get("RFX_SPLIT_TAILS", "1") != "0":
+                    # layer1 / layer2 tails (3x3 64 -> 64 / 128 -> 128, then the 1x1 expansion): two split kernels beat the fused fp32
+                    # kernel (the 3x3 runs 1.3-1.45x faster on the bf16 pipe; measured per block in profiles/r06_split_conv_bench.json)
+                    split2, split3 = True, w3.shape[1] >= 128
+                else:
+                    # the tail stays on the fp32 kernels: fused and two-kernel forms stay bit-identical
+                    split2 = split3 = False
                 blk = {
                     "c1": ConvPlan(w1, _bn(sd, p + ".bn1"), 1, 0, ACT_RELU, device, split=w1.shape[1] >= 128),
-                    "c2": ConvPlan(sd[p + ".conv2.weight"], _bn(sd, p + ".bn2"), s, 1, ACT_RELU, device, split=s == 2),   # stride 2: rfx_conv3x3_split_s2_f32
-                    "c3": ConvPlan(sd[p + ".conv3.weight"], _bn(sd, p + ".bn3"), 1, 0, ACT_RELU, device),
+                    "c2": ConvPlan(w2, _bn(sd, p + ".bn2"), s, 1, ACT_RELU, device, split=split2),
+                    "c3": ConvPlan(w3, _bn(sd, p + ".bn3"), 1, 0, ACT_RELU, device, split=split3),
                     "ds": None,
                 }
-                if not ops.bottleneck_tail_shape(blk["c2"], blk["c3"]):
-                    blk["c3"] = ConvPlan(sd[p + ".conv3.weight"], _bn(sd, p + ".bn3"), 1, 0, ACT_RELU, device, split=True)
-                    if s == 1:   # layer3's 256 -> 256 3x3 (K = 2304): rfx_conv3x3_split_f32
-                        blk["c2"] = ConvPlan(sd[p + ".conv2.weight"], _bn(sd, p + ".bn2"), s, 1, ACT_RELU, device, split=True)
                 if (p + ".downsample.0.weight") in sd:
                     wd = sd[p + ".downsample.0.weight"]       # the stride-2 projections (256 -> 512, 512 -> 1024): split kernel, strided pixels
                     blk["ds"] = ConvPlan(wd, _bn(sd, p + ".downsample.1"), s, 0, ACT_NONE, device, split=wd.shape[1] >= 128)
-                if ops.bottleneck_tail_shape(blk["c2"], blk["c3"]):
-                    if ops.conv_split_enabled() and os.environ.get("RFX_SPLIT_TAILS", "1") != "0":
-                        # layer1 / layer2 tails (3x3 64 -> 64 / 128 -> 128, then the 1x1 expansion): two split kernels beat the fused fp32
-                        # kernel (the 3x3 runs 1.3-1.45x faster on the bf16 pipe; measured per block in profiles/r06_split_conv_bench.json)
-                        blk["c2"] = ConvPlan(sd[p + ".conv2.weight"], _bn(sd, p + ".bn2"), s, 1, ACT_RELU, device, split=True)
-                        blk["c3"] = ConvPlan(sd[p + ".conv3.weight"], _bn(sd, p + ".bn3"), 1, 0, ACT_RELU, device,
-                                             split=blk["c3"].Cin >= 128)
+                if tail:
                     # the tail's 3x3 (K = 576 / 1152) sums in chunks of 4 K steps -- in the fused kernel and, with this argument,
                     # in the stand-alone one (RFX_FUSE_BOTTLENECK=0): the two forms stay bit-identical
                     blk["c2"].k_chunk = 4

@@ -20,17 +20,18 @@ def _stream(dev=None):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _call(name, dev, *args):
-    """lib.<name>(*args, stream) on ``dev``: the stream is torch's current stream OF THAT DEVICE and the HIP
-    current device is switched for the launch when the tensors do not live on it (ctypes bypasses torch's
-    device guard)."""
-    fn = getattr(_lib.load(), name)
+def _on_device(dev, fn, *args):
+    """fn(*args, stream) with ``dev`` the HIP current device: the stream is torch's current stream OF THAT DEVICE, and the HIP
+    current device is switched for the call when it is another one (ctypes bypasses torch's device guard)."""
     if dev.index is not None and dev.index != torch.cuda.current_device():
         with torch.cuda.device(dev):
-            rc = fn(*args, _stream(dev))
-    else:
-        rc = fn(*args, _stream())
-    _lib.check(rc, name)
+            return fn(*args, _stream(dev))
+    return fn(*args, _stream())
+
+
+def _call(name, dev, *args):
+    """lib.<name>(*args, stream) on the device the tensors live on (_on_device)."""
+    _lib.check(_on_device(dev, getattr(_lib.load(), name), *args), name)
 
 
 def _one_device(*tensors):
@@ -109,6 +110,11 @@ class Profiler:
         e1.record(torch.cuda.current_stream(getattr(e0, "_rfx_dev", None)))
         return e1
 
+    @staticmethod
+    def record_conv(kid, flops, e0, shape, nbytes):
+        """End the event pair ``e0`` opened and append the launch's ``conv`` tuple (bench.py decodes exactly this layout)."""
+        Profiler.active().conv.append((kid, flops, e0, Profiler.end(e0), shape, nbytes))
+
 
 class launch_group:
     """``with ops.launch_group(device):`` -- the convolution ops issued inside are RECORDED by the library and launched at exit
@@ -148,11 +154,7 @@ class launch_group:
                 return False
             prev = lib.rfx_group_side_streams(1 if self.side else 0)
             try:
-                if self.dev.index is not None and self.dev.index != torch.cuda.current_device():
-                    with torch.cuda.device(self.dev):
-                        rc = lib.rfx_group_end(_stream(self.dev))
-                else:
-                    rc = lib.rfx_group_end(_stream())
+                rc = _on_device(self.dev, lib.rfx_group_end)
             finally:
                 lib.rfx_group_side_streams(prev)
             _lib.check(rc, "rfx_group_end")
@@ -207,13 +209,83 @@ def split_weights(w2d):
     return pieces.view(3, Mpad, Cin // 16, 2, 8).permute(2, 0, 3, 1, 4).contiguous().view(torch.int16)
 
 
+def split_weights_3x3(w):
+    """(Cout, Cin, 3, 3) float32 -> rfx_conv3x3_split_f32's wS3: split_weights of every tap, [c / 16][tap][piece][h][m][8]."""
+    return torch.stack([split_weights(w[:, :, kh, kw]) for kh in range(3) for kw in range(3)], dim=1).contiguous()
+
+
+def pack_wT(w):
+    """(Cout, Cin, KH, KW) float32 -> rfx_conv2d_f32's wT: the (K, Cout) transpose, zero-padded to (Kpad, Mpad) (32 / 128)."""
+    Cout, K = w.shape[0], w[0].numel()
+    wT = torch.zeros((K + 31) // 32 * 32, (Cout + 127) // 128 * 128, dtype=torch.float32)
+    wT[:K, :Cout] = w.reshape(Cout, K).t()
+    return wT
+
+
+def pack_ktab(w, dilation=1):
+    """rfx_conv2d_f32's gather table of a (Cout, Cin, KH, KW) weight: per k, c << 8 | row offset << 4 | column offset (-1 past K)."""
+    _, Cin, KH, KW = w.shape
+    K = Cin * KH * KW
+    k = torch.arange(K)
+    c, r = k // (KH * KW), k % (KH * KW)
+    ktab = torch.full(((K + 31) // 32 * 32,), -1, dtype=torch.int32)
+    # the gather adds these offsets to the window origin as they are: a dilated convolution stores kh*d / kw*d
+    ktab[:K] = ((c << 8) | (((r // KW) * dilation) << 4) | ((r % KW) * dilation)).int()
+    # per 32-k block: [16 even k | 16 odd k] (the order in which one MFMA lane-half consumes them)
+    return ktab.view(-1, 16, 2).permute(0, 2, 1).reshape(-1).contiguous()
+
+
+def pack_wP(w):
+    """(Cout, Cin, 3, 3) float32 -> rfx_conv3x3_f32's order: wP[mt][s][h][m][kk] = W[mt*128 + m][s*72 + 2*kk + h]; a Cin that is not
+    a multiple of 8 (the 49-channel correlation volume) gets zero rows for the missing channels of its last K step."""
+    Cout, Cin = w.shape[:2]
+    Mpad, Kp = (Cout + 127) // 128 * 128, (Cin + 7) // 8 * 72
+    wp = torch.zeros(Mpad, Kp, dtype=torch.float32)
+    wp[:Cout, :Cin * 9] = w.reshape(Cout, Cin * 9)
+    return wp.view(Mpad // 128, 128, Kp // 72, 36, 2).permute(0, 2, 4, 1, 3).contiguous()
+
+
+def pack_wQ(w2d):
+    """(Cout, Cin) float32 -> 1x1 weights in the order rfx_conv3x3_conv1x1_f32 reads them: wQ[q][h][m][j] = W[m][8q + 2j + h]."""
+    Cout, Cin = w2d.shape
+    return w2d.t().reshape(Cin // 8, 4, 2, Cout).permute(0, 2, 3, 1).contiguous()      # [q][j][h][m] -> [q][h][m][j]
+
+
+def conv_route(Cin, Cout, KH, KW, stride, pad, dilation, split, split_enabled):
+    """The kernel family a convolution of this geometry runs on, fixed when its plan is built (``split``: the caller asked for the
+    split kernels; ``split_enabled``: conv_split_enabled()).  Each route holds only its own weight packs:
+        dilated      rfx_conv2d_dilated_f32                                                     wT + ktab
+        split3x3     rfx_conv3x3_split_f32                                                      wS
+        split3x3_s2  rfx_conv3x3_split_s2_f32                                                   wS
+        split1x1     rfx_conv1x1_split_f32 / rfx_conv1x1_split_strided_f32 (stride 2)           wS
+        fp32_3x3     rfx_conv3x3_f32 / rfx_conv3x3_s2_f32, or rfx_conv2d_f32 where the library's
+                     *_kernel_id says so for the launch's shape                                 wP + wT + ktab
+        gemm         rfx_conv2d_f32 (implicit GEMM; the k-major 1x1 kernel is one of its instances)   wT + ktab"""
+    if dilation != 1:
+        return "dilated"
+    if split and split_enabled:
+        if KH == 1 and KW == 1 and stride in (1, 2) and pad == 0 and Cin % 16 == 0:
+            return "split1x1"
+        if KH == 3 and KW == 3 and pad == 1:
+            if stride == 1 and Cin >= 16:
+                return "split3x3"
+            if stride == 2 and Cin % 16 == 0 and Cout >= 128:
+                return "split3x3_s2"
+    if KH == 3 and KW == 3 and pad == 1 and Cin >= 8 and (stride == 1 or (stride == 2 and Cin % 8 == 0)):
+        return "fp32_3x3"
+    return "gemm"
+
+
 class ConvPlan:
-    """Packed weights + folded BatchNorm of one convolution (see rfx_conv2d_f32 in include/rfx_api.h)."""
+    """Packed weights + folded BatchNorm of one convolution (see rfx_conv2d_f32 in include/rfx_api.h).  ``route`` (conv_route) names
+    the kernel family every call goes to; the packs of the other routes are None."""
 
     def __init__(self, weight, bn=None, stride=1, pad=0, act=ACT_NONE, device=None, eps=1e-5, dilation=1, bias=None, split=False):
         # weight: (Cout, Cin, KH, KW) float32 (any device); bn: dict(weight,bias,running_mean,running_var) or None;
         # dilation > 1: rfx_conv2d_dilated_f32 (the sky-segmentation encoder, segNet/segModel.py:196-205); bias: the convolution's own
-        # bias (segModel.py:243,245: the classifier convolutions), only without bn
+        # bias (segModel.py:243,245: the classifier convolutions), only without bn;
+        # split=True: the convolution runs on the split kernels (float32 sums from exact bf16 operand pieces on the bf16 matrix
+        # cores: csrc/conv1x1s.hip, csrc/conv3x3s.hip) where the shape allows it and RFX_CONV_SPLIT != 0
         w = weight.detach().float().cpu()
         self.Cout, self.Cin, self.KH, self.KW = w.shape
         self.stride, self.pad, self.act, self.dilation = stride, pad, act, int(dilation)
@@ -222,41 +294,20 @@ class ConvPlan:
         # rfx_conv3x3_f32's k_chunk: 0 = the library's rule (chunks for K >= 2048); 4 = chunks of 4 K steps whatever K is -- set by
         # the nets on the 3x3 convolution of a Bottleneck tail, so that the two-kernel form equals the fused kernel bit for bit
         self.k_chunk = 0
-        K = self.Cin * self.KH * self.KW
-        Kpad, Mpad = (K + 31) // 32 * 32, (self.Cout + 127) // 128 * 128
-        wT = torch.zeros(Kpad, Mpad, dtype=torch.float32)
-        wT[:K, :self.Cout] = w.reshape(self.Cout, K).t()
-        self.w2d = w.reshape(self.Cout, K) if (self.KH == 1 and self.KW == 1) else None   # kept for quad_weights()
+        self.route = conv_route(self.Cin, self.Cout, self.KH, self.KW, stride, pad, self.dilation, split, conv_split_enabled())
+        dev = self._device = device or "cuda"
+        # every pack of the route is uploaded here, never at first use: a first use inside a HIP-graph capture would capture the copy
+        self.wS = self.wP = self.wT = self.ktab = None
+        if self.route == "split1x1":
+            self.wS = split_weights(w.reshape(self.Cout, self.Cin)).to(dev)
+        elif self.route in ("split3x3", "split3x3_s2"):
+            self.wS = split_weights_3x3(w).to(dev)
+        else:
+            self.wT, self.ktab = pack_wT(w).to(dev), pack_ktab(w, self.dilation).to(dev)
+            if self.route == "fp32_3x3":
+                self.wP = pack_wP(w).to(dev)
+        self.w2d = w.reshape(self.Cout, self.Cin) if (self.KH == 1 and self.KW == 1) else None   # kept for quad_weights()
         self._wq = None
-        self.wP = None
-        # split=True: a 1x1 / stride 1 convolution runs on rfx_conv1x1_split_f32 (float32 sums from exact bf16 operand pieces on the
-        # bf16 matrix cores: csrc/conv1x1s.hip) where the shape allows it and RFX_CONV_SPLIT != 0
-        self.wS = None
-        if (split and conv_split_enabled() and self.KH == 1 and self.KW == 1 and stride in (1, 2) and pad == 0 and self.dilation == 1
-                and self.Cin % 16 == 0):
-            self.wS = split_weights(w.reshape(self.Cout, K)).to(device or "cuda")
-        elif (split and conv_split_enabled() and self.KH == 3 and self.KW == 3 and pad == 1 and self.dilation == 1
-                and ((stride == 1 and self.Cin >= 16) or (stride == 2 and self.Cin % 16 == 0 and self.Cout >= 128))):
-            # rfx_conv3x3_split_f32's wS3: [c / 16][tap][piece][h][m][8]
-            self.wS = torch.stack([split_weights(w[:, :, kh, kw]) for kh in range(3) for kw in range(3)], dim=1).contiguous().to(device or "cuda")
-        if (self.KH == 3 and self.KW == 3 and pad == 1 and self.dilation == 1 and self.Cin >= 8
-                and (stride == 1 or (stride == 2 and self.Cin % 8 == 0))):
-            # rfx_conv3x3_f32's order: wP[mt][s][h][m][kk] = W[mt*128 + m][s*72 + 2*kk + h]; a Cin that is not a multiple of 8
-            # (the 49-channel correlation volume) gets zero rows for the missing channels of its last K step
-            Kp = (self.Cin + 7) // 8 * 72
-            wp = torch.zeros(Mpad, Kp, dtype=torch.float32)
-            wp[:self.Cout, :K] = w.reshape(self.Cout, K)
-            wp = wp.view(Mpad // 128, 128, Kp // 72, 36, 2).permute(0, 2, 4, 1, 3).contiguous()
-            self.wP = wp.to(device or "cuda")
-        k = torch.arange(K)
-        c, r = k // (self.KH * self.KW), k % (self.KH * self.KW)
-        ktab = torch.full((Kpad,), -1, dtype=torch.int32)
-        # the gather adds these offsets to the window origin as they are: a dilated convolution stores kh*d / kw*d
-        ktab[:K] = ((c << 8) | (((r // self.KW) * self.dilation) << 4) | ((r % self.KW) * self.dilation)).int()
-        # per 32-k block: [16 even k | 16 odd k] (the order in which one MFMA lane-half consumes them)
-        ktab = ktab.view(-1, 16, 2).permute(0, 2, 1).reshape(-1).contiguous()
-        dev = device or "cuda"
-        self.wT, self.ktab = wT.to(dev), ktab.to(dev)
         if bn is not None:
             # eval-mode BatchNorm as ATen's CPU kernel evaluates it: alpha = w * (1/sqrt(var+eps)), beta = b - mean*alpha
             invstd = 1.0 / torch.sqrt(bn["running_var"].detach().float().cpu() + eps)
@@ -269,12 +320,9 @@ class ConvPlan:
             self.scale = self.shift = None
 
     def quad_weights(self):
-        """1x1 weights in the order rfx_conv3x3_conv1x1_f32 reads them: wQ[q][h][m][j] = W[m][8q + 2j + h]."""
+        """pack_wQ of a 1x1 plan on its device, for rfx_conv3x3_conv1x1_f32 (cached; the nets' first use is in the warm-up)."""
         if getattr(self, "_wq", None) is None:
-            w = self.w2d                                            # (Cout, Cin) on the CPU
-            Cout, Cin = w.shape
-            q = w.t().reshape(Cin // 8, 4, 2, Cout)                  # [q][j][h][m]
-            self._wq = q.permute(0, 2, 3, 1).contiguous().to(self.wT.device)   # [q][h][m][j]
+            self._wq = pack_wQ(self.w2d).to(self._device)
         return self._wq
 
     def out_hw(self, H, W):
@@ -291,71 +339,98 @@ class ConvPlan:
         res = _dev(residual, "residual") if residual is not None else None
         if res is not None and res.shape != out.shape:
             raise ValueError("residual shape %s != output shape %s" % (tuple(res.shape), tuple(out.shape)))
+        self._RUN[self.route](self, x, res, out, self.act if act is None else act)
+        return out
+
+    # One method per route: launch into ``out`` and, under a Profiler, record the launch.
+
+    def _run_dilated(self, x, res, out, act):       # records nothing
+        N, C, H, W = x.shape
+        _call("rfx_conv2d_dilated_f32", _one_device(x, res, self.wT), _p(x), _p(self.wT), _p(self.ktab), _p(self.scale), _p(self.shift),
+              _p(res), _p(out), N, C, H, W, self.Cout, self.KH, self.KW, self.stride, self.pad, self.dilation, act)
+
+    def _run_split3x3(self, x, res, out, act):      # both strides
+        N, C, H, W = x.shape
+        e0 = Profiler.begin(x)
+        xin, Cp = x, C
+        if C % 16:
+            # the 49-channel correlation volume: the kernel takes whole blocks of 16 channels -- the input goes into a zero-padded
+            # buffer (one device copy, 5 % of the layer's time; the padded weights are zero: split_weights)
+            Cp = (C + 15) // 16 * 16
+            xin = torch.zeros((N, Cp, H, W), dtype=torch.float32, device=x.device)
+            xin[:, :C].copy_(x)
+            launch_group.keep(xin)              # inside a group the kernel reads it at the block's end, after this call returns
+        _call("rfx_conv3x3_split_f32" if self.stride == 1 else "rfx_conv3x3_split_s2_f32", _one_device(xin, res, self.wS), _p(xin),
+              _p(self.wS), _p(self.scale), _p(self.shift), _p(res), _p(out), N, Cp, H, W, self.Cout, act)
+        if e0 is not None:
+            Ho, Wo = out.shape[2:]
+            Profiler.record_conv(KID_SPLIT_3X3 | (2 if self.Cout > 64 else 1) | (4 if self.stride != 1 else 0),
+                                 2.0 * N * Ho * Wo * self.Cout * self.Cin * 9, e0, (N, self.Cin, H, W, self.Cout, 3, self.stride),
+                                 4.0 * (N * C * H * W + N * self.Cout * Ho * Wo * (2 if res is not None else 1)) + 54.0 * self.Cout * self.Cin)
+
+    def _run_split1x1(self, x, res, out, act):
+        N, C, H, W = x.shape
+        e0 = Profiler.begin(x)
+        if self.stride == 1:
+            _call("rfx_conv1x1_split_f32", _one_device(x, res, self.wS), _p(x), _p(self.wS), _p(self.scale), _p(self.shift), _p(res), _p(out),
+                  N, C, H * W, self.Cout, act)
+        else:
+            _call("rfx_conv1x1_split_strided_f32", _one_device(x, res, self.wS), _p(x), _p(self.wS), _p(self.scale), _p(self.shift), _p(res),
+                  _p(out), N, C, H, W, self.Cout, self.stride, act)
+        if e0 is not None:
+            Ho, Wo = out.shape[2:]
+            Profiler.record_conv(KID_SPLIT_1X1 | (2 if self.Cout > 64 else 1) | (4 if self.stride != 1 else 0),
+                                 2.0 * N * Ho * Wo * self.Cout * self.Cin, e0, (N, self.Cin, H, W, self.Cout, 1, self.stride),
+                                 4.0 * (N * C * Ho * Wo + N * self.Cout * Ho * Wo * (2 if res is not None else 1)) + 6.0 * self.Cout * self.Cin)
+
+    def _run_fp32_3x3(self, x, res, out, act):
+        # the direct kernels where the library takes them for this launch's shape, else the implicit GEMM
+        N, C, H, W = x.shape
+        Ho, Wo = out.shape[2:]
         lib = _lib.load()
-        if self.dilation != 1:
-            _call("rfx_conv2d_dilated_f32", _one_device(x, res, self.wT), _p(x), _p(self.wT), _p(self.ktab), _p(self.scale), _p(self.shift),
-                  _p(res), _p(out), N, C, H, W, self.Cout, self.KH, self.KW, self.stride, self.pad, self.dilation,
-                  self.act if act is None else act)
-            return out
-        if self.wS is not None and self.KH == 3:
-            e0 = Profiler.begin(x)
-            xin, Cp = x, C
-            if C % 16:
-                # the 49-channel correlation volume: the kernel takes whole blocks of 16 channels -- the input goes into a zero-padded
-                # buffer (one device copy, 5 % of the layer's time; the padded weights are zero: split_weights)
-                Cp = (C + 15) // 16 * 16
-                xin = torch.zeros((N, Cp, H, W), dtype=torch.float32, device=x.device)
-                xin[:, :C].copy_(x)
-                launch_group.keep(xin)              # inside a group the kernel reads it at the block's end, after this call returns
-            _call("rfx_conv3x3_split_f32" if self.stride == 1 else "rfx_conv3x3_split_s2_f32", _one_device(xin, res, self.wS), _p(xin),
-                  _p(self.wS), _p(self.scale), _p(self.shift), _p(res), _p(out), N, Cp, H, W, self.Cout, self.act if act is None else act)
-            if e0 is not None:
-                e1 = Profiler.end(e0)
-                Profiler.active().conv.append((KID_SPLIT_3X3 | (2 if self.Cout > 64 else 1) | (4 if self.stride != 1 else 0),
-                                               2.0 * N * Ho * Wo * self.Cout * self.Cin * 9, e0, e1, (N, self.Cin, H, W, self.Cout, 3, self.stride),
-                                               4.0 * (N * C * H * W + N * self.Cout * Ho * Wo * (2 if res is not None else 1)) + 54.0 * self.Cout * self.Cin))
-            return out
-        if self.wS is not None:
-            e0 = Profiler.begin(x)
-            if self.stride == 1:
-                _call("rfx_conv1x1_split_f32", _one_device(x, res, self.wS), _p(x), _p(self.wS), _p(self.scale), _p(self.shift), _p(res), _p(out),
-                      N, C, H * W, self.Cout, self.act if act is None else act)
-            else:
-                _call("rfx_conv1x1_split_strided_f32", _one_device(x, res, self.wS), _p(x), _p(self.wS), _p(self.scale), _p(self.shift), _p(res),
-                      _p(out), N, C, H, W, self.Cout, self.stride, self.act if act is None else act)
-            if e0 is not None:
-                e1 = Profiler.end(e0)
-                Profiler.active().conv.append((KID_SPLIT_1X1 | (2 if self.Cout > 64 else 1) | (4 if self.stride != 1 else 0),
-                                               2.0 * N * Ho * Wo * self.Cout * self.Cin, e0, e1, (N, self.Cin, H, W, self.Cout, 1, self.stride),
-                                               4.0 * (N * C * Ho * Wo + N * self.Cout * Ho * Wo * (2 if res is not None else 1)) + 6.0 * self.Cout * self.Cin))
-            return out
-        kid0 = 0
-        if self.wP is not None:
-            kid0 = (lib.rfx_conv3x3_kernel_id(N, self.Cin, self.Cout, Ho, Wo, self.k_chunk) if self.stride == 1 else
-                    lib.rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo))
+        kid0 = (lib.rfx_conv3x3_kernel_id(N, self.Cin, self.Cout, Ho, Wo, self.k_chunk) if self.stride == 1 else
+                lib.rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo))
+        if not kid0 & (32 | 8192):
+            return self._run_gemm(x, res, out, act)
         e0 = Profiler.begin(x)
         if kid0 & 32:
             _call("rfx_conv3x3_f32", _one_device(x, res, self.wP), _p(x), _p(self.wP), _p(self.scale), _p(self.shift),
-                  _p(res), _p(out), N, C, H, W, self.Cout, self.act if act is None else act, self.k_chunk)
-        elif kid0 & 8192:
-            _call("rfx_conv3x3_s2_f32", _one_device(x, res, self.wP), _p(x), _p(self.wP), _p(self.scale), _p(self.shift),
-                  _p(res), _p(out), N, C, H, W, self.Cout, self.act if act is None else act)
+                  _p(res), _p(out), N, C, H, W, self.Cout, act, self.k_chunk)
         else:
-            _call("rfx_conv2d_f32", _one_device(x, res, self.wT), _p(x), _p(self.wT), _p(self.ktab), _p(self.scale),
-                  _p(self.shift), _p(res), _p(out), N, C, H, W, self.Cout, self.KH, self.KW, self.stride, self.pad,
-                  self.act if act is None else act)
+            _call("rfx_conv3x3_s2_f32", _one_device(x, res, self.wP), _p(x), _p(self.wP), _p(self.scale), _p(self.shift),
+                  _p(res), _p(out), N, C, H, W, self.Cout, act)
         if e0 is not None:
-            e1 = Profiler.end(e0)
-            flops = 2.0 * N * Ho * Wo * self.Cout * self.Cin * self.KH * self.KW
-            nbytes = 4.0 * (N * C * H * W + N * self.Cout * Ho * Wo * (2 if res is not None else 1)
-                            + self.Cout * self.Cin * self.KH * self.KW)
-            kid = kid0 if (kid0 & 32) else lib.rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo)
-            Profiler.active().conv.append((kid, flops, e0, e1, (N, self.Cin, H, W, self.Cout, self.KH, self.stride), nbytes))
-        return out
+            self._record_fp32(kid0, e0, x, res, out)
+
+    def _run_gemm(self, x, res, out, act):
+        N, C, H, W = x.shape
+        e0 = Profiler.begin(x)
+        _call("rfx_conv2d_f32", _one_device(x, res, self.wT), _p(x), _p(self.wT), _p(self.ktab), _p(self.scale),
+              _p(self.shift), _p(res), _p(out), N, C, H, W, self.Cout, self.KH, self.KW, self.stride, self.pad, act)
+        if e0 is not None:
+            self._record_fp32(0, e0, x, res, out)
+
+    def _record_fp32(self, kid0, e0, x, res, out):
+        N, C, H, W = x.shape
+        Ho, Wo = out.shape[2:]
+        kid = kid0 if (kid0 & 32) else _lib.load().rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo)
+        flops = 2.0 * N * Ho * Wo * self.Cout * self.Cin * self.KH * self.KW
+        nbytes = 4.0 * (N * C * H * W + N * self.Cout * Ho * Wo * (2 if res is not None else 1)
+                        + self.Cout * self.Cin * self.KH * self.KW)
+        Profiler.record_conv(kid, flops, e0, (N, self.Cin, H, W, self.Cout, self.KH, self.stride), nbytes)
+
+    _RUN = {"dilated": _run_dilated, "split3x3": _run_split3x3, "split3x3_s2": _run_split3x3, "split1x1": _run_split1x1,
+            "fp32_3x3": _run_fp32_3x3, "gemm": _run_gemm}
+
+
+# what bottleneck_tail_shape reads of a plan: the nets ask it about a layer before they pack anything (scale: not None where a
+# BatchNorm or a bias is folded)
+ConvGeometry = collections.namedtuple("ConvGeometry", "Cout Cin KH KW stride pad act scale")
 
 
 def bottleneck_tail_shape(plan2, plan3):
-    """Do conv2 (3x3) + conv3 (1x1 expansion) of a Bottleneck have the shape rfx_conv3x3_conv1x1_f32 serves?"""
+    """Do conv2 (3x3) + conv3 (1x1 expansion) of a Bottleneck have the shape rfx_conv3x3_conv1x1_f32 serves?  (ConvPlans or
+    ConvGeometry tuples.)"""
     return (plan2.KH == 3 and plan2.KW == 3 and plan2.stride == 1 and plan2.pad == 1 and plan2.Cin % 8 == 0
             and plan2.Cout in (64, 128) and plan2.act in (ACT_NONE, ACT_RELU) and plan3.KH == 1 and plan3.KW == 1
             and plan3.stride == 1 and plan3.pad == 0 and plan3.Cin == plan2.Cout and plan3.Cout % 128 == 0
@@ -383,12 +458,9 @@ def bottleneck_tail(x, plan2, plan3, residual=None):
           _p(plan2.shift), plan2.act, _p(plan3.quad_weights()), _p(plan3.scale), _p(plan3.shift), _p(res), plan3.act,
           _p(out), N, C, H, W, plan2.Cout, plan3.Cout)
     if e0 is not None:
-        e1 = Profiler.end(e0)
-        flops = 2.0 * N * H * W * (plan2.Cout * plan2.Cin * 9 + plan3.Cout * plan3.Cin)
-        nbytes = 4.0 * N * H * W * (C + plan3.Cout * (2 if res is not None else 1))
-        kid = _lib.load().rfx_conv3x3_conv1x1_kernel_id(N, H, W, plan2.Cout)
-        Profiler.active().conv.append((kid, flops, e0, e1,
-                                       (N, C, H, W, plan3.Cout, 3, 1), nbytes))
+        Profiler.record_conv(_lib.load().rfx_conv3x3_conv1x1_kernel_id(N, H, W, plan2.Cout),
+                             2.0 * N * H * W * (plan2.Cout * plan2.Cin * 9 + plan3.Cout * plan3.Cin), e0, (N, C, H, W, plan3.Cout, 3, 1),
+                             4.0 * N * H * W * (C + plan3.Cout * (2 if res is not None else 1)))
     return out
 
 
@@ -434,9 +506,8 @@ def stem_conv_maxblur(x, plan):
     _call("rfx_stem_conv3x3_maxblur_f32", _one_device(x, plan.wT), _p(x), _p(plan.wT), _p(plan.scale), _p(plan.shift), _p(out), N, H, W,
                                                        plan.Cout)
     if e0 is not None:
-        e1 = Profiler.end(e0)
-        Profiler.active().conv.append((256, 2.0 * N * H * W * plan.Cout * 27, e0, e1, (N, 3, H, W, plan.Cout, 3, 1),
-                      4.0 * (N * 3 * H * W + N * plan.Cout * Ho * Wo)))
+        Profiler.record_conv(256, 2.0 * N * H * W * plan.Cout * 27, e0, (N, 3, H, W, plan.Cout, 3, 1),
+                             4.0 * (N * 3 * H * W + N * plan.Cout * Ho * Wo))
     return out
 
 
@@ -455,9 +526,8 @@ def stem_conv7_maxpool(x, plan):
     _call("rfx_stem_conv7x7_maxpool_f32", _one_device(x, plan.wT), _p(x), _p(plan.wT), _p(plan.scale), _p(plan.shift), _p(out), N, H, W,
                                                        plan.Cout)
     if e0 is not None:
-        e1 = Profiler.end(e0)
-        Profiler.active().conv.append((257, 2.0 * N * Hc * Wc * plan.Cout * 147, e0, e1, (N, 3, H, W, plan.Cout, 7, 2),
-                      4.0 * (N * 3 * H * W + N * plan.Cout * Hp * Wp)))
+        Profiler.record_conv(257, 2.0 * N * Hc * Wc * plan.Cout * 147, e0, (N, 3, H, W, plan.Cout, 7, 2),
+                             4.0 * (N * 3 * H * W + N * plan.Cout * Hp * Wp))
     return out
 
 
