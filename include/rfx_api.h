@@ -94,26 +94,34 @@ int rfx_conv2d_f32(const float* in, const float* wT, const int32_t* ktab, const 
  * caller attribute algorithmic FLOPs to the kernel instance rocprofv3 reports. */
 int rfx_conv2d_tile_variant(int N, int Cout, int Hout, int Wout);
 
-/* Full kernel-instance id a convolution of this geometry runs as: bits 0-1 = tile variant above, bit 2 = 1x1 specialisation, bit 3 =
- * wave-specialised form (4 MFMA + 4 loader wavefronts), bit 4 = 16-byte pixel-side loads (1x1, stride 1):
- * the template arguments <TM,TN,ONE,WS,VECB> rocprofv3 prints.  Bit 5 = the direct 3x3 / stride 1 / pad 1 kernel
- * conv3x3_direct_kernel<TM, PT_C> (Cin >= 8), TM = 2 if bits 0-1 are 0 else 1; bits 6-7 = output patch shape
- * (0: 8x16, 1: 16x8, 2: 32x4 -- the one that pads the H x W map least); bit 11 = 256-pixel (16x16) patches, conv3x3_direct_kernel<1, 16, false, 4>
- * (Cout <= 64 on launches of >= 1024 such patches: twice the pixels per staged weight image); bit 12 = the instance with a ragged last K
- * step (Cin % 8 != 0), conv3x3_direct_kernel<TM, PT_C, false, 2, true>.  Bit 10 = the k-major 1x1 / stride 1 kernel
- * conv1x1_kmajor_kernel<TM, VEC> (Cin % 32 == 0; TM = 2 - bits 0-1, VEC = bit 4).  Bit 5 set = the geometry is served by
- * rfx_conv3x3_f32 below (the host mirrors call it then); rfx_conv2d_f32 itself always runs the implicit-GEMM kernel. */
+/* Kernel-instance id a convolution of this geometry runs as, for a profiler-side caller and for the host mirrors' routing.  THE bit
+ * layout of every *_kernel_id of this header (the library writes it in one place, csrc/conv_dispatch.h ConvInstance::id()):
+ *   bits 8-13 name the kernel family, none of them set = the implicit-GEMM kernel of rfx_conv2d_f32:
+ *     (none)  conv2d_mfma_kernel<TM, TN, ONE, WS, VECB>: bits 0-1 = tile variant (rfx_conv2d_tile_variant), bit 2 = 1x1 specialisation,
+ *             bit 3 = wave-specialised form (4 MFMA + 4 loader wavefronts), bit 4 = 16-byte pixel-side loads (1x1, stride 1)
+ *     bit 10  conv1x1_kmajor_kernel<TM, VEC, KCH>, the k-major 1x1 / stride 1 kernel rfx_conv2d_f32 runs for Cin % 32 == 0, Cin >= 64
+ *             (bit 2 is set with it): bit 0 = 64-channel tiles (TM = 1), bit 4 = VEC
+ *     bit 5   conv3x3_direct_kernel<TM, PT_C, false, TN, RAG, KCH>, the direct 3x3 / stride 1 / pad 1 kernel (Cin >= 8), served by
+ *             rfx_conv3x3_f32 (the host mirrors call it then; rfx_conv2d_f32 itself never runs it): bit 0 = 64-channel tiles (TM = 1),
+ *             bits 6-7 = output patch shape (0: 8x16, 1: 16x8, 2: 32x4 -- the one that pads the stacked N x (H x W) maps least),
+ *             bit 11 = 256-pixel (16x16) patches, TN = 4 (Cout <= 64 on launches of >= 1024 such patches: twice the pixels per staged
+ *             weight image), bit 12 = the instance with a ragged last K step, RAG (Cin % 8 != 0)
+ *     bit 13  conv3x3_s2_kernel<TM, KCH>, the direct 3x3 / STRIDE 2 / pad 1 kernel (Cin % 8 == 0), served by rfx_conv3x3_s2_f32: ResNet-50
+ *             layer2.0 / layer3.0 conv2 (model/resnet50.py:75), the first convolution of FeatureExtractor layer2 / layer3
+ *             (model/model.py:86-95): bit 0 = 64-channel tiles (TM = 1)
+ *     bit 9   conv3x3_direct_kernel<TM, PT_C, true, 2, false, KCH>, the fused Bottleneck tail rfx_conv3x3_conv1x1_f32: bit 0 = 64-channel
+ *             mid tile (TM = 1), bits 6-7 = output patch shape as for bit 5
+ *     (bit 8: the fused stems; bits 15-16: the split-arithmetic kernels -- ids of the Python profiler, not of the library)
+ *   bit 14 = chunked accumulation (KCH > 0): on layers whose K is long -- 3x3 / stride 1 with K = 9 Cin >= 2048 and the 3x3 of a Bottleneck
+ *     tail (KCH = 4: a chunk = 4 K steps = 288 products), 3x3 / stride 2 with K >= 1152 (KCH = 4), 1x1 / stride 1 with K >= 512 (KCH = 8:
+ *     256 products, 64-channel tiles at every launch size) -- the accumulators are added to a running total at the end of every chunk and
+ *     restarted, the K-blocked sum of the reference's CPU kernels (MKL sgemm / oneDNN) instead of ONE fma chain over K: 2.7-3.8x less
+ *     round-off against float64 at K = 2304 / 4608.  On those 3x3 layers rfx_conv2d_f32 (its implicit-GEMM kernel: a chain) and
+ *     rfx_conv3x3_f32 therefore differ in the last bits -- everywhere else they are bit-identical; the long-K 1x1 layers run chunked
+ *     through rfx_conv2d_f32 itself.  RFX_C3_CHUNK=0 / RFX_C1_CHUNK=0: chains (A/B runs).
+ * The answer is the one the launch functions act on at the moment of the call: between rfx_group_begin and rfx_group_end it is the
+ * instance a recorded launch takes.  A query sees no pointer: bit 4 is cleared at launch for an input that is not 16-byte aligned. */
 int rfx_conv2d_kernel_id(int N, int Cin, int Cout, int KH, int KW, int stride, int pad, int Hout, int Wout);
-/* (round 4) bit 13 = the direct 3x3 / STRIDE 2 / pad 1 kernel conv3x3_s2_kernel<TM> (Cin % 8 == 0, TM = 2 - bit 0), served by
- * rfx_conv3x3_s2_f32 below: ResNet-50 layer2.0 / layer3.0 conv2 (model/resnet50.py:75) and the first convolution of
- * FeatureExtractor layer2 / layer3 (model/model.py:86-95).
- * bit 14 = chunked accumulation: on layers whose K is long -- 3x3 / stride 1 with K = 9 Cin >= 2048 (conv3x3_direct_kernel<TM, PT_C,
- * false, 2, false, 4>, a chunk = 4 K steps = 288 products) and 1x1 / stride 1 with K >= 1024 (conv1x1_kmajor_kernel<1, VEC, 8>, a chunk
- * = 256 products, 64-channel tiles at every launch size) -- the accumulators are added to a running total at the end of every chunk and
- * restarted, the K-blocked sum of the reference's CPU kernels (MKL sgemm / oneDNN) instead of ONE fma chain over K: 2.7-3.8x less
- * round-off against float64 at K = 2304 / 4608.  On those 3x3 layers rfx_conv2d_f32 (its implicit-GEMM kernel: a chain) and
- * rfx_conv3x3_f32 therefore differ in the last bits -- everywhere else they are bit-identical; the 1x1 layers with K >= 1024 run chunked
- * through rfx_conv2d_f32 itself.  RFX_C3_CHUNK=0 / RFX_C1_CHUNK=0: chains (A/B runs). */
 
 /* 3x3 / stride 1 / pad 1 convolution, Cin >= 8 (a Cin that is not a multiple of 8 -- the 49-channel correlation volume in
  * front of the heads -- takes ceil(Cin/8) K steps, the packed weights carrying zero rows for the missing channels) (ResNet Bottleneck conv2 at stride 1, model/resnet50.py:75; the
@@ -122,7 +130,7 @@ int rfx_conv2d_kernel_id(int N, int Cin, int Cout, int KH, int KW, int stride, i
  * rfx_conv2d_f32; the weights come packed in the kernel's own LDS order so that staging is a straight copy:
  *     wP[mt][s][h][m][kk] = w[mt*128 + m, c, kh, kw]   with k = (c*3 + kh)*3 + kw = s*72 + 2*kk + h,
  *     mt < roundup(Cout,128)/128, s < ceil(Cin/8), h < 2, m < 128, kk < 36; zero for mt*128 + m >= Cout and for c >= Cin; 16-byte aligned.
- * k_chunk (ABI 8): 0 = the library's rule (chunked accumulation, bit 14 above, for K = 9 Cin >= 2048); 4 = close a chunk every 4 K
+ * k_chunk (ABI 8): 0 = the library's rule (chunked accumulation, bit 14 of rfx_conv2d_kernel_id, for K = 9 Cin >= 2048); 4 = close a chunk every 4 K
  * steps (288 products) whatever K is -- what rfx_conv3x3_conv1x1_f32 does in its 3x3 phase since round 5, so that a Bottleneck
  * tail run as two kernels (this one with k_chunk = 4, then the 1x1) equals the fused kernel bit for bit.  Other values: RFX_E_ARG.
  * rfx_conv3x3_kernel_id: the instance this call launches (bits as rfx_conv2d_kernel_id). */
@@ -131,7 +139,7 @@ int rfx_conv3x3_f32(const float* in, const float* wP, const float* scale, const 
 int rfx_conv3x3_kernel_id(int N, int Cin, int Cout, int H, int W, int k_chunk);
 /* The same for stride 2 (pad 1, Cin % 8 == 0): out (N, Cout, (H-1)/2+1, (W-1)/2+1); wP as above.  Bit-identical to
  * rfx_conv2d_f32 on the same geometry for K = 9 Cin < 1152 ONLY: from Cin = 128 on (K >= 1152) this kernel sums in chunks of 288
- * products (conv3x3_s2_kernel<TM, 4>: bit 14 of the kernel id), the implicit-GEMM kernel behind rfx_conv2d_f32 in ONE chain -- the two
+ * products (conv3x3_s2_kernel<TM, 4>: bit 14 of rfx_conv2d_kernel_id), the implicit-GEMM kernel behind rfx_conv2d_f32 in ONE chain -- the two
  * then differ in the last bit, and so do trunk features when the host mirror is switched to the generic kernel (RFX_CONV_S2=0 /
  * RFX_CONV_DIRECT=0 are A/B switches for experiments, not product settings: they change the sums). */
 int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float* scale, const float* shift, const float* residual,
@@ -148,8 +156,7 @@ int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float* scale, con
  * Round 5: the 3x3 phase (K = 9 Cmid = 576 / 1152) closes a chunk every 4 K steps (288 products) into a second accumulator set --
  * the last place the device summed a long K as ONE fma chain while the reference's oneDNN kernels block it.
  * Bit-identical to rfx_conv3x3_f32(k_chunk = 4) followed by the 1x1 through rfx_conv2d_f32.  RFX_C3_TAIL_CHUNK=0: round 4's chain. */
-/* Kernel instance of the launch below (conv3x3_direct_kernel<TM, PT_C, true, 2, false, KCH> as rocprofv3 prints it): bit 9 set, bit 0 =
- * 64-channel mid tile (TM = 1), bits 6-7 = output patch shape as in rfx_conv2d_kernel_id, bit 14 = chunked (KCH = 4). */
+/* Kernel instance of the launch below (bits as rfx_conv2d_kernel_id: bit 9 and its fields). */
 int rfx_conv3x3_conv1x1_kernel_id(int N, int H, int W, int Cmid);
 int rfx_conv3x3_conv1x1_f32(const float* in, const float* wP2, const float* scale2, const float* shift2, int act2,
                             const float* wQ3, const float* scale3, const float* shift3, const float* residual, int act3,

@@ -21,9 +21,9 @@
 // Epilogue fused: y = fma(acc, scale[m], shift[m]) (+ residual) -> ReLU / sigmoid; stores coalesced
 // along the pixel dimension (the MFMA C/D column index is the pixel).
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "group.h"
-#include <stdlib.h>
 
 struct ConvArgs {
     const float* in;
@@ -363,8 +363,8 @@ static int conv_group_launch(const void* blob, const unsigned* gx, int n, hipStr
     return rfx_group_launch_impl<ConvArgs>(conv2d_mfma_group_kernel<TM, TN, ONE, WS, VECB>, WS ? 512 : 256, blob, gx, n, st);
 }
 
-template <int TM, int TN, bool ONE, bool WS, bool VECB = false>
-static int launch_conv(ConvArgs& a, hipStream_t st) {
+template <int TM, int TN, bool ONE, bool WS, bool VECB>
+static int launch_conv(ConvArgs& a, hipStream_t st, bool recording) {
     constexpr int BM = 64 * TM, BN = 64 * TN;
     a.tilesM = (a.Cout + BM - 1) / BM;
     a.tilesP = (int)((a.P + BN - 1) / BN);
@@ -373,102 +373,35 @@ static int launch_conv(ConvArgs& a, hipStream_t st) {
 #ifdef RFX_TRACE
     a.trace = g_trace;
 #endif
-    if (rfx_group_recording()) return rfx_group_record(&conv_group_launch<TM, TN, ONE, WS, VECB>, &a, sizeof(a), (unsigned)nwg);
+    if (recording) return rfx_group_record(&conv_group_launch<TM, TN, ONE, WS, VECB>, &a, sizeof(a), (unsigned)nwg);
     hipLaunchKernelGGL((conv2d_mfma_kernel<TM, TN, ONE, WS, VECB>), dim3((unsigned)nwg), dim3(WS ? 512 : 256), 0, st, a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
 
-int rfx_conv3x3_direct_launch(const float* in, const float* wP, const float* scale, const float* shift,
-                              const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int Mpad,
-                              int act, int tm, int patch_cols, hipStream_t st, bool chunked);  // conv3x3.hip
-int rfx_conv3x3_patch_cols(int N, int H, int W, bool fused);                                       // conv3x3.hip
-int rfx_conv3x3_s2_launch(const float* in, const float* wP, const float* scale, const float* shift, const float* residual,
-                          float* out, int N, int Cin, int H, int W, int Cout, int act, int tm, hipStream_t st);   // conv3x3.hip
-bool rfx_conv3x3_wide_patch(int N, int H, int W, int Cout, int patch_cols);                          // conv3x3.hip
-int rfx_conv1x1_kmajor_launch(const float* in, const float* wT, const float* scale, const float* shift, const float* residual,
-                              float* out, int N, int Cin, int HW, int Cout, int Mpad, int act, int tm, bool vec,
-                              hipStream_t st, bool chunked);                            // conv1x1.hip
-bool rfx_conv3x3_chunked(int Cin);                                                                   // conv3x3.hip
-bool rfx_conv3x3_tail_chunked();                                                                     // conv3x3.hip
-bool rfx_conv3x3_s2_chunked(int Cin);                                                                // conv3x3.hip
+// Every instance of the implicit-GEMM kernel the library builds (conv_dispatch.h decides which one a launch takes): the three tiles
+// with and without the 1x1 specialisation, wave-specialised on the two larger tiles, and the three 1x1 tiles with vectorised
+// pixel-side loads (never wave-specialised).
+struct GemmEntry {
+    int key;
+    int (*launch)(ConvArgs&, hipStream_t, bool recording);
+};
+#define G(TM, TN, ONE, WS, VECB) {ConvInstance::gemm(TM, TN, ONE, WS, VECB).id(), &launch_conv<TM, TN, ONE, WS, VECB>}
+static const GemmEntry kGemm[] = {
+    G(2, 2, false, false, false), G(2, 2, true, false, false), G(2, 2, false, true, false), G(2, 2, true, true, false),
+    G(1, 2, false, false, false), G(1, 2, true, false, false), G(1, 2, false, true, false), G(1, 2, true, true, false),
+    G(1, 1, false, false, false), G(1, 1, true, false, false),
+    G(2, 2, true, false, true), G(1, 2, true, false, true), G(1, 1, true, false, true),
+};
+#undef G
 
-// tile choice: the largest tile that still gives >= ~2 workgroups per CU (256 CUs).
-// 0: 128x128 (conv2d_mfma_kernel<2,2>), 1: 64x128 (<1,2>), 2: 64x64 (<1,1>)
 extern "C" int rfx_conv2d_tile_variant(int N, int Cout, int Hout, int Wout) {
-    static const int forced = getenv("RFX_CONV_FORCE_VARIANT") ? atoi(getenv("RFX_CONV_FORCE_VARIANT")) : -1;  // experiments
-    if (forced >= 0) return forced;
-    const long long P = (long long)N * Hout * Wout;
-    const long long b22 = (long long)((Cout + 127) / 128) * ((P + 127) / 128);
-    const long long b12 = (long long)((Cout + 63) / 64) * ((P + 127) / 128);
-    if (Cout > 64 && b22 >= 512) return 0;
-    if (b12 >= 512 || P >= 8192) return 1;
-    return 2;
-}
-
-static int conv_ws_env() {
-    static const int v = getenv("RFX_CONV_WS") ? atoi(getenv("RFX_CONV_WS")) : -1;
-    return v;
-}
-
-// Kernel instance rfx_conv2d_f32 launches for this geometry: bits 0-1 tile variant (0: <2,2>, 1: <1,2>, 2: <1,1>),
-// bit 2 = 1x1 specialisation (ONE), bit 3 = wave-specialised form (WS), bit 4 = vectorised pixel-side loads
-// (VECB), i.e. the template arguments of conv2d_mfma_kernel<TM,TN,ONE,WS,VECB> that rocprofv3 prints.
-// bit 10 = the k-major 1x1 / stride 1 kernel of conv1x1.hip (conv1x1_kmajor_kernel<TM, VEC>, TM = 2 - (bits 0-1), VEC = bit 4).
-// bit 5 = the direct 3x3 / stride 1 / pad 1 kernel of conv3x3.hip (conv3x3_direct_kernel<TM, PT_C>, TM = 2 - (bits 0-1 != 0),
-// output patch 128/PT_C x PT_C with PT_C = 16 / 8 / 4 for bits 6-7 = 0 / 1 / 2).
-static int conv_kernel_id(int N, int Cin, int Cout, int KH, int KW, int stride, int pad, int Hout, int Wout, bool allow_direct,
-                          int k_chunk = 0) {
-    static const int direct_env = getenv("RFX_CONV_DIRECT") ? atoi(getenv("RFX_CONV_DIRECT")) : 1;
-    if (allow_direct && direct_env && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin >= 8) {
-        const int pc = rfx_conv3x3_patch_cols(N, Hout, Wout, false), pr = 128 / pc;
-        const long long tiles = (((long long)N * (Hout + 1) + pr - 1) / pr) * ((Wout + pc - 1) / pc);
-        const bool big = Cout > 64 && tiles * ((Cout + 127) / 128) >= 512;
-        const bool rag = Cin % 8 != 0;
-        // bit 14 = chunked accumulation (K >= 2048: conv3x3_direct_kernel<TM, PT_C, false, 2, false, 4>; never on the 256-pixel patches)
-        // ... or asked for by the caller (k_chunk > 0: the 3x3 convolution of a Bottleneck tail run on its own, rfx_conv3x3_f32)
-        const bool chk = !rag && (rfx_conv3x3_chunked(Cin) || (k_chunk > 0 && rfx_conv3x3_tail_chunked()));
-        return 32 | (big ? 0 : 1) | (pc == 16 ? 0 : (pc == 8 ? 64 : 128)) |
-               (!big && !rag && rfx_conv3x3_wide_patch(N, Hout, Wout, Cout, pc) ? 2048 : 0) | (rag ? 4096 : 0) | (chk ? 16384 : 0);
-    }
-    // bit 13 = the direct 3x3 / stride 2 / pad 1 kernel conv3x3_s2_kernel<TM> (Cin % 8 == 0; TM = 2 - bit 0); never inside a
-    // grouped launch (it has no grouped form: a recorded group keeps the implicit-GEMM kernel)
-    static const int s2_env = getenv("RFX_CONV_S2") ? atoi(getenv("RFX_CONV_S2")) : 1;
-    if (allow_direct && direct_env && s2_env && KH == 3 && KW == 3 && stride == 2 && pad == 1 && Cin % 8 == 0 && Cin >= 8) {
-        // its 8 x 16 output patches tile every image on their own (no stacked-batch trick at stride 2): on maps that pad badly
-        // the implicit-GEMM kernel, which tiles the flattened pixel axis, wins.  Measured break-even (scripts/ubench/
-        // conv_s2_bench.py, profiles/r04_conv_s2_ab.json): +8..16 % at 100 % / 94 % useful pixels, +-0 at 88 %, -12 % at 74 %.
-        // Round 5: the layers with K = 9 Cin >= 1152 sum in chunks in this kernel (bit 14) -- they take it on EVERY map and inside
-        // grouped launches too (it has a grouped form now), so that a layer's sums never depend on the map size or the batch; the
-        // shorter-K layers keep the rule above (either kernel: the same chain, bit-identical).
-        const long long th = (Hout + 7) / 8, tw = (Wout + 15) / 16;
-        const bool chk = rfx_conv3x3_s2_chunked(Cin);
-        if (chk || ((long long)Hout * Wout * 100 >= 90 * th * 8 * tw * 16 && !rfx_group_recording())) {
-            const bool big = Cout > 64 && (long long)N * th * tw * ((Cout + 127) / 128) >= 512;
-            return 8192 | (big ? 0 : 1) | (chk ? 16384 : 0);
-        }
-    }
-    const int variant = rfx_conv2d_tile_variant(N, Cout, Hout, Wout);
-    const bool one = (KH == 1 && KW == 1 && pad == 0);
-    static const int kmajor_env = getenv("RFX_CONV_1X1") ? atoi(getenv("RFX_CONV_1X1")) : 1;   // experiments: 0 = generic kernel
-    // bit 14 = chunked accumulation (K >= 1024: conv1x1_kmajor_kernel<1, VEC, 8>, 64-channel tiles, at EVERY launch size -- a result
-    // must not depend on how many pairs share the launch); RFX_C1_CHUNK=0: off
-    // round 5: from K = 512 on (layer2 conv1, layer3.0 conv1: two chunks of 256); RFX_C1_CHUNK=<min K> (0: never; 1: the default 512)
-    static const int c1chunk = getenv("RFX_C1_CHUNK") ? atoi(getenv("RFX_C1_CHUNK")) : 1;
-    const bool chk = c1chunk && Cin >= (c1chunk > 1 ? c1chunk : 512);
-    if (kmajor_env && one && stride == 1 && Cin % 32 == 0 && Cin >= 64 && (variant != 2 || chk) && (long long)N * Hout * Wout >= 4) {
-        return 1024 | 4 | (chk ? 1 : variant) | (((long long)Hout * Wout) % 4 == 0 ? 16 : 0) | (chk ? 16384 : 0);   // conv1x1.hip
-    }
-    const int env = conv_ws_env();
-    const bool ws = variant == 2 ? false : (env > 0);  // off by default: since the branch-free epilogue the single-role kernel is as fast
-    static const int vec_env = getenv("RFX_CONV_VECB") ? atoi(getenv("RFX_CONV_VECB")) : 1;
-    const bool vecb = vec_env && one && !ws && stride == 1 && ((long long)Hout * Wout) % 4 == 0;
-    return variant | (one ? 4 : 0) | (ws ? 8 : 0) | (vecb ? 16 : 0);
+    return conv_tile_variant(conv_knobs(), N, Cout, Hout, Wout);
 }
 
 extern "C" int rfx_conv2d_kernel_id(int N, int Cin, int Cout, int KH, int KW, int stride, int pad, int Hout,
                                     int Wout) {
-    return conv_kernel_id(N, Cin, Cout, KH, KW, stride, pad, Hout, Wout, true);
+    return conv_decide(conv_knobs(), {N, Cin, Cout, KH, KW, stride, pad, Hout, Wout}, true, 0, true, rfx_group_recording()).id();
 }
 
 // The direct 3x3 kernel with the weights in its own packed order (conv3x3.hip); bit 5 of rfx_conv2d_kernel_id says when
@@ -480,15 +413,13 @@ extern "C" int rfx_conv3x3_f32(const float* in, const float* wP, const float* sc
     if (reinterpret_cast<uintptr_t>(wP) & 15) return RFX_E_ARG;
     if ((long long)Cin * H * W > 0x7fffffffLL) return RFX_E_LIMIT;
     if (k_chunk != 0 && k_chunk != 4) return RFX_E_ARG;                      // the one chunk length the kernels are built for
-    const int kid = conv_kernel_id(N, Cin, Cout, 3, 3, 1, 1, H, W, true, k_chunk);
-    const int pc = rfx_conv3x3_patch_cols(N, H, W, false);
-    const int tm = (kid & 32) ? ((kid & 3) ? 1 : 2) : (Cout > 64 ? 2 : 1);   // RFX_CONV_DIRECT=0 only changes the host's choice
-    return rfx_conv3x3_direct_launch(in, wP, scale, shift, residual, out, N, Cin, H, W, Cout, (Cout + 127) / 128 * 128, act,
-                                     tm, pc, rfx_stream(stream), (kid & 16384) != 0);
+    const bool recording = rfx_group_recording();
+    return rfx_conv3x3_direct_launch(conv_direct3x3(conv_knobs(), N, Cin, Cout, H, W, k_chunk, recording), in, wP, scale, shift, residual,
+                                     out, N, Cin, H, W, Cout, (Cout + 127) / 128 * 128, act, recording, rfx_stream(stream));
 }
 
 extern "C" int rfx_conv3x3_kernel_id(int N, int Cin, int Cout, int H, int W, int k_chunk) {
-    return conv_kernel_id(N, Cin, Cout, 3, 3, 1, 1, H, W, true, k_chunk);
+    return conv_decide(conv_knobs(), {N, Cin, Cout, 3, 3, 1, 1, H, W}, true, k_chunk, true, rfx_group_recording()).id();
 }
 
 // The direct stride-2 kernel with the packed weights of rfx_conv3x3_f32 (bit 13 of rfx_conv2d_kernel_id says when it applies).
@@ -497,11 +428,9 @@ extern "C" int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float*
                                   void* stream) {
     if (!in || !wP || !out || N <= 0 || Cin < 8 || Cin % 8 != 0 || H <= 0 || W <= 0 || Cout <= 0) return RFX_E_ARG;
     if (reinterpret_cast<uintptr_t>(wP) & 15) return RFX_E_ARG;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int kid = conv_kernel_id(N, Cin, Cout, 3, 3, 2, 1, Ho, Wo, true);
-    int tm = (kid & 8192) ? ((kid & 1) ? 1 : 2) : (Cout > 64 ? 2 : 1);
-    if (const char* e = getenv("RFX_S2_TM")) tm = atoi(e) == 1 ? 1 : (atoi(e) == 2 ? 2 : tm);      // experiments
-    return rfx_conv3x3_s2_launch(in, wP, scale, shift, residual, out, N, Cin, H, W, Cout, act, tm, rfx_stream(stream));
+    const bool recording = rfx_group_recording();
+    const ConvInstance ci = conv_direct3x3_s2(conv_knobs(), N, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1, recording);
+    return rfx_conv3x3_s2_launch(ci, in, wP, scale, shift, residual, out, N, Cin, H, W, Cout, act, recording, rfx_stream(stream));
 }
 
 // dil = 1: rfx_conv2d_f32.  dil > 1 (rfx_conv2d_dilated_f32): the gather adds the ktab's (kh, kw) fields to the window origin
@@ -509,7 +438,7 @@ extern "C" int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float*
 // 4-bit field limit know about the dilation.
 static int conv2d_impl(const float* in, const float* wT, const int32_t* ktab, const float* scale,
                        const float* shift, const float* residual, float* out, int N, int Cin, int Hin,
-                       int Win, int Cout, int KH, int KW, int stride, int pad, int dil, int act, void* stream) {
+                       int Win, int Cout, int KH, int KW, int stride, int pad, int dil, int act, void* stream, bool recording) {
     if (!in || !wT || !ktab || !out) return RFX_E_ARG;
     if (N <= 0 || Cin <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || dil <= 0)
         return RFX_E_ARG;
@@ -526,40 +455,19 @@ static int conv2d_impl(const float* in, const float* wT, const int32_t* ktab, co
     a.Mpad = (Cout + 127) / 128 * 128;
     a.P = (long long)N * a.Hout * a.Wout;
     hipStream_t st = rfx_stream(stream);
-    const bool one = (KH == 1 && KW == 1 && pad == 0);
-    // The wave-specialised form pays off where the gather is the heavy part and the K loop is long: KxK (K > 1)
-    // convolutions on the 128x128 tile (measured +5 % there, -5...-15 % on 1x1 and 64-wide tiles, which keep the
-    // single-role kernel with two independent workgroups per CU).  RFX_CONV_WS=0/1 forces it off/on for A/B runs.
-    int kid = conv_kernel_id(N, Cin, Cout, KH, KW, stride, pad, a.Hout, a.Wout, false);
-    if (reinterpret_cast<uintptr_t>(in) & 15) kid &= ~16;  // VECB needs 16-B aligned planes
-    if (kid & 1024)
-        return rfx_conv1x1_kmajor_launch(in, wT, scale, shift, residual, out, N, Cin, Hin * Win, Cout, a.Mpad, act,
-                                         (kid & 3) ? 1 : 2, (kid & 16) != 0, st, (kid & 16384) != 0);
-    const int variant = kid & 3;
-    const bool ws = (kid & 8) != 0;
-    const bool vecb = (kid & 16) != 0;
-    if (vecb) {  // 1x1, stride 1, Hout*Wout % 4 == 0: vectorised pixel-side loads (never wave-specialised)
-        switch (variant) {
-            case 0: return launch_conv<2, 2, true, false, true>(a, st);
-            case 1: return launch_conv<1, 2, true, false, true>(a, st);
-            default: return launch_conv<1, 1, true, false, true>(a, st);
-        }
-    }
-    switch (variant) {
-        case 0:
-            if (ws) return one ? launch_conv<2, 2, true, true>(a, st) : launch_conv<2, 2, false, true>(a, st);
-            return one ? launch_conv<2, 2, true, false>(a, st) : launch_conv<2, 2, false, false>(a, st);
-        case 1:
-            if (ws) return one ? launch_conv<1, 2, true, true>(a, st) : launch_conv<1, 2, false, true>(a, st);
-            return one ? launch_conv<1, 2, true, false>(a, st) : launch_conv<1, 2, false, false>(a, st);
-        default: return one ? launch_conv<1, 1, true, false>(a, st) : launch_conv<1, 1, false, false>(a, st);
-    }
+    const ConvInstance ci = conv_decide(conv_knobs(), {N, Cin, Cout, KH, KW, stride, pad, a.Hout, a.Wout}, false, 0,
+                                        (reinterpret_cast<uintptr_t>(in) & 15) == 0, recording);
+    if (ci.family == CONV_KMAJOR)
+        return rfx_conv1x1_kmajor_launch(ci, in, wT, scale, shift, residual, out, N, Cin, Hin * Win, Cout, a.Mpad, act, recording, st);
+    const GemmEntry* e = conv_find(kGemm, ci);
+    return e ? e->launch(a, st, recording) : RFX_E_ARG;
 }
 
 extern "C" int rfx_conv2d_f32(const float* in, const float* wT, const int32_t* ktab, const float* scale,
                               const float* shift, const float* residual, float* out, int N, int Cin, int Hin,
                               int Win, int Cout, int KH, int KW, int stride, int pad, int act, void* stream) {
-    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, 1, act, stream);
+    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, 1, act, stream,
+                       rfx_group_recording());
 }
 
 extern "C" int rfx_conv2d_dilated_f32(const float* in, const float* wT, const int32_t* ktab, const float* scale,
@@ -567,5 +475,6 @@ extern "C" int rfx_conv2d_dilated_f32(const float* in, const float* wT, const in
                                       int Win, int Cout, int KH, int KW, int stride, int pad, int dilation, int act,
                                       void* stream) {
     if (dilation == 1) return RFX_E_ARG;      // the undilated geometries belong to rfx_conv2d_f32 / rfx_conv3x3_f32
-    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, dilation, act, stream);
+    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, dilation, act, stream,
+                       rfx_group_recording());
 }

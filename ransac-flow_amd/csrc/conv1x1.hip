@@ -18,6 +18,7 @@
 // in front of the MFMAs (that cost the direct 3x3 kernel 13 %, scripts/ubench/conv_bench.py).
 // k runs in the same pairs and the same order as in conv.hip: bit-identical results.
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "group.h"
 
@@ -245,8 +246,8 @@ static int c1_group_launch(const void* blob, const unsigned* gx, int n, hipStrea
     return rfx_group_launch_impl<C1Args>(conv1x1_kmajor_group_kernel<TM, VEC, KCH>, 256, blob, gx, n, st);
 }
 
-template <int TM, bool VEC, int KCH = 0>
-int launch_1x1(C1Args& a, hipStream_t st) {
+template <int TM, bool VEC, int KCH>
+int launch_1x1(C1Args& a, hipStream_t st, bool recording) {
     a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
     a.tilesP = (int)((a.P + 127) / 128);
     const long long nwg = (long long)a.tilesM * a.tilesP;
@@ -259,25 +260,31 @@ int launch_1x1(C1Args& a, hipStream_t st) {
         slots = (2 * cus + 7) / 8 * 8;
     }
     const unsigned grid = (unsigned)(nwg < slots ? (nwg + 7) / 8 * 8 : slots);
-    if (rfx_group_recording()) return rfx_group_record(&c1_group_launch<TM, VEC, KCH>, &a, sizeof(a), grid);
+    if (recording) return rfx_group_record(&c1_group_launch<TM, VEC, KCH>, &a, sizeof(a), grid);
     hipLaunchKernelGGL((conv1x1_kmajor_kernel<TM, VEC, KCH>), dim3(grid), dim3(256), 0, st, a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
 
+// Every instance the library builds: K >= 512 in chunks of 8 steps (256 k) on 64-channel tiles, else one chain on either tile
+struct C1Entry {
+    int key;
+    int (*launch)(C1Args&, hipStream_t, bool recording);
+};
+#define K1(TM, VEC, KCH) {ConvInstance::kmajor(TM, VEC, KCH).id(), &launch_1x1<TM, VEC, KCH>}
+const C1Entry kKmajor[] = {K1(1, true, 8), K1(1, false, 8), K1(2, true, 0), K1(2, false, 0), K1(1, true, 0), K1(1, false, 0)};
+#undef K1
+
 }  // namespace
 
-// Internal entry used by rfx_conv2d_f32 (conv.hip).  Preconditions checked by the caller: 1x1, stride 1, pad 0,
-// Cin % 32 == 0, Cin >= 64, N*HW >= 4; tm = 2 -> 128 output channels per workgroup, tm = 1 -> 64; vec: HW % 4 == 0 and `in` 16-byte
-// aligned (16-byte pixel loads).
-int rfx_conv1x1_kmajor_launch(const float* in, const float* wT, const float* scale, const float* shift, const float* residual,
-                              float* out, int N, int Cin, int HW, int Cout, int Mpad, int act, int tm, bool vec,
-                              hipStream_t st, bool chunked) {
+// Internal entry used by rfx_conv2d_f32 (conv.hip); preconditions: conv_dispatch.h
+int rfx_conv1x1_kmajor_launch(const ConvInstance& ci, const float* in, const float* wT, const float* scale, const float* shift,
+                              const float* residual, float* out, int N, int Cin, int HW, int Cout, int Mpad, int act,
+                              bool recording, hipStream_t st) {
     C1Args a;
     a.in = in; a.wT = wT; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.Cin = Cin; a.HW = HW; a.Cout = Cout; a.act = act; a.Mpad = Mpad;
     a.P = (long long)N * HW;
-    if (chunked) return vec ? launch_1x1<1, true, 8>(a, st) : launch_1x1<1, false, 8>(a, st);     // K >= 1024: chunks of 8 steps (256 k)
-    if (tm == 2) return vec ? launch_1x1<2, true>(a, st) : launch_1x1<2, false>(a, st);
-    return vec ? launch_1x1<1, true>(a, st) : launch_1x1<1, false>(a, st);
+    const C1Entry* e = conv_find(kKmajor, ci);
+    return e ? e->launch(a, st, recording) : RFX_E_ARG;
 }

@@ -21,9 +21,9 @@
 // Numerics: k runs channel-major, taps row-major -- the same order as conv.hip / the packed weight matrix, so the
 // result is bit-identical to the implicit-GEMM kernel.
 #include "common.h"
+#include "conv_dispatch.h"
 #include "conv_epilogue.h"
 #include "group.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -740,58 +740,11 @@ static int c3s2_group_launch(const void* blob, const unsigned* gx, int n, hipStr
     return rfx_group_launch_impl<C3Args>(conv3x3_s2_group_kernel<TM, KCH>, 256, blob, gx, n, st);
 }
 
-}  // namespace
-
-// Chunked accumulation (KCH above) for the layers whose single fma chain is longest: K = 9 Cin >= 2048.  RFX_C3_CHUNK=0 turns it off
-// (A/B runs: the chain form is what rfx_conv2d_f32's implicit-GEMM kernel computes).
-bool rfx_conv3x3_chunked(int Cin) {
-    static const int en = getenv("RFX_C3_CHUNK") ? atoi(getenv("RFX_C3_CHUNK")) : 1;
-    return en && Cin % CH == 0 && Cin * 9 >= 2048;
-}
-// Round 5: the stride-2 kernel's long-K layers (K >= 1152) -- RFX_C3_S2_CHUNK=0: chains
-bool rfx_conv3x3_s2_chunked(int Cin) {
-    static const int en = getenv("RFX_C3_S2_CHUNK") ? atoi(getenv("RFX_C3_S2_CHUNK")) : 1;
-    return en && Cin * 9 >= 1152;
-}
-// Round 5: the Bottleneck tails (K = 576 / 1152) close their chunks as well -- RFX_C3_TAIL_CHUNK=0: the round-4 chains (A/B runs)
-bool rfx_conv3x3_tail_chunked() {
-    static const int en = getenv("RFX_C3_TAIL_CHUNK") ? atoi(getenv("RFX_C3_TAIL_CHUNK")) : 1;
-    return en != 0;
-}
-
-// 256-pixel (16 x 16) patches for a layer whose output channels fit ONE 64-channel tile: only for launches that still fill the
-// chip two generations deep with the larger patch, never inside a grouped launch (latency-bound: more, smaller workgroups win).
-bool rfx_conv3x3_wide_patch(int N, int H, int W, int Cout, int patch_cols) {
-    static const int en = getenv("RFX_C3_WIDE") ? atoi(getenv("RFX_C3_WIDE")) : 1;
-    if (!en || rfx_group_recording() || patch_cols != 16 || Cout > 64) return false;
-    const long long tiles = (((long long)N * (H + 1) + 15) / 16) * ((W + 15) / 16);
-    return tiles >= 1024;
-}
-
-// Patch shape for a batch of N H x W maps stacked as above: the fewest padded pixels (ties: the widest, whose row segments
-// coalesce best).  The fused Bottleneck tail writes Cexp channels per pixel from a narrow patch in short row segments:
-// measured on equal work its 16x8 patch is ~9 % and its 32x4 patch ~40 % slower than 8x16, while the plain 3x3 kernel is
-// indifferent (scripts/ubench/conv_bench.py on the 25x33 ... 112x148 maps of the pyramid) -- hence the weights.
-int rfx_conv3x3_patch_cols(int N, int H, int W, bool fused) {
-    // grouped launches (group.h): ONE patch shape for every problem of the group, so that a layer is one launch and not
-    // one per shape -- the group is latency-bound, a few padded pixels on the small maps cost less than a serial launch
-    static const int uniform = getenv("RFX_GROUP_UNIFORM") ? atoi(getenv("RFX_GROUP_UNIFORM")) : 1;
-    if (uniform && rfx_group_recording()) return 16;
-    int best = 16;
-    long long best_cost = -1;
-    for (int pc = 16; pc >= 4; pc >>= 1) {
-        const int pr = 128 / pc;
-        const long long area = (((long long)N * (H + 1) + pr - 1) / pr) * ((W + pc - 1) / pc);
-        const long long cost = area * (!fused || pc == 16 ? 100 : (pc == 8 ? 109 : 140));
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = pc; }
-    }
-    return best;
-}
-
-template <int TM, int PTC, bool FUSE = false, int TN = 2, bool RAG = false, int KCH = 0>
-static int launch_direct(C3Args& a, hipStream_t st) {
+template <int TM, int PTC, bool FUSE, int TN, bool RAG, int KCH>
+int launch_direct(C3Args& a, hipStream_t st, bool recording) {
     using G = Patch<PTC, TN>;
     const long long rows = (long long)a.N * (a.H + 1);
+    a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
     a.tilesH = (int)((rows + G::PT_R - 1) / G::PT_R);
     a.tilesW = (a.W + G::PT_C - 1) / G::PT_C;
     const long long nwg = (long long)a.tilesM * a.tilesH * a.tilesW;
@@ -799,19 +752,68 @@ static int launch_direct(C3Args& a, hipStream_t st) {
     // 32-bit byte offsets inside the images one input patch can touch
     const long long span = (G::PR + a.H) / (a.H + 1) + 1;
     if (span * a.Cin * a.H * a.W * 4 > 0xffffffffLL) return RFX_E_LIMIT;
-    if constexpr (TN == 2 && !RAG) {
-        if (rfx_group_recording()) return rfx_group_record(&c3_group_launch<TM, PTC, FUSE, KCH>, &a, sizeof(a), (unsigned)nwg);
+    if constexpr (TN == 2 && !RAG) {      // the other instances have no grouped form: launched at once
+        if (recording) return rfx_group_record(&c3_group_launch<TM, PTC, FUSE, KCH>, &a, sizeof(a), (unsigned)nwg);
     }
     hipLaunchKernelGGL((conv3x3_direct_kernel<TM, PTC, FUSE, TN, RAG, KCH>), dim3((unsigned)nwg), dim3(256), 0, st, a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
 
-// Internal entry used by rfx_conv2d_f32 (conv.hip).  Preconditions checked by the caller: 3x3, stride 1, pad 1,
-// Cin % 8 == 0.  tm = 2 -> 128 output channels per workgroup, tm = 1 -> 64; patch_cols in {16, 8, 4}.
-int rfx_conv3x3_direct_launch(const float* in, const float* wP, const float* scale, const float* shift,
-                              const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int Mpad,
-                              int act, int tm, int patch_cols, hipStream_t st, bool chunked) {
+template <int TM, int KCH>
+int launch_s2(C3Args& a, hipStream_t st, bool recording) {
+    const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
+    a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
+    a.tilesH = (Ho + s2::PT_R - 1) / s2::PT_R;
+    a.tilesW = (Wo + s2::PT_C - 1) / s2::PT_C;
+    const long long nwg = (long long)a.tilesM * a.tilesH * a.tilesW * a.N;
+    if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
+    if ((long long)a.Cin * a.H * a.W * 4 > 0xffffffffLL) return RFX_E_LIMIT;                    // 32-bit byte offsets inside one image
+    if (recording) return rfx_group_record(&c3s2_group_launch<TM, KCH>, &a, sizeof(a), (unsigned)nwg);
+    hipLaunchKernelGGL((conv3x3_s2_kernel<TM, KCH>), dim3((unsigned)nwg), dim3(256), 0, st, a);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+// Every instance the library builds (conv_dispatch.h decides which one a launch takes), template arguments as the kernels take them
+struct C3Entry {
+    int key;
+    int (*launch)(C3Args&, hipStream_t, bool recording);
+};
+template <int TM, int PTC, bool FUSE, int TN, bool RAG, int KCH> constexpr ConvInstance direct_instance() {
+    return FUSE ? ConvInstance::fused_tail(TM, PTC, KCH) : ConvInstance::direct3x3(TM, PTC, TN, RAG, KCH);
+}
+#define D(...) {direct_instance<__VA_ARGS__>().id(), &launch_direct<__VA_ARGS__>}
+const C3Entry kDirect[] = {
+    // <TM, PT_C, FUSE, TN, RAG, KCH>: plain, and in chunks of 4 K steps (288 k)
+    D(2, 16, false, 2, false, 0), D(2, 8, false, 2, false, 0), D(2, 4, false, 2, false, 0),
+    D(1, 16, false, 2, false, 0), D(1, 8, false, 2, false, 0), D(1, 4, false, 2, false, 0),
+    D(2, 16, false, 2, false, 4), D(2, 8, false, 2, false, 4), D(2, 4, false, 2, false, 4),
+    D(1, 16, false, 2, false, 4), D(1, 8, false, 2, false, 4), D(1, 4, false, 2, false, 4),
+    // 256-pixel patches (64-channel tiles only)
+    D(1, 16, false, 4, false, 0), D(1, 16, false, 4, false, 4),
+    // ragged last K step (Cin % 8 != 0)
+    D(2, 16, false, 2, true, 0), D(2, 8, false, 2, true, 0), D(2, 4, false, 2, true, 0),
+    D(1, 16, false, 2, true, 0), D(1, 8, false, 2, true, 0), D(1, 4, false, 2, true, 0),
+    // the fused Bottleneck tail
+    D(2, 16, true, 2, false, 0), D(2, 8, true, 2, false, 0), D(2, 4, true, 2, false, 0),
+    D(1, 16, true, 2, false, 0), D(1, 8, true, 2, false, 0), D(1, 4, true, 2, false, 0),
+    D(2, 16, true, 2, false, 4), D(2, 8, true, 2, false, 4), D(2, 4, true, 2, false, 4),
+    D(1, 16, true, 2, false, 4), D(1, 8, true, 2, false, 4), D(1, 4, true, 2, false, 4),
+};
+#undef D
+#define S2(TM, KCH) {ConvInstance::direct3x3_s2(TM, KCH).id(), &launch_s2<TM, KCH>}
+const C3Entry kStride2[] = {S2(2, 0), S2(1, 0), S2(2, 4), S2(1, 4)};
+#undef S2
+
+int launch_from(const C3Entry* e, C3Args& a, hipStream_t st, bool recording) { return e ? e->launch(a, st, recording) : RFX_E_ARG; }
+
+}  // namespace
+
+// Internal entry used by rfx_conv3x3_f32 (conv.hip); preconditions: conv_dispatch.h
+int rfx_conv3x3_direct_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
+                              const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int Mpad, int act,
+                              bool recording, hipStream_t st) {
     C3Args a;
     a.in = in; a.wT = wP; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.act = act; a.Mpad = Mpad;
@@ -819,42 +821,13 @@ int rfx_conv3x3_direct_launch(const float* in, const float* wP, const float* sca
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();
 #endif
-    const int BM = 64 * tm;
-    a.tilesM = (Cout + BM - 1) / BM;
-    if (Cin % CH != 0) {          // ragged last K step: separate instances (never recorded into a grouped launch: launched at once)
-        if (tm == 2) {
-            if (patch_cols == 16) return launch_direct<2, 16, false, 2, true>(a, st);
-            if (patch_cols == 8) return launch_direct<2, 8, false, 2, true>(a, st);
-            return launch_direct<2, 4, false, 2, true>(a, st);
-        }
-        if (patch_cols == 16) return launch_direct<1, 16, false, 2, true>(a, st);
-        if (patch_cols == 8) return launch_direct<1, 8, false, 2, true>(a, st);
-        return launch_direct<1, 4, false, 2, true>(a, st);
-    }
-    if (tm == 2) {
-        if (chunked) {      // K >= 2048 (or asked for by the caller): chunks of 4 K steps (288 k)
-            if (patch_cols == 16) return launch_direct<2, 16, false, 2, false, 4>(a, st);
-            if (patch_cols == 8) return launch_direct<2, 8, false, 2, false, 4>(a, st);
-            return launch_direct<2, 4, false, 2, false, 4>(a, st);
-        }
-        if (patch_cols == 16) return launch_direct<2, 16>(a, st);
-        if (patch_cols == 8) return launch_direct<2, 8>(a, st);
-        return launch_direct<2, 4>(a, st);
-    }
-    if (chunked) {          // a single image / tiny batch runs the long-K layers on 64-channel tiles: same chunks
-        if (patch_cols == 16) return rfx_conv3x3_wide_patch(N, H, W, Cout, 16) ? launch_direct<1, 16, false, 4, false, 4>(a, st)
-                                                                               : launch_direct<1, 16, false, 2, false, 4>(a, st);
-        if (patch_cols == 8) return launch_direct<1, 8, false, 2, false, 4>(a, st);
-        return launch_direct<1, 4, false, 2, false, 4>(a, st);
-    }
-    if (patch_cols == 16) return rfx_conv3x3_wide_patch(N, H, W, Cout, 16) ? launch_direct<1, 16, false, 4>(a, st) : launch_direct<1, 16>(a, st);
-    if (patch_cols == 8) return launch_direct<1, 8>(a, st);
-    return launch_direct<1, 4>(a, st);
+    return launch_from(ci.family == CONV_DIRECT3 ? conv_find(kDirect, ci) : nullptr, a, st, recording);
 }
 
-// 3x3 / stride 2 / pad 1, Cin % 8 == 0: the direct stride-2 kernel above.  tm = 2 -> 128 output channels per workgroup, 1 -> 64.
-int rfx_conv3x3_s2_launch(const float* in, const float* wP, const float* scale, const float* shift, const float* residual,
-                          float* out, int N, int Cin, int H, int W, int Cout, int act, int tm, hipStream_t st) {
+// Internal entry used by rfx_conv3x3_s2_f32 (conv.hip): the direct stride-2 kernel above
+int rfx_conv3x3_s2_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
+                          const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int act, bool recording,
+                          hipStream_t st) {
     C3Args a;
     a.in = in; a.wT = wP; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.act = act; a.Mpad = (Cout + 127) / 128 * 128;
@@ -862,39 +835,15 @@ int rfx_conv3x3_s2_launch(const float* in, const float* wP, const float* scale, 
 #ifdef RFX_TRACE
     a.trace = nullptr;
 #endif
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int BM = 64 * tm;
-    a.tilesM = (Cout + BM - 1) / BM;
-    a.tilesH = (Ho + s2::PT_R - 1) / s2::PT_R;
-    a.tilesW = (Wo + s2::PT_C - 1) / s2::PT_C;
-    const long long nwg = (long long)a.tilesM * a.tilesH * a.tilesW * N;
-    if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    if ((long long)Cin * H * W * 4 > 0xffffffffLL) return RFX_E_LIMIT;                    // 32-bit byte offsets inside one image
-    // round 5: K = 9 Cin >= 1152 closes a chunk every 4 K steps (288 products), like the stride-1 kernel (RFX_C3_S2_CHUNK=0: chains)
-    const bool chk = rfx_conv3x3_s2_chunked(Cin);
-    if (rfx_group_recording()) {
-        if (chk) return tm == 2 ? rfx_group_record(&c3s2_group_launch<2, 4>, &a, sizeof(a), (unsigned)nwg)
-                                : rfx_group_record(&c3s2_group_launch<1, 4>, &a, sizeof(a), (unsigned)nwg);
-        return tm == 2 ? rfx_group_record(&c3s2_group_launch<2, 0>, &a, sizeof(a), (unsigned)nwg)
-                       : rfx_group_record(&c3s2_group_launch<1, 0>, &a, sizeof(a), (unsigned)nwg);
-    }
-    if (chk) {
-        if (tm == 2) hipLaunchKernelGGL((conv3x3_s2_kernel<2, 4>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_s2_kernel<1, 4>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    } else if (tm == 2) hipLaunchKernelGGL((conv3x3_s2_kernel<2>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_s2_kernel<1>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return launch_from(conv_find(kStride2, ci), a, st, recording);
 }
 
 // Bottleneck tail in one kernel: out = act3(bn3(conv1x1(act2(bn2(conv3x3(in))))) + residual)  (model/resnet50.py:71-79,93-103).
 // The 3x3 convolution must be direct-eligible (stride 1, pad 1, Cin % 8 == 0) with Cmid in {64, 128} so that one workgroup
 // tile holds all of its channels; Cexp % 128 == 0.
-// Kernel instance rfx_conv3x3_conv1x1_f32 launches (for a profiler-side caller, as rfx_conv2d_kernel_id): bit 9 = fused
-// tail, bit 0 = 64-channel mid tile (TM = 1), bits 6-7 = output patch shape (0: 8x16, 1: 16x8, 2: 32x4).
+// Kernel instance rfx_conv3x3_conv1x1_f32 launches (for a profiler-side caller; bits as rfx_conv2d_kernel_id).
 extern "C" int rfx_conv3x3_conv1x1_kernel_id(int N, int H, int W, int Cmid) {
-    const int pc = rfx_conv3x3_patch_cols(N, H, W, true);
-    return 512 | (Cmid == 64 ? 1 : 0) | (pc == 16 ? 0 : (pc == 8 ? 64 : 128)) | (rfx_conv3x3_tail_chunked() ? 16384 : 0);   // bit 14: chunked
+    return conv_decide_tail(conv_knobs(), N, H, W, Cmid, rfx_group_recording()).id();
 }
 
 extern "C" int rfx_conv3x3_conv1x1_f32(const float* in, const float* wP2, const float* scale2, const float* shift2, int act2,
@@ -911,25 +860,7 @@ extern "C" int rfx_conv3x3_conv1x1_f32(const float* in, const float* wP2, const 
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();
 #endif
-    a.tilesM = 1;
-    hipStream_t st = rfx_stream(stream);
-    const int pc = rfx_conv3x3_patch_cols(N, H, W, true);
-    if (rfx_conv3x3_tail_chunked()) {        // round 5: chunks of 4 K steps (288 k) in the 3x3 phase, like rfx_conv3x3_f32(k_chunk = 4)
-        if (Cmid == 128) {
-            if (pc == 16) return launch_direct<2, 16, true, 2, false, 4>(a, st);
-            if (pc == 8) return launch_direct<2, 8, true, 2, false, 4>(a, st);
-            return launch_direct<2, 4, true, 2, false, 4>(a, st);
-        }
-        if (pc == 16) return launch_direct<1, 16, true, 2, false, 4>(a, st);
-        if (pc == 8) return launch_direct<1, 8, true, 2, false, 4>(a, st);
-        return launch_direct<1, 4, true, 2, false, 4>(a, st);
-    }
-    if (Cmid == 128) {
-        if (pc == 16) return launch_direct<2, 16, true>(a, st);
-        if (pc == 8) return launch_direct<2, 8, true>(a, st);
-        return launch_direct<2, 4, true>(a, st);
-    }
-    if (pc == 16) return launch_direct<1, 16, true>(a, st);   // the 256-pixel patch buys the fused tail nothing (100.9 vs 100.5 TFLOP/s): its loss is the expansion phase
-    if (pc == 8) return launch_direct<1, 8, true>(a, st);
-    return launch_direct<1, 4, true>(a, st);
+    const bool recording = rfx_group_recording();
+    // round 5: chunks of 4 K steps (288 k) in the 3x3 phase, like rfx_conv3x3_f32(k_chunk = 4)
+    return launch_from(conv_find(kDirect, conv_decide_tail(conv_knobs(), N, H, W, Cmid, recording)), a, rfx_stream(stream), recording);
 }

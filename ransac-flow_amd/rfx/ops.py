@@ -183,6 +183,8 @@ def _p(t):
 
 KID_SPLIT_3X3 = 65536      # ... of rfx_conv3x3_split_f32
 KID_SPLIT_1X1 = 32768      # Profiler kernel id of rfx_conv1x1_split_f32 (| 1: 64-channel tiles, | 2: 128-channel tiles)
+KID_DIRECT_3X3 = 32        # bit 5 of the library's ids (include/rfx_api.h, rfx_conv2d_kernel_id): served by rfx_conv3x3_f32
+KID_DIRECT_3X3_S2 = 8192   # bit 13: served by rfx_conv3x3_s2_f32
 
 
 def conv_split_enabled():
@@ -390,10 +392,10 @@ class ConvPlan:
         lib = _lib.load()
         kid0 = (lib.rfx_conv3x3_kernel_id(N, self.Cin, self.Cout, Ho, Wo, self.k_chunk) if self.stride == 1 else
                 lib.rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo))
-        if not kid0 & (32 | 8192):
+        if not kid0 & (KID_DIRECT_3X3 | KID_DIRECT_3X3_S2):
             return self._run_gemm(x, res, out, act)
         e0 = Profiler.begin(x)
-        if kid0 & 32:
+        if kid0 & KID_DIRECT_3X3:
             _call("rfx_conv3x3_f32", _one_device(x, res, self.wP), _p(x), _p(self.wP), _p(self.scale), _p(self.shift),
                   _p(res), _p(out), N, C, H, W, self.Cout, act, self.k_chunk)
         else:
@@ -413,7 +415,7 @@ class ConvPlan:
     def _record_fp32(self, kid0, e0, x, res, out):
         N, C, H, W = x.shape
         Ho, Wo = out.shape[2:]
-        kid = kid0 if (kid0 & 32) else _lib.load().rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo)
+        kid = kid0 if (kid0 & KID_DIRECT_3X3) else _lib.load().rfx_conv2d_kernel_id(N, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, Ho, Wo)
         flops = 2.0 * N * Ho * Wo * self.Cout * self.Cin * self.KH * self.KW
         nbytes = 4.0 * (N * C * H * W + N * self.Cout * Ho * Wo * (2 if res is not None else 1)
                         + self.Cout * self.Cin * self.KH * self.KW)

@@ -1139,3 +1139,31 @@ def test_split_3x3_stride2_convolution_against_float64_and_the_fp32_kernel(dev, 
     with ops.launch_group(dev, False):
         yg = psp(x)
     assert torch.equal(yg, ysp)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,eager_id,bit,recording_id", [
+    ((3, 8, 64, 15, 40, 1), 97, 64, 33),          # direct 3x3: 16x8 patches alone, the group's uniform 8x16 patches while recording
+    ((4, 8, 64, 240, 320, 1), 2081, 2048, 33),    # direct 3x3: 256-pixel patches alone, never inside a grouped launch
+    ((2, 64, 128, 32, 64, 2), 8193, 8192, 2)])    # 3x3 / stride 2, K = 576: the direct kernel alone, the implicit GEMM while recording
+def test_recording_changes_the_instance_not_the_result(dev, shape, eager_id, bit, recording_id):
+    """While a grouped launch records, the fp32 dispatch (csrc/conv_dispatch.h, `recording`) picks another kernel instance for these
+    launches; include/rfx_api.h promises the same sums in the same order: bit-equal outputs on random float32 data."""
+    from rfx import _lib
+    N, Cin, Cout, H, W, stride = shape
+    g = torch.Generator().manual_seed(Cin + Cout + H)
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) * (2.0 / (9 * Cin)) ** 0.5
+    p = ops.ConvPlan(w, None, stride, 1, ops.ACT_RELU, dev)
+    assert p.route == "fp32_3x3"
+    x = torch.randn(N, Cin, H, W, generator=g).to(dev)
+    Ho, Wo = p.out_hw(H, W)
+    lib = _lib.load()
+    kid = (lambda: lib.rfx_conv3x3_kernel_id(N, Cin, Cout, Ho, Wo, 0)) if stride == 1 else \
+        (lambda: lib.rfx_conv2d_kernel_id(N, Cin, Cout, 3, 3, stride, 1, Ho, Wo))
+    assert kid() == eager_id and eager_id & bit
+    y = p(x)
+    with ops.launch_group(dev, False):
+        assert kid() == recording_id and not recording_id & bit
+        yg = p(x)
+    assert kid() == eager_id
+    assert float(y.abs().max()) > 0 and torch.equal(yg, y), "%d of %d elements differ" % (int((yg != y).sum()), y.numel())
