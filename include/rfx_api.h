@@ -44,9 +44,9 @@ const char* rfx_version(void);
  * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes; 12: the ragged forms of the
  * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32; 13:
  * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
- * rfx_multih_accept_ragged_d2_f32).  A binding
+ * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 14
+#define RFX_ABI_VERSION 15
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -632,6 +632,32 @@ int rfx_conv3x3_split_f32(const float* in, const void* wS3, const float* scale, 
  * (model/model.py:32).  out (N,Cout,Ho,Wo), Ho = (H - 1) / 2 + 1; same wS3; Cin % 16 == 0; 128-channel tiles. */
 int rfx_conv3x3_split_s2_f32(const float* in, const void* wS3, const float* scale, const float* shift, const float* residual,
                              float* out, int N, int Cin, int H, int W, int Cout, int act, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * rfx_conv1x1_expand64_f32 (ABI 15): the 1x1 / stride 1 / pad 0 convolution of rfx_conv2d_f32 for Cin = 64 and Cout = 256 (the
+ * 64 -> 256 expansions of ResNet-50 layer1, model/resnet50.py:77-79) as a kernel of its own (csrc/conv1x1e.hip): the whole weight
+ * matrix stays in LDS for the life of a persistent workgroup, a wavefront produces every output channel of its 32 pixels from
+ * operands it loads once.
+ *     out[n,m,p] = act(fmaf(sum_k in[n,k,p] * w[m,k], scale[m], shift[m]) + residual[n,m,p])
+ * Same k pairs in the same ascending order, one fma chain per output, same epilogue: BIT-IDENTICAL to rfx_conv2d_f32 on this geometry.
+ * wT: rfx_conv2d_f32's pack of the (Cout, 64, 1, 1) weight (wT[k][Mpad], Mpad = Cout here); scale / shift (Cout) or NULL (1 / 0);
+ * residual (N,Cout,HW) or NULL; act = RFX_ACT_NONE or RFX_ACT_RELU.  in (N,64,HW), out (N,Cout,HW) float32, any HW.
+ * Launch: min(CUs, ceil(T / 8)) workgroups of 8 wavefronts, T = ceil(N * HW / 32) pixel tiles; wavefront w of workgroup g walks the
+ * tiles 8 g + w, 8 g + w + 8 * workgroups, ...
+ * Returns RFX_E_ARG for Cin != 64, stride != 1, Cout % 256 != 0, another activation, or while a grouped launch records
+ * (rfx_group_begin: the group keeps rfx_conv2d_f32's launches); RFX_E_LIMIT for Cout > 256.
+ * ------------------------------------------------------------------------------------------ */
+int rfx_conv1x1_expand64_f32(const float* in, const float* wT, const float* scale, const float* shift, const float* residual,
+                             float* out, int N, int Cin, int HW, int Cout, int stride, int act, void* stream);
+/* ... two-source form: a Bottleneck's conv3 and its projection shortcut in one launch (model/resnet50.py:93-103 with :139-143),
+ *     d   = fmaf(sum_k in_b[n,k,p] * w_b[m,k], scale_b[m], shift_b[m])                  (rounded to float32)
+ *     out = relu(fmaf(sum_k in_a[n,k,p] * w_a[m,k], scale_a[m], shift_a[m]) + d)
+ * -- the operations, in their order, of rfx_conv2d_f32(in_b, ..., RFX_ACT_NONE) followed by rfx_conv2d_f32(in_a, ..., residual = d,
+ * RFX_ACT_RELU): bit-identical to that pair, and d never goes to memory.  in_a, in_b (N,64,HW) over the same pixels; both weight
+ * sets as above, both with Cin = 64; errors as above. */
+int rfx_conv1x1_expand64_dual_f32(const float* in_a, const float* wT_a, const float* scale_a, const float* shift_a,
+                                  const float* in_b, const float* wT_b, const float* scale_b, const float* shift_b, float* out,
+                                  int N, int Cin, int HW, int Cout, int stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sky segmentation forward pass: SegNet.getSky (segNet/segEval.py:23-43) = ResNet-50-dilated encoder

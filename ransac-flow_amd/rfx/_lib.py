@@ -26,6 +26,8 @@ SIGNATURES = {
     "rfx_conv3x3_split_s2_f32": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     "rfx_conv1x1_split_strided_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "rfx_conv1x1_split_tile_channels": (c_int, [c_int] * 4),
+    "rfx_conv1x1_expand64_f32": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    "rfx_conv1x1_expand64_dual_f32": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p]),
     "rfx_adaptive_avgpool2d_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "rfx_softmax_accum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_float, c_int, c_void_p]),
     "rfx_argmax_mask_f32": (c_int, [c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -102,7 +104,7 @@ SIGNATURES = {
                                         + [c_void_p] * 12 + [c_longlong] + [c_int] * 3 + [c_void_p]),
 }
 
-ABI_VERSION = 14    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 15    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

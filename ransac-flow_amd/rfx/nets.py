@@ -64,13 +64,28 @@ class ResNet50Trunk:
         x = ops.stem_conv7_maxpool(x, self.conv1)  # conv1 + BN + ReLU + MaxPool2d(3, 2, 1) in one kernel
         for blk in self.blocks:
             o = blk["c1"](x)
+            form = self.expand64_form(blk)
+            if form == "dual":
+                # layer1.0: conv3 and the projection shortcut in one launch -- the 256-channel shortcut never goes to memory
+                x = ops.conv1x1_expand64(blk["c2"](o), blk["c3"], shortcut=(x, blk["ds"]))
+                continue
             r = blk["ds"](x) if blk["ds"] is not None else x
             if ops.bottleneck_tail_eligible(blk["c2"], blk["c3"]):
                 x = ops.bottleneck_tail(o, blk["c2"], blk["c3"], residual=r)   # conv2 + conv3 in one kernel
+            elif form == "plain":
+                x = ops.conv1x1_expand64(blk["c2"](o), blk["c3"], residual=r)   # layer1.1 / layer1.2
             else:
                 o = blk["c2"](o)
                 x = blk["c3"](o, residual=r)  # relu(bn3(conv3(o)) + r)
         return x
+
+    @staticmethod
+    def expand64_form(blk):
+        """The form of ops.conv1x1_expand64 a block's conv3 takes in __call__ ("dual", "plain" or None): the 64 -> 256 expansions of
+        layer1 where they run as a kernel of their own (not inside the fused tail) and RFX_EXPAND64 is not 0."""
+        if ops.bottleneck_tail_eligible(blk["c2"], blk["c3"]):
+            return None
+        return ops.expand64_form(blk["c3"], blk["ds"])
 
 
     def forward_group(self, xs, side_streams=True):

@@ -466,6 +466,93 @@ def bottleneck_tail(x, plan2, plan3, residual=None):
     return out
 
 
+_EXPAND64 = None      # RFX_EXPAND64, read once (expand64_enabled)
+
+
+def expand64_enabled():
+    """RFX_EXPAND64=0 (environment, read once per process): the 64 -> 256 expansions of the trunk's layer1 stay on rfx_conv2d_f32's
+    k-major kernel, shortcut and conv3 as two launches (A/B runs and tests).  Both settings return the same bits."""
+    global _EXPAND64
+    if _EXPAND64 is None:
+        _EXPAND64 = os.environ.get("RFX_EXPAND64", "1") != "0"
+    return _EXPAND64
+
+
+def expand64_eligible(plan):
+    """Does a convolution (ConvPlan or ConvGeometry) have the geometry rfx_conv1x1_expand64_f32 serves?  1x1, stride 1, pad 0,
+    Cin = 64, Cout a multiple of the 256 channels a workgroup's resident weights cover (and no more than them), a folded scale, activation
+    none or ReLU.  Pure: no environment, no device."""
+    return (plan.KH == 1 and plan.KW == 1 and plan.stride == 1 and plan.pad == 0 and getattr(plan, "dilation", 1) == 1
+            and plan.Cin == 64 and plan.Cout % 256 == 0 and plan.Cout <= 256 and plan.scale is not None
+            and plan.act in (ACT_NONE, ACT_RELU))
+
+
+# Launch sizes (N * H * W pixels) from which the measured rule sends a form to conv1x1e.hip (scripts/ubench/expand64_bench.py,
+# profiles/expand64_ab.json; DESIGN.md 5).  The persistent launch costs ~35 us (plain) / ~50 us (two-source) before its first
+# tile -- every workgroup copies the weights into LDS -- so single pairs' maps (<= 76 800 pixels) stay on rfx_conv2d_f32's
+# launches; between the two limits only the two-source form wins by more than the old launches' spread (plain at 271 360 pixels:
+# 1.03x, inside it).
+EXPAND64_MIN_PIXELS = {"plain": 300000, "dual": 100000}
+
+
+def expand64_form(plan3, plan_ds=None, pixels=None):
+    """The form of rfx_conv1x1_expand64_f32 a Bottleneck's conv3 takes: "dual" (with its projection shortcut ``plan_ds``, ACT_NONE,
+    over the same pixels), "plain" (conv3 + residual alone) or None (rfx_conv2d_f32's launches: RFX_EXPAND64=0, a geometry the
+    kernel does not serve, a plan on another route, or -- ``pixels`` given -- a launch size at which the old launches measured no
+    slower).  A block whose shortcut is ineligible takes no form at all: its conv3 would read the shortcut back from memory."""
+    def ok(p):
+        return expand64_eligible(p) and getattr(p, "route", "gemm") == "gemm"
+    if not expand64_enabled() or not ok(plan3) or plan3.act != ACT_RELU:
+        return None
+    if plan_ds is not None:
+        form = "dual" if (ok(plan_ds) and plan_ds.act == ACT_NONE and plan_ds.Cout == plan3.Cout) else None
+    else:
+        form = "plain"
+    if form is not None and pixels is not None and pixels < EXPAND64_MIN_PIXELS[form]:
+        return None
+    return form
+
+
+def conv1x1_expand64(x, plan, residual=None, shortcut=None):
+    """plan(x, residual=residual) -- or, with ``shortcut`` = (xs, plan_s), plan(x, residual=plan_s(xs)) -- on conv1x1e.hip where
+    expand64_form() says so for this launch, else as those calls themselves (also inside a launch_group, whose grouped launches
+    keep rfx_conv2d_f32's kernels): the same bits either way.  Under a Profiler the launch is recorded under the kernel id
+    rfx_conv2d_f32 runs ``plan`` at for this geometry, with the FLOPs of both GEMMs and the bytes the launch moves."""
+    if residual is not None and shortcut is not None:
+        raise ValueError("conv1x1_expand64: a residual or a shortcut, not both")
+    x = _dev(x, "conv input")
+    N, C, H, W = x.shape
+    plan_s = shortcut[1] if shortcut is not None else None
+    form = expand64_form(plan, plan_s, N * H * W)
+    if getattr(launch_group._tls, "active", None) is not None:
+        form = None
+    if form is None:
+        return plan(x, residual=plan_s(shortcut[0]) if shortcut is not None else residual)
+    if C != plan.Cin:
+        raise ValueError("conv expects %d input channels, got %d" % (plan.Cin, C))
+    out = torch.empty((N, plan.Cout, H, W), dtype=torch.float32, device=x.device)
+    e0 = Profiler.begin(x)
+    if form == "dual":
+        xs = _dev(shortcut[0], "shortcut input")
+        if xs.shape != x.shape:
+            raise ValueError("shortcut input shape %s != conv input shape %s" % (tuple(xs.shape), tuple(x.shape)))
+        _call("rfx_conv1x1_expand64_dual_f32", _one_device(x, xs, plan.wT, plan_s.wT), _p(x), _p(plan.wT), _p(plan.scale), _p(plan.shift),
+              _p(xs), _p(plan_s.wT), _p(plan_s.scale), _p(plan_s.shift), _p(out), N, C, H * W, plan.Cout, 1)
+    else:
+        res = _dev(residual, "residual") if residual is not None else None
+        if res is not None and res.shape != out.shape:
+            raise ValueError("residual shape %s != output shape %s" % (tuple(res.shape), tuple(out.shape)))
+        _call("rfx_conv1x1_expand64_f32", _one_device(x, res, plan.wT), _p(x), _p(plan.wT), _p(plan.scale), _p(plan.shift), _p(res), _p(out),
+              N, C, H * W, plan.Cout, 1, plan.act)
+    if e0 is not None:
+        gemms = 2 if form == "dual" else 1
+        planes = plan.Cout * (2 if (form == "plain" and residual is not None) else 1)
+        Profiler.record_conv(_lib.load().rfx_conv2d_kernel_id(N, plan.Cin, plan.Cout, 1, 1, 1, 0, H, W),
+                             gemms * 2.0 * N * H * W * plan.Cout * plan.Cin, e0, (N, plan.Cin, H, W, plan.Cout, 1, 1),
+                             4.0 * (N * H * W * (gemms * C + planes) + gemms * plan.Cout * plan.Cin))
+    return out
+
+
 def maxpool2d(x, k, stride, pad=0):
     x = _dev(x, "maxpool input")
     N, C, H, W = x.shape
