@@ -23,6 +23,7 @@
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
+#include "conv_tile.h"
 #include "group.h"
 
 struct ConvArgs {
@@ -88,21 +89,18 @@ __device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsign
     const int t = tid & 255;  // staging index (WS: the loader wavefronts are threads 256..511)
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-aware bijective remap: each XCD (observed: block b -> XCD b%8) walks a contiguous chunk of
-    // the tile space, m-tile fastest, so the blocks that share one im2col pixel tile run on one L2.
-    const int nwg = a.tilesM * a.tilesP;
-    int bid = (int)bx;
     RFX_STAMP(0);
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    // m-tile fastest: the blocks that share one im2col pixel tile run on one L2
+    const int bid = xcd_remap(bx, a.tilesM * a.tilesP);
     const int tm_idx = bid % a.tilesM;
     const int tp_idx = bid / a.tilesM;
     const int m0 = tm_idx * BM;
     const long long n0 = (long long)tp_idx * BN;
 
-    if (tid < BM) {  // folded BatchNorm of this block's output channels -> LDS (visible after the first barrier)
+    // folded BatchNorm of this block's output channels -> LDS (visible after the first barrier).  A second copy of stage_bn
+    // (conv_tile.h), kept on purpose: through the helper the 64-channel instances allocate 117 / 119 VGPRs where the committed
+    // resource table pins 121 / 123
+    if (tid < BM) {
         const int m = m0 + t;
         s_scale[t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
         s_shift[t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
@@ -246,12 +244,7 @@ __device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsign
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    acc_zero(acc);
 
     const int lrow = lane >> 5, lcol = lane & 31;
     auto compute = [&](int cur) {
@@ -328,15 +321,7 @@ __device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsign
     // epilogue (conv_epilogue.h): this lane's pixel of each 32-pixel sub-tile -> plane offset
     size_t pix_off[TN];
     bool pix_ok[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        long long pp = n0 + (wn * TN + j) * 32 + lcol;
-        pix_ok[j] = pp < a.P;
-        if (!pix_ok[j]) pp = a.P - 1;
-        const int n = (int)(pp / HWo);
-        const int rem = (int)(pp - (long long)n * HWo);
-        pix_off[j] = (size_t)n * a.Cout * HWo + rem;
-    }
+    pix_linear<TN>(pix_off, pix_ok, n0 + wn * TN * 32 + lcol, a.P, HWo, a.Cout);
     conv_epilogue<TM, TN, WS>(acc, s_scale, s_shift, a.res, a.out, a.act, a.Cout, (size_t)HWo, m0, wm, lrow, pix_off, pix_ok,
                               m0 + BM <= a.Cout);
 #ifdef RFX_TRACE

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
+#include "conv_tile.h"
 #include "group.h"
 
 namespace {
@@ -61,11 +62,10 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
     const int nwg = a.tilesM * a.tilesP;
     const int nk = a.Cin / BK;                   // >= 2 (launch precondition)
 
-    // tile v -> (m0, n0): XCD-aware bijective remap, m-tile fastest (the workgroups that share one pixel tile sit on one L2;
-    // gridDim.x is a multiple of 8, so v % 8 is the XCD of this workgroup for every tile it walks)
+    // tile v -> (m0, n0), m-tile fastest (the workgroups that share one pixel tile sit on one L2; gridDim.x is a multiple of 8, so
+    // v % 8 is the XCD of this workgroup for every tile it walks)
     auto tile_origin = [&](int v, int& m0, long long& n0) {
-        const int q = nwg / 8, r = nwg % 8, xcd = v % 8, j = v / 8;
-        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+        const int bid = xcd_remap((unsigned)v, nwg);
         m0 = (bid % a.tilesM) * BM;
         n0 = (long long)(bid / a.tilesM) * BN;
     };
@@ -92,13 +92,7 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
         if (VEC) *reinterpret_cast<f32x4*>(&Bs[buf][brow + 8 * j][bcol]) = rv[j];
         else     Bs[buf][brow + 2 * j][bcol] = rb[j];
     };
-    auto put_scale = [&](int slot, int m0) {
-        if (t < BM) {
-            const int m = m0 + t;
-            s_scale[slot][t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
-            s_shift[slot][t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
-        }
-    };
+    auto put_scale = [&](int slot, int m0) { stage_bn<BM>(s_scale[slot], s_shift[slot], a.scale, a.shift, m0, a.Cout); };
 
     int v = (int)bx;
     int m0; long long n0;
@@ -135,15 +129,8 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
 
         f32x16 acc[TM][2];
         f32x16 tot[TM][2];                                    // only live in the KCH > 0 instances
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[i][j][r] = 0.0f;
-                    if constexpr (KCH > 0) tot[i][j][r] = 0.0f;
-                }
+        acc_zero(acc);
+        if constexpr (KCH > 0) acc_zero(tot);
 
         for (int s = 0; s < nk; ++s, ++g) {
             const int cur = g & 1;
@@ -197,14 +184,7 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (KCH > 0) {
-                if ((s + 1) % KCH == 0 || s + 1 == nk) {      // wave-uniform: close the chunk
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
-                }
+                if ((s + 1) % KCH == 0 || s + 1 == nk) acc_close_chunk(tot, acc);      // wave-uniform
             }
             __syncthreads();   // step s+1 is complete in the other buffer; everyone is done reading this one
         }
@@ -213,14 +193,7 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
         {
             size_t pix_off[2];
             bool pix_ok[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                long long pp = n0 + wn * 64 + j * 32 + lcol;
-                pix_ok[j] = pp < a.P;
-                if (!pix_ok[j]) pp = a.P - 1;
-                const long long n = pp / a.HW;
-                pix_off[j] = (size_t)n * a.Cout * HW + (size_t)(pp - n * a.HW);
-            }
+            pix_linear<2>(pix_off, pix_ok, n0 + wn * 64 + lcol, a.P, a.HW, a.Cout);
             conv_epilogue<TM, 2, false>(KCH > 0 ? tot : acc, s_scale[it & 1], s_shift[it & 1], a.res, a.out, a.act, a.Cout, HW, m0, wm, lrow,
                                         pix_off, pix_ok, m0 + BM <= a.Cout);
         }

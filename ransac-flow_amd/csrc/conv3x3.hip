@@ -23,8 +23,8 @@
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_epilogue.h"
+#include "conv_tile.h"
 #include "group.h"
-#include <type_traits>
 
 namespace {
 
@@ -63,22 +63,34 @@ struct C3Args {
     long long* trace;
 #endif
 };
-// 1: the fused tail drains the epilogue of expansion pass p inside the K loop of pass p + 1 (round 5, VERDICT r4 #6: "the one structural
-// conv idea still on the table"); 0 (default): the burst form.  MEASURED NEGATIVE on one box, same library otherwise
-// (profiles/r05_conv_ab.jsonl, 128 / 64 images): 64-channel tail 101.4 -> 98.2 TFLOP/s at 120x160, 101.9 -> 98.4 at 240x320, 86.8 -> 82.4 at
-// 100x132; 128-channel tail 110.0 -> 111.2 at 60x80, 86.7 -> 90.3 at 50x66 (four passes: three hidden epilogues).  The residual loads and
-// the stores of a piece share the CU's in-order vector-memory path with the expansion's weight stream (2 x 16 bytes per lane and quad
-// step from L2): spread over the K loop they delay the weights the next MFMAs wait for, which costs the 2-pass tail more than the one
-// hidden epilogue saves.  Kept as a build flag (make exp NAME=inter SRC=conv3x3 DEFS=-DRFX_C3F_INTERLEAVE=1); bit-identical either way.
-#ifndef RFX_C3F_INTERLEAVE
-#define RFX_C3F_INTERLEAVE 0
-#endif
 #ifdef RFX_TRACE
 #define RFX_STAMP(i) do { if (threadIdx.x == 0 && a.trace) a.trace[(size_t)blockIdx.x * 4 + (i)] = wall_clock64(); } while (0)
 extern "C" long long* rfx_debug_trace_ptr();
 #else
 #define RFX_STAMP(i)
 #endif
+
+// Staging roles of the packed weights wP (rfx_api.h): the image of a (128-channel tile, K step) is two parity planes of 128 rows x 36
+// k-pairs; a workgroup's share is A_F4 consecutive float4 (TM = 2: the whole 36 KB image; TM = 1: the rows of its 64-channel half
+// inside both planes); thread t copies float4 t, t + 256, ... (TM = 1: the 128 surplus slots of the last round re-copy float4
+// 0..127 -- same value to the same place).  The bodies keep the per-thread tables; the helpers return one entry (filling the
+// tables through array references costs the 32x4-patch instances a register or two).
+template <int TM>
+struct WpStage {
+    static constexpr int A_F4 = 2 * 64 * TM * KK / 4, NA = (A_F4 + 255) / 256;     // 2304 / 1152 float4, 9 / 5 per thread
+    static constexpr int PLANE_B = 128 * KK * 4;                                    // bytes of one parity plane of a packed image
+    static constexpr size_t STEP_B = (size_t)2 * PLANE_B;                           // bytes per (tile, step)
+    static __device__ __forceinline__ int lds_f4(int t, int j) {          // float4 index inside As of thread t's j-th copy
+        const int L = t + 256 * j;
+        return L >= A_F4 ? L - A_F4 : L;
+    }
+    static __device__ __forceinline__ unsigned src_off(int L) {           // its byte offset inside the packed image of a step
+        return TM == 2 ? (unsigned)(L * 16) : (unsigned)((L / (A_F4 / 2)) * PLANE_B + (L % (A_F4 / 2)) * 16);
+    }
+    static __device__ __forceinline__ const char* tile(const float* wP, int m0, int nsteps) {      // this tile's image of step 0
+        return reinterpret_cast<const char*>(wP) + (size_t)(m0 / 128) * nsteps * STEP_B + (TM == 1 ? ((m0 >> 6) & 1) * (PLANE_B / 2) : 0);
+    }
+};
 
 // FUSE = true: the workgroup's tile holds ALL channels of the 3x3 convolution (Cout == 64*TM); instead of going to HBM
 // the tile (after bn + ReLU) becomes, in LDS, the B operand of the 1x1 expansion that follows it in a Bottleneck, and
@@ -121,14 +133,9 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
     const int wm = wave >> 1, wn = wave & 1;
     const int lrow = lane >> 5, lcol = lane & 31;
 
-    const int tilesP = a.tilesH * a.tilesW;     // tilesH counts patch rows of the whole stack
-    const int nwg = a.tilesM * tilesP;
-    int bid = (int)bx;
     RFX_STAMP(0);
-    {   // XCD-aware bijective remap, m-tile fastest: the workgroups sharing one input patch sit on one L2
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    // m-tile fastest: the workgroups sharing one input patch sit on one L2 (tilesH counts patch rows of the whole stack)
+    const int bid = xcd_remap(bx, a.tilesM * a.tilesH * a.tilesW);
     const int m0 = (bid % a.tilesM) * BM;
     const int pt = bid / a.tilesM;
     const int R0 = (pt / a.tilesW) * PT_R, ow0 = (pt % a.tilesW) * PT_C;    // first stack row / column of the patch
@@ -137,36 +144,22 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
     const int nbase = (R0 > 0 ? R0 - 1 : 0) / Hs;                            // image of the first input row of the patch
     const float* inn = a.in + (size_t)nbase * a.Cin * HW;                    // 32-bit patch offsets are relative to it
 
-    if (t < BM) {
-        const int m = m0 + t;
-        s_scale[t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
-        s_shift[t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
-    }
+    stage_bn<BM>(s_scale, s_shift, a.scale, a.shift, m0, a.Cout);
 
     // ---- staging roles ----
-    // weights: the packed image of this tile and step is A_F4 consecutive float4 (TM = 2: the whole 36 KB image;
-    // TM = 1: the rows of this 64-channel half inside both parity planes); thread t copies float4 t, t+256, ...
-    // (TM = 1: the 128 surplus slots of the last round re-copy float4 0..127 -- same value to the same place).
-    constexpr int A_F4 = 2 * BM * KK / 4, NA = (A_F4 + 255) / 256;     // 2304 / 1152 float4, 9 / 5 per thread
-    constexpr int PLANE_B = 128 * KK * 4;                              // bytes of one parity plane of a packed image
+    constexpr int NA = WpStage<TM>::NA;
+    constexpr size_t step_b = WpStage<TM>::STEP_B;
     unsigned aoff[NA];    // byte offset inside the packed image of a step
     int alds[NA];         // float4 index inside As
 #pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        int L = t + 256 * j;
-        if (L >= A_F4) L -= A_F4;
-        alds[j] = L;
-        aoff[j] = TM == 2 ? (unsigned)(L * 16) : (unsigned)((L / (A_F4 / 2)) * PLANE_B + (L % (A_F4 / 2)) * 16);
-    }
-    const size_t step_b = (size_t)2 * PLANE_B;                         // bytes per (tile, step)
+    for (int j = 0; j < NA; ++j) { alds[j] = WpStage<TM>::lds_f4(t, j); aoff[j] = WpStage<TM>::src_off(alds[j]); }
     // Cin need not be a multiple of CH (the 49-channel correlation volume in front of the heads, model/model.py:213): the
     // packed weights carry zero rows for the missing channels of the last K step, and the patch slots of those channels are
     // zero filled (their loads point at the first channel of the step: a valid address) -- the sum gains exact zeros only.
     const int nsteps = (a.Cin + CH - 1) / CH;
     const int crem = a.Cin - (nsteps - 1) * CH;                        // channels of the last K step
     const bool ragged = RAG && crem != CH;                             // RAG: its own kernel instance (the host picks it when Cin % 8 != 0)
-    const char* wtile = reinterpret_cast<const char*>(a.wT) + (size_t)(m0 / 128) * nsteps * step_b +
-                        (TM == 1 ? ((m0 >> 6) & 1) * (PLANE_B / 2) : 0);
+    const char* wtile = WpStage<TM>::tile(a.wT, m0, nsteps);
     // input patch: NB of the CH*PR*PC (1440 or 1632) patch elements per thread (the surplus slots land in the unused
     // columns of the last patch row, so that every load is consumed unconditionally: no divergent store).
     unsigned boffB[NB];   // byte offset inside one channel group (cl*HW + gy*W + gx)*4; 0 with bok=false -> zero
@@ -228,22 +221,10 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    acc_zero(acc);
 
     f32x16 tot[KCH ? TM : 1][KCH ? TN : 1];
-    if constexpr (KCH > 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.0f;
-    }
+    if constexpr (KCH > 0) acc_zero(tot);
     load_global(0, ragged && nsteps == 1);
     store_lds(ragged && nsteps == 1);
     __syncthreads();
@@ -286,14 +267,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (KCH > 0) {
-            if ((s + 1) % KCH == 0 || s + 1 == nsteps) {      // wave-uniform: close the chunk
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
-            }
+            if ((s + 1) % KCH == 0 || s + 1 == nsteps) acc_close_chunk(tot, acc);      // wave-uniform
         }
         __syncthreads();   // everyone is done reading the tile
         store_lds(lastn);   // tile s+1
@@ -341,25 +315,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
         // The weights come in "quad" order wQ[q][lrow][m][4] = W3[m][8q + 2j + lrow] (j = 0..3): the four A operands a lane
         // needs for k-pairs 4q..4q+3 are ONE 16-byte load, and consecutive lanes (channels) read consecutive 16 bytes.
         // (a 256-pixel patch runs the expansion over its two 128-pixel halves one after the other: sub-tiles ph*4 + wn*2 + j)
-        //
-        // Round 5, INTERLEAVED EPILOGUE: a pass ends with 64 outputs per lane that each cost a residual load, a
-        // fused multiply-add, an add, a max and a store -- 64 KB in + 64 KB out per pass and workgroup, issued as ONE burst
-        // during which this workgroup's share of the matrix pipe idles (~10 us of a 15 us pass, scripts/dbg/fused_trace.py).
-        // Here the finished accumulators of pass p stay in registers (`prev`) and are drained during the K loop of pass p + 1, a
-        // PV-value piece per 16-MFMA quad step: the piece's residual loads are issued one step ahead (double buffer), its
-        // arithmetic and stores run in the shadow of the step's MFMAs.  Only the LAST pass's epilogue is still exposed.  Same
-        // operations per element in the same order: bit-identical.  Taken when the tail has a residual and a ReLU (every
-        // Bottleneck of the trunk) and its folded bn3 vectors fit the 2 x 512-float LDS image; RFX_C3F_INTERLEAVE=0 (build
-        // flag) keeps round 4's burst form for A/B timing.
         constexpr int NQ = BM / 8, AHEAD = 2;
-        constexpr int PV = 64 / NQ;                                // outputs of the previous pass finished per quad step
-        static_assert(16 % PV == 0, "a piece stays inside one 32x32 sub-tile");
-        __shared__ float s_bn3[RFX_C3F_INTERLEAVE ? 1024 : 2];
-        const bool inter = RFX_C3F_INTERLEAVE && a.Cexp <= 512 && a.Cexp >= 256 && a.res != nullptr && a.act3 == RFX_ACT_RELU;
-        if (inter) {
-            for (int i = t; i < a.Cexp; i += 256) { s_bn3[i] = a.scale3[i]; s_bn3[512 + i] = a.shift3[i]; }
-            __syncthreads();
-        }
 #pragma unroll 1
         for (int ph = 0; ph < TN / 2; ++ph) {
         size_t pix_off[2];
@@ -367,42 +323,10 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
 #pragma unroll
         for (int j = 0; j < 2; ++j) pixel_of(ph * 4 + wn * 2 + j, pix_off[j], pix_ok[j]);
         const float* t2col = T2 + lrow * NPX + ph * 128 + wn * 64 + lcol;    // + 2kk*NPX (+ 32 for the second sub-tile)
-        f32x16 prev[2][2];
-        float rres[2][PV];
-        // element offset of output v (= sub-tile s = v >> 4 [i = s >> 1, j = s & 1], accumulator register r = v & 15) of the pass at mp
-        auto out_off = [&](int v, int mp) {
-            const int s_ = v >> 4, r = v & 15;
-            return pix_off[s_ & 1] + (size_t)(mp + (wm * 2 + (s_ >> 1)) * 32 + 4 * lrow + (r & 3) + 8 * (r >> 2)) * HW;
-        };
-        auto piece_loads = [&](int piece, int slot, int pmp) {
-#pragma unroll
-            for (int u = 0; u < PV; ++u) rres[slot][u] = a.res[out_off(piece * PV + u, pmp)];
-        };
-        auto piece_finish = [&](int piece, int slot, int pmp) {
-            float x[PV];
-#pragma unroll
-            for (int u = 0; u < PV; ++u) {
-                const int v = piece * PV + u, s_ = v >> 4, r = v & 15;
-                const int ch = pmp + (wm * 2 + (s_ >> 1)) * 32 + 4 * lrow + (r & 3) + 8 * (r >> 2);
-                x[u] = fmaf(prev[s_ >> 1][s_ & 1][r], s_bn3[ch], s_bn3[512 + ch]);
-                x[u] += rres[slot][u];
-                x[u] = x[u] > 0.0f ? x[u] : 0.0f;
-            }
-            if (pix_ok[((piece * PV) >> 4) & 1]) {
-#pragma unroll
-                for (int u = 0; u < PV; ++u) a.out[out_off(piece * PV + u, pmp)] = x[u];
-            }
-        };
-        // one pass: K loop over the mid tile; HAVE_PREV: the previous pass (at pmp) is drained piece by piece inside it
-        auto run_pass = [&](auto have_prev, int mp, int pmp, f32x16 (&acc2)[2][2]) {
-            constexpr bool HP = decltype(have_prev)::value;
+        // one pass: K loop over the mid tile
+        auto run_pass = [&](int mp, f32x16 (&acc2)[2][2]) {
             const f32x4* wq0 = reinterpret_cast<const f32x4*>(a.wT3) + (size_t)lrow * a.Cexp + mp + wm * 64 + lcol;   // + q*2*Cexp (+ 32)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc2[i][j][r] = 0.0f;
+            acc_zero(acc2);
             // L2 -> registers, two quads (8 k-pairs = 32 MFMAs) ahead of use
             // (measured, round 3, profiles/r03_fused_tail_expansion_experiment.jsonl + r03_fused_tail_late_prefetch.jsonl: 4 quads
             // ahead +-0; the pass's residual values fetched in front of this loop -6 % (vmcnt retires in order: the loop's weight
@@ -425,12 +349,10 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
 #pragma unroll
             for (int q = 0; q < AHEAD && q < NQ; ++q) load_w(q, q);
             read_b(0, 0);
-            if constexpr (HP) piece_loads(0, 0, pmp);
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 if (q + AHEAD < NQ) load_w(q + AHEAD, (q + AHEAD) % (AHEAD + 1));
                 if (q + 1 < NQ) read_b(q + 1, (q + 1) & 1);
-                if constexpr (HP) { if (q + 1 < NQ) piece_loads(q + 1, (q + 1) & 1, pmp); }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -442,30 +364,14 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
                     acc2[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1, b1, acc2[1][1], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (HP) piece_finish(q, q & 1, pmp);     // VALU + stores of the piece: issued behind the step's MFMAs
             }
         };
-        if (inter) {
+        for (int mp = 0; mp < a.Cexp; mp += 128) {
             f32x16 acc2[2][2];
-            run_pass(std::false_type{}, 0, 0, acc2);
-            for (int mp = 128; mp < a.Cexp; mp += 128) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) prev[i][j] = acc2[i][j];
-                run_pass(std::true_type{}, mp, mp - 128, acc2);
-            }
-            // the last pass's epilogue is the only exposed one
-            const int lp = a.Cexp - 128;
-            conv_epilogue<2, 2, false>(acc2, a.scale3 + lp, a.shift3 + lp, a.res, a.out, a.act3, a.Cexp, HW, lp, wm, lrow, pix_off, pix_ok, true);
-        } else {
-            for (int mp = 0; mp < a.Cexp; mp += 128) {
-                f32x16 acc2[2][2];
-                run_pass(std::false_type{}, mp, 0, acc2);
-                // scale3 / shift3 are read straight from global memory (L1 hits): conv_epilogue only indexes the pointers
-                conv_epilogue<2, 2, false>(acc2, a.scale3 + mp, a.shift3 + mp, a.res, a.out, a.act3, a.Cexp, HW, mp, wm, lrow, pix_off,
-                                           pix_ok, true);
-            }
+            run_pass(mp, acc2);
+            // scale3 / shift3 are read straight from global memory (L1 hits): conv_epilogue only indexes the pointers
+            conv_epilogue<2, 2, false>(acc2, a.scale3 + mp, a.shift3 + mp, a.res, a.out, a.act3, a.Cexp, HW, mp, wm, lrow, pix_off,
+                                       pix_ok, true);
         }
         }   // pixel halves
     }
@@ -529,12 +435,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned 
     const int lrow = lane >> 5, lcol = lane & 31;
     const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
     const int tilesP = a.tilesH * a.tilesW;           // patches per image
-    const int nwg = a.tilesM * tilesP * a.N;
-    int bid = (int)bx;
-    {   // XCD-aware bijective remap, m-tile fastest
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(bx, a.tilesM * tilesP * a.N);      // m-tile fastest
     const int m0 = (bid % a.tilesM) * BM;
     int pt = bid / a.tilesM;
     const int n = pt / tilesP;
@@ -543,27 +444,16 @@ __device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned 
     const size_t HW = (size_t)a.H * a.W, HWo = (size_t)Ho * Wo;
     const float* inn = a.in + (size_t)n * a.Cin * HW;
 
-    if (t < BM) {
-        const int m = m0 + t;
-        s_scale[t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
-        s_shift[t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
-    }
-    // ---- staging roles: weights exactly as in conv3x3_direct_body
-    constexpr int A_F4 = 2 * BM * KK / 4, NA = (A_F4 + 255) / 256;
-    constexpr int PLANE_B = 128 * KK * 4;
-    unsigned aoff[NA];
-    int alds[NA];
+    stage_bn<BM>(s_scale, s_shift, a.scale, a.shift, m0, a.Cout);
+    // ---- staging roles
+    constexpr int NA = WpStage<TM>::NA;
+    constexpr size_t step_b = WpStage<TM>::STEP_B;
+    unsigned aoff[NA];    // byte offset inside the packed image of a step
+    int alds[NA];         // float4 index inside As
 #pragma unroll
-    for (int j = 0; j < NA; ++j) {
-        int L = t + 256 * j;
-        if (L >= A_F4) L -= A_F4;
-        alds[j] = L;
-        aoff[j] = TM == 2 ? (unsigned)(L * 16) : (unsigned)((L / (A_F4 / 2)) * PLANE_B + (L % (A_F4 / 2)) * 16);
-    }
-    const size_t step_b = (size_t)2 * PLANE_B;
+    for (int j = 0; j < NA; ++j) { alds[j] = WpStage<TM>::lds_f4(t, j); aoff[j] = WpStage<TM>::src_off(alds[j]); }
     const int nsteps = a.Cin / CH;
-    const char* wtile = reinterpret_cast<const char*>(a.wT) + (size_t)(m0 / 128) * nsteps * step_b +
-                        (TM == 1 ? ((m0 >> 6) & 1) * (PLANE_B / 2) : 0);
+    const char* wtile = WpStage<TM>::tile(a.wT, m0, nsteps);
     // input patch = 136 rows (R = channel * 17 + patch row) x 33 columns per K step.  Thread t stages column px = t & 31 of
     // the rows R = (t >> 5) + 8 u, u = 0..16 (8 x 17 = 136 exactly) and, for t < 136, column 32 of row t -- 18 loads, and NO
     // per-element address tables: the LDS word of (R, px) is R * BS2 + f(px), affine in u (an immediate of the store), and the
@@ -638,21 +528,9 @@ __device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned 
         else return pixb_cur + koff2(2 * kk) + lrow * (koff2(2 * kk + 1) - koff2(2 * kk));
     };
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    acc_zero(acc);
     f32x16 tot[KCH ? TM : 1][KCH ? TN : 1];
-    if constexpr (KCH > 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.0f;
-    }
+    if constexpr (KCH > 0) acc_zero(tot);
     {
         const char* base = reinterpret_cast<const char*>(inn);
 #pragma unroll
@@ -694,14 +572,7 @@ __device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned 
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (KCH > 0) {
-            if ((s + 1) % KCH == 0 || s + 1 == nsteps) {      // wave-uniform: close the chunk
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
-            }
+            if ((s + 1) % KCH == 0 || s + 1 == nsteps) acc_close_chunk(tot, acc);      // wave-uniform
         }
         __syncthreads();
         store_lds();

@@ -1,5 +1,5 @@
 // conv3x3s.hip -- 3x3 / pad 1 convolutions, stride 1 and (second half of the file) stride 2 (+ folded BatchNorm, residual, ReLU) with
-// float32 results on the bf16 matrix cores by EXACT operand splitting -- the scheme of conv1x1s.hip (read its header first) applied to
+// float32 results on the bf16 matrix cores by EXACT operand splitting -- the scheme of conv_split.h (read its header first) applied to
 // the heaviest layer class of the path: ResNet-50 conv2 of every Bottleneck (model/resnet50.py:75), every BasicBlock convolution of the
 // FeatureExtractor (model/model.py:32-35), conv1 / conv2 / conv3 of the NetFlowCoarse / NetMatchability stacks (model/model.py:170-181;
 // the 49-channel conv1 through a zero-padded 64-channel copy of its input, rfx/ops.py).
@@ -12,21 +12,26 @@
 // at a per-lane base + a compile-time tap offset.  The weights of a (channel block, tap) stage come split and packed from the host
 // (rfx_api.h: "wS3"), 12 KB per stage, global -> LDS by global_load_lds into a double-buffered image (no staging registers; an explicit
 // vmcnt in front of the stage's ONE barrier publishes it); a stage = 6 MFMAs per 32 x 32 tile (hi*hi in its
-// own accumulator, the five small terms in a second one: conv1x1s.hip).  k order: channel block, tap, 16 channels -- irrelevant for
+// own accumulator, the five small terms in a second one: conv_split.h).  k order: channel block, tap, 16 channels -- irrelevant for
 // the result's quality (every product exact, 16 products per rounding), different from the fp32 kernels' channel-major order.
 // The images of a batch are tiled as ONE tall map with a virtual zero row between images (as conv3x3.hip): only the last patch row
 // of the whole batch is ragged; outputs on a virtual row are dropped.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_split.h"
+#include "conv_tile.h"
 #include "group.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// Shared with the other conv units (conv_tile.h, conv_split.h): the tile remap, the accumulator helpers, the split primitives, BN
+// staging and the register-staged weight roles of the stride-1 body.  This file's own copies of the stacked-rows pixel offsets, of
+// the 8-float split loop (split_word in conv_split.h is conv1x1s.hip's) and of the DMA weight roles, in both bodies, and the BN
+// staging of the stride-2 body are written out on purpose: through a helper the compiler lays the activation-staging blocks of
+// these kernels out of line and pairs the split's subtractions (v_pk_add_f32).  With all of them as helpers, 14 of the 15 3x3 shapes
+// of scripts/ubench/split_bench.py ran 0.6 - 2 % slower, 6 of them beyond the parent's spread and one more on its boundary
+// (profiles/conv_helpers_ab.json).
 
 // Patch geometry.  WM = wavefronts along the channels: 2 -> 128 channels x (8 x 16) pixels per workgroup; 1 (Cout <= 64) -> 64 channels x
 // (16 x 16) pixels, the four wavefronts along the rows: every wavefront keeps 2 x 2 MFMA tiles (24 MFMAs per stage) and the weight image of
@@ -43,28 +48,6 @@ struct C3SArgs {
     int N, Cin, H, W, Cout, act, Mpad;
     int tilesM, tilesW, tilesS;     // channel tiles, column tiles, row tiles of the N * (H + 1) - 1 row stack
 };
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    const bf16x2 h = __builtin_convertvector(v, bf16x2);
-    unsigned u;
-    __builtin_memcpy(&u, &h, 4);
-    return u;
-}
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-    hi = pack_bf16(a, b);
-    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);            // exact
-    mid = pack_bf16(ra, rb);
-    lo = pack_bf16(ra - __uint_as_float(mid << 16), rb - __uint_as_float(mid & 0xffff0000u));
-}
-__device__ __forceinline__ bf16x8 as_frag(const u32x4& w) {
-    bf16x8 f;
-    __builtin_memcpy(&f, &w, 16);
-    return f;
-}
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // ADMA: the weight image of a stage goes global -> LDS by global_load_lds (no registers, no ds_write, and no wait for it in front of the
 // stage's MFMAs: the wait (vmcnt(0)) sits in front of the barrier that publishes the image).
@@ -101,21 +84,15 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
     const int nk = a.Cin / 16;
     const int Hs = a.H + 1;                             // rows per image in the stack (the last one virtual)
 
-    int m0, row0, col0;
-    {
-        const int v = (int)bx, q = nwg / 8, r = nwg % 8, xcd = v % 8, j = v / 8;
-        int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-        m0 = (bid % a.tilesM) * BM; bid /= a.tilesM;
-        col0 = (bid % a.tilesW) * PT_C;
-        row0 = (bid / a.tilesW) * PT_R;
-    }
-    // A staging: words t + 256 j of the stage image [piece][h][BM] <- wS[(kb * 9 + tap)][piece][h][m0 + m]; 256 words = 2 (TM = 2) or
-    // 4 (TM = 1) [piece][h] rows: word t + 256 j sits (256 / BM) * j rows below word t
+    int bid = xcd_remap(bx, nwg);
+    const int m0 = (bid % a.tilesM) * BM; bid /= a.tilesM;
+    const int col0 = (bid % a.tilesW) * PT_C, row0 = (bid / a.tilesW) * PT_R;
+    // A staging: the stage image of q = kb * 9 + tap, words t + 256 j <- wS[q][piece][h][m0 + m]; 256 words = A_ROWS [piece][h] rows.
+    // Through registers (ADMA = false): SplitWeights; the DMA form below shares its source pointer
     constexpr int A_ROWS = 256 / BM;
-    const u32x4* wsrc = a.wS + (size_t)(t / BM) * a.Mpad + m0 + t % BM;              // + q * 6 * Mpad + A_ROWS * j * Mpad
-    // piece j of a thread exists for every thread (compile time) or for the first wavefronts only (TM = 1: 384 words): no per-lane
-    // branches around the loads -- a divergent region makes the compiler drain the vector-memory counter between two loads
-    auto a_on = [&](int j) { return (j + 1) * 256 <= A_WORDS || t + 256 * j < A_WORDS; };
+    SplitWeights<BM, 256> wa;
+    wa.init(a.wS, a.Mpad, m0);
+    const u32x4* wsrc = wa.src;                                                      // + q * 6 * Mpad + A_ROWS * j * Mpad
     // B staging: item it = t (+ 256): h = it / 180, patch pixel it % 180 -> 8 channels of one input pixel (or zeros)
     const float* bsrc[NBI];
     bool b_ok[NBI], b_on[NBI];
@@ -132,18 +109,9 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
         bsrc[u] = b_ok[u] ? a.in + ((size_t)n * a.Cin + 8 * h) * HW + (size_t)y * a.W + x : a.in;   // + kb * 16 * HW + i * HW
         b_word[u] = h * PP + pp;
     }
-    u32x4 ra[NA];
     float rb[8];                                        // one staging item at a time: item 0 and item 1 of a block share the registers
-    auto load_a = [&](int q) {
-#pragma unroll
-        for (int j = 0; j < NA; ++j)
-            ra[j] = wsrc[((size_t)q * 6 + (a_on(j) ? A_ROWS * j : 0)) * a.Mpad];              // off lanes: any valid word
-    };
-    auto store_a = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NA; ++j)
-            if (a_on(j)) (&As[buf][0][0][0])[t + 256 * j] = ra[j];
-    };
+    auto load_a = [&](int q) { wa.load(q, a.Mpad); };
+    auto store_a = [&](int buf) { wa.store(&As[buf][0][0][0]); };
     auto dma_a = [&](int q, int buf) {                  // piece j of this wavefront: words 256 j + 64 wave .. + 63 of the stage image
 #pragma unroll
         for (int j = 0; j < NA; ++j)
@@ -169,11 +137,7 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
         dst[2 * PP] = mid;
         dst[4 * PP] = lo;
     };
-    if (t < BM) {
-        const int m = m0 + t;
-        s_scale[t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
-        s_shift[t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
-    }
+    stage_bn<BM>(s_scale, s_shift, a.scale, a.shift, m0, a.Cout);
     if (ADMA) dma_a(0, 0);
     else { load_a(0); store_a(0); }
 #pragma unroll
@@ -184,12 +148,8 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
     __syncthreads();
 
     f32x16 acc[TM][2], low[TM][2];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.0f; low[i][j][r] = 0.0f; }
+    acc_zero(acc);
+    acc_zero(low);
 
     // per-lane fragment bases (16-byte words): A row, B patch pixel of output (4 wn + 2 j + lcol / 16, lcol % 16) at tap (0, 0)
     const int a_base = lrow * BM + wm * TM * 32 + lcol;
@@ -320,12 +280,7 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] += low[i][j][r];
+    acc_add(acc, low);
 
     size_t pix_off[2];
     bool pix_ok[2];
@@ -410,14 +365,9 @@ __device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const u
     const int nk = a.Cin / 16;
     const int Hs = a.Ho + 1, Hin = 2 * Hs;              // output / input rows per image in the stacks
 
-    int m0, row0, col0;
-    {
-        const int v = (int)bx, q = nwg / 8, r = nwg % 8, xcd = v % 8, j = v / 8;
-        int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-        m0 = (bid % a.tilesM) * BM; bid /= a.tilesM;
-        col0 = (bid % a.tilesW) * 16;
-        row0 = (bid / a.tilesW) * 8;
-    }
+    int bid = xcd_remap(bx, nwg);
+    const int m0 = (bid % a.tilesM) * BM; bid /= a.tilesM;
+    const int col0 = (bid % a.tilesW) * 16, row0 = (bid / a.tilesW) * 8;
     const u32x4* wsrc = a.wS + (size_t)(t / BM) * a.Mpad + m0 + t % BM;              // + (q * 6 + 2 j) * Mpad
     const float* bsrc[S2_NBI];
     bool b_ok[S2_NBI];
@@ -467,7 +417,7 @@ __device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const u
         for (int i = 0; i < 8; ++i) r4[i] = bsrc[4][((size_t)kb * 16 + i) * HW];
         put(r4, 4);
     };
-    if (t < BM) {
+    if (t < BM) {      // written out: through stage_bn (conv_tile.h) this kernel's staging blocks are laid out differently
         const int m = m0 + t;
         s_scale[t] = (a.scale && m < a.Cout) ? a.scale[m] : 1.0f;
         s_shift[t] = (a.shift && m < a.Cout) ? a.shift[m] : 0.0f;
@@ -475,12 +425,8 @@ __device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const u
     dma_a(0, 0);                                        // lands before the first block's staging barrier (vmcnt(0) below)
 
     f32x16 acc[TM][2], low[TM][2];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.0f; low[i][j][r] = 0.0f; }
+    acc_zero(acc);
+    acc_zero(low);
 
     const int a_base = lrow * BM + wm * TM * 32 + lcol;
     int b_base[2];
@@ -544,12 +490,7 @@ __device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const u
             __syncthreads();
         }
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] += low[i][j][r];
+    acc_add(acc, low);
 
     size_t pix_off[2];
     bool pix_ok[2];
@@ -581,9 +522,7 @@ static int c3s2_group_launch(const void* blob, const unsigned* gx, int n, hipStr
 
 extern "C" int rfx_conv3x3_split_f32(const float* in, const void* wS3, const float* scale, const float* shift, const float* residual,
                                      float* out, int N, int Cin, int H, int W, int Cout, int act, void* stream) {
-    if (!in || !wS3 || !out || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return RFX_E_ARG;
-    if (Cin % 16 != 0) return RFX_E_ARG;
-    if (act != RFX_ACT_NONE && act != RFX_ACT_RELU && act != RFX_ACT_SIGMOID) return RFX_E_ARG;
+    if (const int rc = conv_check_common(in, wS3, out, N, Cin, H, W, Cout, act)) return rc;
     if ((long long)N * (H + 1) > 0x7fffffffLL) return RFX_E_LIMIT;
     C3SArgs a;
     a.in = in; a.wS = reinterpret_cast<const u32x4*>(wS3); a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
@@ -593,9 +532,7 @@ extern "C" int rfx_conv3x3_split_f32(const float* in, const void* wS3, const flo
 
 extern "C" int rfx_conv3x3_split_s2_f32(const float* in, const void* wS3, const float* scale, const float* shift, const float* residual,
                                         float* out, int N, int Cin, int H, int W, int Cout, int act, void* stream) {
-    if (!in || !wS3 || !out || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return RFX_E_ARG;
-    if (Cin % 16 != 0) return RFX_E_ARG;
-    if (act != RFX_ACT_NONE && act != RFX_ACT_RELU && act != RFX_ACT_SIGMOID) return RFX_E_ARG;
+    if (const int rc = conv_check_common(in, wS3, out, N, Cin, H, W, Cout, act)) return rc;
     C3S2Args a;
     a.in = in; a.wS = reinterpret_cast<const u32x4*>(wS3); a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1; a.Cout = Cout; a.act = act;
