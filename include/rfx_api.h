@@ -248,13 +248,11 @@ int rfx_copy_cols_f32(const float* src, float* dst, long long rows, int w_src, i
  * ------------------------------------------------------------------------------------------ */
 int rfx_corr_neigh_f32(const float* x, const float* y, float* out, int N, int C, int H, int W, int K,
                        void* stream);
-/* Same operation with the kernel configuration forced (tuning / tests / roofline decomposition; variant 0 = the
- * automatic choice of rfx_corr_neigh_f32): 1..3 = 64/32/16-row x 16-column tiles, 4 = 16 rows x 80 columns (whole
- * 480x640-pair feature-map width) plain, 5 = the tuned 16x80 kernel (3 tap groups, hand-pipelined LDS reads, balanced wave
- * map, masked DMA, equal row tiles), 6 = 5 with 2 tap groups, 7 / 8 = the tuned kernel with 48- / 64-column tiles, 9 = 32x32.  Variants 1..9 give
- * bit-identical results (channel-ordered fmaf sums).  Unknown variant -> RFX_E_ARG.  (The roofline-decomposition variants 21..24
- * -- compute / DMA / LDS reads / FMAs removed, WRONG results -- exist only in experiment builds, -DRFX_CORR_EXPERIMENTS:
- * `make exp NAME=correxp SRC=corr DEFS=-DRFX_CORR_EXPERIMENTS`; the product library rejects them.) */
+/* Same operation with the tile shape forced (tuning / tests; variant 0 = the automatic choice of rfx_corr_neigh_f32, which
+ * returns one of these six): 1 / 2 / 3 = 64 / 32 / 16-row x 16-column tiles; 5 = the tuned 16-row x 80-column kernel (whole
+ * 480x640-pair feature-map width: 3 tap groups, hand-pipelined LDS reads, balanced wave map, masked DMA, equal row tiles),
+ * 7 / 8 = the tuned kernel with 48- / 64-column tiles.  All six give bit-identical results (channel-ordered fmaf sums).
+ * Any other variant -> RFX_E_ARG. */
 int rfx_corr_neigh_variant_f32(const float* x, const float* y, float* out, int N, int C, int H, int W, int K,
                                int variant, void* stream);
 

@@ -28,7 +28,6 @@
 // Requires W % 4 == 0 for the 16-byte DMA path; other widths use the plain fallback kernel below.
 #include "common.h"
 #include <hip/hip_ext.h>
-#include <stdlib.h>
 #include <vector>
 
 namespace {
@@ -57,54 +56,42 @@ inline void corr_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, Args...
 
 constexpr int TC = 16;           // columns per wavefront
 
-// Kernel configuration: tile TR x 16*NCB, CK channels per chunk, NS-deep LDS ring, NG groups of window rows (one
-// wavefront per 16x16 block and group), PF = software-pipeline distance of the LDS reads in (channel, window row)
-// steps (0 = compiler-scheduled reads), SB: sched_barrier pinning of the step order, OPT: bit set of BAL / ZM / XPAD / PRIO below.
-template <int TR_, int NCB_, int CK_, int NS_, int NG_ = 2, int PF_ = 0, int SB_ = 0, int OPT_ = 0>
+// Kernel configuration: tile TR x 16*NCB columns, in one of two families (each with and without the BIDIR epilogue):
+//   plain: 2 groups of window rows (4+3; 3 waves / SIMD, 168 VGPRs), ring of 3, compiler-scheduled LDS reads, out-of-image lanes
+//          fetch the 16-byte zero block, full TR-row tiles;
+//   TUNED: 3 groups (3+2+2; 4 waves / SIMD, 128 VGPRs), ring of 4, LDS reads hand-pipelined one (channel, window row) step ahead
+//          (corr7_steps), halo / padding slots zeroed ONCE with the DMA lanes that would fetch zeros masked off, x rows padded to
+//          the y row stride (conflict-free ds_read_b128 of x), s_setprio 1 for the waves of the 3-row group, H split into equal
+//          row tiles, and at NCB == 5 the SIMD-balanced wave map below.
+template <int TR_, int NCB_, bool TUNED_, bool BIDIR_>
 struct Cfg {
-    static constexpr int TR = TR_, NCB = NCB_, CK = CK_, NS = NS_, NG = NG_, PF = PF_, SB = SB_;
-    static constexpr bool BAL = OPT_ & 1;   // wave -> (block, tap group) map that equalises the FMA count per SIMD
-    static constexpr bool ZM = OPT_ & 2;    // halo / padding slots zeroed ONCE, DMA lanes that would fetch zeros masked off
-    static constexpr bool XPAD = OPT_ & 4;  // x rows padded to the y row stride (conflict-free ds_read_b128 of x)
-    static constexpr bool PRIO = OPT_ & 8;  // s_setprio 1 for the waves of the largest tap group
-    static constexpr bool BIDIR = OPT_ & 16; // also write corr(y, x): the same products at mirrored taps / shifted pixels
-    static constexpr bool LDW = OPT_ & 32;   // DMA issued only by the waves of the LIGHT tap groups (3 pieces each), none by the heavy one
-    // ROT: register-bank rotation of the accumulators.  v_fmac_f32 acc, x, y issues in ~2.3 cycles per wave64 instruction with
-    // two of its three VGPR operands in one bank (bank = register number mod 4) and in ~4.4 with all three
-    // (scripts/ubench/valu_bank.hip, profiles/r03_valu_bank.txt).  acc[d][.] / x[d] / y[d+j+1] live in even-aligned 4-register
-    // tuples, so element index = bank offset: with the plain layout acc[d], x[d] and y[d+j+1] share a bank for one tap column
-    // in seven whenever the tuples' bases agree mod 4 (they do in the compiled kernel: v_fmac_f32 v70, v90, v98).  Storing
-    // the sum of (pixel d, tap column j) in tuple element (d+j)&3 puts acc and y one element apart -- an odd bank distance
-    // that even-aligned bases cannot cancel -- so a three-way clash is impossible whatever the allocator does.
-    static constexpr bool ROT = OPT_ & 64;
+    static constexpr int TR = TR_, NCB = NCB_;
+    static constexpr bool TUNED = TUNED_;
+    static constexpr bool BIDIR = BIDIR_;   // also write corr(y, x): the same products at mirrored taps / shifted pixels
+    static constexpr int CK = 2;                               // channels per chunk
+    static constexpr int NS = TUNED ? 4 : 3;                   // LDS ring depth
+    static constexpr int NG = TUNED ? 3 : 2;                   // groups of window rows (one wavefront per 16x16 block and group)
     static constexpr int NW = TR / 16 * NCB * NG;              // waves per workgroup: strips x column blocks x tap-row groups
     static constexpr int YR = TR + 6;                          // halo rows
     static constexpr int YQ = 4 * NCB + 2;                     // float4 per halo row (cols c0-4 .. c0+16*NCB+3)
-    static constexpr int XQ = XPAD ? 4 * NCB + 2 : 4 * NCB;    // float4 slots per x row (4*NCB used)
+    static constexpr int XQ = TUNED ? 4 * NCB + 2 : 4 * NCB;   // float4 slots per x row (4*NCB used)
     static constexpr int Y_SLOTS = CK * YR * YQ;               // float4 slots of the y halo tile
     static constexpr int Y_PIECES = (Y_SLOTS + 63) / 64;
     static constexpr int X_SLOTS = CK * TR * XQ;
     static constexpr int X_PIECES = (X_SLOTS + 63) / 64;
-    // LDW: a DMA piece costs its issuing wave 100-200 cycles inside a compute phase (MI355X_MICROARCH.md), as much as ~50 of its
-    // FMAs; the wave of the 3-row tap group already has 1.5x the FMAs of the others, so the pieces are dealt to the NL waves of
-    // the 2-row groups only (3 each instead of 2 for everyone) and every wave of a SIMD's {H,L,L,L} set is busy about equally.
-    static constexpr int NL = LDW ? NW - NW / NG : NW;         // waves that issue DMA
-    static constexpr int PPW = (Y_PIECES + X_PIECES + NL - 1) / NL;   // DMA pieces per issuing wave per chunk (padded)
-    static constexpr int N_PIECES = PPW * NL;                  // incl. padding pieces (dump area, never read)
+    static constexpr int PPW = (Y_PIECES + X_PIECES + NW - 1) / NW;   // DMA pieces per wave per chunk (padded)
+    static constexpr int N_PIECES = PPW * NW;                  // incl. padding pieces (dump area, never read)
     static constexpr int BUF_SLOTS = N_PIECES * 64;
-    // window rows of group g: [row_begin(g), row_begin(g+1))  -- 2 groups: 4+3, 3 groups: 3+2+2, 4 groups: 2+2+2+1
-    static constexpr int row_begin(int g) { return NG == 2 ? (g == 0 ? 0 : g == 1 ? 4 : 7)
-                                                   : NG == 3 ? (g == 0 ? 0 : g == 1 ? 3 : g == 2 ? 5 : 7)
-                                                             : (g >= 4 ? 7 : 2 * g); }
+    // window rows of group g: [row_begin(g), row_begin(g+1))  -- 2 groups: 4+3, 3 groups: 3+2+2
+    static constexpr int row_begin(int g) { return NG == 2 ? (g == 0 ? 0 : g == 1 ? 4 : 7) : (g == 0 ? 0 : g == 1 ? 3 : g == 2 ? 5 : 7); }
     static constexpr int WAVES_PER_SIMD = NG == 2 ? 3 : 4;     // register budget: 168 / 128 VGPRs
     // wave -> (16x16 block, tap group).  The hardware deals a workgroup's waves to the 4 SIMDs cyclically (w, w+4, w+8 ..
-    // share one), and the groups are unequal (4 vs 3 window rows; 3 vs 2 vs 2), so the plain map w -> (w / NG, w % NG)
-    // can stack three 4-row waves on one SIMD (672 FMAs per chunk against an average of 490).  The balanced maps put
-    // {L,L,L} {L,L,H} {H,H} {H,H} (NG = 2, 10 waves: worst SIMD 560) or 3 x {H,L,L,L} + {H,H,L} (NG = 3, 15 waves: 504).
-    static constexpr bool BALANCED = BAL && TR == 16 && NCB == 5 && (NG == 2 || NG == 3);
+    // share one), and the groups are unequal (3 vs 2 vs 2 window rows), so the plain map w -> (w / NG, w % NG) of the 15-wave
+    // tile gives one SIMD {H,L,L,H} (560 FMAs per chunk against an average of 490); the balanced map puts 3 x {H,L,L,L} + {H,H,L}
+    // on the SIMDs (worst: 504).  The 12- and 9-wave tiles get one wave of each group per SIMD from the plain map.
+    static constexpr bool BALANCED = TUNED && NCB == 5;
     static constexpr int wave_group(int w) {
         if (!BALANCED) return w % NG;
-        if (NG == 2) return (w == 2 || w == 3 || w == 6 || w == 7 || w == 9) ? 0 : 1;
         return (w <= 3 || w == 7) ? 0 : ((w <= 6 || w == 8 || w == 9) ? 1 : 2);
     }
     static constexpr int wave_block(int w) {           // rank of w among the waves of its group
@@ -113,18 +100,9 @@ struct Cfg {
         for (int v = 0; v < w; ++v) r += wave_group(v) == wave_group(w);
         return r;
     }
-    static constexpr int loader_rank(int w) {          // rank of w among the DMA-issuing waves; -1: this wave issues none
-        if (!LDW) return w;
-        if (wave_group(w) == 0) return -1;
-        int r = 0;
-        for (int v = 0; v < w; ++v) r += wave_group(v) != 0;
-        return r;
-    }
-    static_assert(!LDW || (BAL && TR == 16 && NCB == 5 && NG == 3), "LDW is defined for the balanced 15-wave map");
-    static_assert(NG >= 2 && NG <= 4, "2..4 tap-row groups");
-    static_assert(PF >= 0 && PF <= 2, "LDS read pipeline distance 0..2 steps");
+    static_assert(!TUNED || TR == 16, "the tuned family has 16-row tiles");
     static_assert(NW * 64 <= 1024, "workgroup too large");
-    static_assert(NS >= 2 && NS <= 5 && (NS - 2) * PPW <= 15, "ring depth / vmcnt immediate out of range (wait_vm)");
+    static_assert((NS - 2) * PPW <= 15, "vmcnt immediate out of range (wait_vm)");
     static_assert((size_t)NS * BUF_SLOTS * 16 <= 160 * 1024, "LDS ring exceeds 160 KiB");
 };
 
@@ -148,37 +126,27 @@ __device__ __forceinline__ void lds_wait(f32x4& a, f32x4& b, f32x4& c, f32x4& d)
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(K));
 }
 
-// One (channel, window row) step of a chunk, ST = 0 .. CK*NI-1, recursively unrolled (the offsets must be immediates).
+// One (channel, window row) step of a chunk, ST = 0 .. CK*NI-1, recursively unrolled (the offsets must be immediates).  The reads
+// of step ST+1 are issued before the FMAs of step ST.
 template <class G, int I0, int I1, int ST>
 __device__ __forceinline__ void corr7_steps(f32x4 (&wq)[G::CK * (I1 - I0)][3], f32x4 (&xq)[G::CK], float (&acc)[4][(I1 - I0) * 7],
                                             unsigned ya, unsigned xa) {
-    constexpr int NI = I1 - I0, NSTEP = G::CK * NI, PF = G::PF;
+    constexpr int NI = I1 - I0, NSTEP = G::CK * NI;
     constexpr int YROW = G::YQ * 16, YCH = G::YR * G::YQ * 16, XCH = G::TR * G::XQ * 16;
-    if constexpr (ST == 0) {          // pipeline fill: steps 0 .. PF-1 (+ the x quad of channel 0)
+    if constexpr (ST == 0) {          // pipeline fill: step 0 (+ the x quad of channel 0)
         lds_read128<0>(xq[0], xa);
         lds_read128<I0 * YROW>(wq[0][0], ya);
         lds_read128<I0 * YROW + 16>(wq[0][1], ya);
         lds_read128<I0 * YROW + 32>(wq[0][2], ya);
-        if constexpr (PF >= 2 && NSTEP > 1) {
-            constexpr int o = (1 / NI) * YCH + (I0 + 1 % NI) * YROW;
-            if constexpr (1 % NI == 0) lds_read128<(1 / NI) * XCH>(xq[1 / NI], xa);
-            lds_read128<o>(wq[1][0], ya); lds_read128<o + 16>(wq[1][1], ya); lds_read128<o + 32>(wq[1][2], ya);
-        }
-        if constexpr (PF >= 3 && NSTEP > 2) {
-            constexpr int o = (2 / NI) * YCH + (I0 + 2 % NI) * YROW;
-            if constexpr (2 % NI == 0) lds_read128<(2 / NI) * XCH>(xq[2 / NI], xa);
-            lds_read128<o>(wq[2][0], ya); lds_read128<o + 16>(wq[2][1], ya); lds_read128<o + 32>(wq[2][2], ya);
-        }
     }
-    constexpr int S2 = ST + PF;       // the step whose reads are issued now
+    constexpr int S2 = ST + 1;        // the step whose reads are issued now
     if constexpr (S2 < NSTEP) {
         constexpr int o = (S2 / NI) * YCH + (I0 + S2 % NI) * YROW;
         if constexpr (S2 % NI == 0) lds_read128<(S2 / NI) * XCH>(xq[S2 / NI], xa);
         lds_read128<o>(wq[S2][0], ya); lds_read128<o + 16>(wq[S2][1], ya); lds_read128<o + 32>(wq[S2][2], ya);
     }
-    // reads issued after those of step ST: steps ST+1 .. min(ST+PF, NSTEP-1), 3 each + 1 for a step that opens a channel
-    constexpr int LAST = S2 < NSTEP ? S2 : NSTEP - 1;
-    constexpr int NEWER = 3 * (LAST - ST) + (LAST / NI - ST / NI);
+    // reads issued after those of step ST: the 3 of step ST+1, + 1 where that step opens a channel
+    constexpr int NEWER = S2 < NSTEP ? 3 + (S2 % NI == 0 ? 1 : 0) : 0;
     constexpr int ch = ST / NI, r = ST % NI;
     lds_wait<NEWER>(wq[ST][0], wq[ST][1], wq[ST][2], xq[ch]);
     const f32x4 w0 = wq[ST][0], w1 = wq[ST][1], w2 = wq[ST][2], xv = xq[ch];
@@ -190,10 +158,9 @@ __device__ __forceinline__ void corr7_steps(f32x4 (&wq)[G::CK * (I1 - I0)][3], f
         for (int j = 0; j < 7; ++j) {
             const int e = d + j + 1;
             const float yv = e < 4 ? w0[e & 3] : (e < 8 ? w1[e & 3] : w2[e & 3]);
-            float& a = acc[G::ROT ? (d + j) & 3 : d][r * 7 + j];
+            float& a = acc[d][r * 7 + j];
             a = fmaf(xv[d], yv, a);
         }
-    if constexpr (G::SB) __builtin_amdgcn_sched_barrier(0);
     if constexpr (ST + 1 < NSTEP) corr7_steps<G, I0, I1, ST + 1>(wq, xq, acc, ya, xa);
 }
 
@@ -213,18 +180,18 @@ __device__ __forceinline__ void wait_vm(int n) {
 // (I1-I0) accumulators per lane).  Splitting the 49 taps over NG wavefronts divides the register footprint (3 or 4
 // instead of 2 wavefronts per SIMD); all groups read the same LDS tile, so the DMA traffic is unchanged.
 template <class G, int I0, int I1>
-__device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const float* yn, const int* off, int lw, int amask,
+__device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const float* yn, const int* off, int wave, int amask,
                                             int strip, int cb, int lane, int nchunks, size_t HW,
                                             float* __restrict__ out, float* __restrict__ out21, int n, int row0, int c0, int H,
                                             int W, int trv) {
-    constexpr int NI = I1 - I0, NS = G::NS, CK = G::CK, PF = G::PF, TR = G::TR;
+    constexpr int NI = I1 - I0, NS = G::NS, CK = G::CK, TR = G::TR;
     auto issue = [&](int chunk, int buf) {
         const size_t cbase = (size_t)chunk * CK * HW;
 #pragma unroll
         for (int i = 0; i < G::PPW; ++i) {
-            const int pi = lw + G::NL * i;             // lw < 0 (a wave that issues no DMA): amask == 0, nothing below runs
+            const int pi = wave + G::NW * i;
             const float* base = (pi < G::Y_PIECES ? yn : xn) + cbase;
-            if constexpr (G::ZM) {
+            if constexpr (G::TUNED) {
                 // slots outside the image were zeroed once: their lanes are masked off (no fetch, no LDS write) and a piece
                 // without any image data is not issued at all (amask / npieces are wave-uniform: the vmcnt arithmetic below
                 // counts THIS wave's issues).  No zero block, hence no scalar load in the loop: an SMEM op in flight would
@@ -233,13 +200,12 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
                     if (off[i] >= 0)
                         __builtin_amdgcn_global_load_lds((gptr_t)(base + off[i]), (lptr_t)(smem + buf * G::BUF_SLOTS + pi * 64), 16, 0, 0);
             } else {
-                static_assert(G::ZM || !G::LDW, "LDW needs the masked issue");
                 const float* src = off[i] >= 0 ? base + off[i] : rfx_zero16;
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + buf * G::BUF_SLOTS + pi * 64), 16, 0, 0);
             }
         }
     };
-    const int npieces = G::ZM ? __builtin_popcount((unsigned)amask) : G::PPW;   // DMA instructions per chunk of this wave
+    const int npieces = G::TUNED ? __builtin_popcount((unsigned)amask) : G::PPW;   // DMA instructions per chunk of this wave
     float acc[4][NI * 7];
 #pragma unroll
     for (int d = 0; d < 4; ++d)
@@ -262,7 +228,7 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
         wait_vm(younger * npieces);
         __builtin_amdgcn_s_barrier();  // all waves: chunk s visible, and everyone is done reading buffer (s-1)%NS
         if (s + NS - 1 < nchunks) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);  // (s+NS-1)%NS == (s-1)%NS
-        if constexpr (PF > 0) {
+        if constexpr (G::TUNED) {
             // hand-pipelined LDS reads (see lds_read128): byte addresses of this lane's first window quad / x quad
             const unsigned ya = lds_base + (unsigned)(buf * G::BUF_SLOTS + yoff) * 16u;
             const unsigned xa = lds_base + (unsigned)(buf * G::BUF_SLOTS + G::Y_PIECES * 64 + xoff) * 16u;
@@ -288,25 +254,7 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
                 }
             }
         }
-        if constexpr (G::ROT) {
-            // keep every accumulator quad a REGISTER TUPLE (element index = bank offset) across the loop: an empty asm with a
-            // 128-bit operand is the only way to tell the allocator so
-#pragma unroll
-            for (int q = 0; q < NI * 7; ++q) {
-                f32x4 tq = {acc[0][q], acc[1][q], acc[2][q], acc[3][q]};
-                asm volatile("" : "+v"(tq));
-                acc[0][q] = tq[0]; acc[1][q] = tq[1]; acc[2][q] = tq[2]; acc[3][q] = tq[3];
-            }
-        }
         buf = buf == NS - 1 ? 0 : buf + 1;
-    }
-    if constexpr (G::ROT) {                     // undo the rotation: pixel d of tap column j sits in element (d+j)&3
-#pragma unroll
-        for (int q = 0; q < NI * 7; ++q) {
-            const int j = q % 7;
-            const float t0 = acc[(0 + j) & 3][q], t1 = acc[(1 + j) & 3][q], t2 = acc[(2 + j) & 3][q], t3 = acc[(3 + j) & 3][q];
-            acc[0][q] = t0; acc[1][q] = t1; acc[2][q] = t2; acc[3][q] = t3;
-        }
     }
     const int gr = row0 + tr, gc = c0 + cb * TC + 4 * tc;
     if (tr < trv && gr < H && gc < W) {
@@ -358,7 +306,8 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
     const int tpi = tilesR * tilesC;
     const int nwg = N * tpi;
     int bid = blockIdx.x;
-    {   // XCD-aware bijective remap: all tiles of one image on one XCD (halo re-reads hit that L2)
+    {   // XCD-aware bijective remap: all tiles of one image on one XCD (halo re-reads hit that L2).  xcd_remap() (common.h) written
+        // out: through the helper the six 16-column-tile instances compile to different set-up code
         const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
     }
@@ -371,18 +320,14 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
     const float* xn = x + (size_t)n * C * HW;
     const float* yn = y + (size_t)n * C * HW;
 
-    // per-lane source offsets of the PPW DMA pieces this wave issues per chunk; -1 = 16-byte zero block
-    int lw = wave;
-    if constexpr (G::LDW) {
-        constexpr unsigned long long lmap = []() { unsigned long long m = 0; for (int w = 0; w < G::NW; ++w) m |= (unsigned long long)(G::loader_rank(w) & 15) << (4 * w); return m; }();
-        lw = (int)((lmap >> (4 * wave)) & 15);
-        if (lw == 15) lw = -1;
-    }
+    // per-lane source offsets of the PPW DMA pieces this wave issues per chunk; -1 = 16-byte zero block / zeroed slot
     int off[G::PPW];
     int amask = 0;
 #pragma unroll
     for (int i = 0; i < G::PPW; ++i) {
-        const int pi = lw < 0 ? G::N_PIECES : lw + G::NL * i;
+        // wave is never negative.  The select is kept on purpose: without it the set-up code of the two 16x16-tile instances comes
+        // out one instruction (a v_bfe_i32) shorter than in the build the recorded measurements were taken on
+        const int pi = wave < 0 ? G::N_PIECES : wave + G::NW * i;
         int o = -1;
         if (pi < G::Y_PIECES) {
             const int s = pi * 64 + lane;
@@ -401,17 +346,17 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
                 if (q < 4 * NCB && rr < trv && gr < H && gc < W) o = (int)(ch * HW) + gr * W + gc;
             }
         }
-        if (G::ZM && __ballot(o >= 0) != 0ull) amask |= 1 << i;     // wave-uniform: this piece carries image data
+        if (G::TUNED && __ballot(o >= 0) != 0ull) amask |= 1 << i;     // wave-uniform: this piece carries image data
         off[i] = o;
     }
-    if (G::ZM) {
+    if (G::TUNED) {
         // zero the out-of-image / padding slots of every ring buffer ONCE: the DMA never writes them again
 #pragma unroll
         for (int i = 0; i < G::PPW; ++i)
-            if (off[i] < 0 && lw >= 0) {
+            if (off[i] < 0) {
                 const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int b = 0; b < G::NS; ++b) smem[b * G::BUF_SLOTS + (lw + G::NL * i) * 64 + lane] = z;
+                for (int b = 0; b < G::NS; ++b) smem[b * G::BUF_SLOTS + (wave + G::NW * i) * 64 + lane] = z;
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the raw s_barrier of the main loop does not wait for ds_write
     }
@@ -424,287 +369,19 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
     }
     const int strip = sc / NCB, cb = sc - strip * NCB;
     const int nch = C / G::CK;
-#define RFX_STRIP(g) corr7_strip<G, G::row_begin(g), G::row_begin(g + 1)>(smem, xn, yn, off, lw, amask, strip, cb, lane, nch, HW, out, out21, n, row0, c0, H, W, trv)
-    if (G::PRIO && grp == 0) __builtin_amdgcn_s_setprio(1);   // the 4-/3-row group has the most FMAs per chunk: let it win VALU arbitration
+#define RFX_STRIP(g) corr7_strip<G, G::row_begin(g), G::row_begin(g + 1)>(smem, xn, yn, off, wave, amask, strip, cb, lane, nch, HW, out, out21, n, row0, c0, H, W, trv)
+    if (G::TUNED && grp == 0) __builtin_amdgcn_s_setprio(1);   // the 3-row group has the most FMAs per chunk: let it win VALU arbitration
     if (grp == 0) RFX_STRIP(0);
     else if (grp == 1) RFX_STRIP(1);
     if constexpr (NG > 2) { if (grp == 2) RFX_STRIP(2); }
-    if constexpr (NG > 3) { if (grp == 3) RFX_STRIP(3); }
 #undef RFX_STRIP
 }
 
-
-// ======================================================================================================================
-// Round 4: the DPP form.  The tuned kernel above reads a 12-float y window (three ds_read_b128) per (channel, tap row) step
-// for 28 FMAs; with 15 waves that is 240 b128 reads = 245 KB of LDS reads per 2-channel chunk and CU, ~1900 clocks at 128 B/clk
-// -- the "compute only" run of that kernel takes as long as its "DMA only" run (142 vs 129 us at N = 64), which is why the two
-// cannot hide behind each other.  The window's left and right quads are the OWN quads of the lanes next door, so here a lane
-// reads ONE quad per step (its own 4 pixels of y row r+i) and takes the other 8 floats from its neighbours inside the FMA:
-//     v_fmac_f32_dpp acc, y_own[e], x[d] row_shr:1      (window element e < 4: the left neighbour's quad)
-//     v_fmac_f32_dpp acc, y_own[e], x[d] row_shl:1      (e >= 8: the right neighbour's)
-// -- no extra instruction, the same channel-ordered fma chain (bit-identical results), a third of the LDS reads.
-// DPP shifts work inside rows of 16 lanes, so a tile row of NQ output quads (+ one halo quad on each side) is cut into segments
-// of at most 16 consecutive quads that overlap by two: the first and last lane of a segment only HOLD a quad for their
-// neighbour (their own sums are discarded), 14 of 16 lanes are productive (20 of 24 for an 80-column tile: segments of 16 + 8,
-// two 8-lane segments share a DPP row).  lane -> (tile row, quad) is pure integer arithmetic on the lane id (dpp_map).
-template <int TR_, int NCB_, int CK_, int NS_, int NG_, int OPT_ = 0>
-struct CfgD {
-    static constexpr int TR = TR_, NCB = NCB_, CK = CK_, NS = NS_, NG = NG_;
-    static constexpr bool BIDIR = OPT_ & 16;
-    static constexpr int NQ = 4 * NCB;                         // output quads per tile row
-    static constexpr int NSEGF = NQ / 14;                      // full 16-lane segments per row (14 productive lanes each)
-    static constexpr int REM = NQ - 14 * NSEGF;                // productive lanes of the partial segment (0: none)
-    static constexpr int LP = REM ? REM + 2 : 16;              // lanes of the partial segment
-    static constexpr int PPR = REM ? 16 / LP : 0;              // partial segments packed into one DPP row
-    static constexpr int RG = REM ? PPR : 1;                   // tile rows per packing group
-    static constexpr int DG = RG * NSEGF + (REM ? 1 : 0);      // DPP rows per packing group
-    static constexpr int DROWS = (TR + RG - 1) / RG * DG;      // DPP rows of a tile
-    static constexpr int WPG = (DROWS + 3) / 4;                // waves per tap-row group
-    static constexpr int NW = WPG * NG;
-    static constexpr int YR = TR + 6, YQ = NQ + 2, XQ = NQ;
-    static constexpr int Y_SLOTS = CK * YR * YQ, Y_PIECES = (Y_SLOTS + 63) / 64;
-    static constexpr int X_SLOTS = CK * TR * XQ, X_PIECES = (X_SLOTS + 63) / 64;
-    static constexpr int PPW = (Y_PIECES + X_PIECES + NW - 1) / NW;
-    static constexpr int N_PIECES = PPW * NW;
-    static constexpr int BUF_SLOTS = N_PIECES * 64;
-    static constexpr int row_begin(int g) { return NG == 2 ? (g == 0 ? 0 : g == 1 ? 4 : 7) : (g == 0 ? 0 : g == 1 ? 3 : g == 2 ? 5 : 7); }
-    static constexpr int WAVES_PER_SIMD = (NW + 3) / 4;
-    // wave -> tap group so that the waves the hardware deals to one SIMD (w, w+4, w+8, ..) mix heavy and light groups
-    static constexpr int wave_group(int w) { return (w % 4 + w / 4) % NG; }
-    static constexpr int wave_block(int w) { int r = 0; for (int v = 0; v < w; ++v) r += wave_group(v) == wave_group(w); return r; }
-    static_assert(NG == 2 || NG == 3, "2 or 3 tap-row groups");
-    static_assert(NW * 64 <= 1024, "workgroup too large");
-    static_assert((NS - 2) * PPW <= 15, "vmcnt immediate out of range");
-    static_assert((size_t)NS * BUF_SLOTS * 16 <= 160 * 1024, "LDS ring exceeds 160 KiB");
-};
-
-// (DPP row R of the tile, position p in it) -> tile row, quad (-1 / NQ = halo holders), productive?
 template <class G>
-__device__ __forceinline__ void dpp_map(int R, int p, int& row, int& quad, bool& prod) {
-    const int k = R / G::DG, m = R - k * G::DG;
-    if (m < G::RG * G::NSEGF) {
-        row = k * G::RG + m / G::NSEGF;
-        quad = (m % G::NSEGF) * 14 + p - 1;
-        prod = p >= 1 && p <= 14;
-    } else {
-        const int sub = p / G::LP, q = p - sub * G::LP;
-        row = k * G::RG + sub;
-        quad = G::NSEGF * 14 + q - 1;
-        prod = sub < G::PPR && q >= 1 && q <= G::REM;
-        if (sub >= G::PPR) { row = 0; quad = 0; }
-    }
-}
-
-template <int CTL>   // 0: own lane, 1: row_shr:1 (value of lane-1), 2: row_shl:1 (value of lane+1)
-__device__ __forceinline__ void fmac_dpp(float& acc, float y, float x) {
-    if constexpr (CTL == 0) asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(y), "v"(x));
-    else if constexpr (CTL == 1) asm volatile("v_fmac_f32_dpp %0, %1, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0" : "+v"(acc) : "v"(y), "v"(x));
-    else asm volatile("v_fmac_f32_dpp %0, %1, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0" : "+v"(acc) : "v"(y), "v"(x));
-}
-
-// (channel, tap row) steps of one chunk; reads run one step ahead with counted waits as in corr7_steps
-template <class G, int I0, int I1, int ST>
-__device__ __forceinline__ void corr7_dpp_steps(f32x4 (&yq)[G::CK * (I1 - I0)], f32x4 (&xq)[G::CK], float (&acc)[4][(I1 - I0) * 7],
-                                                unsigned ya, unsigned xa) {
-    constexpr int NI = I1 - I0, NSTEP = G::CK * NI;
-    constexpr int YROW = G::YQ * 16, YCH = G::YR * G::YQ * 16, XCH = G::TR * G::XQ * 16;
-    if constexpr (ST == 0) {
-        lds_read128<0>(xq[0], xa);
-        lds_read128<I0 * YROW>(yq[0], ya);
-    }
-    constexpr int S2 = ST + 1;
-    if constexpr (S2 < NSTEP) {
-        if constexpr (S2 % NI == 0) lds_read128<(S2 / NI) * XCH>(xq[S2 / NI], xa);
-        lds_read128<(S2 / NI) * YCH + (I0 + S2 % NI) * YROW>(yq[S2], ya);
-    }
-    constexpr int NEWER = S2 < NSTEP ? 1 + (S2 % NI == 0 ? 1 : 0) : 0;
-    constexpr int ch = ST / NI, r = ST % NI;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(yq[ST]), "+v"(xq[ch]) : "n"(NEWER));
-    const f32x4 yv = yq[ST], xv = xq[ch];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            const int e = d + j + 1;                       // element of the 12-float window: 0-3 left, 4-7 own, 8-11 right quad
-            float& a = acc[d][r * 7 + j];
-            if (e < 4) fmac_dpp<1>(a, yv[e & 3], xv[d]);
-            else if (e < 8) fmac_dpp<0>(a, yv[e & 3], xv[d]);
-            else fmac_dpp<2>(a, yv[e & 3], xv[d]);
-        }
-    if constexpr (ST + 1 < NSTEP) corr7_dpp_steps<G, I0, I1, ST + 1>(yq, xq, acc, ya, xa);
-}
-
-template <class G, int I0, int I1>
-__device__ __forceinline__ void corr7_dpp_strip(f32x4* smem, const float* xn, const float* yn, const int* off, int wave, int amask,
-                                                int blk, int lane, int nchunks, size_t HW, float* __restrict__ out,
-                                                float* __restrict__ out21, int n, int row0, int H, int W, int trv) {
-    constexpr int NI = I1 - I0, NS = G::NS, CK = G::CK;
-    auto issue = [&](int chunk, int buf) {
-        const size_t cbase = (size_t)chunk * CK * HW;
-#pragma unroll
-        for (int i = 0; i < G::PPW; ++i) {
-            const int pi = wave + G::NW * i;
-            const float* base = (pi < G::Y_PIECES ? yn : xn) + cbase;
-            if ((amask >> i) & 1)
-                if (off[i] >= 0)
-                    __builtin_amdgcn_global_load_lds((gptr_t)(base + off[i]), (lptr_t)(smem + buf * G::BUF_SLOTS + pi * 64), 16, 0, 0);
-        }
-    };
-    const int npieces = __builtin_popcount((unsigned)amask);
-    float acc[4][NI * 7];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int q = 0; q < NI * 7; ++q) acc[d][q] = 0.f;
-    int tr, quad;
-    bool prod;
-    dpp_map<G>(blk * 4 + (lane >> 4), lane & 15, tr, quad, prod);
-    if (tr >= G::TR) { tr = 0; prod = false; }                  // DPP rows past the tile (DROWS not a multiple of 4)
-    const int yoff = tr * G::YQ + quad + 1;                      // own quad of y row tr (+ tap row, + channel added as immediates)
-    const int xoff = tr * G::XQ + (quad < 0 ? 0 : (quad >= G::NQ ? G::NQ - 1 : quad));
-    const unsigned lds_base = (unsigned)(uintptr_t)(lptr_t)smem;
-#pragma unroll
-    for (int p = 0; p < NS - 1; ++p)
-        if (p < nchunks) issue(p, p);
-    int buf = 0;
-    for (int s = 0; s < nchunks; ++s) {
-        const int younger = nchunks - 1 - s < NS - 2 ? nchunks - 1 - s : NS - 2;
-        wait_vm(younger * npieces);
-        __builtin_amdgcn_s_barrier();
-        if (s + NS - 1 < nchunks) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);
-        const unsigned ya = lds_base + (unsigned)(buf * G::BUF_SLOTS + yoff) * 16u;
-        const unsigned xa = lds_base + (unsigned)(buf * G::BUF_SLOTS + G::Y_PIECES * 64 + xoff) * 16u;
-        f32x4 yq[CK * NI];
-        f32x4 xq[CK];
-        corr7_dpp_steps<G, I0, I1, 0>(yq, xq, acc, ya, xa);
-        buf = buf == NS - 1 ? 0 : buf + 1;
-    }
-    const int gr = row0 + tr, gc = quad * 4;
-    if (prod && tr < trv && gr < H && gc < W) {
-        float* o = out + (size_t)n * 49 * HW + (size_t)gr * W + gc;
-#pragma unroll
-        for (int q = 0; q < NI * 7; ++q) {
-            f32x4 v = {acc[0][q], acc[1][q], acc[2][q], acc[3][q]};
-            *reinterpret_cast<f32x4*>(o + (size_t)(I0 * 7 + q) * HW) = v;
-        }
-        if constexpr (G::BIDIR) {                               // see corr7_strip: the reverse volume from the same sums
-            float* o21 = out21 + (size_t)n * 49 * HW;
-#pragma unroll
-            for (int q = 0; q < NI * 7; ++q) {
-                const int i = I0 + q / 7, j = q % 7;
-                float* pl = o21 + (size_t)((6 - i) * 7 + (6 - j)) * HW;
-                const int dr = gr + i - 3;
-                if ((unsigned)dr < (unsigned)H) {
-#pragma unroll
-                    for (int d = 0; d < 4; ++d) {
-                        const int dc = gc + d + j - 3;
-                        if ((unsigned)dc < (unsigned)W) pl[(size_t)dr * W + dc] = acc[d][q];
-                    }
-                }
-                const int sr = gr - (i - 3);
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const int sc = gc + d - (j - 3);
-                    if ((unsigned)sr >= (unsigned)H || (unsigned)sc >= (unsigned)W) pl[(size_t)gr * W + gc + d] = 0.f;
-                }
-            }
-        }
-    }
-}
-
-template <class G>
-__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dpp_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, float* __restrict__ out21, int N, int C,
-    int H, int W, int tilesR, int trv) {
-    constexpr int TR = G::TR, NG = G::NG;
-    __shared__ __attribute__((aligned(16))) f32x4 smem[G::NS * G::BUF_SLOTS];
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int nwg = N * tilesR;
-    int bid = blockIdx.x;
-    {   // XCD-aware bijective remap: all tiles of one image on one XCD (halo re-reads hit that L2)
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    const int n = bid / tilesR;
-    const int row0 = (bid - n * tilesR) * trv;
-    const size_t HW = (size_t)H * W;
-    const float* xn = x + (size_t)n * C * HW;
-    const float* yn = y + (size_t)n * C * HW;
-    int off[G::PPW];
-    int amask = 0;
-#pragma unroll
-    for (int i = 0; i < G::PPW; ++i) {
-        const int pi = wave + G::NW * i;
-        int o = -1;
-        if (pi < G::Y_PIECES) {
-            const int s = pi * 64 + lane;
-            if (s < G::Y_SLOTS) {
-                const int ch = s / (G::YR * G::YQ), rem = s - ch * (G::YR * G::YQ);
-                const int rr = rem / G::YQ, q = rem - rr * G::YQ;
-                const int gr = row0 + rr - 3, gc = -4 + 4 * q;
-                if (rr < trv + 6 && (unsigned)gr < (unsigned)H && (unsigned)gc < (unsigned)W) o = (int)(ch * HW) + gr * W + gc;
-            }
-        } else if (pi < G::Y_PIECES + G::X_PIECES) {
-            const int s = (pi - G::Y_PIECES) * 64 + lane;
-            if (s < G::X_SLOTS) {
-                const int ch = s / (TR * G::XQ), rem = s - ch * (TR * G::XQ);
-                const int rr = rem / G::XQ, q = rem - rr * G::XQ;
-                const int gr = row0 + rr, gc = 4 * q;
-                if (rr < trv && gr < H && gc < W) o = (int)(ch * HW) + gr * W + gc;
-            }
-        }
-        if (__ballot(o >= 0) != 0ull) amask |= 1 << i;
-        off[i] = o;
-    }
-    // zero the out-of-image / padding slots of every ring buffer ONCE: the DMA never writes them
-#pragma unroll
-    for (int i = 0; i < G::PPW; ++i)
-        if (off[i] < 0) {
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int b = 0; b < G::NS; ++b) smem[b * G::BUF_SLOTS + (wave + G::NW * i) * 64 + lane] = z;
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    constexpr unsigned long long gmap = []() { unsigned long long m = 0; for (int w = 0; w < G::NW; ++w) m |= (unsigned long long)G::wave_group(w) << (2 * w); return m; }();
-    constexpr unsigned long long bmap = []() { unsigned long long m = 0; for (int w = 0; w < G::NW; ++w) m |= (unsigned long long)G::wave_block(w) << (4 * w); return m; }();
-    const int grp = (int)((gmap >> (2 * wave)) & 3), blk = (int)((bmap >> (4 * wave)) & 15);
-    const int nch = C / G::CK;
-#define RFX_DSTRIP(g) corr7_dpp_strip<G, G::row_begin(g), G::row_begin(g + 1)>(smem, xn, yn, off, wave, amask, blk, lane, nch, HW, out, out21, n, row0, H, W, trv)
-    if (grp == 0) RFX_DSTRIP(0);
-    else if (grp == 1) RFX_DSTRIP(1);
-    if constexpr (NG > 2) { if (grp == 2) RFX_DSTRIP(2); }
-#undef RFX_DSTRIP
-}
-
-template <class G>
-static void launch_corr_dpp(const float* x, const float* y, float* out, int N, int C, int H, int W, hipStream_t st, float* out21 = nullptr) {
+static void launch_corr(const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W, hipStream_t st) {
     const int tilesR = (H + G::TR - 1) / G::TR;
-    const int trv = (H + tilesR - 1) / tilesR;                  // equal row tiles (60 = 4 x 15)
-    corr_launch((corr7_dpp_kernel<G>), dim3((unsigned)(N * tilesR)), dim3(G::NW * 64), st, x, y, out, out21, N, C, H, W,
-                       tilesR, trv);
-}
-
-// Small launches (the multi-homography rounds of the evaluation drivers run the correlation on the 8-16 pairs that are still
-// active: 48-200 workgroups of 16-row tiles on 256 CUs) are bound by the lifetime of ONE workgroup, not by bandwidth.
-// Experiment knob RFX_CORR_MIN_WGS = n: equal row tiles are made shorter than 16 rows until the grid reaches n workgroups or a
-// tile would fall under 8 rows.  Measured (profiles/r03_corr_small_launches.txt, both directions of 8-24 pairs): n = 256 is a
-// wash (+-5 %: the 6 halo rows of a shorter tile cost what the extra workgroups gain), n = 512 is 35-60 % slower -> default 0.
-static int corr_min_wgs() {
-    static const int v = []() { const char* e = getenv("RFX_CORR_MIN_WGS"); return e ? atoi(e) : 0; }();
-    return v;
-}
-
-template <class G>
-static void launch_corr(const float* x, const float* y, float* out, int N, int C, int H, int W, hipStream_t st, bool even = false,
-                        float* out21 = nullptr) {
-    int tilesR = (H + G::TR - 1) / G::TR;
     const int tilesC = (W + TC * G::NCB - 1) / (TC * G::NCB);
-    if (even) {
-        const long long want = corr_min_wgs();
-        while ((long long)N * tilesR * tilesC < want && (H + tilesR) / (tilesR + 1) >= 8) ++tilesR;
-    }
-    const int trv = even ? (H + tilesR - 1) / tilesR : G::TR;      // equal row tiles (60 = 4 x 15) or full 16-row strips
+    const int trv = G::TUNED ? (H + tilesR - 1) / tilesR : G::TR;  // equal row tiles (60 = 4 x 15) or full TR-row tiles
     corr_launch((corr7_dma_kernel<G>), dim3((unsigned)(N * tilesR * tilesC)), dim3(G::NW * 64), st, x, y, out,
                        out21, N, C, H, W, tilesR, tilesC, trv);
 }
@@ -733,52 +410,20 @@ __global__ __launch_bounds__(256) void corr7_plain_kernel(const float* __restric
     }
 }
 
-// Variant table (rfx_corr_neigh_variant_f32 / RFX_CORR_VARIANT; 0 = automatic).  All product variants are bit-identical.
-//   1: 64x16 tile   2: 32x16   3: 16x16          16-column tiles of round 1 (ring of 3, 2 tap groups)
-//   4: 16x80 plain (ring of 4, 2 tap groups, compiler-scheduled LDS reads)
-//   5: 16x80 TUNED  = 3 tap groups (15 waves, 128 VGPRs), hand-pipelined LDS reads one step ahead, SIMD-balanced wave map,
-//      zero slots written once + masked DMA lanes, conflict-free x rows, s_setprio for the 3-row group, equal row tiles
-//   6: as 5 with 2 tap groups (10 waves)      7 / 8: the tuned kernel with 48- / 64-column tiles      9: 32x32 (plain)
-//   21 / 22 / 23 / 24: variant 5 with the compute / the DMA / the LDS reads / the FMAs removed -- WRONG RESULTS, for the
-//            roofline decomposition in scripts/ubench/corr_bench.py only (how long does each side take alone?)
-using CfgTuned = Cfg<16, 5, 2, 4, 3, 1, 0, 15>;
-using CfgTuned4 = Cfg<16, 4, 2, 4, 3, 1, 0, 14>;   // 64-column tiles: 12 waves, one of each tap group per SIMD by construction
-using CfgTuned3 = Cfg<16, 3, 2, 4, 3, 1, 0, 14>;   // 48-column tiles: 9 waves
-// BIDIR forms (OPT bit 16) of the tile shapes the automatic choice can return: same main loop, second store in the epilogue
-using CfgTunedB = Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 16>;
-using CfgTuned4B = Cfg<16, 4, 2, 4, 3, 1, 0, 14 | 16>;
-using CfgTuned3B = Cfg<16, 3, 2, 4, 3, 1, 0, 14 | 16>;
+// Variant table (rfx_corr_neigh_variant_f32 / RFX_CORR_VARIANT; 0 = automatic): the six tile shapes auto_variant() returns.
+// All are bit-identical; every other number is RFX_E_ARG.  BIDIR: the form that also writes corr(y, x) to out21.
+//   1: 64x16   2: 32x16   3: 16x16      plain 16-column tiles
+//   5: 16x80   8: 16x64   7: 16x48      tuned tiles (15 / 12 / 9 waves)
+template <bool BIDIR>
 static int launch_variant(int v, const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W,
                           hipStream_t st) {
-    if (out21) {
-        switch (v) {
-            case 1: launch_corr<Cfg<64, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
-            case 2: launch_corr<Cfg<32, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
-            case 3: launch_corr<Cfg<16, 1, 2, 3, 2, 0, 0, 16>>(x, y, out, N, C, H, W, st, false, out21); break;
-            case 5: launch_corr<CfgTunedB>(x, y, out, N, C, H, W, st, true, out21); break;
-            case 7: launch_corr<CfgTuned3B>(x, y, out, N, C, H, W, st, true, out21); break;
-            case 8: launch_corr<CfgTuned4B>(x, y, out, N, C, H, W, st, true, out21); break;
-            case 14: if (W > 80) return RFX_E_ARG; launch_corr_dpp<CfgD<16, 5, 2, 4, 2, 16>>(x, y, out, N, C, H, W, st, out21); break;
-            default: return RFX_E_ARG;
-        }
-        return RFX_OK;
-    }
     switch (v) {
-        case 1: launch_corr<Cfg<64, 1, 2, 3>>(x, y, out, N, C, H, W, st); break;
-        case 2: launch_corr<Cfg<32, 1, 2, 3>>(x, y, out, N, C, H, W, st); break;
-        case 3: launch_corr<Cfg<16, 1, 2, 3>>(x, y, out, N, C, H, W, st); break;
-        case 4: launch_corr<Cfg<16, 5, 2, 4>>(x, y, out, N, C, H, W, st); break;
-        case 5: launch_corr<CfgTuned>(x, y, out, N, C, H, W, st, true); break;
-        case 6: launch_corr<Cfg<16, 5, 2, 4, 2, 1, 0, 15>>(x, y, out, N, C, H, W, st, true); break;
-        case 7: launch_corr<CfgTuned3>(x, y, out, N, C, H, W, st, true); break;
-        case 8: launch_corr<CfgTuned4>(x, y, out, N, C, H, W, st, true); break;
-        case 9: launch_corr<Cfg<32, 2, 2, 3>>(x, y, out, N, C, H, W, st); break;
-        case 10: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 5 + DMA on the light waves
-        case 11: launch_corr<Cfg<16, 5, 2, 5, 3, 1, 0, 15 | 32>>(x, y, out, N, C, H, W, st, true); break;   // 10 with a ring of 5
-        case 12: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 5 + accumulator bank rotation
-        case 13: launch_corr<Cfg<16, 5, 2, 4, 3, 1, 0, 15 | 32 | 64>>(x, y, out, N, C, H, W, st, true); break;   // 12 + DMA on the light waves
-        case 14: if (W > 80) return RFX_E_ARG; launch_corr_dpp<CfgD<16, 5, 2, 4, 2>>(x, y, out, N, C, H, W, st); break;   // DPP form, 80-column tiles, 2 tap groups
-        case 15: if (W > 80) return RFX_E_ARG; launch_corr_dpp<CfgD<16, 5, 2, 3, 2>>(x, y, out, N, C, H, W, st); break;   // 14 with a ring of 3
+        case 1: launch_corr<Cfg<64, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 2: launch_corr<Cfg<32, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 3: launch_corr<Cfg<16, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 5: launch_corr<Cfg<16, 5, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 7: launch_corr<Cfg<16, 3, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 8: launch_corr<Cfg<16, 4, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
         default: return RFX_E_ARG;
     }
     return RFX_OK;
@@ -789,8 +434,6 @@ static int launch_variant(int v, const float* x, const float* y, float* out, flo
 // taken when the launch still gives most CUs a workgroup.  Otherwise 16-column tiles, as tall as the workgroup count allows
 // (>= 1024 workgroups).
 static int auto_variant(int N, int H, int W) {
-    static const int force = []() { const char* e = getenv("RFX_CORR_FORCE"); return e ? atoi(e) : 0; }();   // experiments
-    if (force == 14 && W > 32 && W <= 80) return 14;
     const long long tc = (W + TC - 1) / TC;
     const long long r16 = (H + 15) / 16;
     if (W > 32 && (long long)N * r16 * ((W + 79) / 80) >= 128) {
@@ -821,7 +464,7 @@ extern "C" int rfx_corr_neigh_variant_f32(const float* x, const float* y, float*
     hipStream_t st = rfx_stream(stream);
     if (dma_ok(x, y, out, nullptr, C, W)) {
         if ((long long)N * ((H + 15) / 16) * ((W + TC - 1) / TC) > 0x7fffffffLL) return RFX_E_LIMIT;
-        const int rc = launch_variant(variant == 0 ? auto_variant(N, H, W) : variant, x, y, out, nullptr, N, C, H, W, st);
+        const int rc = launch_variant<false>(variant == 0 ? auto_variant(N, H, W) : variant, x, y, out, nullptr, N, C, H, W, st);
         if (rc != RFX_OK) return rc;
     } else {
         const long long NP = (long long)N * H * W;
@@ -845,7 +488,7 @@ extern "C" int rfx_corr_neigh_bidir_f32(const float* x, const float* y, float* o
     if ((long long)C * H * W > 0x7fffffffLL) return RFX_E_LIMIT;
     if (!dma_ok(x, y, out_xy, out_yx, C, W)) return RFX_E_ARG;       // the host mirrors pad the width to a multiple of 4
     if ((long long)N * ((H + 15) / 16) * ((W + TC - 1) / TC) > 0x7fffffffLL) return RFX_E_LIMIT;
-    const int rc = launch_variant(auto_variant(N, H, W), x, y, out_xy, out_yx, N, C, H, W, rfx_stream(stream));
+    const int rc = launch_variant<true>(auto_variant(N, H, W), x, y, out_xy, out_yx, N, C, H, W, rfx_stream(stream));
     if (rc != RFX_OK) return rc;
     RFX_LAUNCH_CHECK();
     return RFX_OK;

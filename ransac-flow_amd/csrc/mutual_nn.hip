@@ -50,15 +50,12 @@ __device__ __forceinline__ void mnn_close_chunk(f32x16 (&tot)[2][2], f32x16 (&ac
             for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.0f; }
 }
 
-// Arg-max epilogue of a (128 WA) x 128 score tile held in the accumulators of the (2 WA) x 2 wavefronts (C/D layout: column = lcol,
+// Arg-max epilogue of a 128 x 128 score tile held in the accumulators of the 2 x 2 wavefronts (C/D layout: column = lcol,
 // row = (r&3) + 8*(r>>2) + 4*lrow): per-tile column and row maxima (value, first index) -> the workspace.  xval / xidx:
-// max(2 WA x 128, 2 x 128 WA) floats / ints of LDS that no wavefront reads any more.  `ta` indexes the column partials: one slot
-// per TILE row (a 256-row tile fills every second slot of the 128-row layout; the reduce kernel walks tilesA slots).
-template <int WA = 1>
+// 2 x 128 floats / ints of LDS that no wavefront reads any more.
 __device__ __forceinline__ void mnn_tile_epilogue(f32x16 (&acc)[2][2], const MnnArgs& a, float* xval, int* xidx, int i0, int j0,
                                                   int ta, int tb, float* rowPartVal, int* rowPartIdx, float* colPartVal,
                                                   int* colPartIdx) {
-    constexpr int NWM = 2 * WA, ROWS = 128 * WA;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int lrow = lane >> 5, lcol = lane & 31;
@@ -88,8 +85,7 @@ __device__ __forceinline__ void mnn_tile_epilogue(f32x16 (&acc)[2][2], const Mnn
     if (t < 128 && j0 + t < a.nB) {
         float bv = xval[t];
         int bi = xidx[t];
-#pragma unroll
-        for (int w = 1; w < NWM; ++w) take_min_idx(bv, bi, xval[w * 128 + t], xidx[w * 128 + t]);   // row blocks in increasing order
+        take_min_idx(bv, bi, xval[128 + t], xidx[128 + t]);   // row blocks in increasing order
         colPartVal[(size_t)ta * a.nB + j0 + t] = bv;
         colPartIdx[(size_t)ta * a.nB + j0 + t] = bi;
     }
@@ -116,15 +112,15 @@ __device__ __forceinline__ void mnn_tile_epilogue(f32x16 (&acc)[2][2], const Mnn
             }
             if (lcol == 0) {
                 const int li = (wm * 2 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lrow;
-                xval[wn * ROWS + li] = bv;
-                xidx[wn * ROWS + li] = bj;
+                xval[wn * 128 + li] = bv;
+                xidx[wn * 128 + li] = bj;
             }
         }
     __syncthreads();
-    if (t < ROWS && i0 + t < a.nA) {
+    if (t < 128 && i0 + t < a.nA) {
         float bv = xval[t];
         int bj = xidx[t];
-        take_min_idx(bv, bj, xval[ROWS + t], xidx[ROWS + t]);
+        take_min_idx(bv, bj, xval[128 + t], xidx[128 + t]);
         rowPartVal[(size_t)tb * a.nA + i0 + t] = bv;
         rowPartIdx[(size_t)tb * a.nA + i0 + t] = bj;
     }
@@ -155,11 +151,7 @@ __global__ __launch_bounds__(256, 2) void mnn_tile_kernel(MnnArgs a) {
     int* colPartIdx = reinterpret_cast<int*>(ws + a.oColPartIdx);
 
     const int nwg = a.tilesA * a.tilesB;
-    int bid = blockIdx.x;
-    {   // XCD-aware bijective remap; column tile fastest so an XCD's L2 keeps one A panel hot
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, nwg);   // column tile fastest so an XCD's L2 keeps one A panel hot
     const int tb = bid % a.tilesB, ta = bid / a.tilesB;
     const int i0 = ta * BM, j0 = tb * BN;
 
@@ -308,29 +300,22 @@ __global__ __launch_bounds__(256, 2) void mnn_tile_kernel(MnnArgs a) {
 // the arg-max skips.  The 0/1 column mask (quick_start/coarseAlignFeatMatch.py:143 multiplies the target features by it) is
 // applied to the finished accumulators: for a 0/1 mask the same values up to the sign of a zero, which no comparison sees.
 // Same k pairing and order as the kernel above: bit-identical scores.  Requires C % 32 == 0, C >= 64.
-// WA = 2 (round 5 experiment; opt-in: RFX_MNN_WA=2): a 256 x 128 tile on 512 threads = 4 x 2 wavefronts, ONE workgroup
-// per CU (96 KB of LDS) instead of two 128 x 128 ones: the same 8 wavefronts per CU and the same 64 x 64 wavefront tiles (64 + 64
-// accumulator registers), but a K step stages (256 + 128) x 32 floats for 512 MFMAs where two small tiles stage 2 x (128 + 128) x 32
-// -- 25 % fewer operand bytes through the CU's load path per MFMA and 25 % fewer panel (re-)fetches from L2 / the Infinity Cache.
-// Same k order per score: identical match lists (scripts/ubench/mnn_bench.py).  MEASURED NEGATIVE on one box
-// (profiles/r05_mnn_tile_{128x128,256x128}.json): 106.7 -> 104.6 TFLOP/s at config 3's shape (64 x 13 065 x 1 200), 107.0 -> 104.5 at
-// quick_start's, 104.2 -> 98.5 at config 5's (8 x 25 747 x 8 250).  The tile kernel is therefore NOT bound by operand bytes per MFMA
-// (nor, a fortiori, by the 4.6x panel re-fetch traffic the counters show: it is served by L2 / the Infinity Cache at ~1 TB/s): one
-// barrier per K step across EIGHT wavefronts costs more than two independent 4-wave workgroups lose to each other.  128 x 128 stays.
+// A 256 x 128 tile on 512 threads (one workgroup per CU) was measured slower than two 128 x 128 workgroups:
+// profiles/r05_mnn_tile_{128x128,256x128}.json.
 //
 // The three steps are device functions that the single-pair / dense kernels call with their launch arguments and the ragged kernels
 // (below) with a copy narrowed to the workgroup's own pair.  The tile and the compaction body hold barriers: every thread of the
 // workgroup calls the body, as the LAST statement of its kernel.
-template <bool VEC, int WA>
+template <bool VEC>
 __device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
-    constexpr int BMA = BM * WA, NT = 256 * WA;
-    constexpr int A_TPR = VEC ? BMA / 4 : BMA;     // threads per A row
+    constexpr int NT = 256;
+    constexpr int A_TPR = VEC ? BM / 4 : BM;       // threads per A row
     constexpr int A_RPR = NT / A_TPR;              // A rows per round of all threads: 8 (VEC) / 2 (scalar)
     constexpr int NLA = BK / A_RPR;                // A loads per thread and K step: 4 / 16
     constexpr int B_TPR = VEC ? BN / 4 : BN;
-    constexpr int B_RPR = NT / B_TPR;              // 8 * WA / 2 * WA
-    constexpr int NLB = BK / B_RPR;                // 4 / WA, 16 / WA
-    __shared__ __attribute__((aligned(16))) float As[2][BK][BMA];
+    constexpr int B_RPR = NT / B_TPR;
+    constexpr int NLB = BK / B_RPR;
+    __shared__ __attribute__((aligned(16))) float As[2][BK][BM];
     __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -344,13 +329,9 @@ __device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
     float* colPartVal = reinterpret_cast<float*>(ws + a.oColPartVal);
     int* colPartIdx = reinterpret_cast<int*>(ws + a.oColPartIdx);
     const int nwg = a.tilesA * a.tilesB;
-    int bid = blockIdx.x;
-    {   // XCD-aware bijective remap; column tile fastest so an XCD's L2 keeps one A panel hot
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_remap(blockIdx.x, nwg);   // column tile fastest so an XCD's L2 keeps one A panel hot
     const int tb = bid % a.tilesB, ta = bid / a.tilesB;
-    const int i0 = ta * BMA, j0 = tb * BN;
+    const int i0 = ta * BM, j0 = tb * BN;
     // staging roles: row t / TPR (+ RPR per round), cells (t % TPR) * (VEC ? 4 : 1) ..
     const int arow_s = t / A_TPR, acol_s = (t % A_TPR) * (VEC ? 4 : 1);
     const int brow_s = t / B_TPR, bcol_s = (t % B_TPR) * (VEC ? 4 : 1);
@@ -403,7 +384,7 @@ __device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
     const float* brow = &Bs[0][lrow][wn * 64 + lcol];
     for (int s = 0; s < nk; ++s) {
         const int cur = s & 1;
-        const float* ap = arow + cur * (BK * BMA);
+        const float* ap = arow + cur * (BK * BM);
         const float* bp = brow + cur * (BK * BN);
         const int k2 = (s + 2 < nk ? s + 2 : nk - 1) * BK;      // past the end: re-load the last step (never consumed)
         float af[2][4][2], bf[2][4][2];
@@ -412,7 +393,7 @@ __device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
             for (int e = 0; e < 4; ++e) {
                 const int kk = c * 4 + e;
 #pragma unroll
-                for (int i = 0; i < 2; ++i) af[slot][e][i] = ap[2 * kk * BMA + i * 32];
+                for (int i = 0; i < 2; ++i) af[slot][e][i] = ap[2 * kk * BM + i * 32];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) bf[slot][e][j] = bp[2 * kk * BN + j * 32];
             }
@@ -457,13 +438,13 @@ __device__ __forceinline__ void mnn_tile_kmajor_body(const MnnArgs& a) {
                 for (int r = 0; r < 16; ++r) tot[i][j][r] *= mk;
         }
     }
-    mnn_tile_epilogue<WA>(tot, a, &As[0][0][0], reinterpret_cast<int*>(&Bs[0][0][0]), i0, j0, ta, tb, rowPartVal, rowPartIdx, colPartVal,
-                          colPartIdx);
+    mnn_tile_epilogue(tot, a, &As[0][0][0], reinterpret_cast<int*>(&Bs[0][0][0]), i0, j0, ta, tb, rowPartVal, rowPartIdx, colPartVal,
+                      colPartIdx);
 }
 
-template <bool VEC, int WA = 1>
-__global__ __launch_bounds__(256 * WA, WA == 1 ? 2 : 1) void mnn_tile_kmajor_kernel(MnnArgs a) {
-    mnn_tile_kmajor_body<VEC, WA>(a);
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void mnn_tile_kmajor_kernel(MnnArgs a) {
+    mnn_tile_kmajor_body<VEC>(a);
 }
 
 // blockIdx.y = the pair; one thread per row of A, then per row of B
@@ -585,7 +566,7 @@ __device__ __forceinline__ bool mnn_ragged_pair(MnnArgs& a, const MnnRagged& r, 
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void mnn_tile_ragged_kernel(MnnArgs a, MnnRagged r) {
     if (!mnn_ragged_pair(a, r, blockIdx.y) || (int)blockIdx.x >= a.tilesA * a.tilesB) return;
-    mnn_tile_kmajor_body<VEC, 1>(a);
+    mnn_tile_kmajor_body<VEC>(a);
 }
 
 __global__ __launch_bounds__(256) void mnn_reduce_ragged_kernel(MnnArgs a, MnnRagged r) {
@@ -639,16 +620,9 @@ static int mnn_launch(MnnArgs& a, int batch, hipStream_t st) {
     const char* fe = getenv("RFX_MNN_FORM");                  // 1: force the transposed-image kernel (tests, A/B timing)
     const int form = fe ? atoi(fe) : 0;
     const bool kmajor = form != 1 && a.C % BK == 0 && a.C >= 2 * BK && (vec ? (a.ldA >= 4 && a.ldB >= 4) : true);
-    // 256 x 128 tiles (WA = 2): measured slower than two 128 x 128 workgroups per CU (see the kernel) -- only with RFX_MNN_WA=2
-    static const int wa_env = getenv("RFX_MNN_WA") ? atoi(getenv("RFX_MNN_WA")) : 1;
-    const long long nwg2 = (long long)((a.nA + 2 * BM - 1) / (2 * BM)) * a.tilesB;
-    if (kmajor && wa_env == 2 && nwg2 * batch >= 512) {
-        a.tilesA = (a.nA + 2 * BM - 1) / (2 * BM);
-        if (vec) hipLaunchKernelGGL((mnn_tile_kmajor_kernel<true, 2>), dim3((unsigned)nwg2, batch), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((mnn_tile_kmajor_kernel<false, 2>), dim3((unsigned)nwg2, batch), dim3(512), 0, st, a);
-    } else if (kmajor) {
-        if (vec) hipLaunchKernelGGL((mnn_tile_kmajor_kernel<true, 1>), dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((mnn_tile_kmajor_kernel<false, 1>), dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
+    if (kmajor) {
+        if (vec) hipLaunchKernelGGL(mnn_tile_kmajor_kernel<true>, dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(mnn_tile_kmajor_kernel<false>, dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
     } else if (vec) hipLaunchKernelGGL(mnn_tile_kernel<true>, dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(mnn_tile_kernel<false>, dim3((unsigned)nwg, batch), dim3(256), 0, st, a);
     RFX_LAUNCH_CHECK();

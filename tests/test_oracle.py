@@ -863,7 +863,7 @@ def test_kernel_resources_are_what_design_says():
             assert r["wg_per_cu"] * ((r["wg"] + 63) // 64) >= 8, r                    # >= 2 wavefronts per SIMD on every tiled kernel
     hot = ["conv3x3_direct_kernel<2, 16, false, 2, false, 4>", "conv3x3_direct_kernel<2, 16, false, 2, false, 0>",
            "conv3x3_direct_kernel<1, 16, false, 2, false, 4>", "conv1x1_kmajor_kernel<1, true, 8>", "conv1x1_kmajor_kernel<1, true, 0>",
-           "conv2d_mfma_kernel<2, 2, true, false, false>", "mnn_tile_kmajor_kernel<true, 1>", "mnn_tile_kmajor_kernel<false, 1>",
+           "conv2d_mfma_kernel<2, 2, true, false, false>", "mnn_tile_kmajor_kernel<true>", "mnn_tile_kmajor_kernel<false>",
            "stem7_conv_maxpool_kernel", "stem_conv_maxblur_kernel", "ransac_dlt_kernel<false>", "ransac_dlt_kernel<true>",
            "l2norm_nchw_kernel", "l2norm_nchw_q4_kernel"]
     for k in hot:
