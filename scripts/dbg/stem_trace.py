@@ -1,12 +1,18 @@
-"""Experiment: per-workgroup phase timing of stem7_conv_maxpool_kernel (library built with `make trace`): s_memtime stamps at
-0 start | 1 patch in LDS | 2 after barrier | 3 MFMA phase + C tile done | 4 after barrier | 5 pooled + stored.
-usage: RFX_LIB=ransac-flow_amd/librfx_trace.so python scripts/dbg/stem_trace.py"""
-import ctypes, os, sys
+"""Experiment: per-workgroup phase timing of stem7_conv_maxpool_kernel (library built with `make trace`): s_memtime words per
+workgroup (csrc/stem.hip): 0 start | 1 patch in LDS | 2 after the barrier | 3 sum over the channel groups of MFMA phase + tile
+stores + barrier | 4 sum of pooling pass + stores + barrier | 5 end | 6 channel groups walked.
+Matrix-pipe busy = MFMA cycles of a wave (sub-tiles per wave x 74 MFMAs x 64 cycles, per channel group) / workgroup life x resident
+workgroups per CU (--resident, from profiles/r06_kernel_resources.tsv).
+usage: RFX_LIB=ransac-flow_amd/librfx_trace.so python scripts/dbg/stem_trace.py [--resident 2]"""
+import argparse, ctypes, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "ransac-flow_amd"))
 import torch
 from rfx import _lib, ops, weights
 from rfx.ops import ConvPlan, ACT_RELU
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--resident", type=int, default=2)
+a = ap.parse_args()
 lib = _lib.load()
 dev = torch.device("cuda:0")
 sd = weights.resnet50_trunk_sd(0, randomize_bn=True)
@@ -25,11 +31,14 @@ for (N, H, W) in ((64, 480, 640), (64, 960, 1280)):
     lib.rfx_debug_trace(ctypes.c_void_p(0))
     t = trace.cpu().view(-1, 8)
     t = t[t[:, 5] > 0].double()
-    d = t[:, 1:6] - t[:, 0:5]
-    names = ["load+stage", "barrier1", "mfma+ctile", "barrier2", "pool+store"]
-    tot = (t[:, 5] - t[:, 0])
-    print("%dx%dx%d: %d workgroups, event %.3f ms, ticks per workgroup: total %.0f (p90 %.0f)" % (N, H, W, t.shape[0], e0.elapsed_time(e1), tot.mean(), tot.quantile(0.9)))
-    for k, nm in enumerate(names):
-        print("   %-12s mean %8.0f  p10 %8.0f  p90 %8.0f  (%.1f %%)" % (nm, d[:, k].mean(), d[:, k].quantile(0.1), d[:, k].quantile(0.9), 100 * d[:, k].mean() / tot.mean()))
-    span = t[:, 5].max() - t[:, 0].min()
-    print("   span %.0f ticks -> %.3f GHz-equivalent tick rate; concurrency %.1f workgroups in flight (512 slots)" % (span, span / (e0.elapsed_time(e1) * 1e6), float(tot.sum() / span)))
+    tot = t[:, 5] - t[:, 0]
+    groups = t[:, 6].mean()
+    phases = [("load+stage", t[:, 2] - t[:, 0]), ("mfma+tile", t[:, 3]), ("pool+store", t[:, 4])]
+    print("%dx%dx%d: %d workgroups x %.0f channel groups, event %.3f ms, ticks per workgroup: total %.0f (p90 %.0f)"
+          % (N, H, W, t.shape[0], groups, e0.elapsed_time(e1), tot.mean(), tot.quantile(0.9)))
+    for nm, d in phases:
+        print("   %-12s mean %8.0f  p10 %8.0f  p90 %8.0f  (%.1f %%)" % (nm, d.mean(), d.quantile(0.1), d.quantile(0.9), 100 * d.mean() / tot.mean()))
+    # the matrix work of a wave: 3 sub-tile slots x 74 MFMAs x 64 cycles per channel group (ticks taken as shader cycles, as in
+    # DESIGN_LOG's round-6 entry, where the figure matched the PMC's)
+    mfma_cycles = 3 * 74 * 64 * float(groups)
+    print("   MFMA cycles per wave %.0f -> matrix pipe busy %.3f with %d resident workgroups" % (mfma_cycles, a.resident * mfma_cycles / tot.mean(), a.resident))
