@@ -44,9 +44,10 @@ const char* rfx_version(void);
  * entry points -- mutual NN, feature norm scatter, match gather -- for batches of pairs of different sizes; 12: the ragged forms of the
  * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32; 13:
  * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
- * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32).  A binding
+ * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32; 16:
+ * rfx_group_stats, and the fine-stage entry points record inside a group).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 15
+#define RFX_ABI_VERSION 16
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -54,7 +55,10 @@ int rfx_abi_version(void);
  * sizes.  A single pair runs the trunk on 8 images of 8 sizes (7 pyramid levels + the target,
  * quick_start/coarseAlignFeatMatch.py:92-125): layer by layer that is 8 launches of 2-150 workgroups on 256 CUs, bound
  * by one workgroup lifetime per layer AND level.  Between rfx_group_begin() and rfx_group_end() the convolution entry
- * points (rfx_conv2d_f32, rfx_conv3x3_f32, rfx_conv3x3_conv1x1_f32, rfx_stem_conv7x7_maxpool_f32) validate and RECORD
+ * points (rfx_conv2d_f32, rfx_conv3x3_f32, rfx_conv3x3_conv1x1_f32, rfx_stem_conv7x7_maxpool_f32) and, since ABI 16, the
+ * fine-stage entry points (rfx_stem_conv3x3_maxblur_f32, rfx_blurpool2d_f32, rfx_l2norm_nchw_f32, rfx_flow_head_f32,
+ * rfx_resize_bilinear_f32, rfx_corr_neigh_f32 / _variant_f32 / _bidir_f32, rfx_warp_grid_f32, rfx_grid_sample_f32,
+ * rfx_compose_flow_f32: PredFlowMask over several shape groups as one chain of grouped launches) validate and RECORD
  * their launch instead of issuing it; rfx_group_end(stream) issues, per kernel instance, one launch whose blockIdx.y
  * selects the problem (up to 8 per launch).  The device code of a problem is the single launch's, so results are
  * bit-identical.  Recording is per host thread, groups do not nest, every other entry point launches immediately;
@@ -63,11 +67,15 @@ int rfx_abi_version(void);
  * concurrently on two library-owned side streams forked from / joined to `stream`; rfx_group_side_streams(0) turns that off
  * for the calling host thread (returns the previous setting) -- a caller that already runs several grouped chains on streams
  * of its own (rfx/pipeline.py: the images of a single pair as two chains) wants each chain serial on its stream.
+ * A recorded call may not read what another call of the SAME group writes: all launches are issued at rfx_group_end.
+ * rfx_group_stats: cumulative counts of the calling host thread -- rfx_group_end calls and the kernel launches they issued
+ * (one per kernel instance and chunk of 8 problems); either pointer may be NULL.
  * ------------------------------------------------------------------------------------------ */
 int rfx_group_begin(void);
 int rfx_group_end(void* stream);
 int rfx_group_abort(void);
 int rfx_group_side_streams(int enable);
+int rfx_group_stats(long long* groups, long long* launches);
 
 /* ------------------------------------------------------------------------------------------
  * Convolution family (ResNet-50 conv1..layer3 trunk: model/resnet50.py:68-104,112-169 as used by
@@ -168,7 +176,7 @@ int rfx_maxpool2d_f32(const float* in, float* out, int NC, int Hin, int Win, int
                       int pad, void* stream);
 
 /* Anti-aliased down-sampling (model/downsample.py:12-46, filt_size=3): reflect-pad 1, depthwise
- * [1 2 1]x[1 2 1]/16, stride.  Hout = (Hin-1)/stride+1. */
+ * [1 2 1]x[1 2 1]/16, stride.  Hout = (Hin-1)/stride+1.  Records inside a group (rfx_group_begin). */
 int rfx_blurpool2d_f32(const float* in, float* out, int NC, int Hin, int Win, int stride, void* stream);
 
 /* Fused MaxPool2d(kernel 2, stride 1) + BlurPool(stride): the FeatureExtractor stem `self.maxpool`
@@ -179,7 +187,7 @@ int rfx_maxblurpool2d_f32(const float* in, float* out, int NC, int Hin, int Win,
  * pad 1) + folded BatchNorm + ReLU + MaxPool2d(2, stride 1) + BlurPool(stride 2).  in (N,3,H,W); wT / scale / shift as
  * for rfx_conv2d_f32 (the packed weights of that convolution: K = 27 -> Kpad = 32 rows); out (N,Cout,(H-2)/2+1,(W-2)/2+1).
  * Bit-identical to rfx_conv2d_f32(act = ReLU) followed by rfx_maxblurpool2d_f32(stride 2); the full-resolution
- * Cout-channel map never goes to HBM.  Cout % 32 == 0. */
+ * Cout-channel map never goes to HBM.  Cout % 32 == 0.  Records inside a group (rfx_group_begin). */
 int rfx_stem_conv3x3_maxblur_f32(const float* in, const float* wT, const float* scale, const float* shift, float* out,
                                  int N, int H, int W, int Cout, void* stream);
 
@@ -194,7 +202,8 @@ int rfx_stem_conv7x7_maxpool_f32(const float* in, const float* wT, const float* 
  * quick_start/align2images.py:87-88).  `in` is dense; element (n,c,p) of the result goes to
  * out[n*out_batch_stride + c*out_chan_stride + p] (0 = dense defaults C*HW / HW), which lets the coarse
  * aligner write every pyramid scale straight into the concatenated (C, nA) match matrix
- * (quick_start/coarseAlignFeatMatch.py:108,115).  In-place allowed for the dense case. */
+ * (quick_start/coarseAlignFeatMatch.py:108,115).  In-place allowed for the dense case.  Records inside a group
+ * (rfx_group_begin): the four-wavefront kernel (C % 4 == 0, C >= 32) and the one-wavefront kernel are two kernel instances. */
 int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, int HW, long long out_batch_stride,
                         long long out_chan_stride, void* stream);
 /* (ABI 11) The same norm, sums bit for bit, for the N images of one shape bucket of a ragged batch (quick_start/
@@ -206,12 +215,13 @@ int rfx_l2norm_nchw_scatter_f32(const float* in, float* out, int N, int C, int H
 
 /* NetFlowCoarse tail (model/model.py:228-233): softmax over the K*K logits, expectation of the tap
  * offsets; flow[n,0] = sum_q p_q * gx_q / cols * 2, flow[n,1] = sum_q p_q * gy_q / rows * 2 with
- * q = i*K+j, gx_q = j-K/2, gy_q = i-K/2.  logits (N,K*K,rows,cols) -> flow (N,2,rows,cols). */
+ * q = i*K+j, gx_q = j-K/2, gy_q = i-K/2.  logits (N,K*K,rows,cols) -> flow (N,2,rows,cols).  Records inside a group
+ * (rfx_group_begin). */
 int rfx_flow_head_f32(const float* logits, float* flow, int N, int K, int rows, int cols, void* stream);
 
 /* Bilinear resize of NCHW maps: F.interpolate(mode='bilinear', align_corners=False)
  * (quick_start/align2images.py:92, evaluation/evalHpatch/evaluation.py:37-40) or
- * F.upsample_bilinear (= align_corners=True; model/model.py:234,309). */
+ * F.upsample_bilinear (= align_corners=True; model/model.py:234,309).  Records inside a group (rfx_group_begin). */
 int rfx_resize_bilinear_f32(const float* in, float* out, int NC, int Hin, int Win, int Hout, int Wout,
                             int align_corners, void* stream);
 
@@ -252,7 +262,9 @@ int rfx_corr_neigh_f32(const float* x, const float* y, float* out, int N, int C,
  * returns one of these six): 1 / 2 / 3 = 64 / 32 / 16-row x 16-column tiles; 5 = the tuned 16-row x 80-column kernel (whole
  * 480x640-pair feature-map width: 3 tap groups, hand-pipelined LDS reads, balanced wave map, masked DMA, equal row tiles),
  * 7 / 8 = the tuned kernel with 48- / 64-column tiles.  All six give bit-identical results (channel-ordered fmaf sums).
- * Any other variant -> RFX_E_ARG. */
+ * Any other variant -> RFX_E_ARG.  Records inside a group (rfx_group_begin; also rfx_corr_neigh_f32): every problem keeps the
+ * tile shape it gets alone, problems of different tile shapes (and the plain kernel of W % 4 != 0) are different kernel
+ * instances.  Recording while rfx_corr_timing is enabled -> RFX_E_ARG. */
 int rfx_corr_neigh_variant_f32(const float* x, const float* y, float* out, int N, int C, int H, int W, int K,
                                int variant, void* stream);
 
@@ -264,7 +276,8 @@ int rfx_corr_neigh_variant_f32(const float* x, const float* y, float* out, int N
  * (the same channel-ordered products, so the values are bit-identical to a second rfx_corr_neigh_f32 call), and zero where
  * the source pixel lies outside the image: the kernel stores every accumulator twice instead of reading 2*C*H*W floats a
  * second time -- (2C + 2K^2)*4 bytes per pixel instead of 2*(2C + K^2)*4.  Requires W % 4 == 0, C % 2 == 0 and 16-byte aligned
- * pointers (the host mirror pads other widths with rfx_copy_cols_f32); K must be 7. */
+ * pointers (the host mirror pads other widths with rfx_copy_cols_f32); K must be 7.  Records inside a group (rfx_group_begin) like
+ * rfx_corr_neigh_variant_f32; recording while rfx_corr_timing is enabled -> RFX_E_ARG. */
 int rfx_corr_neigh_bidir_f32(const float* x, const float* y, float* out_xy, float* out_yx, int N, int C, int H, int W, int K,
                              void* stream);
 /* Kernel-duration capture for the roofline of THIS kernel (bench.py): while a host thread has it enabled, every correlation launch of
@@ -279,10 +292,10 @@ int rfx_corr_timing_collect(float* us_out, int cap);
  * Warping (kornia HomographyWarper.warp_grid: quick_start/align2images.py:61,65;
  * F.grid_sample: quick_start/align2images.py:66,95,97, evaluation/evalHpatch/evaluation.py:25,45).
  * ------------------------------------------------------------------------------------------ */
-/* grid[b,y,x,:] = proj( Hm[b] * (lin(x,w), lin(y,h), 1) ),  lin(i,n) = -1 + 2 i/(n-1). */
+/* grid[b,y,x,:] = proj( Hm[b] * (lin(x,w), lin(y,h), 1) ),  lin(i,n) = -1 + 2 i/(n-1).  Records inside a group (rfx_group_begin). */
 int rfx_warp_grid_f32(const float* Hm, float* grid, int B, int h, int w, void* stream);
 
-/* bilinear, zeros padding; input (N,C,Hi,Wi), grid (N,Ho,Wo,2) -> out (N,C,Ho,Wo). */
+/* bilinear, zeros padding; input (N,C,Hi,Wi), grid (N,Ho,Wo,2) -> out (N,C,Ho,Wo).  Records inside a group (rfx_group_begin). */
 int rfx_grid_sample_f32(const float* in, const float* grid, float* out, int N, int C, int Hi, int Wi,
                         int Ho, int Wo, int align_corners, void* stream);
 
@@ -293,7 +306,7 @@ int rfx_grid_sample_f32(const float* in, const float* grid, float* out, int N, i
  * the full-resolution pass of the KITTI driver, which composes at the ORIGINAL image size on a coarse grid of the
  * fine-stage size (evaluation/evalKITTI/evaluation.py:302 with :49-81).  If inb != NULL it
  * receives the in-bounds mask (N,H,W) = (-1<=fx<=1)&(-1<=fy<=1) as 0/1 floats; if flowUp != NULL it
- * receives the (clamped) sampling grid (N,H,W,2). */
+ * receives the (clamped) sampling grid (N,H,W,2).  Records inside a group (rfx_group_begin). */
 int rfx_compose_flow_f32(const float* flowDown, const float* coarseGrid, float* flow12, float* inb,
                          float* flowUp, int N, int hd, int wd, int Hc, int Wc, int H, int W, int clamp, void* stream);
 

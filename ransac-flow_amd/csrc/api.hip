@@ -21,6 +21,7 @@ struct Recorder {
     std::vector<Pending> buckets;  // one per kernel instance, in first-seen order
 };
 thread_local Recorder g_rec;
+thread_local long long g_stat_groups = 0, g_stat_launches = 0;   // rfx_group_stats
 
 // The kernel instances of one group are independent: the second and third run on side streams forked from / joined to the
 // caller's stream with events (also inside a HIP-graph capture, where this becomes a fork/join of the captured graph).
@@ -87,6 +88,7 @@ extern "C" int rfx_group_begin(void) {
 extern "C" int rfx_group_end(void* stream) {
     if (!g_rec.on) return RFX_E_ARG;
     g_rec.on = false;
+    ++g_stat_groups;
     int rc = RFX_OK;
     static const bool dbg = getenv("RFX_GROUP_DEBUG") != nullptr;
     if (dbg) {
@@ -118,6 +120,7 @@ extern "C" int rfx_group_end(void* stream) {
         for (int i = 0; i < n && rc == RFX_OK; i += RFX_MAX_GROUP) {
             const int m = n - i < RFX_MAX_GROUP ? n - i : RFX_MAX_GROUP;
             rc = b.fn(b.blob.data() + (size_t)i * b.arg_size, b.gx.data() + i, m, st);
+            if (rc == RFX_OK) ++g_stat_launches;
         }
         if (rc != RFX_OK) break;
         ++bi;
@@ -141,4 +144,10 @@ extern "C" int rfx_group_side_streams(int enable) {
     const int prev = g_side_on ? 1 : 0;
     g_side_on = enable != 0;
     return prev;
+}
+
+extern "C" int rfx_group_stats(long long* groups, long long* launches) {
+    if (groups) *groups = g_stat_groups;
+    if (launches) *launches = g_stat_launches;
+    return RFX_OK;
 }

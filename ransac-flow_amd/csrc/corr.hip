@@ -27,6 +27,7 @@
 //
 // Requires W % 4 == 0 for the 16-byte DMA path; other widths use the plain fallback kernel below.
 #include "common.h"
+#include "group.h"
 #include <hip/hip_ext.h>
 #include <vector>
 
@@ -294,10 +295,20 @@ __device__ __forceinline__ void corr7_strip(f32x4* smem, const float* xn, const 
     }
 }
 
+// Argument block of the DMA kernels.  The body is a typed device function of (arguments, the problem's own block index): the single
+// launch and the grouped launch (group.h) both call it.
+struct CorrArgs {
+    const float* x; const float* y; float* out; float* out21;
+    int N, C, H, W, tilesR, tilesC, trv;
+};
+
 template <class G>
-__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, float* __restrict__ out21, int N, int C,
-    int H, int W, int tilesR, int tilesC, int trv) {
+__device__ __forceinline__ void corr7_dma_body(const CorrArgs& a, const unsigned bx) {
+    const float* __restrict__ x = a.x;
+    const float* __restrict__ y = a.y;
+    float* __restrict__ out = a.out;
+    float* __restrict__ out21 = a.out21;
+    const int N = a.N, C = a.C, H = a.H, W = a.W, tilesR = a.tilesR, tilesC = a.tilesC, trv = a.trv;
     constexpr int TR = G::TR, NCB = G::NCB, NG = G::NG;
     __shared__ __attribute__((aligned(16))) f32x4 smem[G::NS * G::BUF_SLOTS];
 
@@ -305,9 +316,11 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int tpi = tilesR * tilesC;
     const int nwg = N * tpi;
-    int bid = blockIdx.x;
+    int bid = (int)bx;
     {   // XCD-aware bijective remap: all tiles of one image on one XCD (halo re-reads hit that L2).  xcd_remap() (common.h) written
-        // out: through the helper the six 16-column-tile instances compile to different set-up code
+        // out: through the helper the six 16-column-tile instances compile to different set-up code.  nwg is the PROBLEM's own
+        // workgroup count, also in a grouped launch (whose gridDim.x is the largest problem's): the map stays a bijection of
+        // [0, nwg); there it is a locality hint only (workgroups of the other problems share the XCD round-robin)
         const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
     }
@@ -378,21 +391,50 @@ __global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_k
 }
 
 template <class G>
-static void launch_corr(const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W, hipStream_t st) {
+__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_kernel(CorrArgs a) {
+    corr7_dma_body<G>(a, blockIdx.x);
+}
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block.  One bucket per tile variant: a
+// problem keeps the variant auto_variant() gives it alone.
+template <class G>
+__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_group_kernel(RfxGroupArgs<CorrArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    corr7_dma_body<G>(g.p[y], blockIdx.x);
+}
+
+template <class G>
+static int corr_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<CorrArgs>(corr7_dma_group_kernel<G>, G::NW * 64, blob, gx, n, st);
+}
+
+template <class G>
+static int launch_corr(const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W, hipStream_t st) {
     const int tilesR = (H + G::TR - 1) / G::TR;
     const int tilesC = (W + TC * G::NCB - 1) / (TC * G::NCB);
     const int trv = G::TUNED ? (H + tilesR - 1) / tilesR : G::TR;  // equal row tiles (60 = 4 x 15) or full TR-row tiles
-    corr_launch((corr7_dma_kernel<G>), dim3((unsigned)(N * tilesR * tilesC)), dim3(G::NW * 64), st, x, y, out,
-                       out21, N, C, H, W, tilesR, tilesC, trv);
+    const CorrArgs a = {x, y, out, out21, N, C, H, W, tilesR, tilesC, trv};
+    const unsigned nwg = (unsigned)(N * tilesR * tilesC);
+    if (rfx_group_recording()) return rfx_group_record(&corr_group_launch<G>, &a, sizeof(a), nwg);   // never with t_timing: entry points
+    corr_launch((corr7_dma_kernel<G>), dim3(nwg), dim3(G::NW * 64), st, a);
+    return RFX_OK;
 }
 
 // Plain fallback for widths that are not a multiple of 4 (never hit by the reference's /8 feature maps of
 // x16-rounded images, kept so the entry point is total): one thread per output pixel.
-__global__ __launch_bounds__(256) void corr7_plain_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                          float* __restrict__ out, long long NP, int C, int H, int W) {
+struct CorrPlainArgs { const float* x; const float* y; float* out; long long NP; int C, H, W; };
+
+// (grid-stride by the problem's own grid gx: in a grouped launch gridDim.x is the largest problem's)
+__device__ __forceinline__ void corr7_plain_body(const CorrPlainArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ x = a.x;
+    const float* __restrict__ y = a.y;
+    float* __restrict__ out = a.out;
+    const long long NP = a.NP;
+    const int C = a.C, H = a.H, W = a.W;
     const size_t HW = (size_t)H * W;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < NP;
-         p += (long long)gridDim.x * blockDim.x) {
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < NP;
+         p += (long long)gx * blockDim.x) {
         const long long n = p / HW;
         const int px = (int)(p - n * HW);
         const int r = px / W, c = px - r * W;
@@ -410,6 +452,18 @@ __global__ __launch_bounds__(256) void corr7_plain_kernel(const float* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void corr7_plain_kernel(CorrPlainArgs a) { corr7_plain_body(a, blockIdx.x, gridDim.x); }
+
+__global__ __launch_bounds__(256) void corr7_plain_group_kernel(RfxGroupArgs<CorrPlainArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    corr7_plain_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int corr_plain_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<CorrPlainArgs>(corr7_plain_group_kernel, 256, blob, gx, n, st);
+}
+
 // Variant table (rfx_corr_neigh_variant_f32 / RFX_CORR_VARIANT; 0 = automatic): the six tile shapes auto_variant() returns.
 // All are bit-identical; every other number is RFX_E_ARG.  BIDIR: the form that also writes corr(y, x) to out21.
 //   1: 64x16   2: 32x16   3: 16x16      plain 16-column tiles
@@ -418,15 +472,14 @@ template <bool BIDIR>
 static int launch_variant(int v, const float* x, const float* y, float* out, float* out21, int N, int C, int H, int W,
                           hipStream_t st) {
     switch (v) {
-        case 1: launch_corr<Cfg<64, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
-        case 2: launch_corr<Cfg<32, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
-        case 3: launch_corr<Cfg<16, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
-        case 5: launch_corr<Cfg<16, 5, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
-        case 7: launch_corr<Cfg<16, 3, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
-        case 8: launch_corr<Cfg<16, 4, true, BIDIR>>(x, y, out, out21, N, C, H, W, st); break;
+        case 1: return launch_corr<Cfg<64, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st);
+        case 2: return launch_corr<Cfg<32, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st);
+        case 3: return launch_corr<Cfg<16, 1, false, BIDIR>>(x, y, out, out21, N, C, H, W, st);
+        case 5: return launch_corr<Cfg<16, 5, true, BIDIR>>(x, y, out, out21, N, C, H, W, st);
+        case 7: return launch_corr<Cfg<16, 3, true, BIDIR>>(x, y, out, out21, N, C, H, W, st);
+        case 8: return launch_corr<Cfg<16, 4, true, BIDIR>>(x, y, out, out21, N, C, H, W, st);
         default: return RFX_E_ARG;
     }
-    return RFX_OK;
 }
 
 // Tile shape by traffic first, parallelism second.  A tile spanning the image width has no column halo and its row-halo
@@ -460,6 +513,7 @@ extern "C" int rfx_corr_neigh_variant_f32(const float* x, const float* y, float*
                                           int variant, void* stream) {
     if (!x || !y || !out || N <= 0 || C <= 0 || H <= 0 || W <= 0) return RFX_E_ARG;
     if (K != 7) return RFX_E_ARG;
+    if (rfx_group_recording() && t_timing) return RFX_E_ARG;        // the dispatch-event capture belongs to single launches
     if ((long long)C * H * W > 0x7fffffffLL) return RFX_E_LIMIT;
     hipStream_t st = rfx_stream(stream);
     if (dma_ok(x, y, out, nullptr, C, W)) {
@@ -470,7 +524,9 @@ extern "C" int rfx_corr_neigh_variant_f32(const float* x, const float* y, float*
         const long long NP = (long long)N * H * W;
         long long g = (NP + 255) / 256;
         if (g > 8192) g = 8192;
-        hipLaunchKernelGGL(corr7_plain_kernel, dim3((unsigned)g), dim3(256), 0, st, x, y, out, NP, C, H, W);
+        const CorrPlainArgs a = {x, y, out, NP, C, H, W};
+        if (rfx_group_recording()) return rfx_group_record(&corr_plain_group_launch, &a, sizeof(a), (unsigned)g);
+        hipLaunchKernelGGL(corr7_plain_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
     }
     RFX_LAUNCH_CHECK();
     return RFX_OK;
@@ -485,6 +541,7 @@ extern "C" int rfx_corr_neigh_bidir_f32(const float* x, const float* y, float* o
                                         int K, void* stream) {
     if (!x || !y || !out_xy || !out_yx || N <= 0 || C <= 0 || H <= 0 || W <= 0) return RFX_E_ARG;
     if (K != 7) return RFX_E_ARG;
+    if (rfx_group_recording() && t_timing) return RFX_E_ARG;        // the dispatch-event capture belongs to single launches
     if ((long long)C * H * W > 0x7fffffffLL) return RFX_E_LIMIT;
     if (!dma_ok(x, y, out_xy, out_yx, C, W)) return RFX_E_ARG;       // the host mirrors pad the width to a multiple of 4
     if ((long long)N * ((H + 15) / 16) * ((W + TC - 1) / TC) > 0x7fffffffLL) return RFX_E_LIMIT;

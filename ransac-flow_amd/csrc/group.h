@@ -3,7 +3,7 @@
 // A single 480x640 pair runs the ResNet-50 trunk on 8 images of 8 different sizes (7 pyramid levels + the target,
 // quick_start/coarseAlignFeatMatch.py:92-125).  Layer by layer that is 8 launches of 2-150 workgroups each on 256 CUs: the
 // pass is bound by one workgroup lifetime per layer AND level.  Between rfx_group_begin() and rfx_group_end() the
-// convolution entry points do not launch; they record (kernel instance, argument block, grid), and rfx_group_end() issues,
+// convolution entry points, the two stems and the fine-stage kernels (warp.hip, pool.hip, corr.hip) do not launch; they record (kernel instance, argument block, grid), and rfx_group_end() issues,
 // per kernel instance, ONE launch whose blockIdx.y selects the problem (argument block p[blockIdx.y], workgroups past that
 // problem's own grid exit at once).  The device code of a problem is the single-launch kernel's body, unchanged: results are
 // bit-identical by construction.  Everything recorded in one group must be mutually independent.
@@ -26,6 +26,7 @@ int rfx_group_record(rfx_group_launch_fn fn, const void* args, size_t arg_size, 
 // Generic launcher body for a grouped kernel K(RfxGroupArgs<A>) with BLOCK threads.
 template <class A, class K>
 static int rfx_group_launch_impl(K kernel, int block, const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    static_assert(sizeof(RfxGroupArgs<A>) <= 2048, "grouped argument block: keep it well under the 4 KB kernarg limit");
     RfxGroupArgs<A> g;
     unsigned gmax = 0;
     const A* src = static_cast<const A*>(blob);

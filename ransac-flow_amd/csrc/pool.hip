@@ -7,6 +7,7 @@
 // One thread per output element, consecutive threads along W (coalesced); grids are capped and
 // grid-strided.  All arithmetic fp32 with the operation order of the ATen CPU kernels.
 #include "common.h"
+#include "group.h"
 #include <math.h>
 
 static inline int grid_for(long long total, int block) {
@@ -58,13 +59,24 @@ __device__ __forceinline__ int reflect1(int i, int n) {  // ReflectionPad2d(1): 
     return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
 }
 
-__global__ __launch_bounds__(256) void blurpool2d_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                         long long total, int Hin, int Win, int Hout, int Wout,
-                                                         int stride) {
+// The kernels that also run grouped (group.h) have their body in a typed device function of (argument block, the problem's own
+// block index bx, the problem's own grid gx): the grid-stride loops stride by gx -- in a grouped launch gridDim.x is the LARGEST
+// problem's grid.
+struct PlaneArgs { const float* in; float* out; long long total; int Hin, Win, Hout, Wout, stride; };      // blurpool
+struct L2NormArgs { const float* in; float* out; long long NP; int C, HW; long long obs, ocs; };
+struct FlowHeadArgs { const float* logits; float* flow; long long NP; int K, rows, cols; };
+struct ResizeArgs { const float* in; float* out; long long total; int Hin, Win, Hout, Wout; float sh, sw; int align; };
+
+__device__ __forceinline__ void blurpool2d_body(const PlaneArgs& a, const unsigned bx, const unsigned gx) {
+    const long long total = a.total;
+    const int Hin = a.Hin, Win = a.Win, Hout = a.Hout, Wout = a.Wout, stride = a.stride;
     // depthwise 3x3 filter [1 2 1]^T [1 2 1] / 16 accumulated in the (kh, kw) order of a direct conv
     const float w[3] = {0.25f, 0.5f, 0.25f};
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
+    // (the pointers enter the loop as restrict-qualified parameters, like the kernel arguments they were: the loop keeps its
+    // two-pixel unrolled form with all loads ahead of the stores)
+    [&](const float* __restrict__ in, float* __restrict__ out) {
+    for (long long idx = (long long)bx * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gx * blockDim.x) {
         const int ow = (int)(idx % Wout);
         const long long r = idx / Wout;
         const int oh = (int)(r % Hout);
@@ -82,14 +94,30 @@ __global__ __launch_bounds__(256) void blurpool2d_kernel(const float* __restrict
         }
         out[idx] = acc;
     }
+    }(a.in, a.out);
+}
+
+__global__ __launch_bounds__(256) void blurpool2d_kernel(PlaneArgs a) { blurpool2d_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
+__global__ __launch_bounds__(256) void blurpool2d_group_kernel(RfxGroupArgs<PlaneArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    blurpool2d_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int blurpool2d_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<PlaneArgs>(blurpool2d_group_kernel, 256, blob, gx, n, st);
 }
 
 extern "C" int rfx_blurpool2d_f32(const float* in, float* out, int NC, int Hin, int Win, int stride, void* stream) {
     if (!in || !out || NC <= 0 || Hin < 2 || Win < 2 || stride <= 0) return RFX_E_ARG;
     const int Hout = (Hin + 2 - 3) / stride + 1, Wout = (Win + 2 - 3) / stride + 1;
     const long long total = (long long)NC * Hout * Wout;
-    hipLaunchKernelGGL(blurpool2d_kernel, dim3(grid_for(total, 256)), dim3(256), 0, rfx_stream(stream), in, out,
-                       total, Hin, Win, Hout, Wout, stride);
+    const PlaneArgs a = {in, out, total, Hin, Win, Hout, Wout, stride};
+    const unsigned gx = (unsigned)grid_for(total, 256);
+    if (rfx_group_recording()) return rfx_group_record(&blurpool2d_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(blurpool2d_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -255,10 +283,13 @@ extern "C" int rfx_maxblurpool2d_f32(const float* in, float* out, int NC, int Hi
 // it outweighs the convolution round-off (whose effect on a score averages down to ~2e-8) by an order of magnitude: the reference's
 // own two executions share the chain's rounding pattern almost entirely, the device's four-chain norm did not -- this, not the trunk,
 // was the bulk of the device's excess arg-max near-tie flips.
-__global__ __launch_bounds__(64) void l2norm_nchw_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                         long long NP, int C, int HW, long long obs, long long ocs) {
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < NP;
-         p += (long long)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void l2norm_nchw_body(const L2NormArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ in = a.in;
+    float* __restrict__ out = a.out;
+    const long long NP = a.NP, obs = a.obs, ocs = a.ocs;
+    const int C = a.C, HW = a.HW;
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < NP;
+         p += (long long)gx * blockDim.x) {
         const long long n = p / HW;
         const int px = (int)(p - n * HW);
         const float* src = in + (size_t)n * C * HW + px;
@@ -279,17 +310,34 @@ __global__ __launch_bounds__(64) void l2norm_nchw_kernel(const float* __restrict
     }
 }
 
+__global__ __launch_bounds__(64) void l2norm_nchw_kernel(L2NormArgs a) { l2norm_nchw_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
+__global__ __launch_bounds__(64) void l2norm_nchw_group_kernel(RfxGroupArgs<L2NormArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    l2norm_nchw_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int l2norm_nchw_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<L2NormArgs>(l2norm_nchw_group_kernel, 64, blob, gx, n, st);
+}
+
 // Same arithmetic with four wavefronts per 64 pixels doing the LOADS (wavefront q fetches the channels c = q (mod 4), 32 loads in
 // flight per thread: on the trunk's 1-5 k-pixel maps the kernel is pure load latency) while the chain itself stays ONE chain: the
 // values of 128 consecutive channels go through a 32 KB LDS tile and wavefront 0 walks them in channel order.  Bit-identical to the
 // kernel above.  The division pass is shared out over the four wavefronts again.
-__global__ __launch_bounds__(256) void l2norm_nchw_q4_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                             long long NP, int C, int HW, long long obs, long long ocs) {
+// (one workgroup per 64 pixels, no grid-stride loop: the grid argument of the common body signature is unused)
+__device__ __forceinline__ void l2norm_nchw_q4_body(const L2NormArgs& a, const unsigned bx, const unsigned) {
+    const float* __restrict__ in = a.in;
+    float* __restrict__ out = a.out;
+    const long long NP = a.NP, obs = a.obs, ocs = a.ocs;
+    const int C = a.C, HW = a.HW;
     constexpr int CB = 128;                        // channels per LDS block
     __shared__ float tile[CB][64];
     __shared__ float nrm_s[64];
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const long long p = (long long)blockIdx.x * 64 + lane;
+    const long long p = (long long)bx * 64 + lane;
     const bool pv = p < NP;
     const long long pc = pv ? p : 0;
     const long long n = pc / HW;
@@ -331,6 +379,19 @@ __global__ __launch_bounds__(256) void l2norm_nchw_q4_kernel(const float* __rest
         for (int u = 0; u < 8; ++u) dst[(size_t)(c + 4 * u) * ocs] = __fdiv_rn(v[u], d);
     }
     for (; c < C; c += 4) dst[(size_t)c * ocs] = __fdiv_rn(src[(size_t)c * HW], d);
+}
+
+__global__ __launch_bounds__(256) void l2norm_nchw_q4_kernel(L2NormArgs a) { l2norm_nchw_q4_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
+__global__ __launch_bounds__(256) void l2norm_nchw_q4_group_kernel(RfxGroupArgs<L2NormArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    l2norm_nchw_q4_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int l2norm_nchw_q4_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<L2NormArgs>(l2norm_nchw_q4_group_kernel, 256, blob, gx, n, st);
 }
 
 // The norm of l2norm_nchw_q4_kernel for the N images of one shape bucket of a ragged batch, image n written to out + dst_off[n]
@@ -393,14 +454,18 @@ extern "C" int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, in
     const long long NP = (long long)N * HW;
     const long long ocs = out_chan_stride ? out_chan_stride : HW;
     const long long obs = out_batch_stride ? out_batch_stride : (long long)C * HW;
+    const L2NormArgs a = {in, out, NP, C, HW, obs, ocs};
+    const bool recording = rfx_group_recording();
     if (C % 4 == 0 && C >= 32 && (NP + 63) / 64 <= 0x7fffffffLL) {
-        hipLaunchKernelGGL(l2norm_nchw_q4_kernel, dim3((unsigned)((NP + 63) / 64)), dim3(256), 0, rfx_stream(stream), in, out,
-                           NP, C, HW, obs, ocs);
+        const unsigned gx = (unsigned)((NP + 63) / 64);
+        if (recording) return rfx_group_record(&l2norm_nchw_q4_group_launch, &a, sizeof(a), gx);
+        hipLaunchKernelGGL(l2norm_nchw_q4_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
         RFX_LAUNCH_CHECK();
         return RFX_OK;
     }
-    hipLaunchKernelGGL(l2norm_nchw_kernel, dim3(grid_for(NP, 64)), dim3(64), 0, rfx_stream(stream), in, out, NP, C, HW,
-                       obs, ocs);
+    const unsigned gx = (unsigned)grid_for(NP, 64);
+    if (recording) return rfx_group_record(&l2norm_nchw_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(l2norm_nchw_kernel, dim3(gx), dim3(64), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -419,11 +484,14 @@ extern "C" int rfx_l2norm_nchw_scatter_f32(const float* in, float* out, int N, i
 
 // softmax over K*K taps + expectation of the tap offsets.  One thread per pixel; the K*K logits of a
 // pixel are HW apart (coalesced across the wave).  K*K <= 64 logits are kept in registers.
-__global__ __launch_bounds__(256) void flow_head_kernel(const float* __restrict__ logits, float* __restrict__ flow,
-                                                        long long NP, int K, int rows, int cols) {
+__device__ __forceinline__ void flow_head_body(const FlowHeadArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ logits = a.logits;
+    float* __restrict__ flow = a.flow;
+    const long long NP = a.NP;
+    const int K = a.K, rows = a.rows, cols = a.cols;
     const int HW = rows * cols, KK = K * K, half = K / 2;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < NP;
-         p += (long long)gridDim.x * blockDim.x) {
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < NP;
+         p += (long long)gx * blockDim.x) {
         const long long n = p / HW;
         const int px = (int)(p - n * HW);
         const float* src = logits + (size_t)n * KK * HW + px;
@@ -447,11 +515,26 @@ __global__ __launch_bounds__(256) void flow_head_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void flow_head_kernel(FlowHeadArgs a) { flow_head_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
+__global__ __launch_bounds__(256) void flow_head_group_kernel(RfxGroupArgs<FlowHeadArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    flow_head_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int flow_head_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<FlowHeadArgs>(flow_head_group_kernel, 64, blob, gx, n, st);
+}
+
 extern "C" int rfx_flow_head_f32(const float* logits, float* flow, int N, int K, int rows, int cols, void* stream) {
     if (!logits || !flow || N <= 0 || K <= 0 || (K & 1) == 0 || rows <= 0 || cols <= 0) return RFX_E_ARG;
     const long long NP = (long long)N * rows * cols;
-    hipLaunchKernelGGL(flow_head_kernel, dim3(grid_for(NP, 64)), dim3(64), 0, rfx_stream(stream), logits, flow, NP, K,
-                       rows, cols);
+    const FlowHeadArgs a = {logits, flow, NP, K, rows, cols};
+    const unsigned gx = (unsigned)grid_for(NP, 64);
+    if (rfx_group_recording()) return rfx_group_record(&flow_head_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(flow_head_kernel, dim3(gx), dim3(64), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -463,11 +546,15 @@ __device__ __forceinline__ float src_index(float scale, int dst, bool align_corn
     return s < 0.f ? 0.f : s;
 }
 
-__global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                              long long total, int Hin, int Win, int Hout, int Wout,
-                                                              float sh, float sw, int align) {
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void resize_bilinear_body(const ResizeArgs& a, const unsigned bx, const unsigned gx) {
+    const long long total = a.total;
+    const int Hin = a.Hin, Win = a.Win, Hout = a.Hout, Wout = a.Wout, align = a.align;
+    const float sh = a.sh, sw = a.sw;
+    // (the pointers enter the loop as restrict-qualified parameters, like the kernel arguments they were: the loop keeps its
+    // two-pixel unrolled form with all loads ahead of the stores)
+    [&](const float* __restrict__ in, float* __restrict__ out) {
+    for (long long idx = (long long)bx * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gx * blockDim.x) {
         const int ox = (int)(idx % Wout);
         const long long r = idx / Wout;
         const int oy = (int)(r % Hout);
@@ -486,6 +573,20 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
         const float r1 = fmaf(v11, lx, __fmul_rn(v10, hx));
         out[idx] = fmaf(r1, ly, __fmul_rn(r0, hy));
     }
+    }(a.in, a.out);
+}
+
+__global__ __launch_bounds__(256) void resize_bilinear_kernel(ResizeArgs a) { resize_bilinear_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
+__global__ __launch_bounds__(256) void resize_bilinear_group_kernel(RfxGroupArgs<ResizeArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    resize_bilinear_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int resize_bilinear_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<ResizeArgs>(resize_bilinear_group_kernel, 256, blob, gx, n, st);
 }
 
 extern "C" int rfx_resize_bilinear_f32(const float* in, float* out, int NC, int Hin, int Win, int Hout, int Wout,
@@ -500,8 +601,10 @@ extern "C" int rfx_resize_bilinear_f32(const float* in, float* out, int NC, int 
         sw = (float)Win / (float)Wout;
     }
     const long long total = (long long)NC * Hout * Wout;
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_for(total, 256)), dim3(256), 0, rfx_stream(stream), in, out,
-                       total, Hin, Win, Hout, Wout, sh, sw, align_corners);
+    const ResizeArgs a = {in, out, total, Hin, Win, Hout, Wout, sh, sw, align_corners};
+    const unsigned gx = (unsigned)grid_for(total, 256);
+    if (rfx_group_recording()) return rfx_group_record(&resize_bilinear_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

@@ -52,13 +52,13 @@ __device__ __forceinline__ float umaxf(float x, float y) {
     return __uint_as_float(a > b ? a : b);
 }
 
-__global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
+__device__ __forceinline__ void stem_conv_maxblur_body(const StemArgs& a, const unsigned bx) {
     __shared__ float P[3][PRW][PCL];          // input patch
     __shared__ float C[MCH * CPS];            // conv + BN + ReLU outputs of ONE channel group under the tile: [channel][CR][CST], planes CPS apart
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int lrow = lane >> 5, lcol = lane & 31;
-    int bid = blockIdx.x;                                     // one workgroup per pooled tile, all channel groups
+    int bid = (int)bx;                                        // one workgroup per pooled tile, all channel groups
     const int tw = bid % a.tilesW; bid /= a.tilesW;
     const int th = bid % a.tilesH;
     const int n = bid / a.tilesH;
@@ -203,6 +203,21 @@ __global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
     }
     __syncthreads();                                  // the next group overwrites C
     }
+}
+
+__global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
+    stem_conv_maxblur_body(a, blockIdx.x);
+}
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block
+__global__ __launch_bounds__(256) void stem_conv_maxblur_group_kernel(RfxGroupArgs<StemArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    stem_conv_maxblur_body(g.p[y], blockIdx.x);
+}
+
+static int stem3_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<StemArgs>(stem_conv_maxblur_group_kernel, 256, blob, gx, n, st);
 }
 
 
@@ -448,6 +463,7 @@ extern "C" int rfx_stem_conv3x3_maxblur_f32(const float* in, const float* wT, co
     a.tilesH = (a.Ho + TH - 1) / TH; a.tilesW = (a.Wo + TW - 1) / TW; a.chGroups = Cout / MCH;
     const long long nwg = (long long)N * a.tilesH * a.tilesW;      // a workgroup walks all channel groups of its tile
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
+    if (rfx_group_recording()) return rfx_group_record(&stem3_group_launch, &a, sizeof(a), (unsigned)nwg);
     hipLaunchKernelGGL(stem_conv_maxblur_kernel, dim3((unsigned)nwg), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;

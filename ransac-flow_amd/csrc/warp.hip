@@ -8,6 +8,7 @@
 // All HBM-bound gathers: one thread per output pixel, consecutive threads along W; channels looped in
 // the thread so the 4 corner offsets / weights are computed once per pixel.
 #include "common.h"
+#include "group.h"
 #include <math.h>
 
 namespace {
@@ -53,10 +54,24 @@ __device__ __forceinline__ Corners corners(float gx, float gy, int Hi, int Wi, i
     return c;
 }
 
-__global__ __launch_bounds__(256) void warp_grid_kernel(const float* __restrict__ Hm, float* __restrict__ grid,
-                                                        long long total, int h, int w) {
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
+// Argument blocks of the three fine-stage kernels.  Each kernel body is a typed device function of (arguments, the problem's own
+// block index bx, the problem's own grid gx): the single launch passes blockIdx.x / gridDim.x, the grouped launch (group.h) passes
+// blockIdx.x / the grid the problem recorded -- the grid-stride loops stride by THAT, not by the launch's gridDim.x, which is the
+// largest problem's.
+struct WarpGridArgs { const float* Hm; float* grid; long long total; int h, w; };
+struct GridSampleArgs { const float* in; const float* grid; float* out; long long NP; int C, Hi, Wi, Ho, Wo, align; };
+struct ComposeFlowArgs {
+    const float* flowDown; const float* coarse; float* flow12; float* inb; float* flowUp;
+    long long NP; int hd, wd, Hc, Wc, H, W; float sh, sw; int clampf;
+};
+
+__device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ Hm = a.Hm;
+    float* __restrict__ grid = a.grid;
+    const long long total = a.total;
+    const int h = a.h, w = a.w;
+    for (long long idx = (long long)bx * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gx * blockDim.x) {
         const int x = (int)(idx % w);
         const long long r = idx / w;
         const int y = (int)(r % h);
@@ -74,12 +89,24 @@ __global__ __launch_bounds__(256) void warp_grid_kernel(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void grid_sample_kernel(const float* __restrict__ in, const float* __restrict__ grid,
-                                                          float* __restrict__ out, long long NP, int C, int Hi, int Wi,
-                                                          int Ho, int Wo, int align) {
+__global__ __launch_bounds__(256) void warp_grid_kernel(WarpGridArgs a) { warp_grid_body(a, blockIdx.x, gridDim.x); }
+
+// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and grid
+__global__ __launch_bounds__(256) void warp_grid_group_kernel(RfxGroupArgs<WarpGridArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    warp_grid_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+__device__ __forceinline__ void grid_sample_body(const GridSampleArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ in = a.in;
+    const float* __restrict__ grid = a.grid;
+    float* __restrict__ out = a.out;
+    const long long NP = a.NP;
+    const int C = a.C, Hi = a.Hi, Wi = a.Wi, Ho = a.Ho, Wo = a.Wo, align = a.align;
     const size_t HWi = (size_t)Hi * Wi, HWo = (size_t)Ho * Wo;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < NP;
-         p += (long long)gridDim.x * blockDim.x) {
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < NP;
+         p += (long long)gx * blockDim.x) {
         const long long n = p / (long long)HWo;
         const size_t px = (size_t)(p - n * (long long)HWo);
         const float2 g = reinterpret_cast<const float2*>(grid)[p];
@@ -99,19 +126,31 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(const float* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void grid_sample_kernel(GridSampleArgs a) { grid_sample_body(a, blockIdx.x, gridDim.x); }
+
+__global__ __launch_bounds__(256) void grid_sample_group_kernel(RfxGroupArgs<GridSampleArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    grid_sample_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
 __device__ __forceinline__ float src_index(float scale, int dst) {  // align_corners=False
     const float s = scale * ((float)dst + 0.5f) - 0.5f;
     return s < 0.f ? 0.f : s;
 }
 
-__global__ __launch_bounds__(256) void compose_flow_kernel(const float* __restrict__ flowDown,
-                                                           const float* __restrict__ coarse, float* __restrict__ flow12,
-                                                           float* __restrict__ inb, float* __restrict__ flowUp,
-                                                           long long NP, int hd, int wd, int Hc, int Wc, int H, int W,
-                                                           float sh, float sw, int clampf) {
+__device__ __forceinline__ void compose_flow_body(const ComposeFlowArgs& a, const unsigned bx, const unsigned gx) {
+    const float* __restrict__ flowDown = a.flowDown;
+    const float* __restrict__ coarse = a.coarse;
+    float* __restrict__ flow12 = a.flow12;
+    float* __restrict__ inb = a.inb;
+    float* __restrict__ flowUp = a.flowUp;
+    const long long NP = a.NP;
+    const int hd = a.hd, wd = a.wd, Hc = a.Hc, Wc = a.Wc, H = a.H, W = a.W, clampf = a.clampf;
+    const float sh = a.sh, sw = a.sw;
     const size_t HW = (size_t)H * W, hw = (size_t)hd * wd, HWc = (size_t)Hc * Wc;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < NP;
-         p += (long long)gridDim.x * blockDim.x) {
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < NP;
+         p += (long long)gx * blockDim.x) {
         const long long n = p / (long long)HW;
         const int px = (int)(p - n * (long long)HW);
         const int y = px / W, x = px - y * W;
@@ -151,6 +190,24 @@ __global__ __launch_bounds__(256) void compose_flow_kernel(const float* __restri
         reinterpret_cast<float2*>(flow12)[p] = o;
         if (inb) inb[p] = (ox >= -1.0f && ox <= 1.0f && oy >= -1.0f && oy <= 1.0f) ? 1.0f : 0.0f;
     }
+}
+
+__global__ __launch_bounds__(256) void compose_flow_kernel(ComposeFlowArgs a) { compose_flow_body(a, blockIdx.x, gridDim.x); }
+
+__global__ __launch_bounds__(256) void compose_flow_group_kernel(RfxGroupArgs<ComposeFlowArgs> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    compose_flow_body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+static int warp_grid_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<WarpGridArgs>(warp_grid_group_kernel, 256, blob, gx, n, st);
+}
+static int grid_sample_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<GridSampleArgs>(grid_sample_group_kernel, 256, blob, gx, n, st);
+}
+static int compose_flow_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+    return rfx_group_launch_impl<ComposeFlowArgs>(compose_flow_group_kernel, 256, blob, gx, n, st);
 }
 
 // Multi-homography merge of the offline flow assembly (evaluation/evalHpatch/getResults.py:48-61,
@@ -231,7 +288,10 @@ __global__ __launch_bounds__(256) void flow_grad_clamp_kernel(const float* __res
 extern "C" int rfx_warp_grid_f32(const float* Hm, float* grid, int B, int h, int w, void* stream) {
     if (!Hm || !grid || B <= 0 || h <= 0 || w <= 0) return RFX_E_ARG;
     const long long total = (long long)B * h * w;
-    hipLaunchKernelGGL(warp_grid_kernel, dim3(grid_for(total, 256)), dim3(256), 0, rfx_stream(stream), Hm, grid, total, h, w);
+    const WarpGridArgs a = {Hm, grid, total, h, w};
+    const unsigned gx = (unsigned)grid_for(total, 256);
+    if (rfx_group_recording()) return rfx_group_record(&warp_grid_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(warp_grid_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -240,8 +300,10 @@ extern "C" int rfx_grid_sample_f32(const float* in, const float* grid, float* ou
                                    int Ho, int Wo, int align_corners, void* stream) {
     if (!in || !grid || !out || N <= 0 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return RFX_E_ARG;
     const long long NP = (long long)N * Ho * Wo;
-    hipLaunchKernelGGL(grid_sample_kernel, dim3(grid_for(NP, 256)), dim3(256), 0, rfx_stream(stream), in, grid, out, NP,
-                       C, Hi, Wi, Ho, Wo, align_corners);
+    const GridSampleArgs a = {in, grid, out, NP, C, Hi, Wi, Ho, Wo, align_corners};
+    const unsigned gx = (unsigned)grid_for(NP, 256);
+    if (rfx_group_recording()) return rfx_group_record(&grid_sample_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(grid_sample_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
@@ -253,8 +315,10 @@ extern "C" int rfx_compose_flow_f32(const float* flowDown, const float* coarseGr
         return RFX_E_ARG;
     const long long NP = (long long)N * H * W;
     const float sh = (float)hd / (float)H, sw = (float)wd / (float)W;
-    hipLaunchKernelGGL(compose_flow_kernel, dim3(grid_for(NP, 256)), dim3(256), 0, rfx_stream(stream), flowDown,
-                       coarseGrid, flow12, inb, flowUp, NP, hd, wd, Hc, Wc, H, W, sh, sw, clamp);
+    const ComposeFlowArgs a = {flowDown, coarseGrid, flow12, inb, flowUp, NP, hd, wd, Hc, Wc, H, W, sh, sw, clamp};
+    const unsigned gx = (unsigned)grid_for(NP, 256);
+    if (rfx_group_recording()) return rfx_group_record(&compose_flow_group_launch, &a, sizeof(a), gx);
+    hipLaunchKernelGGL(compose_flow_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

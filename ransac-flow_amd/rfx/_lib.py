@@ -19,6 +19,7 @@ SIGNATURES = {
     "rfx_group_end": (c_int, [c_void_p]),
     "rfx_group_abort": (c_int, []),
     "rfx_group_side_streams": (c_int, [c_int]),
+    "rfx_group_stats": (c_int, [c_void_p, c_void_p]),
     "rfx_conv2d_f32": (c_int, [c_void_p] * 7 + [c_int] * 10 + [c_void_p]),
     "rfx_conv2d_dilated_f32": (c_int, [c_void_p] * 7 + [c_int] * 11 + [c_void_p]),
     "rfx_conv1x1_split_f32": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
@@ -104,7 +105,7 @@ SIGNATURES = {
                                         + [c_void_p] * 12 + [c_longlong] + [c_int] * 3 + [c_void_p]),
 }
 
-ABI_VERSION = 15    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 16    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

@@ -143,6 +143,27 @@ class FeatureExtractorNet:
             x = blk["c2"](o, residual=r)
         return x
 
+    def forward_group(self, xs, side_streams=True):
+        """The same pass over several inputs of DIFFERENT sizes (the shape groups of a ragged fine stage), layer by layer with one
+        grouped launch per kernel instance and layer (ops.launch_group): bit-identical to [self(x) for x in xs].  Outputs get new
+        names inside a group and are rebound after it (launch_group's contract, as in ResNet50Trunk.forward_group)."""
+        dev = xs[0].device
+        with ops.launch_group(dev, side_streams):
+            xs = [ops.stem_conv_maxblur(x, self.conv1) for x in xs]
+        for blk in self.blocks:
+            with ops.launch_group(dev, side_streams):          # c1 and the shortcut's blur both read x only: one group
+                os_ = [blk["c1"](x) for x in xs]
+                bs = [ops.blurpool2d(x, blk["stride"]) for x in xs] if blk["ds"] is not None else None
+            if bs is not None:
+                with ops.launch_group(dev, side_streams):
+                    rs = [blk["ds"](b) for b in bs]
+            else:
+                rs = xs
+            with ops.launch_group(dev, side_streams):
+                ys = [blk["c2"](o, residual=r) for o, r in zip(os_, rs)]
+            xs = ys
+        return xs
+
 
 class _HeadTrunk:
     def __init__(self, sd, last_act, device):
@@ -153,6 +174,25 @@ class _HeadTrunk:
 
     def __call__(self, coef):
         return self.c4(self.c3(self.c2(self.c1(coef))))
+
+    def forward_group(self, coefs, side_streams=True, halves_out=None):
+        """[self(c) for c in coefs] for volumes of different sizes, one grouped launch per kernel instance and layer.  The 49-channel
+        volumes must come from an earlier group: c1 copies them into its zero-padded input eagerly (launch_group's contract).
+        ``halves_out``: one (out_a, out_b) per input -- the last convolution then runs on the two halves of each batch as two
+        problems and writes them to out_a / out_b (views of two packed buffers: PredFlowMask's match12Down8 / match21Down8);
+        returns those pairs."""
+        dev = coefs[0].device
+        xs = coefs
+        for c in (self.c1, self.c2, self.c3):
+            with ops.launch_group(dev, side_streams):
+                ys = [c(x) for x in xs]
+            xs = ys
+        with ops.launch_group(dev, side_streams):
+            if halves_out is None:
+                ys = [self.c4(x) for x in xs]
+            else:
+                ys = [(self.c4(x[:x.shape[0] // 2], out=oa), self.c4(x[x.shape[0] // 2:], out=ob)) for x, (oa, ob) in zip(xs, halves_out)]
+        return ys
 
 
 class NetFlowCoarseNet:
@@ -168,6 +208,19 @@ class NetFlowCoarseNet:
             flow = ops.resize_bilinear(flow, (flow.shape[2] * 8, flow.shape[3] * 8), align_corners=True)
         return flow
 
+    def forward_group(self, coefs, up8X=True, side_streams=True, outs=None):
+        """[self(c, up8X) for c in coefs] for volumes of different sizes: the trunk, the flow head and the x8 resize as grouped
+        launches, bit-identical to the per-input calls.  ``outs``: where the /8 flows go (views of a packed buffer)."""
+        dev = coefs[0].device
+        logits = self.trunk.forward_group(coefs, side_streams)
+        with ops.launch_group(dev, side_streams):
+            flows = [ops.flow_head(l, self.k, out=None if outs is None else outs[i]) for i, l in enumerate(logits)]
+        if up8X:
+            with ops.launch_group(dev, side_streams):
+                ups = [ops.resize_bilinear(f, (f.shape[2] * 8, f.shape[3] * 8), align_corners=True) for f in flows]
+            flows = ups
+        return flows
+
 
 class NetMatchabilityNet:
     """model/model.py:254-322: sigmoid fused into the last conv's epilogue."""
@@ -180,3 +233,13 @@ class NetMatchabilityNet:
         if up8X:
             m = ops.resize_bilinear(m, (m.shape[2] * 8, m.shape[3] * 8), align_corners=True)
         return m
+
+    def forward_group(self, feats, up8X=True, side_streams=True):
+        """[self(f, up8X) for f in feats] for volumes of different sizes, as grouped launches, bit-identical to the per-input calls."""
+        dev = feats[0].device
+        ms = self.trunk.forward_group(feats, side_streams)
+        if up8X:
+            with ops.launch_group(dev, side_streams):
+                ups = [ops.resize_bilinear(m, (m.shape[2] * 8, m.shape[3] * 8), align_corners=True) for m in ms]
+            ms = ups
+        return ms

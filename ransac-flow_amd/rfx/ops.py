@@ -117,11 +117,18 @@ class Profiler:
 
 
 class launch_group:
-    """``with ops.launch_group(device):`` -- the convolution ops issued inside are RECORDED by the library and launched at exit
+    """``with ops.launch_group(device):`` -- the convolution ops and the fine-stage ops (stem_conv_maxblur, blurpool2d, l2norm,
+    flow_head, resize_bilinear, corr_neigh / corr_neigh_bidir, warp_grid, grid_sample, compose_flow) issued inside are RECORDED
+    by the library and launched at exit
     as ONE launch per kernel instance (rfx_group_begin / rfx_group_end: blockIdx.y selects the problem).  For the same layer
-    of several independent inputs of different sizes (the 8 images of a single pair's trunk pass); the calls inside must not
-    depend on each other, and their tensors must stay referenced until the block ends (the returned outputs do).  Not used
-    under a Profiler (per-launch events are meaningless for a recorded launch).  Temporaries an op makes for a recorded launch
+    of several independent inputs of different sizes (the 8 images of a single pair's trunk pass, the shape groups of a ragged
+    fine stage); the calls inside must not
+    depend on each other, and their tensors must stay referenced until the block ends (the returned outputs do).  The contract:
+    a recorded op may not READ an output of the same group -- neither on the device nor with an eager torch op on the host side of
+    a mirror (the crop after a padded correlation: use corr_neigh_bidir_group / corr_neigh_group, which pad before the group and
+    crop after it; ConvPlan's copy of a 49-channel input into its zero-padded buffer is such an eager read, so that input must
+    come from an EARLIER group).  Not used
+    under a Profiler (per-launch events are meaningless for a recorded launch: callers take their per-problem path).  Temporaries an op makes for a recorded launch
     (ConvPlan's zero-padded input of a ragged-Cin split convolution) are held by the block (``keep``) until the launch is issued:
     the side streams join the caller's stream before rfx_group_end returns, so releasing them then is stream-ordered."""
     _tls = threading.local()
@@ -131,6 +138,11 @@ class launch_group:
         # run several grouped chains on streams of their own
         self.dev, self.side = torch.device(device), bool(side_streams)
         self._held = []
+
+    @staticmethod
+    def recording():
+        """True inside a ``with ops.launch_group(...)`` block of this thread."""
+        return getattr(launch_group._tls, "active", None) is not None
 
     @staticmethod
     def keep(t):
@@ -163,6 +175,14 @@ class launch_group:
             self._held = []
 
 
+def group_stats():
+    """(groups, launches): this thread's cumulative number of launch_group blocks that ended (rfx_group_end) and of the kernel
+    launches they issued (rfx_group_stats)."""
+    g, n = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(_lib.load().rfx_group_stats(ctypes.byref(g), ctypes.byref(n)), "rfx_group_stats")
+    return g.value, n.value
+
+
 def _dev(t, name="tensor", dtype=torch.float32):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
@@ -185,6 +205,30 @@ KID_SPLIT_3X3 = 65536      # ... of rfx_conv3x3_split_f32
 KID_SPLIT_1X1 = 32768      # Profiler kernel id of rfx_conv1x1_split_f32 (| 1: 64-channel tiles, | 2: 128-channel tiles)
 KID_DIRECT_3X3 = 32        # bit 5 of the library's ids (include/rfx_api.h, rfx_conv2d_kernel_id): served by rfx_conv3x3_f32
 KID_DIRECT_3X3_S2 = 8192   # bit 13: served by rfx_conv3x3_s2_f32
+
+
+# on by default: measured 1.057x on the ragged multi-homography call, its slowest repetition below the per-group form's fastest
+# (profiles/ragged_fine_groups_bench.json)
+FINE_GROUPS_DEFAULT = True
+
+
+def fine_groups_enabled(env=None):
+    """RFX_FINE_GROUPS: the fine stage of the ragged drivers (rounds.RaggedGroup, AlignPipeline._fine_ragged) as ONE chain of grouped
+    launches over all shape groups (AlignPipeline.pred_flow_mask_groups / fine_quickstart_groups) instead of one chain per shape
+    group.  "1" / "0"; unset = FINE_GROUPS_DEFAULT.  Always off under a Profiler (grouped launches are not profiled)."""
+    env = os.environ if env is None else env
+    v = str(env.get("RFX_FINE_GROUPS", "")).strip()
+    on = FINE_GROUPS_DEFAULT if v == "" else v != "0"
+    return on and Profiler.active() is None
+
+
+def _out_or_new(out, shape, ref, what):
+    """``out`` checked against ``shape`` (a contiguous float32 tensor on ref's device, e.g. a view of a packed buffer), or a new tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=ref.device)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != ref.device:
+        raise ValueError("%s: out must be a contiguous float32 %s tensor on %s" % (what, tuple(shape), ref.device))
+    return out
 
 
 def conv_split_enabled():
@@ -331,13 +375,13 @@ class ConvPlan:
         eh, ew = (self.KH - 1) * self.dilation + 1, (self.KW - 1) * self.dilation + 1
         return (H + 2 * self.pad - eh) // self.stride + 1, (W + 2 * self.pad - ew) // self.stride + 1
 
-    def __call__(self, x, residual=None, act=None):
+    def __call__(self, x, residual=None, act=None, out=None):
         x = _dev(x, "conv input")
         N, C, H, W = x.shape
         if C != self.Cin:
             raise ValueError("conv expects %d input channels, got %d" % (self.Cin, C))
         Ho, Wo = self.out_hw(H, W)
-        out = torch.empty((N, self.Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+        out = _out_or_new(out, (N, self.Cout, Ho, Wo), x, "conv")
         res = _dev(residual, "residual") if residual is not None else None
         if res is not None and res.shape != out.shape:
             raise ValueError("residual shape %s != output shape %s" % (tuple(res.shape), tuple(out.shape)))
@@ -690,21 +734,21 @@ def l2norm_scatter(x, out, dst_off, out_chan_stride):
     _call("rfx_l2norm_nchw_scatter_f32", _one_device(x, out, dst_off), _p(x), _p(out), N, C, HW, _p(dst_off), int(out_chan_stride))
     return out
 
-def flow_head(logits, K=7):
+def flow_head(logits, K=7, out=None):
     logits = _dev(logits, "flow logits")
     N, C, R, Cc = logits.shape
     if C != K * K:
         raise ValueError("flow head expects %d logits, got %d" % (K * K, C))
-    out = torch.empty((N, 2, R, Cc), dtype=torch.float32, device=logits.device)
+    out = _out_or_new(out, (N, 2, R, Cc), logits, "flow_head")
     _call("rfx_flow_head_f32", logits.device, _p(logits), _p(out), N, K, R, Cc)
     return out
 
 
-def resize_bilinear(x, size, align_corners=False):
+def resize_bilinear(x, size, align_corners=False, out=None):
     x = _dev(x, "resize input")
     N, C, H, W = x.shape
     Ho, Wo = int(size[0]), int(size[1])
-    out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=x.device)
+    out = _out_or_new(out, (N, C, Ho, Wo), x, "resize_bilinear")
     _call("rfx_resize_bilinear_f32", x.device, _p(x), _p(out), N * C, H, W, Ho, Wo, 1 if align_corners else 0)
     return out
 
@@ -778,6 +822,9 @@ def corr_neigh(x, y, K=7, variant=None):
         raise ValueError("corr_neigh: x %s and y %s differ" % (tuple(x.shape), tuple(y.shape)))
     N, C, H, W = x.shape
     if W % 4 != 0 and variant is None and os.environ.get("RFX_CORR_PAD", "1") == "1":
+        if launch_group.recording():
+            raise RuntimeError("corr_neigh inside a launch_group with W %% 4 != 0 (W = %d): the crop would read a launch that has not "
+                               "run yet -- use ops.corr_neigh_group, which pads before the group and crops after it" % W)
         # the LDS-DMA kernels move 16-byte quads: run them on copies zero-padded to a multiple of 4 columns and crop -- the
         # window's own padding is zero (model/model.py:135,143), so the result is the unpadded one, bit for bit
         Wp = (W + 3) // 4 * 4
@@ -804,6 +851,9 @@ def corr_neigh_bidir(x, y, K=7, out=None):
         raise ValueError("corr_neigh_bidir: x %s and y %s differ" % (tuple(x.shape), tuple(y.shape)))
     N, C, H, W = x.shape
     if W % 4 != 0:
+        if launch_group.recording():
+            raise RuntimeError("corr_neigh_bidir inside a launch_group with W %% 4 != 0 (W = %d): the crop would read a launch that "
+                               "has not run yet -- use ops.corr_neigh_bidir_group, which pads before the group and crops after it" % W)
         Wp = (W + 3) // 4 * 4
         xp, yp = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp)
         both = torch.empty((2 * N, K * K, H, Wp), dtype=torch.float32, device=x.device)
@@ -826,6 +876,58 @@ def corr_neigh_bidir(x, y, K=7, out=None):
     return out[:N], out[N:]
 
 
+def _corr_group(xs, ys, bidir, outs, side_streams):
+    """The padded-width bookkeeping of corr_neigh_group / corr_neigh_bidir_group: widths that are no multiple of 4 are padded with
+    copy_cols BEFORE the group, all problems are recorded in ONE group, the padded results are cropped AFTER it."""
+    if launch_group.recording():
+        raise RuntimeError("corr_neigh(_bidir)_group opens its own launch_group: call it outside one")
+    if len(xs) != len(ys) or not xs:
+        raise ValueError("corr group: one y per x, at least one problem")
+    dev = _one_device(*xs, *ys)
+    work = []
+    for x, y in zip(xs, ys):
+        x, y = _dev(x, "corr x"), _dev(y, "corr y")
+        if x.shape != y.shape:
+            raise ValueError("corr group: x %s and y %s differ" % (tuple(x.shape), tuple(y.shape)))
+        N, C, H, W = x.shape
+        Wp = (W + 3) // 4 * 4
+        if Wp != W:
+            x, y = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp)
+        work.append((x, y, W, Wp))
+    res = []
+    with launch_group(dev, side_streams):
+        for i, (x, y, W, Wp) in enumerate(work):
+            if not bidir:
+                res.append(corr_neigh(x, y))
+                continue
+            out = outs[i] if outs is not None else None
+            if Wp != W or out is None:
+                out = torch.empty((2 * x.shape[0], 49, x.shape[2], Wp), dtype=torch.float32, device=x.device)
+            corr_neigh_bidir(x, y, out=out)
+            res.append(out)
+    final = []
+    for i, ((x, y, W, Wp), r) in enumerate(zip(work, res)):
+        if Wp != W:
+            r = copy_cols(r.view(-1, Wp), W).view(r.shape[0], 49, r.shape[2], W)
+            if bidir and outs is not None and outs[i] is not None:
+                outs[i].copy_(r)
+                r = outs[i]
+        final.append((r[:x.shape[0]], r[x.shape[0]:]) if bidir else r)
+    return final
+
+
+def corr_neigh_group(xs, ys, side_streams=False):
+    """[corr_neigh(x, y) for x, y in zip(xs, ys)] as ONE launch_group: every problem keeps the tile variant it gets alone (problems of
+    different variants are different launches), bit-identical to the single calls."""
+    return _corr_group(xs, ys, False, None, side_streams)
+
+
+def corr_neigh_bidir_group(xs, ys, outs=None, side_streams=False):
+    """[corr_neigh_bidir(x, y, out=o) for ...] as ONE launch_group (see corr_neigh_group).  ``outs``: optional list of (2N,49,H,W)
+    buffers (entries may be None)."""
+    return _corr_group(xs, ys, True, outs, side_streams)
+
+
 def warp_grid(Hm, h, w):
     Hm = _dev(Hm, "homography")
     B = Hm.shape[0]
@@ -846,15 +948,16 @@ def grid_sample(inp, grid, align_corners=False):
     return out
 
 
-def compose_flow(flowDown, coarseGrid, clamp=False, want_inb=False, want_flow_up=False, out_hw=None):
+def compose_flow(flowDown, coarseGrid, clamp=False, want_inb=False, want_flow_up=False, out_hw=None, inb_out=None):
     """flow12 = grid_sample(coarseGrid, [clamp](upsample(flowDown) + identity grid)).  ``out_hw``: output resolution when
-    it differs from the coarse grid's (KITTI full-resolution pass); default = the coarse grid's."""
+    it differs from the coarse grid's (KITTI full-resolution pass); default = the coarse grid's.  ``inb_out``: where the in-bounds
+    mask (N,H,W) goes (a view of a packed buffer) instead of a new tensor."""
     flowDown, coarseGrid = _dev(flowDown, "flowDown"), _dev(coarseGrid, "coarse grid")
     N, two, hd, wd = flowDown.shape
     _, Hc, Wc, _ = coarseGrid.shape
     H, W = (Hc, Wc) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
     flow12 = torch.empty((N, H, W, 2), dtype=torch.float32, device=flowDown.device)
-    inb = torch.empty((N, H, W), dtype=torch.float32, device=flowDown.device) if want_inb else None
+    inb = _out_or_new(inb_out, (N, H, W), flowDown, "compose_flow inb") if want_inb else None
     fup = torch.empty((N, H, W, 2), dtype=torch.float32, device=flowDown.device) if want_flow_up else None
     _call("rfx_compose_flow_f32", _one_device(flowDown, coarseGrid), _p(flowDown), _p(coarseGrid), _p(flow12), _p(inb), _p(fup),
           N, hd, wd, Hc, Wc, H, W, 1 if clamp else 0)

@@ -83,6 +83,25 @@ def cell_coords(n_rows, n_cols, device):
 
 
 
+def packed_group_offsets(bhw_list):
+    """Where the shape groups of a grouped fine stage sit in its packed buffers.  ``bhw_list``: one (B, h, w[, h8, w8]) per group, in
+    group order (h8, w8: the /8 map size, default h // 8, w // 8).  Returns dict(off, off8, total, total8, shapes): group g's full-
+    resolution maps start at element off[g] (B*h*w elements, one plane per pair), its /8 maps at off8[g] (B*h8*w8; the two-channel
+    /8 flow at 2 * off8[g]); total / total8 are the buffer sizes.  Pure Python: no device involved."""
+    off, off8, shapes, t, t8 = [], [], [], 0, 0
+    for e in bhw_list:
+        B, h, w = int(e[0]), int(e[1]), int(e[2])
+        h8, w8 = (int(e[3]), int(e[4])) if len(e) > 3 else (h // 8, w // 8)
+        if B <= 0 or h <= 0 or w <= 0 or h8 <= 0 or w8 <= 0:
+            raise ValueError("packed_group_offsets: empty group %r" % (tuple(e),))
+        off.append(t)
+        off8.append(t8)
+        shapes.append((B, h, w, h8, w8))
+        t += B * h * w
+        t8 += B * h8 * w8
+    return dict(off=off, off8=off8, total=t, total8=t8, shapes=shapes)
+
+
 def ragged_plan(src_sizes, tgt_sizes, min_size, scales, mode="max"):
     """Bucket / offset plan of a ragged batch: pair b's source of size src_sizes[b] = (w, h) gives len(scales) pyramid levels and its
     target of size tgt_sizes[b] one more image, each resized by resize_dims exactly as the one-pair path does (multiples of 16).
@@ -419,14 +438,20 @@ class AlignPipeline:
 
     def _fine_ragged(self, prep, Hs):
         """fine_quickstart of a ragged prep: the pairs grouped by (source, target) image shape, each group through today's dense
-        batch kernels.  Returns one dict per pair, every tensor with a leading batch dimension of 1."""
+        batch kernels -- all groups as one chain of grouped launches (fine_quickstart_groups) with RFX_FINE_GROUPS on, one chain per
+        group otherwise.  Returns one dict per pair, every tensor with a leading batch dimension of 1."""
         groups = collections.OrderedDict()
         for b in range(prep["B"]):
             groups.setdefault((tuple(prep["IsTensor"][b].shape), tuple(prep["ItTensor"][b].shape)), []).append(b)
         out = [None] * prep["B"]
-        for bs in groups.values():
-            sub = dict(IsTensor=torch.cat([prep["IsTensor"][b] for b in bs]), ItTensor=torch.cat([prep["ItTensor"][b] for b in bs]))
-            f = self.fine_quickstart(sub, Hs[bs])
+        subs = [dict(IsTensor=torch.cat([prep["IsTensor"][b] for b in bs]), ItTensor=torch.cat([prep["ItTensor"][b] for b in bs]))
+                for bs in groups.values()]
+        hs = [Hs[bs] for bs in groups.values()]
+        if ops.fine_groups_enabled() and len(subs) > 1:
+            fs = self.fine_quickstart_groups(subs, hs)
+        else:
+            fs = [self.fine_quickstart(sub, h) for sub, h in zip(subs, hs)]
+        for bs, f in zip(groups.values(), fs):
             for k, b in enumerate(bs):
                 out[b] = {key: v[k:k + 1] for key, v in f.items()}
         return out
@@ -581,6 +606,30 @@ class AlignPipeline:
         return dict(flowCoarse=flowCoarse, img1_coarse=img1_coarse, feat1=feat1, feat2=feat2, corr12=corr12,
                     flowDown=flowDown, flow12=flow12, img1_fine=img1_fine)
 
+    def fine_quickstart_groups(self, preps, Hs_list):
+        """[fine_quickstart(p, Hs) for p, Hs in zip(preps, Hs_list)] for shape groups of different sizes: every stage is ONE
+        ops.launch_group over the groups (more than 8 groups: chunked by the library), bit-identical per group."""
+        if len(preps) == 1:
+            return [self.fine_quickstart(preps[0], Hs_list[0])]
+        lg = lambda: ops.launch_group(self.dev, False)
+        Bs = [p["ItTensor"].shape[0] for p in preps]
+        with lg():
+            fcs = [ops.warp_grid(Hs, p["ItTensor"].shape[2], p["ItTensor"].shape[3]) for p, Hs in zip(preps, Hs_list)]
+        with lg():
+            coarse = [ops.grid_sample(p["IsTensor"], fc) for p, fc in zip(preps, fcs)]
+        raw = self.feat.forward_group([torch.cat((c, p["ItTensor"]), dim=0) for c, p in zip(coarse, preps)], False)
+        with lg():
+            fs = [ops.l2norm(f) for f in raw]
+        f1, f2 = [f[:B] for f, B in zip(fs, Bs)], [f[B:] for f, B in zip(fs, Bs)]
+        corr = ops.corr_neigh_group(f1, f2)
+        down = self.flow.forward_group(corr, False, False)
+        with lg():
+            f12 = [ops.compose_flow(d, fc, clamp=False)[0] for d, fc in zip(down, fcs)]
+        with lg():
+            fine = [ops.grid_sample(p["IsTensor"], f) for p, f in zip(preps, f12)]
+        return [dict(flowCoarse=fcs[g], img1_coarse=coarse[g], feat1=f1[g], feat2=f2[g], corr12=corr[g], flowDown=down[g],
+                     flow12=f12[g], img1_fine=fine[g]) for g in range(len(preps))]
+
     @staticmethod
     def _corr_both(featt, feats):
         """(2B,49,h,w) = corr(featt, feats) | corr(feats, featt) (evaluation/evalHpatch/evaluation.py:29,34).  RFX_CORR_BIDIR=0:
@@ -610,6 +659,60 @@ class AlignPipeline:
         match = match12 * inb.unsqueeze(1)
         return dict(flow12=flow12, match=match, flowDown8=flowDown8, match12Down8=match12Down8,
                     match21Down8=match21Down8)
+
+    def pred_flow_mask_groups(self, Is_list, featt_list, Hs_list, hw_list, out=None):
+        """warp_grid + pred_flow_mask for G shape groups in one call: group g = sources Is_list[g] (B_g,3,.,.), normalised target
+        features featt_list[g] (B_g,256,h/8,w/8), homographies Hs_list[g] (B_g,3,3), target size hw_list[g] = (h, w).  Every stage
+        -- warp_grid, grid_sample, FeatureExtractor, l2norm, both correlation directions, flow head, matchability head, resize and
+        compose_flow -- is ONE ops.launch_group over the groups (chains of more than 8 groups are chunked by the library; no side
+        streams: the lock-step groups of the round drivers run on streams of their own).  Returns one dict per group with
+        pred_flow_mask's keys, each tensor bit-identical to pred_flow_mask on that group alone.  match, flowDown8, match12Down8 and
+        match21Down8 are views of ONE packed buffer each, groups in order (packed_group_offsets); ``out``: a dict that receives those
+        buffers under the same keys (what rfx_multih_accept_ragged_f32 reads), plus ``layout``."""
+        G = len(Is_list)
+        if G == 1:
+            (h, w), B = hw_list[0], Is_list[0].shape[0]
+            pm = self.pred_flow_mask(Is_list[0], featt_list[0], ops.warp_grid(Hs_list[0], h, w))
+            if out is not None:
+                out.update({k: pm[k].reshape(-1) for k in ("match", "flowDown8", "match12Down8", "match21Down8")})
+                out["layout"] = packed_group_offsets([(B, h, w) + tuple(featt_list[0].shape[2:])])
+            return [pm]
+        dev = self.dev
+        lg = lambda: ops.launch_group(dev, False)
+        lay = packed_group_offsets([(I.shape[0], hw[0], hw[1], ft.shape[2], ft.shape[3]) for I, hw, ft in zip(Is_list, hw_list, featt_list)])
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        match12, inb = new(lay["total"]), new(lay["total"])
+        f8, m12, m21 = new(2 * lay["total8"]), new(lay["total8"]), new(lay["total8"])
+        cut, cut8 = [], []
+        for (B, h, w, h8, w8), o, o8 in zip(lay["shapes"], lay["off"], lay["off8"]):
+            cut.append(lambda t, B=B, h=h, w=w, o=o: t[o:o + B * h * w].view(B, 1, h, w))
+            cut8.append(lambda t, c, B=B, h8=h8, w8=w8, o8=o8: t[c * o8:c * (o8 + B * h8 * w8)].view(B, c, h8, w8))
+        with lg():
+            fcs = [ops.warp_grid(Hs, h, w) for Hs, (h, w) in zip(Hs_list, hw_list)]
+        with lg():
+            samples = [ops.grid_sample(I, fc) for I, fc in zip(Is_list, fcs)]
+        raw = self.feat.forward_group(samples, False)
+        with lg():
+            feats = [ops.l2norm(f) for f in raw]
+        if os.environ.get("RFX_CORR_BIDIR", "1") == "0":
+            cs = ops.corr_neigh_group([torch.cat((ft, fs), dim=0) for ft, fs in zip(featt_list, feats)],
+                                      [torch.cat((fs, ft), dim=0) for ft, fs in zip(featt_list, feats)])
+        else:
+            cs = [torch.empty((2 * ft.shape[0], 49, ft.shape[2], ft.shape[3]), dtype=torch.float32, device=dev) for ft in featt_list]
+            ops.corr_neigh_bidir_group(featt_list, feats, outs=cs)
+        fd8 = self.flow.forward_group([c[:c.shape[0] // 2] for c in cs], False, False, outs=[cut8[g](f8, 2) for g in range(G)])
+        md = self.match.trunk.forward_group(cs, False, halves_out=[(cut8[g](m12, 1), cut8[g](m21, 1)) for g in range(G)])
+        with lg():                                          # the resize reads match12Down8, compose_flow the /8 flow: independent
+            for g in range(G):
+                B, h, w = lay["shapes"][g][:3]
+                ops.resize_bilinear(md[g][0], (h, w), align_corners=False, out=cut[g](match12))
+            f12 = [ops.compose_flow(fd8[g], fcs[g], clamp=True, want_inb=True, inb_out=cut[g](inb).view(lay["shapes"][g][0], *hw_list[g]))[0]
+                   for g in range(G)]
+        match = torch.mul(match12, inb)                     # match12 * inb of all groups: one multiply over the packed buffers
+        if out is not None:
+            out.update(match=match, flowDown8=f8, match12Down8=m12, match21Down8=m21, layout=lay)
+        return [dict(flow12=f12[g], match=cut[g](match), flowDown8=fd8[g], match12Down8=md[g][0], match21Down8=md[g][1])
+                for g in range(G)]
 
     def pred_flow_mask_kitti(self, IsSample, ItSample, flowCoarse, out_hw=None):
         """evaluation/evalKITTI/evaluation.py:49-81: both images go through the FeatureExtractor here, and the

@@ -296,8 +296,9 @@ class RaggedGroup:
     background maps) of all pairs live in ONE packed buffer (pipeline.ragged_multih_tables), so the filter and the accept kernel
     of a round are one launch each for all active pairs of the group.  Pairs of the slice that share (source shape, target shape)
     form a fine group: their raw images are stacked once, the target features are computed once per target shape, and every round
-    runs warp_grid + PredFlowMask once per fine group over its active members.  The round's matchability and /8 maps are packed in
-    fine-group order (one torch.cat each) and handed to rfx_multih_accept_ragged_f32 with per-active-pair offsets; those offsets
+    runs warp_grid + PredFlowMask over the active members of all fine groups as one chain of grouped launches
+    (AlignPipeline.pred_flow_mask_groups; RFX_FINE_GROUPS off: once per fine group, packed with one torch.cat each).  The round's
+    matchability and /8 maps are packed in fine-group order and handed to rfx_multih_accept_ragged_f32 with per-active-pair offsets; those offsets
     and the groups' gather indices go up in ONE pinned table per round.  ``batch``: prep, feats, tabs, idx1, idx2, cnt, the packed
     Mask / bg, nbH (B,), moff (B,), geom (B,6)."""
 
@@ -364,8 +365,15 @@ class RaggedGroup:
             return
         self.have_featt = True
         pipe, ItT, ft = self.st.pipe, self.ItT, {}
-        for shp, mem in self.tgroups.items():
-            f = ops.l2norm(pipe.feat(torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]]))
+        xs = [torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]] for mem in self.tgroups.values()]
+        if ops.fine_groups_enabled() and len(xs) > 1:
+            # all target shapes as one chain of grouped launches (no side streams: this lock-step group has a stream of its own)
+            raw = pipe.feat.forward_group(xs, False)
+            with ops.launch_group(pipe.dev, False):
+                fs = [ops.l2norm(f) for f in raw]
+        else:
+            fs = [ops.l2norm(pipe.feat(x)) for x in xs]
+        for f, mem in zip(fs, self.tgroups.values()):
             for j, m in enumerate(mem):
                 ft[m] = f[j:j + 1]
         for g in self.fine_groups:
@@ -373,13 +381,24 @@ class RaggedGroup:
 
     def fine(self, A, active, Hs, bestH, res, n_dev):
         rg, T, a, gm = self.rg, self.T, len(active), self.gm
-        # fine stage: per fine group, the dense kernels
-        for ent in rg:
-            g = ent["g"]
-            take = lambda t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
-            h, w = g["hw"]
-            ent["pm"] = self.st.pipe.pred_flow_mask(take(g["Is"], "sel"), take(g["featt"], "sel"), ops.warp_grid(take(Hs, "kidx"), h, w))
-        pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
+        take = lambda ent, t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
+        if ops.fine_groups_enabled():
+            # fine stage: all fine groups as ONE chain of grouped launches; its packed outputs are in fine-group order, which is the
+            # order matches() laid the round's offsets out in -- they go to the accept kernel as they are
+            packed = {}
+            pms = self.st.pipe.pred_flow_mask_groups([take(e, e["g"]["Is"], "sel") for e in rg], [take(e, e["g"]["featt"], "sel") for e in rg],
+                                                     [take(e, Hs, "kidx") for e in rg], [e["g"]["hw"] for e in rg], out=packed)
+            for ent, pm in zip(rg, pms):
+                ent["pm"] = pm
+            pack = lambda key: packed[key]
+        else:
+            # RFX_FINE_GROUPS off: per fine group, the dense kernels
+            for ent in rg:
+                g = ent["g"]
+                h, w = g["hw"]
+                ent["pm"] = self.st.pipe.pred_flow_mask(take(ent, g["Is"], "sel"), take(ent, g["featt"], "sel"),
+                                                        ops.warp_grid(take(ent, Hs, "kidx"), h, w))
+            pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
         accept, gain = ops.multih_accept_ragged(pack("match"), T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
                                                 self.st.maskRegionTh, 0, max(gm[m][0] * gm[m][1] for m in active), bestH=bestH,
                                                 flowDown8=pack("flowDown8"), match12Down8=pack("match12Down8"),

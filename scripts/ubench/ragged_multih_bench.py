@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Multi-homography alignment of a mixed-size set: one ragged multi_h_batched call vs one pair at a time through the dense path.
 
-    timeout -k 10 1100 python scripts/ubench/ragged_multih_bench.py [--pairs 32] [--reps 5] [--out profiles/ragged_multih_bench.json]
+    timeout -k 10 1100 python scripts/ubench/ragged_multih_bench.py [--pairs 32] [--reps 5] [--tag NAME]
+                                                                    [--out profiles/ragged_multih_bench.json]
 
 The set: rfx.synth.make_pair(homography=True) pairs over the size list of ragged_bench.py, BASELINE config 3's settings (variant B,
 nbScale 7, minSize 480, scaleR 2, 10 000 hypotheses, maxCoarse 10, maskRegionTh 0.01, device draws keyed by pair id, the default
@@ -11,6 +12,11 @@ Pre-processing (the pyramids) is outside the timed region of both legs.  Each re
 call, host readbacks included; after two warm-up runs per leg (the loop's HIP-graph captures happen at the second sighting of a
 shape) the legs alternate, --reps repetitions each; median and min-max spread are reported, with the launch counts of the round
 kernels per leg, the shader clock seen before and after, and the host name.
+
+Where the library has the grouped fine stage (RFX_FINE_GROUPS), the ragged call is timed both ways: leg "ragged" with
+RFX_FINE_GROUPS=1 and leg "ragged_per_group" with RFX_FINE_GROUPS=0, interleaved with the loop.  Per leg and call the record also
+holds the kernel launches issued by grouped launches (rfx_group_stats) and the number of eager kernel entry calls (ops._call outside
+a launch_group).  --tag names the build in the record, for A/B runs of two trees in one job.
 """
 import argparse
 import collections
@@ -46,6 +52,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--tag", default="", help="name of this build in the record")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_multih_bench.json"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -64,14 +71,31 @@ def main():
     def run_loop():
         return [pipe.multi_h_batched(p, pair_ids=[b], **kw)[0]["nbH"] for b, p in enumerate(preps)]
 
-    legs = (("ragged", run_ragged), ("loop", run_loop))
+    def with_fine_groups(flag, fn):
+        def run():
+            prev = os.environ.get("RFX_FINE_GROUPS")
+            os.environ["RFX_FINE_GROUPS"] = flag
+            try:
+                return fn()
+            finally:
+                if prev is None:
+                    del os.environ["RFX_FINE_GROUPS"]
+                else:
+                    os.environ["RFX_FINE_GROUPS"] = prev
+        return run
+
+    if hasattr(ops, "fine_groups_enabled"):
+        legs = (("ragged", with_fine_groups("1", run_ragged)), ("ragged_per_group", with_fine_groups("0", run_ragged)), ("loop", run_loop))
+    else:                                                                   # a tree from before the grouped fine stage
+        legs = (("ragged", run_ragged), ("loop", run_loop))
+    group_launches = (lambda: ops.group_stats()[1]) if hasattr(ops, "group_stats") else None
     clock0 = clocks()
     nbh = {}
     for name, fn in legs:
         fn()
         nbh[name] = fn()
     torch.cuda.synchronize(dev)
-    assert nbh["ragged"] == nbh["loop"], (nbh["ragged"], nbh["loop"])         # same work in both legs
+    assert all(nbh[name] == nbh["loop"] for name, _ in legs), nbh             # same work in every leg
     # launch counts of the round kernels, one untimed run per leg
     launches = {}
     for name, fn in legs:
@@ -83,13 +107,23 @@ def main():
                 cnt[_n] += 1
                 return _f(*args, **kwargs)
             setattr(ops, op, counted)
+        eager, call0 = [0], ops._call
+
+        def counting_call(*args, **kwargs):                                 # every kernel entry call of the mirrors goes through ops._call
+            if getattr(ops.launch_group._tls, "active", None) is None:
+                eager[0] += 1
+            return call0(*args, **kwargs)
+        ops._call = counting_call
+        g0 = group_launches() if group_launches else None
         try:
             fn()
         finally:
+            ops._call = call0
             for op, f in saved.items():
                 setattr(ops, op, f)
         rounds = cnt["filter_matches"] + cnt["filter_matches_ragged"]          # one filter launch per round (and lock-step group)
-        launches[name] = dict(per_call=dict(cnt), rounds=rounds, per_round={k: round(v / rounds, 2) for k, v in cnt.items()})
+        launches[name] = dict(per_call=dict(cnt), rounds=rounds, per_round={k: round(v / rounds, 2) for k, v in cnt.items()},
+                              eager_entry_calls=eager[0], grouped_launches=None if g0 is None else group_launches() - g0)
     torch.cuda.synchronize(dev)
     ms = {name: [] for name, _ in legs}
     for _ in range(a.reps):
@@ -100,7 +134,7 @@ def main():
             e1.record()
             e1.synchronize()
             ms[name].append(e0.elapsed_time(e1))
-    res = dict(pairs=a.pairs, reps=a.reps, sizes=sorted({tuple(s) for s in SIZES[:a.pairs]}), settings="config 3: variant B, nbScale 7, "
+    res = dict(tag=a.tag, pairs=a.pairs, reps=a.reps, sizes=sorted({tuple(s) for s in SIZES[:a.pairs]}), settings="config 3: variant B, nbScale 7, "
                "minSize 480, scaleR 2, nbIter 10000, maxCoarse 10, maskRegionTh 0.01, device draws by pair id, degenerate=lapack",
                nbH=nbh["ragged"], homographies=sum(nbh["ragged"]), launches=launches, host=socket.gethostname(),
                sclk_before=clock0, sclk_after=clocks())
