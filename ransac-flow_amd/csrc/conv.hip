@@ -62,7 +62,7 @@ extern "C" long long* rfx_debug_trace_ptr() { return g_trace; }
 // with one 16-byte load (the im2col row of a 1x1 convolution is the NCHW plane itself), mirroring the weight side:
 // 4x fewer gather instructions.
 template <int TM, int TN, bool ONE, bool WS, bool VECB>
-__device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsigned bx) {
+__device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsigned bx, const unsigned) {
     constexpr int BM = 64 * TM, BN = 64 * TN, BK = 32, KK = BK / 2;  // KK k-pairs per step
     constexpr int B_NI = BN / 8;                                      // gathered values per thread per step
     constexpr int A_MG = BM / 4;                                        // groups of 4 consecutive m per tile
@@ -331,25 +331,15 @@ __device__ __forceinline__ void conv2d_mfma_body(const ConvArgs& a, const unsign
 }
 
 template <int TM, int TN, bool ONE, bool WS, bool VECB>
-__global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : 2) void conv2d_mfma_kernel(ConvArgs a) {
-    conv2d_mfma_body<TM, TN, ONE, WS, VECB>(a, blockIdx.x);
-}
+using ConvGemm = RfxFamily<ConvArgs, conv2d_mfma_body<TM, TN, ONE, WS, VECB>, WS ? 512 : 256, WS ? 4 : 2>;
 
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block
 template <int TM, int TN, bool ONE, bool WS, bool VECB>
-__global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : 2) void conv2d_mfma_group_kernel(RfxGroupArgs<ConvArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv2d_mfma_body<TM, TN, ONE, WS, VECB>(g.p[y], blockIdx.x);
+__global__ __launch_bounds__((ConvGemm<TM, TN, ONE, WS, VECB>::BLOCK), (ConvGemm<TM, TN, ONE, WS, VECB>::min_waves())) void conv2d_mfma_kernel(ConvArgs a) {
+    conv2d_mfma_body<TM, TN, ONE, WS, VECB>(a, blockIdx.x, gridDim.x);
 }
 
 template <int TM, int TN, bool ONE, bool WS, bool VECB>
-static int conv_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<ConvArgs>(conv2d_mfma_group_kernel<TM, TN, ONE, WS, VECB>, WS ? 512 : 256, blob, gx, n, st);
-}
-
-template <int TM, int TN, bool ONE, bool WS, bool VECB>
-static int launch_conv(ConvArgs& a, hipStream_t st, bool recording) {
+static int launch_conv(ConvArgs& a, hipStream_t st) {
     constexpr int BM = 64 * TM, BN = 64 * TN;
     a.tilesM = (a.Cout + BM - 1) / BM;
     a.tilesP = (int)((a.P + BN - 1) / BN);
@@ -358,10 +348,7 @@ static int launch_conv(ConvArgs& a, hipStream_t st, bool recording) {
 #ifdef RFX_TRACE
     a.trace = g_trace;
 #endif
-    if (recording) return rfx_group_record(&conv_group_launch<TM, TN, ONE, WS, VECB>, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL((conv2d_mfma_kernel<TM, TN, ONE, WS, VECB>), dim3((unsigned)nwg), dim3(WS ? 512 : 256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return ConvGemm<TM, TN, ONE, WS, VECB>::launch(conv2d_mfma_kernel<TM, TN, ONE, WS, VECB>, a, (unsigned)nwg, st);
 }
 
 // Every instance of the implicit-GEMM kernel the library builds (conv_dispatch.h decides which one a launch takes): the three tiles
@@ -369,7 +356,7 @@ static int launch_conv(ConvArgs& a, hipStream_t st, bool recording) {
 // pixel-side loads (never wave-specialised).
 struct GemmEntry {
     int key;
-    int (*launch)(ConvArgs&, hipStream_t, bool recording);
+    int (*launch)(ConvArgs&, hipStream_t);
 };
 #define G(TM, TN, ONE, WS, VECB) {ConvInstance::gemm(TM, TN, ONE, WS, VECB).id(), &launch_conv<TM, TN, ONE, WS, VECB>}
 static const GemmEntry kGemm[] = {
@@ -398,9 +385,8 @@ extern "C" int rfx_conv3x3_f32(const float* in, const float* wP, const float* sc
     if (reinterpret_cast<uintptr_t>(wP) & 15) return RFX_E_ARG;
     if ((long long)Cin * H * W > 0x7fffffffLL) return RFX_E_LIMIT;
     if (k_chunk != 0 && k_chunk != 4) return RFX_E_ARG;                      // the one chunk length the kernels are built for
-    const bool recording = rfx_group_recording();
-    return rfx_conv3x3_direct_launch(conv_direct3x3(conv_knobs(), N, Cin, Cout, H, W, k_chunk, recording), in, wP, scale, shift, residual,
-                                     out, N, Cin, H, W, Cout, (Cout + 127) / 128 * 128, act, recording, rfx_stream(stream));
+    return rfx_conv3x3_direct_launch(conv_direct3x3(conv_knobs(), N, Cin, Cout, H, W, k_chunk, rfx_group_recording()), in, wP, scale, shift, residual,
+                                     out, N, Cin, H, W, Cout, (Cout + 127) / 128 * 128, act, rfx_stream(stream));
 }
 
 extern "C" int rfx_conv3x3_kernel_id(int N, int Cin, int Cout, int H, int W, int k_chunk) {
@@ -413,9 +399,8 @@ extern "C" int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float*
                                   void* stream) {
     if (!in || !wP || !out || N <= 0 || Cin < 8 || Cin % 8 != 0 || H <= 0 || W <= 0 || Cout <= 0) return RFX_E_ARG;
     if (reinterpret_cast<uintptr_t>(wP) & 15) return RFX_E_ARG;
-    const bool recording = rfx_group_recording();
-    const ConvInstance ci = conv_direct3x3_s2(conv_knobs(), N, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1, recording);
-    return rfx_conv3x3_s2_launch(ci, in, wP, scale, shift, residual, out, N, Cin, H, W, Cout, act, recording, rfx_stream(stream));
+    const ConvInstance ci = conv_direct3x3_s2(conv_knobs(), N, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1, rfx_group_recording());
+    return rfx_conv3x3_s2_launch(ci, in, wP, scale, shift, residual, out, N, Cin, H, W, Cout, act, rfx_stream(stream));
 }
 
 // dil = 1: rfx_conv2d_f32.  dil > 1 (rfx_conv2d_dilated_f32): the gather adds the ktab's (kh, kw) fields to the window origin
@@ -423,7 +408,7 @@ extern "C" int rfx_conv3x3_s2_f32(const float* in, const float* wP, const float*
 // 4-bit field limit know about the dilation.
 static int conv2d_impl(const float* in, const float* wT, const int32_t* ktab, const float* scale,
                        const float* shift, const float* residual, float* out, int N, int Cin, int Hin,
-                       int Win, int Cout, int KH, int KW, int stride, int pad, int dil, int act, void* stream, bool recording) {
+                       int Win, int Cout, int KH, int KW, int stride, int pad, int dil, int act, void* stream) {
     if (!in || !wT || !ktab || !out) return RFX_E_ARG;
     if (N <= 0 || Cin <= 0 || Hin <= 0 || Win <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || dil <= 0)
         return RFX_E_ARG;
@@ -441,18 +426,17 @@ static int conv2d_impl(const float* in, const float* wT, const int32_t* ktab, co
     a.P = (long long)N * a.Hout * a.Wout;
     hipStream_t st = rfx_stream(stream);
     const ConvInstance ci = conv_decide(conv_knobs(), {N, Cin, Cout, KH, KW, stride, pad, a.Hout, a.Wout}, false, 0,
-                                        (reinterpret_cast<uintptr_t>(in) & 15) == 0, recording);
+                                        (reinterpret_cast<uintptr_t>(in) & 15) == 0, rfx_group_recording());
     if (ci.family == CONV_KMAJOR)
-        return rfx_conv1x1_kmajor_launch(ci, in, wT, scale, shift, residual, out, N, Cin, Hin * Win, Cout, a.Mpad, act, recording, st);
+        return rfx_conv1x1_kmajor_launch(ci, in, wT, scale, shift, residual, out, N, Cin, Hin * Win, Cout, a.Mpad, act, st);
     const GemmEntry* e = conv_find(kGemm, ci);
-    return e ? e->launch(a, st, recording) : RFX_E_ARG;
+    return e ? e->launch(a, st) : RFX_E_ARG;
 }
 
 extern "C" int rfx_conv2d_f32(const float* in, const float* wT, const int32_t* ktab, const float* scale,
                               const float* shift, const float* residual, float* out, int N, int Cin, int Hin,
                               int Win, int Cout, int KH, int KW, int stride, int pad, int act, void* stream) {
-    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, 1, act, stream,
-                       rfx_group_recording());
+    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, 1, act, stream);
 }
 
 extern "C" int rfx_conv2d_dilated_f32(const float* in, const float* wT, const int32_t* ktab, const float* scale,
@@ -460,6 +444,5 @@ extern "C" int rfx_conv2d_dilated_f32(const float* in, const float* wT, const in
                                       int Win, int Cout, int KH, int KW, int stride, int pad, int dilation, int act,
                                       void* stream) {
     if (dilation == 1) return RFX_E_ARG;      // the undilated geometries belong to rfx_conv2d_f32 / rfx_conv3x3_f32
-    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, dilation, act, stream,
-                       rfx_group_recording());
+    return conv2d_impl(in, wT, ktab, scale, shift, residual, out, N, Cin, Hin, Win, Cout, KH, KW, stride, pad, dilation, act, stream);
 }

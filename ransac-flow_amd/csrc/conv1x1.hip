@@ -42,7 +42,7 @@ struct C1Args {
 // second set and restarted: the K-blocked sum of the CPU reference's GEMM instead of one fma chain over K = 1024 products (ResNet-50
 // layer3 conv1, model/resnet50.py:71).  64-channel tiles only (TM = 1: 174 + 32 registers; the 128-channel instance has none to spare).
 template <int TM, bool VEC, int KCH = 0>
-__device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsigned bx, const unsigned gsz) {
+__device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsigned bx, const unsigned gx) {
     static_assert(KCH == 0 || TM == 1, "chunked accumulation: 64-channel tiles");
     constexpr int BM = 64 * TM, BN = 128, BK = 32;
     constexpr int A_C4 = BM / 4;                 // float4 per A row: 32 / 16
@@ -119,9 +119,9 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
     const float* arow = &As[0][lrow][wm * TM * 32 + lcol];
     const float* brow_p = &Bs[0][lrow][wn * 64 + lcol];
     int g = 0;                                    // global step counter of this workgroup: LDS buffer = g & 1
-    for (int it = 0; v < nwg; ++it, v += (int)gsz) {
+    for (int it = 0; v < nwg; ++it, v += (int)gx) {
         // the workgroup's next tile (none: this tile again -- its loads are harmless and nobody consumes them)
-        const int vn = v + (int)gsz < nwg ? v + (int)gsz : v;
+        const int vn = v + (int)gx < nwg ? v + (int)gx : v;
         int m0n; long long n0n;
         tile_origin(vn, m0n, n0n);
         const float *wsrc_n, *bsrc_n;
@@ -201,26 +201,17 @@ __device__ __forceinline__ void conv1x1_kmajor_body(const C1Args& a, const unsig
     }
 }
 
+// (grouped, group.h: a problem's persistent workgroups stride by that problem's own grid)
 template <int TM, bool VEC, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv1x1_kmajor_kernel(C1Args a) {
+using Kmajor = RfxFamily<C1Args, conv1x1_kmajor_body<TM, VEC, KCH>, 256, 2>;
+
+template <int TM, bool VEC, int KCH = 0>
+__global__ __launch_bounds__((Kmajor<TM, VEC, KCH>::BLOCK), (Kmajor<TM, VEC, KCH>::min_waves())) void conv1x1_kmajor_kernel(C1Args a) {
     conv1x1_kmajor_body<TM, VEC, KCH>(a, blockIdx.x, gridDim.x);
 }
 
-// grouped form (group.h): blockIdx.y = problem; a problem's persistent workgroups stride by that problem's own grid
-template <int TM, bool VEC, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv1x1_kmajor_group_kernel(RfxGroupArgs<C1Args> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv1x1_kmajor_body<TM, VEC, KCH>(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-template <int TM, bool VEC, int KCH = 0>
-static int c1_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C1Args>(conv1x1_kmajor_group_kernel<TM, VEC, KCH>, 256, blob, gx, n, st);
-}
-
 template <int TM, bool VEC, int KCH>
-int launch_1x1(C1Args& a, hipStream_t st, bool recording) {
+int launch_1x1(C1Args& a, hipStream_t st) {
     a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
     a.tilesP = (int)((a.P + 127) / 128);
     const long long nwg = (long long)a.tilesM * a.tilesP;
@@ -233,16 +224,13 @@ int launch_1x1(C1Args& a, hipStream_t st, bool recording) {
         slots = (2 * cus + 7) / 8 * 8;
     }
     const unsigned grid = (unsigned)(nwg < slots ? (nwg + 7) / 8 * 8 : slots);
-    if (recording) return rfx_group_record(&c1_group_launch<TM, VEC, KCH>, &a, sizeof(a), grid);
-    hipLaunchKernelGGL((conv1x1_kmajor_kernel<TM, VEC, KCH>), dim3(grid), dim3(256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Kmajor<TM, VEC, KCH>::launch(conv1x1_kmajor_kernel<TM, VEC, KCH>, a, grid, st);
 }
 
 // Every instance the library builds: K >= 512 in chunks of 8 steps (256 k) on 64-channel tiles, else one chain on either tile
 struct C1Entry {
     int key;
-    int (*launch)(C1Args&, hipStream_t, bool recording);
+    int (*launch)(C1Args&, hipStream_t);
 };
 #define K1(TM, VEC, KCH) {ConvInstance::kmajor(TM, VEC, KCH).id(), &launch_1x1<TM, VEC, KCH>}
 const C1Entry kKmajor[] = {K1(1, true, 8), K1(1, false, 8), K1(2, true, 0), K1(2, false, 0), K1(1, true, 0), K1(1, false, 0)};
@@ -253,11 +241,11 @@ const C1Entry kKmajor[] = {K1(1, true, 8), K1(1, false, 8), K1(2, true, 0), K1(2
 // Internal entry used by rfx_conv2d_f32 (conv.hip); preconditions: conv_dispatch.h
 int rfx_conv1x1_kmajor_launch(const ConvInstance& ci, const float* in, const float* wT, const float* scale, const float* shift,
                               const float* residual, float* out, int N, int Cin, int HW, int Cout, int Mpad, int act,
-                              bool recording, hipStream_t st) {
+                              hipStream_t st) {
     C1Args a;
     a.in = in; a.wT = wT; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.Cin = Cin; a.HW = HW; a.Cout = Cout; a.act = act; a.Mpad = Mpad;
     a.P = (long long)N * HW;
     const C1Entry* e = conv_find(kKmajor, ci);
-    return e ? e->launch(a, st, recording) : RFX_E_ARG;
+    return e ? e->launch(a, st) : RFX_E_ARG;
 }

@@ -36,7 +36,7 @@ struct C1SArgs {
 // WM wavefronts along the channels x 2 along the pixels, each with a 32 TM x 64 output: <1, 2> / <2, 2> = 64 / 128 channels on 256
 // threads, <2, 4> = the wide tile, 256 channels on 512 threads over the SAME 128-pixel activation image.
 template <int TM, int WM>
-__device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsigned bx) {
+__device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsigned bx, const unsigned) {
     constexpr int BM = 32 * TM * WM, BN = 128, KB = 16, NT = 128 * WM;
     constexpr bool WIDE = WM == 4;
     __shared__ u32x4 As[2][3][2][BM];                   // a stage's weight image: 384 / 768 / 1536 words
@@ -144,36 +144,17 @@ __device__ __forceinline__ void conv1x1_split_body(const C1SArgs& a, const unsig
     conv_epilogue<TM, 2, false>(acc, s_scale, s_shift, a.res, a.out, a.act, a.Cout, HW, m0, wm, lrow, pix_off, pix_ok, m0 + BM <= a.Cout);
 }
 
-template <int TM>
-__global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(C1SArgs a) {
-    conv1x1_split_body<TM, 2>(a, blockIdx.x);
-}
-
-template <int TM>
-__global__ __launch_bounds__(256, 2) void conv1x1_split_group_kernel(RfxGroupArgs<C1SArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv1x1_split_body<TM, 2>(g.p[y], blockIdx.x);
-}
-
+template <int TM> using Split1 = RfxFamily<C1SArgs, conv1x1_split_body<TM, 2>, 256, 2>;
 // the wide tile: 74 KB of LDS, one workgroup of 8 wavefronts per CU -- 2 wavefronts per SIMD, as two 256-thread workgroups have
-__global__ __launch_bounds__(512, 1) void conv1x1_split_wide_kernel(C1SArgs a) {
-    conv1x1_split_body<2, 4>(a, blockIdx.x);
-}
-
-__global__ __launch_bounds__(512, 1) void conv1x1_split_wide_group_kernel(RfxGroupArgs<C1SArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv1x1_split_body<2, 4>(g.p[y], blockIdx.x);
-}
+using Split1Wide = RfxFamily<C1SArgs, conv1x1_split_body<2, 4>, 512, 1>;
 
 template <int TM>
-static int c1s_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C1SArgs>(conv1x1_split_group_kernel<TM>, 256, blob, gx, n, st);
+__global__ __launch_bounds__((Split1<TM>::BLOCK), (Split1<TM>::min_waves())) void conv1x1_split_kernel(C1SArgs a) {
+    conv1x1_split_body<TM, 2>(a, blockIdx.x, gridDim.x);
 }
 
-static int c1s_wide_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C1SArgs>(conv1x1_split_wide_group_kernel, 512, blob, gx, n, st);
+__global__ __launch_bounds__(Split1Wide::BLOCK, Split1Wide::min_waves()) void conv1x1_split_wide_kernel(C1SArgs a) {
+    conv1x1_split_body<2, 4>(a, blockIdx.x, gridDim.x);
 }
 
 // Channels per workgroup tile of a launch: 64 (Cout <= 64), 128, or 256 where the wide tile is the faster one.  Measured (MI355X,
@@ -212,15 +193,8 @@ int launch_split(C1SArgs& a, hipStream_t st) {
     a.tilesP = (int)((a.P + 127) / 128);
     const long long nwg = (long long)a.tilesM * a.tilesP;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    if constexpr (WM == 4) {
-        if (rfx_group_recording()) return rfx_group_record(&c1s_wide_group_launch, &a, sizeof(a), (unsigned)nwg);
-        hipLaunchKernelGGL(conv1x1_split_wide_kernel, dim3((unsigned)nwg), dim3(512), 0, st, a);
-    } else {
-        if (rfx_group_recording()) return rfx_group_record(&c1s_group_launch<TM>, &a, sizeof(a), (unsigned)nwg);
-        hipLaunchKernelGGL((conv1x1_split_kernel<TM>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    }
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    if constexpr (WM == 4) return Split1Wide::launch(conv1x1_split_wide_kernel, a, (unsigned)nwg, st);
+    else return Split1<TM>::launch(conv1x1_split_kernel<TM>, a, (unsigned)nwg, st);
 }
 
 }  // namespace

@@ -110,7 +110,7 @@ struct WpStage {
 // (model/resnet50.py:75 in layer1 / layer2: K = 576 / 1152), fused or not: the caller's k_chunk argument (rfx_conv3x3_f32) asks
 // for the same chunks in the stand-alone kernel, so the fused tail stays bit-identical to its two-kernel form.
 template <int TM, int PTC, bool FUSE, int TN = 2, bool RAG = false, int KCH = 0>
-__device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsigned bx) {
+__device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsigned bx, const unsigned) {
     using G = Patch<PTC, TN>;
     static_assert(KCH == 0 || !RAG, "chunked accumulation: Cin % 8 == 0 instances only");
     // the 36-entry table of B offsets stays in registers where 2 x (TM * TN) accumulator tiles leave room for it (64-channel
@@ -383,23 +383,12 @@ __device__ __forceinline__ void conv3x3_direct_body(const C3Args& a, const unsig
 
 // (three workgroups per CU for the 64-channel fused tail -- 168 VGPRs, 4 spilled -- measured -2.4 %: profiles/r03_fused_tail_3wgs.jsonl)
 template <int TM, int PTC, bool FUSE = false, int TN = 2, bool RAG = false, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv3x3_direct_kernel(C3Args a) {
-    conv3x3_direct_body<TM, PTC, FUSE, TN, RAG, KCH>(a, blockIdx.x);
-}
+using Direct3 = RfxFamily<C3Args, conv3x3_direct_body<TM, PTC, FUSE, TN, RAG, KCH>, 256, 2>;
 
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block
-template <int TM, int PTC, bool FUSE = false, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv3x3_direct_group_kernel(RfxGroupArgs<C3Args> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv3x3_direct_body<TM, PTC, FUSE, 2, false, KCH>(g.p[y], blockIdx.x);
+template <int TM, int PTC, bool FUSE = false, int TN = 2, bool RAG = false, int KCH = 0>
+__global__ __launch_bounds__((Direct3<TM, PTC, FUSE, TN, RAG, KCH>::BLOCK), (Direct3<TM, PTC, FUSE, TN, RAG, KCH>::min_waves())) void conv3x3_direct_kernel(C3Args a) {
+    conv3x3_direct_body<TM, PTC, FUSE, TN, RAG, KCH>(a, blockIdx.x, gridDim.x);
 }
-
-template <int TM, int PTC, bool FUSE, int KCH = 0>
-static int c3_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C3Args>(conv3x3_direct_group_kernel<TM, PTC, FUSE, KCH>, 256, blob, gx, n, st);
-}
-
 
 // ======================================================================================================================
 // Round 4: the direct form for 3x3 / STRIDE 2 / pad 1 (ResNet-50 layer2.0 / layer3.0 conv2, model/resnet50.py:75; the first
@@ -421,7 +410,7 @@ constexpr int NB = (NEL + 255) / 256;                // 18 per thread (the last 
 // FeatureExtractor's 128 -> 256 strided convolution were the last long-K 3x3 layers summed as ONE fma chain.  The B-offset table is
 // recomputed per use there (one v_mad per k-pair) to make room for the second accumulator set.
 template <int TM, int KCH = 0>
-__device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned bx) {
+__device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned bx, const unsigned) {
     using namespace s2;
     constexpr int TN = 2, BM = 64 * TM;
     constexpr int AS_F = 2 * BM * KK, BS_F = CH * PRI * BS2;
@@ -592,28 +581,19 @@ __device__ __forceinline__ void conv3x3_s2_body(const C3Args& a, const unsigned 
         conv_epilogue<TM, TN, (TM > 1)>(acc, s_scale, s_shift, a.res, a.out, a.act, a.Cout, HWo, m0, wm, lrow, pix_off, pix_ok, m0 + BM <= a.Cout);
 }
 
-template <int TM, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv3x3_s2_kernel(C3Args a) {
-    conv3x3_s2_body<TM, KCH>(a, blockIdx.x);
-}
+// (grouped, group.h; round 5: the single-pair trunk pass keeps ONE launch per layer, and a strided layer runs the same kernel --
+// hence the same chunked sums -- whatever the batch it rides in)
+template <int TM, int KCH = 0> using Direct3S2 = RfxFamily<C3Args, conv3x3_s2_body<TM, KCH>, 256, 2>;
 
-// grouped form (group.h; round 5): blockIdx.y = problem -- the single-pair trunk pass keeps ONE launch per layer, and a strided
-// layer runs the same kernel (hence the same chunked sums) whatever the batch it rides in
 template <int TM, int KCH = 0>
-__global__ __launch_bounds__(256, 2) void conv3x3_s2_group_kernel(RfxGroupArgs<C3Args> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv3x3_s2_body<TM, KCH>(g.p[y], blockIdx.x);
-}
-
-template <int TM, int KCH>
-static int c3s2_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C3Args>(conv3x3_s2_group_kernel<TM, KCH>, 256, blob, gx, n, st);
+__global__ __launch_bounds__((Direct3S2<TM, KCH>::BLOCK), (Direct3S2<TM, KCH>::min_waves())) void conv3x3_s2_kernel(C3Args a) {
+    conv3x3_s2_body<TM, KCH>(a, blockIdx.x, gridDim.x);
 }
 
 template <int TM, int PTC, bool FUSE, int TN, bool RAG, int KCH>
-int launch_direct(C3Args& a, hipStream_t st, bool recording) {
+int launch_direct(C3Args& a, hipStream_t st) {
     using G = Patch<PTC, TN>;
+    using F = Direct3<TM, PTC, FUSE, TN, RAG, KCH>;
     const long long rows = (long long)a.N * (a.H + 1);
     a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
     a.tilesH = (int)((rows + G::PT_R - 1) / G::PT_R);
@@ -623,16 +603,15 @@ int launch_direct(C3Args& a, hipStream_t st, bool recording) {
     // 32-bit byte offsets inside the images one input patch can touch
     const long long span = (G::PR + a.H) / (a.H + 1) + 1;
     if (span * a.Cin * a.H * a.W * 4 > 0xffffffffLL) return RFX_E_LIMIT;
-    if constexpr (TN == 2 && !RAG) {      // the other instances have no grouped form: launched at once
-        if (recording) return rfx_group_record(&c3_group_launch<TM, PTC, FUSE, KCH>, &a, sizeof(a), (unsigned)nwg);
-    }
-    hipLaunchKernelGGL((conv3x3_direct_kernel<TM, PTC, FUSE, TN, RAG, KCH>), dim3((unsigned)nwg), dim3(256), 0, st, a);
+    if constexpr (TN == 2 && !RAG) return F::launch(conv3x3_direct_kernel<TM, PTC, FUSE, TN, RAG, KCH>, a, (unsigned)nwg, st);
+    // the other instances have no grouped form: launched at once
+    hipLaunchKernelGGL((conv3x3_direct_kernel<TM, PTC, FUSE, TN, RAG, KCH>), dim3((unsigned)nwg), dim3(F::BLOCK), 0, st, a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
 
 template <int TM, int KCH>
-int launch_s2(C3Args& a, hipStream_t st, bool recording) {
+int launch_s2(C3Args& a, hipStream_t st) {
     const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
     a.tilesM = (a.Cout + 64 * TM - 1) / (64 * TM);
     a.tilesH = (Ho + s2::PT_R - 1) / s2::PT_R;
@@ -640,16 +619,13 @@ int launch_s2(C3Args& a, hipStream_t st, bool recording) {
     const long long nwg = (long long)a.tilesM * a.tilesH * a.tilesW * a.N;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
     if ((long long)a.Cin * a.H * a.W * 4 > 0xffffffffLL) return RFX_E_LIMIT;                    // 32-bit byte offsets inside one image
-    if (recording) return rfx_group_record(&c3s2_group_launch<TM, KCH>, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL((conv3x3_s2_kernel<TM, KCH>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Direct3S2<TM, KCH>::launch(conv3x3_s2_kernel<TM, KCH>, a, (unsigned)nwg, st);
 }
 
 // Every instance the library builds (conv_dispatch.h decides which one a launch takes), template arguments as the kernels take them
 struct C3Entry {
     int key;
-    int (*launch)(C3Args&, hipStream_t, bool recording);
+    int (*launch)(C3Args&, hipStream_t);
 };
 template <int TM, int PTC, bool FUSE, int TN, bool RAG, int KCH> constexpr ConvInstance direct_instance() {
     return FUSE ? ConvInstance::fused_tail(TM, PTC, KCH) : ConvInstance::direct3x3(TM, PTC, TN, RAG, KCH);
@@ -677,14 +653,14 @@ const C3Entry kDirect[] = {
 const C3Entry kStride2[] = {S2(2, 0), S2(1, 0), S2(2, 4), S2(1, 4)};
 #undef S2
 
-int launch_from(const C3Entry* e, C3Args& a, hipStream_t st, bool recording) { return e ? e->launch(a, st, recording) : RFX_E_ARG; }
+int launch_from(const C3Entry* e, C3Args& a, hipStream_t st) { return e ? e->launch(a, st) : RFX_E_ARG; }
 
 }  // namespace
 
 // Internal entry used by rfx_conv3x3_f32 (conv.hip); preconditions: conv_dispatch.h
 int rfx_conv3x3_direct_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
                               const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int Mpad, int act,
-                              bool recording, hipStream_t st) {
+                              hipStream_t st) {
     C3Args a;
     a.in = in; a.wT = wP; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.act = act; a.Mpad = Mpad;
@@ -692,13 +668,12 @@ int rfx_conv3x3_direct_launch(const ConvInstance& ci, const float* in, const flo
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();
 #endif
-    return launch_from(ci.family == CONV_DIRECT3 ? conv_find(kDirect, ci) : nullptr, a, st, recording);
+    return launch_from(ci.family == CONV_DIRECT3 ? conv_find(kDirect, ci) : nullptr, a, st);
 }
 
 // Internal entry used by rfx_conv3x3_s2_f32 (conv.hip): the direct stride-2 kernel above
 int rfx_conv3x3_s2_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
-                          const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int act, bool recording,
-                          hipStream_t st) {
+                          const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int act, hipStream_t st) {
     C3Args a;
     a.in = in; a.wT = wP; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
     a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.act = act; a.Mpad = (Cout + 127) / 128 * 128;
@@ -706,7 +681,7 @@ int rfx_conv3x3_s2_launch(const ConvInstance& ci, const float* in, const float* 
 #ifdef RFX_TRACE
     a.trace = nullptr;
 #endif
-    return launch_from(conv_find(kStride2, ci), a, st, recording);
+    return launch_from(conv_find(kStride2, ci), a, st);
 }
 
 // Bottleneck tail in one kernel: out = act3(bn3(conv1x1(act2(bn2(conv3x3(in))))) + residual)  (model/resnet50.py:71-79,93-103).
@@ -731,7 +706,6 @@ extern "C" int rfx_conv3x3_conv1x1_f32(const float* in, const float* wP2, const 
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();
 #endif
-    const bool recording = rfx_group_recording();
     // round 5: chunks of 4 K steps (288 k) in the 3x3 phase, like rfx_conv3x3_f32(k_chunk = 4)
-    return launch_from(conv_find(kDirect, conv_decide_tail(conv_knobs(), N, H, W, Cmid, recording)), a, rfx_stream(stream), recording);
+    return launch_from(conv_find(kDirect, conv_decide_tail(conv_knobs(), N, H, W, Cmid, rfx_group_recording())), a, rfx_stream(stream));
 }

@@ -66,7 +66,7 @@ __device__ __forceinline__ void lds_wait4(u32x4& a, u32x4& b, u32x4& c, u32x4& d
 }
 
 template <int WM, bool ADMA>
-__device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsigned bx) {
+__device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsigned bx, const unsigned) {
     using G = Geo<WM>;
     constexpr int TM = 2;                               // MFMA tiles per wavefront along the channels (and 2 along the pixels)
     constexpr int BM = G::BM, PT_R = G::PT_R, PP = G::PP, B_ITEMS = G::B_ITEMS, NBI = G::NBI;
@@ -294,21 +294,11 @@ __device__ __forceinline__ void conv3x3_split_body(const C3SArgs& a, const unsig
     conv_epilogue<TM, 2, false>(acc, s_scale, s_shift, a.res, a.out, a.act, a.Cout, HW, m0, wm, lrow, pix_off, pix_ok, m0 + BM <= a.Cout);
 }
 
-template <int TM, bool ADMA>
-__global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(C3SArgs a) {
-    conv3x3_split_body<TM, ADMA>(a, blockIdx.x);
-}
+template <int TM, bool ADMA> using Split3 = RfxFamily<C3SArgs, conv3x3_split_body<TM, ADMA>, 256, 2>;
 
 template <int TM, bool ADMA>
-__global__ __launch_bounds__(256, 2) void conv3x3_split_group_kernel(RfxGroupArgs<C3SArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv3x3_split_body<TM, ADMA>(g.p[y], blockIdx.x);
-}
-
-template <int TM, bool ADMA>
-static int c3s_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C3SArgs>(conv3x3_split_group_kernel<TM, ADMA>, 256, blob, gx, n, st);
+__global__ __launch_bounds__((Split3<TM, ADMA>::BLOCK), (Split3<TM, ADMA>::min_waves())) void conv3x3_split_kernel(C3SArgs a) {
+    conv3x3_split_body<TM, ADMA>(a, blockIdx.x, gridDim.x);
 }
 
 template <int TM, bool ADMA>
@@ -319,10 +309,7 @@ int launch_split3_a(C3SArgs& a, hipStream_t st) {
     a.tilesS = (int)((rows + Geo<TM>::PT_R - 1) / Geo<TM>::PT_R);
     const long long nwg = (long long)a.tilesM * a.tilesW * a.tilesS;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    if (rfx_group_recording()) return rfx_group_record(&c3s_group_launch<TM, ADMA>, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL((conv3x3_split_kernel<TM, ADMA>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Split3<TM, ADMA>::launch(conv3x3_split_kernel<TM, ADMA>, a, (unsigned)nwg, st);
 }
 
 template <int TM>
@@ -350,7 +337,7 @@ struct C3S2Args {
     int tilesM, tilesW, tilesS;
 };
 
-__device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const unsigned bx) {
+__device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const unsigned bx, const unsigned) {
     constexpr int TM = 2, BM = 128;
     constexpr int NA = 3;                               // 768 weight words per stage: 3 per thread
     __shared__ u32x4 As[2][3][2][BM];
@@ -504,18 +491,9 @@ __device__ __forceinline__ void conv3x3_split_s2_body(const C3S2Args& a, const u
     conv_epilogue<TM, 2, false>(acc, s_scale, s_shift, a.res, a.out, a.act, a.Cout, HWo, m0, wm, lrow, pix_off, pix_ok, m0 + BM <= a.Cout);
 }
 
-__global__ __launch_bounds__(256, 2) void conv3x3_split_s2_kernel(C3S2Args a) {
-    conv3x3_split_s2_body(a, blockIdx.x);
-}
-
-__global__ __launch_bounds__(256, 2) void conv3x3_split_s2_group_kernel(RfxGroupArgs<C3S2Args> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    conv3x3_split_s2_body(g.p[y], blockIdx.x);
-}
-
-static int c3s2_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<C3S2Args>(conv3x3_split_s2_group_kernel, 256, blob, gx, n, st);
+using Split3S2 = RfxFamily<C3S2Args, conv3x3_split_s2_body, 256, 2>;
+__global__ __launch_bounds__(Split3S2::BLOCK, Split3S2::min_waves()) void conv3x3_split_s2_kernel(C3S2Args a) {
+    conv3x3_split_s2_body(a, blockIdx.x, gridDim.x);
 }
 
 }  // namespace
@@ -543,9 +521,5 @@ extern "C" int rfx_conv3x3_split_s2_f32(const float* in, const void* wS3, const 
     a.tilesS = (int)(((long long)N * (a.Ho + 1) - 1 + 7) / 8);
     const long long nwg = (long long)a.tilesM * a.tilesW * a.tilesS;
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    hipStream_t st = rfx_stream(stream);
-    if (rfx_group_recording()) return rfx_group_record(&c3s2_group_launch, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL(conv3x3_split_s2_kernel, dim3((unsigned)nwg), dim3(256), 0, st, a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Split3S2::launch(conv3x3_split_s2_kernel, a, (unsigned)nwg, rfx_stream(stream));
 }

@@ -204,10 +204,9 @@ typedef struct ihipStream_t* hipStream_t;   // as the HIP runtime declares it
 // Preconditions, checked by the caller: ci is of the launcher's family and was decided for this geometry and this `in`.
 int rfx_conv3x3_direct_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
                               const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int Mpad, int act,
-                              bool recording, hipStream_t st);
+                              hipStream_t st);
 int rfx_conv3x3_s2_launch(const ConvInstance& ci, const float* in, const float* wP, const float* scale, const float* shift,
-                          const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int act, bool recording,
-                          hipStream_t st);
+                          const float* residual, float* out, int N, int Cin, int H, int W, int Cout, int act, hipStream_t st);
 int rfx_conv1x1_kmajor_launch(const ConvInstance& ci, const float* in, const float* wT, const float* scale, const float* shift,
                               const float* residual, float* out, int N, int Cin, int HW, int Cout, int Mpad, int act,
-                              bool recording, hipStream_t st);
+                              hipStream_t st);

@@ -303,7 +303,7 @@ struct CorrArgs {
 };
 
 template <class G>
-__device__ __forceinline__ void corr7_dma_body(const CorrArgs& a, const unsigned bx) {
+__device__ __forceinline__ void corr7_dma_body(const CorrArgs& a, const unsigned bx, const unsigned) {
     const float* __restrict__ x = a.x;
     const float* __restrict__ y = a.y;
     float* __restrict__ out = a.out;
@@ -390,23 +390,12 @@ __device__ __forceinline__ void corr7_dma_body(const CorrArgs& a, const unsigned
 #undef RFX_STRIP
 }
 
-template <class G>
-__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_kernel(CorrArgs a) {
-    corr7_dma_body<G>(a, blockIdx.x);
-}
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block.  One bucket per tile variant: a
-// problem keeps the variant auto_variant() gives it alone.
-template <class G>
-__global__ __launch_bounds__((G::NW * 64), (G::WAVES_PER_SIMD)) void corr7_dma_group_kernel(RfxGroupArgs<CorrArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    corr7_dma_body<G>(g.p[y], blockIdx.x);
-}
+// grouped (group.h): one bucket per tile variant -- a problem keeps the variant auto_variant() gives it alone
+template <class G> using CorrDma = RfxFamily<CorrArgs, corr7_dma_body<G>, G::NW * 64, G::WAVES_PER_SIMD>;
 
 template <class G>
-static int corr_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<CorrArgs>(corr7_dma_group_kernel<G>, G::NW * 64, blob, gx, n, st);
+__global__ __launch_bounds__((CorrDma<G>::BLOCK), (CorrDma<G>::min_waves())) void corr7_dma_kernel(CorrArgs a) {
+    corr7_dma_body<G>(a, blockIdx.x, gridDim.x);
 }
 
 template <class G>
@@ -416,8 +405,8 @@ static int launch_corr(const float* x, const float* y, float* out, float* out21,
     const int trv = G::TUNED ? (H + tilesR - 1) / tilesR : G::TR;  // equal row tiles (60 = 4 x 15) or full TR-row tiles
     const CorrArgs a = {x, y, out, out21, N, C, H, W, tilesR, tilesC, trv};
     const unsigned nwg = (unsigned)(N * tilesR * tilesC);
-    if (rfx_group_recording()) return rfx_group_record(&corr_group_launch<G>, &a, sizeof(a), nwg);   // never with t_timing: entry points
-    corr_launch((corr7_dma_kernel<G>), dim3(nwg), dim3(G::NW * 64), st, a);
+    if (rfx_group_recording()) return CorrDma<G>::record(a, nwg);   // never with t_timing: entry points
+    corr_launch((corr7_dma_kernel<G>), dim3(nwg), dim3(CorrDma<G>::BLOCK), st, a);
     return RFX_OK;
 }
 
@@ -452,17 +441,8 @@ __device__ __forceinline__ void corr7_plain_body(const CorrPlainArgs& a, const u
     }
 }
 
-__global__ __launch_bounds__(256) void corr7_plain_kernel(CorrPlainArgs a) { corr7_plain_body(a, blockIdx.x, gridDim.x); }
-
-__global__ __launch_bounds__(256) void corr7_plain_group_kernel(RfxGroupArgs<CorrPlainArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    corr7_plain_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int corr_plain_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<CorrPlainArgs>(corr7_plain_group_kernel, 256, blob, gx, n, st);
-}
+using CorrPlain = RfxFamily<CorrPlainArgs, corr7_plain_body, 256>;
+__global__ __launch_bounds__(CorrPlain::BLOCK) void corr7_plain_kernel(CorrPlainArgs a) { corr7_plain_body(a, blockIdx.x, gridDim.x); }
 
 // Variant table (rfx_corr_neigh_variant_f32 / RFX_CORR_VARIANT; 0 = automatic): the six tile shapes auto_variant() returns.
 // All are bit-identical; every other number is RFX_E_ARG.  BIDIR: the form that also writes corr(y, x) to out21.
@@ -522,11 +502,10 @@ extern "C" int rfx_corr_neigh_variant_f32(const float* x, const float* y, float*
         if (rc != RFX_OK) return rc;
     } else {
         const long long NP = (long long)N * H * W;
-        long long g = (NP + 255) / 256;
+        long long g = (NP + CorrPlain::BLOCK - 1) / CorrPlain::BLOCK;
         if (g > 8192) g = 8192;
         const CorrPlainArgs a = {x, y, out, NP, C, H, W};
-        if (rfx_group_recording()) return rfx_group_record(&corr_plain_group_launch, &a, sizeof(a), (unsigned)g);
-        hipLaunchKernelGGL(corr7_plain_kernel, dim3((unsigned)g), dim3(256), 0, st, a);
+        return CorrPlain::launch(corr7_plain_kernel, a, (unsigned)g, st);
     }
     RFX_LAUNCH_CHECK();
     return RFX_OK;

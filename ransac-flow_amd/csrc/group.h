@@ -39,3 +39,62 @@ static int rfx_group_launch_impl(K kernel, int block, const void* blob, const un
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A kernel family = its argument block A, its body -- a __device__ function of (arguments, the problem's own block index bx, the
+// problem's own grid gx; a body without a grid-stride loop leaves gx unnamed) -- its block size and, only where the family has one,
+// the second __launch_bounds__ argument.  RfxFamily makes the grouped kernel, the launcher rfx_group_record() stores and the
+// "record if a group is recording" step from them; the single-launch kernel takes its launch bound from it:
+//     using WarpGrid = RfxFamily<WarpGridArgs, warp_grid_body, 256>;
+//     __global__ __launch_bounds__(WarpGrid::BLOCK) void warp_grid_kernel(WarpGridArgs a) { ...body(a, blockIdx.x, gridDim.x); }
+//     ... return WarpGrid::launch(warp_grid_kernel, a, grid, stream);
+template <class A> using RfxBody = void (*)(const A&, unsigned, unsigned);
+
+// The grouped kernel of family F (an RfxFamily: a class type, so that the kernel's name demangles everywhere and shows the body
+// with its template arguments): blockIdx.y = problem, the body on that problem's argument block and its own grid.  The body is called
+// straight from the kernel, as the hand-written grouped kernels called it, not through one more inlined function: that keeps every
+// instance's machine code what it was (profiles/group_launch_codegen.tsv).
+template <class F>
+__global__ __launch_bounds__(F::BLOCK) void rfx_group_kernel(RfxGroupArgs<typename F::Args> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    F::body(g.p[y], blockIdx.x, g.gx[y]);
+}
+// __launch_bounds__(B) and __launch_bounds__(B, n) are different attributes for every n, so a family without a second argument must
+// not get one from a default: the families that have one take this kernel
+template <class F>
+__global__ __launch_bounds__(F::BLOCK, F::min_waves()) void rfx_group_kernel_w(RfxGroupArgs<typename F::Args> g) {
+    const unsigned y = blockIdx.y;
+    if (blockIdx.x >= g.gx[y]) return;
+    F::body(g.p[y], blockIdx.x, g.gx[y]);
+}
+
+template <class A, RfxBody<A> Body, int BLOCK_, int... MIN_WAVES_>
+struct RfxFamily {
+    static_assert(sizeof...(MIN_WAVES_) <= 1, "at most one second __launch_bounds__ argument");
+    using Args = A;
+    static constexpr RfxBody<A> body = Body;
+    static constexpr int BLOCK = BLOCK_;
+    // the second __launch_bounds__ argument; a compile error in a family declared without one
+    static constexpr int min_waves() {
+        static_assert(sizeof...(MIN_WAVES_) == 1, "this family has no second __launch_bounds__ argument");
+        return (0 + ... + MIN_WAVES_);
+    }
+
+    // the launcher rfx_group_record() stores (and keys the bucket by)
+    static int group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
+        if constexpr (sizeof...(MIN_WAVES_) == 0)
+            return rfx_group_launch_impl<A>(rfx_group_kernel<RfxFamily>, BLOCK, blob, gx, n, st);
+        else
+            return rfx_group_launch_impl<A>(rfx_group_kernel_w<RfxFamily>, BLOCK, blob, gx, n, st);
+    }
+    // the record half alone, for a family with a single-launch statement of its own (corr.hip)
+    static int record(const A& a, unsigned gx) { return rfx_group_record(&group_launch, &a, sizeof(A), gx); }
+    // record where a group is recording, else launch `single`, the family's single-launch kernel, on gx workgroups
+    template <class K> static int launch(K single, const A& a, unsigned gx, hipStream_t st) {
+        if (rfx_group_recording()) return record(a, gx);
+        hipLaunchKernelGGL(single, dim3(gx), dim3(BLOCK), 0, st, a);
+        RFX_LAUNCH_CHECK();
+        return RFX_OK;
+    }
+};

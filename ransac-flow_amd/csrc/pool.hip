@@ -97,29 +97,15 @@ __device__ __forceinline__ void blurpool2d_body(const PlaneArgs& a, const unsign
     }(a.in, a.out);
 }
 
-__global__ __launch_bounds__(256) void blurpool2d_kernel(PlaneArgs a) { blurpool2d_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
-__global__ __launch_bounds__(256) void blurpool2d_group_kernel(RfxGroupArgs<PlaneArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    blurpool2d_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int blurpool2d_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<PlaneArgs>(blurpool2d_group_kernel, 256, blob, gx, n, st);
-}
+using BlurPool = RfxFamily<PlaneArgs, blurpool2d_body, 256>;
+__global__ __launch_bounds__(BlurPool::BLOCK) void blurpool2d_kernel(PlaneArgs a) { blurpool2d_body(a, blockIdx.x, gridDim.x); }
 
 extern "C" int rfx_blurpool2d_f32(const float* in, float* out, int NC, int Hin, int Win, int stride, void* stream) {
     if (!in || !out || NC <= 0 || Hin < 2 || Win < 2 || stride <= 0) return RFX_E_ARG;
     const int Hout = (Hin + 2 - 3) / stride + 1, Wout = (Win + 2 - 3) / stride + 1;
     const long long total = (long long)NC * Hout * Wout;
     const PlaneArgs a = {in, out, total, Hin, Win, Hout, Wout, stride};
-    const unsigned gx = (unsigned)grid_for(total, 256);
-    if (rfx_group_recording()) return rfx_group_record(&blurpool2d_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(blurpool2d_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return BlurPool::launch(blurpool2d_kernel, a, (unsigned)grid_for(total, BlurPool::BLOCK), rfx_stream(stream));
 }
 
 // Fused nn.MaxPool2d(kernel 2, stride 1) + BlurPool(stride): the FeatureExtractor stem (model/model.py:71-72).
@@ -310,18 +296,8 @@ __device__ __forceinline__ void l2norm_nchw_body(const L2NormArgs& a, const unsi
     }
 }
 
-__global__ __launch_bounds__(64) void l2norm_nchw_kernel(L2NormArgs a) { l2norm_nchw_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
-__global__ __launch_bounds__(64) void l2norm_nchw_group_kernel(RfxGroupArgs<L2NormArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    l2norm_nchw_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int l2norm_nchw_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<L2NormArgs>(l2norm_nchw_group_kernel, 64, blob, gx, n, st);
-}
+using L2Norm = RfxFamily<L2NormArgs, l2norm_nchw_body, 64>;
+__global__ __launch_bounds__(L2Norm::BLOCK) void l2norm_nchw_kernel(L2NormArgs a) { l2norm_nchw_body(a, blockIdx.x, gridDim.x); }
 
 // Same arithmetic with four wavefronts per 64 pixels doing the LOADS (wavefront q fetches the channels c = q (mod 4), 32 loads in
 // flight per thread: on the trunk's 1-5 k-pixel maps the kernel is pure load latency) while the chain itself stays ONE chain: the
@@ -381,18 +357,8 @@ __device__ __forceinline__ void l2norm_nchw_q4_body(const L2NormArgs& a, const u
     for (; c < C; c += 4) dst[(size_t)c * ocs] = __fdiv_rn(src[(size_t)c * HW], d);
 }
 
-__global__ __launch_bounds__(256) void l2norm_nchw_q4_kernel(L2NormArgs a) { l2norm_nchw_q4_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
-__global__ __launch_bounds__(256) void l2norm_nchw_q4_group_kernel(RfxGroupArgs<L2NormArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    l2norm_nchw_q4_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int l2norm_nchw_q4_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<L2NormArgs>(l2norm_nchw_q4_group_kernel, 256, blob, gx, n, st);
-}
+using L2NormQ4 = RfxFamily<L2NormArgs, l2norm_nchw_q4_body, 256>;
+__global__ __launch_bounds__(L2NormQ4::BLOCK) void l2norm_nchw_q4_kernel(L2NormArgs a) { l2norm_nchw_q4_body(a, blockIdx.x, gridDim.x); }
 
 // The norm of l2norm_nchw_q4_kernel for the N images of one shape bucket of a ragged batch, image n written to out + dst_off[n]
 // (its pair's columns of the padded featA / featB): one launch per bucket instead of one per image.  Same loads, same chain, same
@@ -455,19 +421,9 @@ extern "C" int rfx_l2norm_nchw_f32(const float* in, float* out, int N, int C, in
     const long long ocs = out_chan_stride ? out_chan_stride : HW;
     const long long obs = out_batch_stride ? out_batch_stride : (long long)C * HW;
     const L2NormArgs a = {in, out, NP, C, HW, obs, ocs};
-    const bool recording = rfx_group_recording();
-    if (C % 4 == 0 && C >= 32 && (NP + 63) / 64 <= 0x7fffffffLL) {
-        const unsigned gx = (unsigned)((NP + 63) / 64);
-        if (recording) return rfx_group_record(&l2norm_nchw_q4_group_launch, &a, sizeof(a), gx);
-        hipLaunchKernelGGL(l2norm_nchw_q4_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-        RFX_LAUNCH_CHECK();
-        return RFX_OK;
-    }
-    const unsigned gx = (unsigned)grid_for(NP, 64);
-    if (recording) return rfx_group_record(&l2norm_nchw_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(l2norm_nchw_kernel, dim3(gx), dim3(64), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    if (C % 4 == 0 && C >= 32 && (NP + 63) / 64 <= 0x7fffffffLL)
+        return L2NormQ4::launch(l2norm_nchw_q4_kernel, a, (unsigned)((NP + 63) / 64), rfx_stream(stream));
+    return L2Norm::launch(l2norm_nchw_kernel, a, (unsigned)grid_for(NP, L2Norm::BLOCK), rfx_stream(stream));
 }
 
 extern "C" int rfx_l2norm_nchw_scatter_f32(const float* in, float* out, int N, int C, int HW, const long long* dst_off,
@@ -515,28 +471,14 @@ __device__ __forceinline__ void flow_head_body(const FlowHeadArgs& a, const unsi
     }
 }
 
-__global__ __launch_bounds__(256) void flow_head_kernel(FlowHeadArgs a) { flow_head_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
-__global__ __launch_bounds__(256) void flow_head_group_kernel(RfxGroupArgs<FlowHeadArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    flow_head_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int flow_head_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<FlowHeadArgs>(flow_head_group_kernel, 64, blob, gx, n, st);
-}
+using FlowHead = RfxFamily<FlowHeadArgs, flow_head_body, 64>;
+__global__ __launch_bounds__(FlowHead::BLOCK) void flow_head_kernel(FlowHeadArgs a) { flow_head_body(a, blockIdx.x, gridDim.x); }
 
 extern "C" int rfx_flow_head_f32(const float* logits, float* flow, int N, int K, int rows, int cols, void* stream) {
     if (!logits || !flow || N <= 0 || K <= 0 || (K & 1) == 0 || rows <= 0 || cols <= 0) return RFX_E_ARG;
     const long long NP = (long long)N * rows * cols;
     const FlowHeadArgs a = {logits, flow, NP, K, rows, cols};
-    const unsigned gx = (unsigned)grid_for(NP, 64);
-    if (rfx_group_recording()) return rfx_group_record(&flow_head_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(flow_head_kernel, dim3(gx), dim3(64), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return FlowHead::launch(flow_head_kernel, a, (unsigned)grid_for(NP, FlowHead::BLOCK), rfx_stream(stream));
 }
 
 // ATen upsample_bilinear2d index rule.
@@ -576,18 +518,8 @@ __device__ __forceinline__ void resize_bilinear_body(const ResizeArgs& a, const 
     }(a.in, a.out);
 }
 
-__global__ __launch_bounds__(256) void resize_bilinear_kernel(ResizeArgs a) { resize_bilinear_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and its own grid
-__global__ __launch_bounds__(256) void resize_bilinear_group_kernel(RfxGroupArgs<ResizeArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    resize_bilinear_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int resize_bilinear_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<ResizeArgs>(resize_bilinear_group_kernel, 256, blob, gx, n, st);
-}
+using ResizeBilinear = RfxFamily<ResizeArgs, resize_bilinear_body, 256>;
+__global__ __launch_bounds__(ResizeBilinear::BLOCK) void resize_bilinear_kernel(ResizeArgs a) { resize_bilinear_body(a, blockIdx.x, gridDim.x); }
 
 extern "C" int rfx_resize_bilinear_f32(const float* in, float* out, int NC, int Hin, int Win, int Hout, int Wout,
                                        int align_corners, void* stream) {
@@ -602,11 +534,7 @@ extern "C" int rfx_resize_bilinear_f32(const float* in, float* out, int NC, int 
     }
     const long long total = (long long)NC * Hout * Wout;
     const ResizeArgs a = {in, out, total, Hin, Win, Hout, Wout, sh, sw, align_corners};
-    const unsigned gx = (unsigned)grid_for(total, 256);
-    if (rfx_group_recording()) return rfx_group_record(&resize_bilinear_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return ResizeBilinear::launch(resize_bilinear_kernel, a, (unsigned)grid_for(total, ResizeBilinear::BLOCK), rfx_stream(stream));
 }
 
 // Row-pitch change: dst[r, 0:wd] = src[r, 0:min(ws, wd)], zero beyond (correlation on maps whose width is not a multiple

@@ -52,7 +52,7 @@ __device__ __forceinline__ float umaxf(float x, float y) {
     return __uint_as_float(a > b ? a : b);
 }
 
-__device__ __forceinline__ void stem_conv_maxblur_body(const StemArgs& a, const unsigned bx) {
+__device__ __forceinline__ void stem_conv_maxblur_body(const StemArgs& a, const unsigned bx, const unsigned) {
     __shared__ float P[3][PRW][PCL];          // input patch
     __shared__ float C[MCH * CPS];            // conv + BN + ReLU outputs of ONE channel group under the tile: [channel][CR][CST], planes CPS apart
 
@@ -205,19 +205,9 @@ __device__ __forceinline__ void stem_conv_maxblur_body(const StemArgs& a, const 
     }
 }
 
-__global__ __launch_bounds__(256) void stem_conv_maxblur_kernel(StemArgs a) {
-    stem_conv_maxblur_body(a, blockIdx.x);
-}
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block
-__global__ __launch_bounds__(256) void stem_conv_maxblur_group_kernel(RfxGroupArgs<StemArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    stem_conv_maxblur_body(g.p[y], blockIdx.x);
-}
-
-static int stem3_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<StemArgs>(stem_conv_maxblur_group_kernel, 256, blob, gx, n, st);
+using Stem3 = RfxFamily<StemArgs, stem_conv_maxblur_body, 256>;
+__global__ __launch_bounds__(Stem3::BLOCK) void stem_conv_maxblur_kernel(StemArgs a) {
+    stem_conv_maxblur_body(a, blockIdx.x, gridDim.x);
 }
 
 
@@ -289,7 +279,7 @@ __device__ __forceinline__ unsigned row_shl0(unsigned v) {
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 + N, 0xf, 0xf, true);
 }
 
-__device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, const unsigned bx) {
+__device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, const unsigned bx, const unsigned) {
     constexpr int TH = r50::TH, TW = r50::TW, CR = r50::CR, PR = r50::PR, PCW = r50::PCW, PHALF = r50::PHALF,
                   PST = r50::PST, HPS = r50::HPS, SPS = r50::SPS, NSUB = r50::NSUB, KKS = r50::KKS, MCH = r50::MCH;
     using r50::koff;
@@ -435,19 +425,9 @@ __device__ __forceinline__ void stem7_conv_maxpool_body(const Stem7Args& a, cons
     RFX_PUT7(6, (long long)a.chGroups);
 }
 
-__global__ __launch_bounds__(256, 2) void stem7_conv_maxpool_kernel(Stem7Args a) {
-    stem7_conv_maxpool_body(a, blockIdx.x);
-}
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block
-__global__ __launch_bounds__(256, 2) void stem7_conv_maxpool_group_kernel(RfxGroupArgs<Stem7Args> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    stem7_conv_maxpool_body(g.p[y], blockIdx.x);
-}
-
-static int stem7_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<Stem7Args>(stem7_conv_maxpool_group_kernel, 256, blob, gx, n, st);
+using Stem7 = RfxFamily<Stem7Args, stem7_conv_maxpool_body, 256, 2>;
+__global__ __launch_bounds__(Stem7::BLOCK, Stem7::min_waves()) void stem7_conv_maxpool_kernel(Stem7Args a) {
+    stem7_conv_maxpool_body(a, blockIdx.x, gridDim.x);
 }
 
 }  // namespace
@@ -463,10 +443,7 @@ extern "C" int rfx_stem_conv3x3_maxblur_f32(const float* in, const float* wT, co
     a.tilesH = (a.Ho + TH - 1) / TH; a.tilesW = (a.Wo + TW - 1) / TW; a.chGroups = Cout / MCH;
     const long long nwg = (long long)N * a.tilesH * a.tilesW;      // a workgroup walks all channel groups of its tile
     if (nwg > 0x7fffffffLL) return RFX_E_LIMIT;
-    if (rfx_group_recording()) return rfx_group_record(&stem3_group_launch, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL(stem_conv_maxblur_kernel, dim3((unsigned)nwg), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Stem3::launch(stem_conv_maxblur_kernel, a, (unsigned)nwg, rfx_stream(stream));
 }
 
 extern "C" int rfx_stem_conv7x7_maxpool_f32(const float* in, const float* wT, const float* scale, const float* shift,
@@ -485,8 +462,5 @@ extern "C" int rfx_stem_conv7x7_maxpool_f32(const float* in, const float* wT, co
 #ifdef RFX_TRACE
     a.trace = rfx_debug_trace_ptr();
 #endif
-    if (rfx_group_recording()) return rfx_group_record(&stem7_group_launch, &a, sizeof(a), (unsigned)nwg);
-    hipLaunchKernelGGL(stem7_conv_maxpool_kernel, dim3((unsigned)nwg), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return Stem7::launch(stem7_conv_maxpool_kernel, a, (unsigned)nwg, rfx_stream(stream));
 }

@@ -89,14 +89,8 @@ __device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsi
     }
 }
 
-__global__ __launch_bounds__(256) void warp_grid_kernel(WarpGridArgs a) { warp_grid_body(a, blockIdx.x, gridDim.x); }
-
-// grouped form (group.h): blockIdx.y = problem, the same body on that problem's argument block and grid
-__global__ __launch_bounds__(256) void warp_grid_group_kernel(RfxGroupArgs<WarpGridArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    warp_grid_body(g.p[y], blockIdx.x, g.gx[y]);
-}
+using WarpGrid = RfxFamily<WarpGridArgs, warp_grid_body, 256>;
+__global__ __launch_bounds__(WarpGrid::BLOCK) void warp_grid_kernel(WarpGridArgs a) { warp_grid_body(a, blockIdx.x, gridDim.x); }
 
 __device__ __forceinline__ void grid_sample_body(const GridSampleArgs& a, const unsigned bx, const unsigned gx) {
     const float* __restrict__ in = a.in;
@@ -126,13 +120,8 @@ __device__ __forceinline__ void grid_sample_body(const GridSampleArgs& a, const 
     }
 }
 
-__global__ __launch_bounds__(256) void grid_sample_kernel(GridSampleArgs a) { grid_sample_body(a, blockIdx.x, gridDim.x); }
-
-__global__ __launch_bounds__(256) void grid_sample_group_kernel(RfxGroupArgs<GridSampleArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    grid_sample_body(g.p[y], blockIdx.x, g.gx[y]);
-}
+using GridSample = RfxFamily<GridSampleArgs, grid_sample_body, 256>;
+__global__ __launch_bounds__(GridSample::BLOCK) void grid_sample_kernel(GridSampleArgs a) { grid_sample_body(a, blockIdx.x, gridDim.x); }
 
 __device__ __forceinline__ float src_index(float scale, int dst) {  // align_corners=False
     const float s = scale * ((float)dst + 0.5f) - 0.5f;
@@ -192,23 +181,8 @@ __device__ __forceinline__ void compose_flow_body(const ComposeFlowArgs& a, cons
     }
 }
 
-__global__ __launch_bounds__(256) void compose_flow_kernel(ComposeFlowArgs a) { compose_flow_body(a, blockIdx.x, gridDim.x); }
-
-__global__ __launch_bounds__(256) void compose_flow_group_kernel(RfxGroupArgs<ComposeFlowArgs> g) {
-    const unsigned y = blockIdx.y;
-    if (blockIdx.x >= g.gx[y]) return;
-    compose_flow_body(g.p[y], blockIdx.x, g.gx[y]);
-}
-
-static int warp_grid_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<WarpGridArgs>(warp_grid_group_kernel, 256, blob, gx, n, st);
-}
-static int grid_sample_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<GridSampleArgs>(grid_sample_group_kernel, 256, blob, gx, n, st);
-}
-static int compose_flow_group_launch(const void* blob, const unsigned* gx, int n, hipStream_t st) {
-    return rfx_group_launch_impl<ComposeFlowArgs>(compose_flow_group_kernel, 256, blob, gx, n, st);
-}
+using ComposeFlow = RfxFamily<ComposeFlowArgs, compose_flow_body, 256>;
+__global__ __launch_bounds__(ComposeFlow::BLOCK) void compose_flow_kernel(ComposeFlowArgs a) { compose_flow_body(a, blockIdx.x, gridDim.x); }
 
 // Multi-homography merge of the offline flow assembly (evaluation/evalHpatch/getResults.py:48-61,
 // evaluation/evalCorr/getResults.py:121-134, evaluation/evalKITTI/getResults.py:126-138): one thread per pixel walks the
@@ -289,11 +263,7 @@ extern "C" int rfx_warp_grid_f32(const float* Hm, float* grid, int B, int h, int
     if (!Hm || !grid || B <= 0 || h <= 0 || w <= 0) return RFX_E_ARG;
     const long long total = (long long)B * h * w;
     const WarpGridArgs a = {Hm, grid, total, h, w};
-    const unsigned gx = (unsigned)grid_for(total, 256);
-    if (rfx_group_recording()) return rfx_group_record(&warp_grid_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(warp_grid_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return WarpGrid::launch(warp_grid_kernel, a, (unsigned)grid_for(total, WarpGrid::BLOCK), rfx_stream(stream));
 }
 
 extern "C" int rfx_grid_sample_f32(const float* in, const float* grid, float* out, int N, int C, int Hi, int Wi,
@@ -301,11 +271,7 @@ extern "C" int rfx_grid_sample_f32(const float* in, const float* grid, float* ou
     if (!in || !grid || !out || N <= 0 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return RFX_E_ARG;
     const long long NP = (long long)N * Ho * Wo;
     const GridSampleArgs a = {in, grid, out, NP, C, Hi, Wi, Ho, Wo, align_corners};
-    const unsigned gx = (unsigned)grid_for(NP, 256);
-    if (rfx_group_recording()) return rfx_group_record(&grid_sample_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(grid_sample_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return GridSample::launch(grid_sample_kernel, a, (unsigned)grid_for(NP, GridSample::BLOCK), rfx_stream(stream));
 }
 
 extern "C" int rfx_compose_flow_f32(const float* flowDown, const float* coarseGrid, float* flow12, float* inb,
@@ -316,11 +282,7 @@ extern "C" int rfx_compose_flow_f32(const float* flowDown, const float* coarseGr
     const long long NP = (long long)N * H * W;
     const float sh = (float)hd / (float)H, sw = (float)wd / (float)W;
     const ComposeFlowArgs a = {flowDown, coarseGrid, flow12, inb, flowUp, NP, hd, wd, Hc, Wc, H, W, sh, sw, clamp};
-    const unsigned gx = (unsigned)grid_for(NP, 256);
-    if (rfx_group_recording()) return rfx_group_record(&compose_flow_group_launch, &a, sizeof(a), gx);
-    hipLaunchKernelGGL(compose_flow_kernel, dim3(gx), dim3(256), 0, rfx_stream(stream), a);
-    RFX_LAUNCH_CHECK();
-    return RFX_OK;
+    return ComposeFlow::launch(compose_flow_kernel, a, (unsigned)grid_for(NP, ComposeFlow::BLOCK), rfx_stream(stream));
 }
 
 extern "C" int rfx_merge_multi_h_f32(const float* flow, const float* match12, long long match12_stride,

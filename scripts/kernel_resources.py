@@ -16,10 +16,18 @@ it; for a kernel without MFMAs, the loops with at least 16 FMAs), ``k_loop_mfma`
 per-tile set-up of a persistent kernel, the epilogue).  A spill outside the K loops costs a few memory instructions per tile; one
 inside is paid per K step.
 
+``--codegen`` prints, per kernel, the number of instructions and a hash of its disassembled instruction stream: opcodes and
+operands, without addresses and encodings; a branch target counts as its offset from the kernel's first instruction, without the
+symbol's name.  Two things that only depend on where the linker put the kernel are left out as well: the pc-relative literal that
+forms the address of a global (s_getpc_b64, then s_add_u32 / s_addc_u32 on that register pair) and the s_nop padding behind a code
+object's last kernel.  Two builds whose rows agree run the same machine code, whatever their kernels are called
+(profiles/group_launch_codegen.tsv).
+
 tests/test_oracle.py holds the table against what DESIGN.md says about the hot kernels.
 """
 import argparse
 import collections
+import hashlib
 import os
 import re
 import subprocess
@@ -171,6 +179,41 @@ def mix_table(pattern, lib=LIB):
     return rows
 
 
+def codegen_table(lib=LIB):
+    """[unit, kernel, instructions, hash of the instruction stream] of every kernel: one disassembly per code object."""
+    rows = []
+    with tempfile.TemporaryDirectory() as d:
+        cos = code_objects(lib, d)
+        for unit, co in zip(unit_names(len(cos)), cos):
+            ks = metadata(co)
+            names = dict(zip([k["name"] for k in ks], demangle([k["name"] for k in ks])))
+            asm = subprocess.run([tool("llvm-objdump"), "-d", co], check=True, capture_output=True, text=True).stdout
+            streams, cur, pc = {}, None, ()
+            for l in asm.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(\S+)>:$", l)
+                if m:
+                    cur, pc = streams.setdefault(m.group(1), []) if m.group(1) in names else None, ()
+                    continue
+                m = cur is not None and re.match(r"^\t([^/]*\S)\s*// [0-9A-F]+:", l)
+                if not m:
+                    continue
+                text = " ".join(m.group(1).split())
+                g = re.match(r"s_getpc_b64 s\[(\d+):(\d+)\]$", text)
+                if g:
+                    pc = ("s_add_u32 s%s, s%s, " % (g.group(1), g.group(1)), "s_addc_u32 s%s, s%s, " % (g.group(2), g.group(2)))
+                elif text.startswith(pc):
+                    text, pc = text[:text.rindex(" ")] + " <pcrel>", tuple(x for x in pc if not text.startswith(x))
+                tgt = re.search(r"<\S+\+0x([0-9a-f]+)>\s*$", l) if text.startswith(("s_cbranch", "s_branch")) else None
+                cur.append(text + (" -> +0x" + tgt.group(1) if tgt else ""))
+            for k in ks:
+                ins = streams.get(k["name"], [])
+                while ins and ins[-1] == "s_nop 0":
+                    ins.pop()
+                rows.append(dict(unit=unit, kernel=names[k["name"]], instructions=len(ins),
+                                 hash=hashlib.sha256("\n".join(ins).encode()).hexdigest()[:16]))
+    return rows
+
+
 def occupancy(vgpr, agpr, lds, wg):
     regs = -(-max(vgpr + agpr, 1) // VGPR_BLOCK) * VGPR_BLOCK       # unified file: arch + acc, rounded to the allocation block
     waves_simd = min(MAX_WAVES, VGPR_FILE // regs)
@@ -202,7 +245,16 @@ def main():
     ap.add_argument("--tsv")
     ap.add_argument("--lib", default=LIB)
     ap.add_argument("--mix", metavar="REGEX", help="instead: the instruction mix of the largest K loop of the kernels matching REGEX")
+    ap.add_argument("--codegen", action="store_true", help="instead: per kernel, a hash of its disassembled instruction stream")
     a = ap.parse_args()
+    if a.codegen:
+        cols = ["unit", "kernel", "instructions", "hash"]
+        text = "\t".join(cols) + "\n" + "".join("\t".join(str(r[c]) for c in cols) + "\n" for r in codegen_table(a.lib))
+        if a.tsv:
+            with open(a.tsv, "w") as f:
+                f.write("# instruction-stream hashes of librfx.so's gfx950 kernels (scripts/kernel_resources.py --codegen)\n" + text)
+        sys.stdout.write(text)
+        return
     if a.mix:
         cols = ["kernel", "bytes"] + MIX
         text = "\t".join(cols) + "\n" + "".join("\t".join(str(r[c]) for c in cols) + "\n" for r in mix_table(a.mix, a.lib))

@@ -227,7 +227,7 @@ def test_wide_instance_against_float64(runs, case, dev):
 
 
 def test_grouped_launch_of_three_sizes(runs, dev):
-    """One recorded launch of three problems of different sizes (conv1x1_split_wide_group_kernel): every member equals its own single
+    """One recorded launch of three problems of different sizes (the wide family's rfx_group_kernel_w): every member equals its own single
     launch, the 128-channel instance's grouped launch, and float64."""
     from test_gpu_conv_exact import exact_reference
     assert runs["wide"]["tile"]["group"] == [256] * 3 and runs["narrow"]["tile"]["group"] == [128] * 3
