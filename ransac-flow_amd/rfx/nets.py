@@ -4,6 +4,7 @@ Each class is built from a reference-keyed ``state_dict`` (see rfx/weights.py), 
 folds eval-mode BatchNorm once, and then runs forward-only on device tensors.  Activations stay NCHW fp32
 from the first layer to the last: there is no layout conversion between kernels.
 """
+import functools
 import os
 
 import torch
@@ -61,23 +62,35 @@ class ResNet50Trunk:
                 self.blocks.append(blk)
 
     def __call__(self, x):
-        x = ops.stem_conv7_maxpool(x, self.conv1)  # conv1 + BN + ReLU + MaxPool2d(3, 2, 1) in one kernel
+        return self._forward([x], True, True)[0]
+
+    def forward_group(self, xs, side_streams=True):
+        """The same pass over several inputs of DIFFERENT sizes (a single pair's 7 pyramid levels + target), layer by layer with
+        one grouped launch per kernel instance and layer instead of one launch per layer and input: bit-identical to
+        [self(x) for x in xs].  The expand64 forms are never used here, whatever the list length."""
+        return self._forward(xs, side_streams, False)
+
+    def _forward(self, xs, side_streams, expand64):
+        """The layer sequence, one ops.stage per layer over the inputs ``xs``.  ``expand64``: layer1's 64 -> 256 expansions may take
+        ops.conv1x1_expand64's forms (expand64_form)."""
+        st = functools.partial(ops.stage, device=xs[0].device, side_streams=side_streams)
+        xs = st(lambda x: ops.stem_conv7_maxpool(x, self.conv1), xs)  # conv1 + BN + ReLU + MaxPool2d(3, 2, 1) in one kernel
         for blk in self.blocks:
-            o = blk["c1"](x)
-            form = self.expand64_form(blk)
+            c1, c2, c3, ds = blk["c1"], blk["c2"], blk["c3"], blk["ds"]
+            form = self.expand64_form(blk) if expand64 else None
             if form == "dual":
                 # layer1.0: conv3 and the projection shortcut in one launch -- the 256-channel shortcut never goes to memory
-                x = ops.conv1x1_expand64(blk["c2"](o), blk["c3"], shortcut=(x, blk["ds"]))
+                xs = st(lambda m, x: ops.conv1x1_expand64(m, c3, shortcut=(x, ds)), st(c2, st(c1, xs)), xs)
                 continue
-            r = blk["ds"](x) if blk["ds"] is not None else x
-            if ops.bottleneck_tail_eligible(blk["c2"], blk["c3"]):
-                x = ops.bottleneck_tail(o, blk["c2"], blk["c3"], residual=r)   # conv2 + conv3 in one kernel
+            # c1 and the projection shortcut both read x only: one stage
+            os_, rs = zip(*st(lambda x: (c1(x), ds(x) if ds is not None else x), xs))
+            if ops.bottleneck_tail_eligible(c2, c3):
+                xs = st(lambda o, r: ops.bottleneck_tail(o, c2, c3, residual=r), os_, rs)   # conv2 + conv3 in one kernel
             elif form == "plain":
-                x = ops.conv1x1_expand64(blk["c2"](o), blk["c3"], residual=r)   # layer1.1 / layer1.2
+                xs = st(lambda m, r: ops.conv1x1_expand64(m, c3, residual=r), st(c2, os_), rs)   # layer1.1 / layer1.2
             else:
-                o = blk["c2"](o)
-                x = blk["c3"](o, residual=r)  # relu(bn3(conv3(o)) + r)
-        return x
+                xs = st(lambda m, r: c3(m, residual=r), st(c2, os_), rs)  # relu(bn3(conv3(o)) + r)
+        return xs
 
     @staticmethod
     def expand64_form(blk):
@@ -86,31 +99,6 @@ class ResNet50Trunk:
         if ops.bottleneck_tail_eligible(blk["c2"], blk["c3"]):
             return None
         return ops.expand64_form(blk["c3"], blk["ds"])
-
-
-    def forward_group(self, xs, side_streams=True):
-        """The same pass over several inputs of DIFFERENT sizes (a single pair's 7 pyramid levels + target), layer by layer
-        with one grouped launch per kernel instance and layer (ops.launch_group) instead of one launch per layer and input:
-        bit-identical to [self(x) for x in xs]."""
-        dev = xs[0].device
-        with ops.launch_group(dev, side_streams):
-            xs = [ops.stem_conv7_maxpool(x, self.conv1) for x in xs]
-        for blk in self.blocks:
-            with ops.launch_group(dev, side_streams):          # c1 and the projection shortcut both read x only: one group
-                os_ = [blk["c1"](x) for x in xs]
-                rs = [blk["ds"](x) for x in xs] if blk["ds"] is not None else xs
-            # outputs get NEW names inside a group and are rebound after it: the recorded launches read their inputs when the
-            # group ends, so every input tensor must stay referenced until then (launch_group's contract)
-            if ops.bottleneck_tail_eligible(blk["c2"], blk["c3"]):
-                with ops.launch_group(dev, side_streams):
-                    ys = [ops.bottleneck_tail(o, blk["c2"], blk["c3"], residual=r) for o, r in zip(os_, rs)]
-            else:
-                with ops.launch_group(dev, side_streams):
-                    ms = [blk["c2"](o) for o in os_]
-                with ops.launch_group(dev, side_streams):
-                    ys = [blk["c3"](m, residual=r) for m, r in zip(ms, rs)]
-            xs = ys
-        return xs
 
 
 class FeatureExtractorNet:
@@ -136,32 +124,21 @@ class FeatureExtractorNet:
                 self.blocks.append(blk)
 
     def __call__(self, x):
-        x = ops.stem_conv_maxblur(x, self.conv1)  # conv1 + BN + ReLU + MaxPool2d(2, stride 1) + BlurPool/2 in one kernel
-        for blk in self.blocks:
-            o = blk["c1"](x)
-            r = blk["ds"](ops.blurpool2d(x, blk["stride"])) if blk["ds"] is not None else x
-            x = blk["c2"](o, residual=r)
-        return x
+        return self.forward_group([x])[0]
 
     def forward_group(self, xs, side_streams=True):
-        """The same pass over several inputs of DIFFERENT sizes (the shape groups of a ragged fine stage), layer by layer with one
-        grouped launch per kernel instance and layer (ops.launch_group): bit-identical to [self(x) for x in xs].  Outputs get new
-        names inside a group and are rebound after it (launch_group's contract, as in ResNet50Trunk.forward_group)."""
-        dev = xs[0].device
-        with ops.launch_group(dev, side_streams):
-            xs = [ops.stem_conv_maxblur(x, self.conv1) for x in xs]
+        """The pass over inputs of DIFFERENT sizes (the shape groups of a ragged fine stage), one ops.stage per layer: bit-identical
+        to [self(x) for x in xs]."""
+        st = functools.partial(ops.stage, device=xs[0].device, side_streams=side_streams)
+        xs = st(lambda x: ops.stem_conv_maxblur(x, self.conv1), xs)  # conv1 + BN + ReLU + MaxPool2d(2, stride 1) + BlurPool/2 in one kernel
         for blk in self.blocks:
-            with ops.launch_group(dev, side_streams):          # c1 and the shortcut's blur both read x only: one group
-                os_ = [blk["c1"](x) for x in xs]
-                bs = [ops.blurpool2d(x, blk["stride"]) for x in xs] if blk["ds"] is not None else None
-            if bs is not None:
-                with ops.launch_group(dev, side_streams):
-                    rs = [blk["ds"](b) for b in bs]
+            c1, c2, ds, s = blk["c1"], blk["c2"], blk["ds"], blk["stride"]
+            if ds is None:
+                os_, rs = st(c1, xs), xs
             else:
-                rs = xs
-            with ops.launch_group(dev, side_streams):
-                ys = [blk["c2"](o, residual=r) for o, r in zip(os_, rs)]
-            xs = ys
+                os_, bs = zip(*st(lambda x: (c1(x), ops.blurpool2d(x, s)), xs))          # c1 and the shortcut's blur both read x only
+                rs = st(ds, bs)
+            xs = st(lambda o, r: c2(o, residual=r), os_, rs)
         return xs
 
 
@@ -173,26 +150,25 @@ class _HeadTrunk:
         self.c4 = ConvPlan(sd["conv4.weight"], None, 1, 1, last_act, device)
 
     def __call__(self, coef):
-        return self.c4(self.c3(self.c2(self.c1(coef))))
+        return self.forward_group([coef])[0]
 
     def forward_group(self, coefs, side_streams=True, halves_out=None):
-        """[self(c) for c in coefs] for volumes of different sizes, one grouped launch per kernel instance and layer.  The 49-channel
-        volumes must come from an earlier group: c1 copies them into its zero-padded input eagerly (launch_group's contract).
-        ``halves_out``: one (out_a, out_b) per input -- the last convolution then runs on the two halves of each batch as two
-        problems and writes them to out_a / out_b (views of two packed buffers: PredFlowMask's match12Down8 / match21Down8);
-        returns those pairs."""
-        dev = coefs[0].device
+        """[self(c) for c in coefs] for volumes of different sizes, one ops.stage per layer.  ``halves_out``: one (out_a, out_b) per
+        input -- the last convolution then runs on the two halves of each batch as two problems and writes them to out_a / out_b
+        (views of two packed buffers: PredFlowMask's match12Down8 / match21Down8 of several groups); returns those pairs.  Without
+        it the last convolution is one launch over each whole batch."""
+        st = functools.partial(ops.stage, device=coefs[0].device, side_streams=side_streams)
         xs = coefs
         for c in (self.c1, self.c2, self.c3):
-            with ops.launch_group(dev, side_streams):
-                ys = [c(x) for x in xs]
-            xs = ys
-        with ops.launch_group(dev, side_streams):
-            if halves_out is None:
-                ys = [self.c4(x) for x in xs]
-            else:
-                ys = [(self.c4(x[:x.shape[0] // 2], out=oa), self.c4(x[x.shape[0] // 2:], out=ob)) for x, (oa, ob) in zip(xs, halves_out)]
-        return ys
+            xs = st(c, xs)
+        if halves_out is None:
+            return st(self.c4, xs)
+        return st(lambda x, o: (self.c4(x[:x.shape[0] // 2], out=o[0]), self.c4(x[x.shape[0] // 2:], out=o[1])), xs, halves_out)
+
+
+def _up8(m):
+    """F.upsample_bilinear x8 (align_corners=True)."""
+    return ops.resize_bilinear(m, (m.shape[2] * 8, m.shape[3] * 8), align_corners=True)
 
 
 class NetFlowCoarseNet:
@@ -203,23 +179,15 @@ class NetFlowCoarseNet:
         self.trunk = _HeadTrunk(sd, ACT_NONE, device)
 
     def __call__(self, coef, up8X=True):
-        flow = ops.flow_head(self.trunk(coef), self.k)
-        if up8X:
-            flow = ops.resize_bilinear(flow, (flow.shape[2] * 8, flow.shape[3] * 8), align_corners=True)
-        return flow
+        return self.forward_group([coef], up8X)[0]
 
     def forward_group(self, coefs, up8X=True, side_streams=True, outs=None):
-        """[self(c, up8X) for c in coefs] for volumes of different sizes: the trunk, the flow head and the x8 resize as grouped
-        launches, bit-identical to the per-input calls.  ``outs``: where the /8 flows go (views of a packed buffer)."""
-        dev = coefs[0].device
-        logits = self.trunk.forward_group(coefs, side_streams)
-        with ops.launch_group(dev, side_streams):
-            flows = [ops.flow_head(l, self.k, out=None if outs is None else outs[i]) for i, l in enumerate(logits)]
-        if up8X:
-            with ops.launch_group(dev, side_streams):
-                ups = [ops.resize_bilinear(f, (f.shape[2] * 8, f.shape[3] * 8), align_corners=True) for f in flows]
-            flows = ups
-        return flows
+        """[self(c, up8X) for c in coefs] for volumes of different sizes: the trunk, the flow head and the x8 resize as stages,
+        bit-identical to the per-input calls.  ``outs``: where the /8 flows go (views of a packed buffer)."""
+        st = functools.partial(ops.stage, device=coefs[0].device, side_streams=side_streams)
+        flows = st(lambda l, o: ops.flow_head(l, self.k, out=o), self.trunk.forward_group(coefs, side_streams),
+                   outs if outs is not None else [None] * len(coefs))
+        return st(_up8, flows) if up8X else flows
 
 
 class NetMatchabilityNet:
@@ -229,17 +197,9 @@ class NetMatchabilityNet:
         self.trunk = _HeadTrunk(sd, ACT_SIGMOID, device)
 
     def __call__(self, feat, up8X=True):
-        m = self.trunk(feat)
-        if up8X:
-            m = ops.resize_bilinear(m, (m.shape[2] * 8, m.shape[3] * 8), align_corners=True)
-        return m
+        return self.forward_group([feat], up8X)[0]
 
     def forward_group(self, feats, up8X=True, side_streams=True):
-        """[self(f, up8X) for f in feats] for volumes of different sizes, as grouped launches, bit-identical to the per-input calls."""
-        dev = feats[0].device
+        """[self(f, up8X) for f in feats] for volumes of different sizes, as stages, bit-identical to the per-input calls."""
         ms = self.trunk.forward_group(feats, side_streams)
-        if up8X:
-            with ops.launch_group(dev, side_streams):
-                ups = [ops.resize_bilinear(m, (m.shape[2] * 8, m.shape[3] * 8), align_corners=True) for m in ms]
-            ms = ups
-        return ms
+        return ops.stage(_up8, ms, device=feats[0].device, side_streams=side_streams) if up8X else ms

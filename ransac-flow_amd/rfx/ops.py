@@ -118,19 +118,13 @@ class Profiler:
 
 class launch_group:
     """``with ops.launch_group(device):`` -- the convolution ops and the fine-stage ops (stem_conv_maxblur, blurpool2d, l2norm,
-    flow_head, resize_bilinear, corr_neigh / corr_neigh_bidir, warp_grid, grid_sample, compose_flow) issued inside are RECORDED
-    by the library and launched at exit
-    as ONE launch per kernel instance (rfx_group_begin / rfx_group_end: blockIdx.y selects the problem).  For the same layer
-    of several independent inputs of different sizes (the 8 images of a single pair's trunk pass, the shape groups of a ragged
-    fine stage); the calls inside must not
-    depend on each other, and their tensors must stay referenced until the block ends (the returned outputs do).  The contract:
-    a recorded op may not READ an output of the same group -- neither on the device nor with an eager torch op on the host side of
-    a mirror (the crop after a padded correlation: use corr_neigh_bidir_group / corr_neigh_group, which pad before the group and
-    crop after it; ConvPlan's copy of a 49-channel input into its zero-padded buffer is such an eager read, so that input must
-    come from an EARLIER group).  Not used
-    under a Profiler (per-launch events are meaningless for a recorded launch: callers take their per-problem path).  Temporaries an op makes for a recorded launch
-    (ConvPlan's zero-padded input of a ragged-Cin split convolution) are held by the block (``keep``) until the launch is issued:
-    the side streams join the caller's stream before rfx_group_end returns, so releasing them then is stream-ordered."""
+    flow_head, resize_bilinear, corr_neigh / corr_neigh_bidir, warp_grid, grid_sample, compose_flow) issued inside are RECORDED by
+    the library and launched at exit as ONE launch per kernel instance (rfx_group_begin / rfx_group_end: blockIdx.y selects the
+    problem).  For the same layer of several independent inputs of different sizes; chains use it through ``stage``, which also
+    keeps the one rule: a recorded op may not READ an output of the same group, on the device or with an eager torch op.  Not used
+    under a Profiler (per-launch events are meaningless for a recorded launch: callers take their per-problem path).  Operands must
+    stay referenced until the block ends; temporaries an op makes for a recorded launch are held by the block (``keep``): the side
+    streams join the caller's stream before rfx_group_end returns, so releasing them then is stream-ordered."""
     _tls = threading.local()
 
     def __init__(self, device, side_streams=True):
@@ -181,6 +175,22 @@ def group_stats():
     g, n = ctypes.c_longlong(0), ctypes.c_longlong(0)
     _lib.check(_lib.load().rfx_group_stats(ctypes.byref(g), ctypes.byref(n)), "rfx_group_stats")
     return g.value, n.value
+
+
+def stage(fn, *lists, device, side_streams=True):
+    """[fn(*row) for row in zip(*lists)] as ONE launch step of a chain over equally long lists (one entry per problem).  Several
+    rows: the calls are recorded in one launch_group(device, side_streams).  One row: fn is called directly -- no group, the
+    single-launch kernel on the current stream, so Profiler events and the correlation's timing capture work as for any eager call.
+    fn receives only its row, which the caller took from EARLIER stages' results: that is what keeps a recorded op from reading an
+    output of its own group.  An eager read inside fn (ConvPlan's copy of a 49-channel input) is of an earlier stage for the same
+    reason.  Ops that cannot be recorded (match_score, torch ops) stay plain list comprehensions between stages."""
+    if len({len(l) for l in lists}) != 1:
+        raise ValueError("stage: lists of different lengths")
+    rows = list(zip(*lists))
+    if len(rows) == 1:
+        return [fn(*rows[0])]
+    with launch_group(device, side_streams):
+        return [fn(*row) for row in rows]
 
 
 def _dev(t, name="tensor", dtype=torch.float32):
@@ -825,11 +835,7 @@ def corr_neigh(x, y, K=7, variant=None):
         if launch_group.recording():
             raise RuntimeError("corr_neigh inside a launch_group with W %% 4 != 0 (W = %d): the crop would read a launch that has not "
                                "run yet -- use ops.corr_neigh_group, which pads before the group and crops after it" % W)
-        # the LDS-DMA kernels move 16-byte quads: run them on copies zero-padded to a multiple of 4 columns and crop -- the
-        # window's own padding is zero (model/model.py:135,143), so the result is the unpadded one, bit for bit
-        Wp = (W + 3) // 4 * 4
-        xp, yp = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp)
-        return copy_cols(corr_neigh(xp, yp, K).view(-1, Wp), W).view(N, K * K, H, W)
+        return _corr_group([x], [y], False, None, False, K)[0]
     out = torch.empty((N, K * K, H, W), dtype=torch.float32, device=x.device)
     e0 = Profiler.begin(x)
     v = int(os.environ.get("RFX_CORR_VARIANT", "0")) if variant is None else int(variant)
@@ -854,15 +860,7 @@ def corr_neigh_bidir(x, y, K=7, out=None):
         if launch_group.recording():
             raise RuntimeError("corr_neigh_bidir inside a launch_group with W %% 4 != 0 (W = %d): the crop would read a launch that "
                                "has not run yet -- use ops.corr_neigh_bidir_group, which pads before the group and crops after it" % W)
-        Wp = (W + 3) // 4 * 4
-        xp, yp = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp)
-        both = torch.empty((2 * N, K * K, H, Wp), dtype=torch.float32, device=x.device)
-        corr_neigh_bidir(xp, yp, K, out=both)
-        res = copy_cols(both.view(-1, Wp), W).view(2 * N, K * K, H, W)
-        if out is not None:
-            out.copy_(res)
-            res = out
-        return res[:N], res[N:]
+        return _corr_group([x], [y], True, [out], False, K)[0]
     if out is None:
         out = torch.empty((2 * N, K * K, H, W), dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != (2 * N, K * K, H, W) or not out.is_contiguous() or out.dtype != torch.float32:
@@ -876,54 +874,56 @@ def corr_neigh_bidir(x, y, K=7, out=None):
     return out[:N], out[N:]
 
 
-def _corr_group(xs, ys, bidir, outs, side_streams):
-    """The padded-width bookkeeping of corr_neigh_group / corr_neigh_bidir_group: widths that are no multiple of 4 are padded with
-    copy_cols BEFORE the group, all problems are recorded in ONE group, the padded results are cropped AFTER it."""
+def _corr_group(xs, ys, bidir, outs, side_streams, K=7):
+    """The one pad-and-crop implementation of the correlation ops.  The LDS-DMA kernels move 16-byte quads: widths that are no
+    multiple of 4 run on copies zero-padded with copy_cols BEFORE the launch step (one stage: one problem launches eagerly, several
+    are recorded in one group) and the results are cropped AFTER it -- the window's own padding is zero (model/model.py:135,143),
+    so the result is the unpadded one, bit for bit.  The one-direction form pads under RFX_CORR_PAD (default), like corr_neigh."""
     if launch_group.recording():
         raise RuntimeError("corr_neigh(_bidir)_group opens its own launch_group: call it outside one")
     if len(xs) != len(ys) or not xs:
         raise ValueError("corr group: one y per x, at least one problem")
-    dev = _one_device(*xs, *ys)
+    pad = bidir or os.environ.get("RFX_CORR_PAD", "1") == "1"
     work = []
-    for x, y in zip(xs, ys):
+    for i, (x, y) in enumerate(zip(xs, ys)):
         x, y = _dev(x, "corr x"), _dev(y, "corr y")
         if x.shape != y.shape:
             raise ValueError("corr group: x %s and y %s differ" % (tuple(x.shape), tuple(y.shape)))
         N, C, H, W = x.shape
-        Wp = (W + 3) // 4 * 4
+        Wp = (W + 3) // 4 * 4 if pad else W
+        out = outs[i] if bidir and outs is not None else None
         if Wp != W:
-            x, y = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp)
-        work.append((x, y, W, Wp))
-    res = []
-    with launch_group(dev, side_streams):
-        for i, (x, y, W, Wp) in enumerate(work):
-            if not bidir:
-                res.append(corr_neigh(x, y))
-                continue
-            out = outs[i] if outs is not None else None
-            if Wp != W or out is None:
-                out = torch.empty((2 * x.shape[0], 49, x.shape[2], Wp), dtype=torch.float32, device=x.device)
-            corr_neigh_bidir(x, y, out=out)
-            res.append(out)
+            x, y, out = copy_cols(x.view(-1, W), Wp).view(N, C, H, Wp), copy_cols(y.view(-1, W), Wp).view(N, C, H, Wp), None
+        work.append((x, y, out))
+
+    def run(x, y, out):
+        if not bidir:
+            return corr_neigh(x, y, K)
+        if out is None:
+            out = torch.empty((2 * x.shape[0], K * K, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+        corr_neigh_bidir(x, y, K, out=out)
+        return out
+    res = stage(run, *zip(*work), device=_one_device(*xs, *ys), side_streams=side_streams)
     final = []
-    for i, ((x, y, W, Wp), r) in enumerate(zip(work, res)):
-        if Wp != W:
-            r = copy_cols(r.view(-1, Wp), W).view(r.shape[0], 49, r.shape[2], W)
+    for i, (x, r) in enumerate(zip(xs, res)):
+        N, W = x.shape[0], x.shape[3]
+        if r.shape[3] != W:
+            r = copy_cols(r.view(-1, r.shape[3]), W).view(r.shape[0], K * K, r.shape[2], W)
             if bidir and outs is not None and outs[i] is not None:
                 outs[i].copy_(r)
                 r = outs[i]
-        final.append((r[:x.shape[0]], r[x.shape[0]:]) if bidir else r)
+        final.append((r[:N], r[N:]) if bidir else r)
     return final
 
 
 def corr_neigh_group(xs, ys, side_streams=False):
-    """[corr_neigh(x, y) for x, y in zip(xs, ys)] as ONE launch_group: every problem keeps the tile variant it gets alone (problems of
+    """[corr_neigh(x, y) for x, y in zip(xs, ys)] as ONE stage: every problem keeps the tile variant it gets alone (problems of
     different variants are different launches), bit-identical to the single calls."""
     return _corr_group(xs, ys, False, None, side_streams)
 
 
 def corr_neigh_bidir_group(xs, ys, outs=None, side_streams=False):
-    """[corr_neigh_bidir(x, y, out=o) for ...] as ONE launch_group (see corr_neigh_group).  ``outs``: optional list of (2N,49,H,W)
+    """[corr_neigh_bidir(x, y, out=o) for ...] as ONE stage (see corr_neigh_group).  ``outs``: optional list of (2N,49,H,W)
     buffers (entries may be None)."""
     return _corr_group(xs, ys, True, outs, side_streams)
 

@@ -447,7 +447,7 @@ class AlignPipeline:
         subs = [dict(IsTensor=torch.cat([prep["IsTensor"][b] for b in bs]), ItTensor=torch.cat([prep["ItTensor"][b] for b in bs]))
                 for bs in groups.values()]
         hs = [Hs[bs] for bs in groups.values()]
-        if ops.fine_groups_enabled() and len(subs) > 1:
+        if ops.fine_groups_enabled():
             fs = self.fine_quickstart_groups(subs, hs)
         else:
             fs = [self.fine_quickstart(sub, h) for sub, h in zip(subs, hs)]
@@ -592,149 +592,126 @@ class AlignPipeline:
         return idx1, idx2, count
 
     # ---------------------------------------------------------------- fine stage
+    def _stage(self, fn, *lists):
+        """ops.stage on this pipeline's device, without side streams: the lock-step groups of the round drivers run on streams of
+        their own."""
+        return ops.stage(fn, *lists, device=self.dev, side_streams=False)
+
+    def feat_l2norm(self, xs):
+        """[l2norm(feat(x)) for x in xs] for image batches of different sizes, as one chain of stages."""
+        return self._stage(ops.l2norm, self.feat.forward_group(xs, False))
+
+    def _features_both(self, a_list, b_list):
+        """Per group, both image batches through the FeatureExtractor as ONE batch -> (features of a, features of b)."""
+        fs = self.feat_l2norm([torch.cat((a, b), dim=0) for a, b in zip(a_list, b_list)])
+        return [f[:a.shape[0]] for f, a in zip(fs, a_list)], [f[a.shape[0]:] for f, a in zip(fs, a_list)]
+
     def fine_quickstart(self, prep, Hs):
         """quick_start/align2images.py:61-97 for a batch: Hs (B,3,3) device tensor."""
-        B, _, h, w = prep["ItTensor"].shape
-        flowCoarse = ops.warp_grid(Hs, h, w)
-        img1_coarse = ops.grid_sample(prep["IsTensor"], flowCoarse)
-        f = ops.l2norm(self.feat(torch.cat((img1_coarse, prep["ItTensor"]), dim=0)))
-        feat1, feat2 = f[:B], f[B:]
-        corr12 = ops.corr_neigh(feat1, feat2)
-        flowDown = self.flow(corr12, False)
-        flow12, _, _ = ops.compose_flow(flowDown, flowCoarse, clamp=False)
-        img1_fine = ops.grid_sample(prep["IsTensor"], flow12)
-        return dict(flowCoarse=flowCoarse, img1_coarse=img1_coarse, feat1=feat1, feat2=feat2, corr12=corr12,
-                    flowDown=flowDown, flow12=flow12, img1_fine=img1_fine)
+        return self.fine_quickstart_groups([prep], [Hs])[0]
 
     def fine_quickstart_groups(self, preps, Hs_list):
-        """[fine_quickstart(p, Hs) for p, Hs in zip(preps, Hs_list)] for shape groups of different sizes: every stage is ONE
-        ops.launch_group over the groups (more than 8 groups: chunked by the library), bit-identical per group."""
-        if len(preps) == 1:
-            return [self.fine_quickstart(preps[0], Hs_list[0])]
-        lg = lambda: ops.launch_group(self.dev, False)
-        Bs = [p["ItTensor"].shape[0] for p in preps]
-        with lg():
-            fcs = [ops.warp_grid(Hs, p["ItTensor"].shape[2], p["ItTensor"].shape[3]) for p, Hs in zip(preps, Hs_list)]
-        with lg():
-            coarse = [ops.grid_sample(p["IsTensor"], fc) for p, fc in zip(preps, fcs)]
-        raw = self.feat.forward_group([torch.cat((c, p["ItTensor"]), dim=0) for c, p in zip(coarse, preps)], False)
-        with lg():
-            fs = [ops.l2norm(f) for f in raw]
-        f1, f2 = [f[:B] for f, B in zip(fs, Bs)], [f[B:] for f, B in zip(fs, Bs)]
+        """fine_quickstart for shape groups of different sizes: every stage is ONE ops.stage over the groups (one group: the eager
+        launches; more than 8 groups: chunked by the library), bit-identical per group."""
+        st = self._stage
+        Is, It = [p["IsTensor"] for p in preps], [p["ItTensor"] for p in preps]
+        fcs = st(lambda Hs, t: ops.warp_grid(Hs, t.shape[2], t.shape[3]), Hs_list, It)
+        coarse = st(ops.grid_sample, Is, fcs)
+        f1, f2 = self._features_both(coarse, It)
         corr = ops.corr_neigh_group(f1, f2)
         down = self.flow.forward_group(corr, False, False)
-        with lg():
-            f12 = [ops.compose_flow(d, fc, clamp=False)[0] for d, fc in zip(down, fcs)]
-        with lg():
-            fine = [ops.grid_sample(p["IsTensor"], f) for p, f in zip(preps, f12)]
+        f12 = st(lambda d, fc: ops.compose_flow(d, fc, clamp=False)[0], down, fcs)
+        fine = st(ops.grid_sample, Is, f12)
         return [dict(flowCoarse=fcs[g], img1_coarse=coarse[g], feat1=f1[g], feat2=f2[g], corr12=corr[g], flowDown=down[g],
                      flow12=f12[g], img1_fine=fine[g]) for g in range(len(preps))]
 
     @staticmethod
     def _corr_both(featt, feats):
-        """(2B,49,h,w) = corr(featt, feats) | corr(feats, featt) (evaluation/evalHpatch/evaluation.py:29,34).  RFX_CORR_BIDIR=0:
-        the two directions as one launch over a doubled batch (each re-reads both feature maps), bit-identical."""
+        """Per group (2B,49,h,w) = corr(featt, feats) | corr(feats, featt) (evaluation/evalHpatch/evaluation.py:29,34): both directions
+        from ONE pass over the features (the reverse volume is the forward one at mirrored taps / shifted pixels:
+        ops.corr_neigh_bidir).  RFX_CORR_BIDIR=0: the two directions as one launch over a doubled batch (each re-reads both feature
+        maps), bit-identical."""
         if os.environ.get("RFX_CORR_BIDIR", "1") == "0":
-            return ops.corr_neigh(torch.cat((featt, feats), dim=0), torch.cat((feats, featt), dim=0))
-        B, _, h, w = featt.shape
-        out = torch.empty((2 * B, 49, h, w), dtype=torch.float32, device=featt.device)
-        ops.corr_neigh_bidir(featt, feats, out=out)
-        return out
+            return ops.corr_neigh_group([torch.cat((ft, fs), dim=0) for ft, fs in zip(featt, feats)],
+                                        [torch.cat((fs, ft), dim=0) for ft, fs in zip(featt, feats)])
+        cs = [torch.empty((2 * ft.shape[0], 49, ft.shape[2], ft.shape[3]), dtype=torch.float32, device=ft.device) for ft in featt]
+        ops.corr_neigh_bidir_group(featt, feats, outs=cs)
+        return cs
+
+    def pred_flow_mask_lists(self, feats, featt, fcs, cycle=False, out_hw=None, out=None):
+        """The PredFlowMask chain after the features, written once, over G shape groups: group g = normalised source features
+        feats[g] and target features featt[g] (B_g,256,h/8,w/8) and the coarse grid fcs[g] (B_g,h,w,2).  Both correlation directions,
+        the flow head and the matchability head (both matchability passes in one batch), then one of two tails:
+          * plain (evaluation/evalHpatch/evaluation.py:23-55): match = match12 * in-bounds(flow12);
+          * ``cycle`` (evalYFCC/evaluation.py:32-58, evalKITTI/evaluation.py:49-81): match = match12 * grid_sample(match21, flowUp) *
+            in-bounds(flow12), at ``out_hw`` (default: the coarse grid's size).  One group per call (ValueError otherwise).
+        Every step is ONE ops.stage over the groups, so one group issues the eager launches.  Returns one dict per group (flow12,
+        match, flowDown8, match12Down8, match21Down8).  flowDown8 -- and, in the plain form, match, match12Down8 and match21Down8 --
+        are views of ONE packed buffer each, groups in order (packed_group_offsets; one group: the group's own tensors); ``out``
+        (plain form): a dict that receives those buffers under the same keys (what rfx_multih_accept_ragged_f32 reads), plus
+        ``layout``."""
+        G = len(fcs)
+        if cycle and G > 1:
+            raise ValueError("the cycle-checked PredFlowMask forms take one shape group per call, got %d" % G)
+        lay = packed_group_offsets([(fc.shape[0], fc.shape[1], fc.shape[2], ft.shape[2], ft.shape[3]) for fc, ft in zip(fcs, featt)])
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
+        cut = lambda t: [t[o:o + B * h * w].view(B, 1, h, w) for (B, h, w, _, _), o in zip(lay["shapes"], lay["off"])]
+        cut8 = lambda t, c=1: [t[c * o8:c * (o8 + B * h8 * w8)].view(B, c, h8, w8) for (B, _, _, h8, w8), o8 in zip(lay["shapes"], lay["off8"])]
+        cs = self._corr_both(featt, feats)
+        f8 = new(2 * lay["total8"])
+        fd8 = self.flow.forward_group([c[:c.shape[0] // 2] for c in cs], False, False, outs=cut8(f8, 2))
+        if G == 1:
+            # one group's batch is written as a whole: the last convolution is one launch over its 2B volumes
+            md = self.match.forward_group(cs, False, False)[0]
+            halves = [(md[:md.shape[0] // 2], md[md.shape[0] // 2:])]
+            m12, m21 = halves[0][0].reshape(-1), halves[0][1].reshape(-1)
+        else:
+            m12, m21 = new(lay["total8"]), new(lay["total8"])
+            halves = self.match.trunk.forward_group(cs, False, halves_out=list(zip(cut8(m12), cut8(m21))))
+        if cycle:
+            B = fcs[0].shape[0]
+            H, W = fcs[0].shape[1:3] if out_hw is None else out_hw
+            m = ops.resize_bilinear(md, (H, W), align_corners=False)
+            flow12, inb, flowUp = ops.compose_flow(fd8[0], fcs[0], clamp=True, want_inb=True, want_flow_up=True, out_hw=(H, W))
+            # (match12 * cycle) * in-bounds, left to right like the reference expression (evalKITTI/evaluation.py:75-77), one kernel
+            f12, match = [flow12], [ops.match_score(m[:B, 0], ops.grid_sample(m[B:], flowUp)[:, 0], inb).unsqueeze(1)]
+        else:
+            match12, inb = new(lay["total"]), new(lay["total"])
+
+            def tail(m, d, fc, m_out, inb_out):                 # the resize reads match12Down8, compose_flow the /8 flow: independent
+                ops.resize_bilinear(m, fc.shape[1:3], align_corners=False, out=m_out)
+                return ops.compose_flow(d, fc, clamp=True, want_inb=True, inb_out=inb_out[:, 0])[0]
+            f12 = self._stage(tail, [h[0] for h in halves], fd8, fcs, cut(match12), cut(inb))
+            packed = torch.mul(match12, inb)                    # match12 * inb of all groups: one multiply over the packed buffers
+            match = cut(packed)
+            if out is not None:
+                out.update(match=packed, flowDown8=f8, match12Down8=m12, match21Down8=m21, layout=lay)
+        return [dict(flow12=f12[g], match=match[g], flowDown8=fd8[g], match12Down8=halves[g][0], match21Down8=halves[g][1])
+                for g in range(G)]
+
+    def _sampled_features(self, Is_list, fcs):
+        """Per group: the sources sampled at the coarse grids -> normalised features."""
+        return self.feat_l2norm(self._stage(ops.grid_sample, Is_list, fcs))
 
     def pred_flow_mask(self, IsTensor, featt, flowCoarse):
         """evaluation/evalHpatch/evaluation.py:23-55 (PredFlowMask) for a batch."""
-        IsSample = ops.grid_sample(IsTensor, flowCoarse)
-        feats = ops.l2norm(self.feat(IsSample))
-        B = IsTensor.shape[0]
-        # both correlation directions from ONE pass over the features (the reverse volume is the forward one at mirrored
-        # taps / shifted pixels: ops.corr_neigh_bidir), both matchability passes in one batch
-        c = self._corr_both(featt, feats)
-        corr12 = c[:B]
-        flowDown8 = self.flow(corr12, False)
-        md = self.match(c, False)
-        match12Down8, match21Down8 = md[:B], md[B:]
-        H, W = flowCoarse.shape[1], flowCoarse.shape[2]
-        match12 = ops.resize_bilinear(match12Down8, (H, W), align_corners=False)
-        flow12, inb, _ = ops.compose_flow(flowDown8, flowCoarse, clamp=True, want_inb=True)
-        match = match12 * inb.unsqueeze(1)
-        return dict(flow12=flow12, match=match, flowDown8=flowDown8, match12Down8=match12Down8,
-                    match21Down8=match21Down8)
+        return self.pred_flow_mask_lists(self._sampled_features([IsTensor], [flowCoarse]), [featt], [flowCoarse])[0]
 
     def pred_flow_mask_groups(self, Is_list, featt_list, Hs_list, hw_list, out=None):
         """warp_grid + pred_flow_mask for G shape groups in one call: group g = sources Is_list[g] (B_g,3,.,.), normalised target
-        features featt_list[g] (B_g,256,h/8,w/8), homographies Hs_list[g] (B_g,3,3), target size hw_list[g] = (h, w).  Every stage
-        -- warp_grid, grid_sample, FeatureExtractor, l2norm, both correlation directions, flow head, matchability head, resize and
-        compose_flow -- is ONE ops.launch_group over the groups (chains of more than 8 groups are chunked by the library; no side
-        streams: the lock-step groups of the round drivers run on streams of their own).  Returns one dict per group with
-        pred_flow_mask's keys, each tensor bit-identical to pred_flow_mask on that group alone.  match, flowDown8, match12Down8 and
-        match21Down8 are views of ONE packed buffer each, groups in order (packed_group_offsets); ``out``: a dict that receives those
-        buffers under the same keys (what rfx_multih_accept_ragged_f32 reads), plus ``layout``."""
-        G = len(Is_list)
-        if G == 1:
-            (h, w), B = hw_list[0], Is_list[0].shape[0]
-            pm = self.pred_flow_mask(Is_list[0], featt_list[0], ops.warp_grid(Hs_list[0], h, w))
-            if out is not None:
-                out.update({k: pm[k].reshape(-1) for k in ("match", "flowDown8", "match12Down8", "match21Down8")})
-                out["layout"] = packed_group_offsets([(B, h, w) + tuple(featt_list[0].shape[2:])])
-            return [pm]
-        dev = self.dev
-        lg = lambda: ops.launch_group(dev, False)
-        lay = packed_group_offsets([(I.shape[0], hw[0], hw[1], ft.shape[2], ft.shape[3]) for I, hw, ft in zip(Is_list, hw_list, featt_list)])
-        new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
-        match12, inb = new(lay["total"]), new(lay["total"])
-        f8, m12, m21 = new(2 * lay["total8"]), new(lay["total8"]), new(lay["total8"])
-        cut, cut8 = [], []
-        for (B, h, w, h8, w8), o, o8 in zip(lay["shapes"], lay["off"], lay["off8"]):
-            cut.append(lambda t, B=B, h=h, w=w, o=o: t[o:o + B * h * w].view(B, 1, h, w))
-            cut8.append(lambda t, c, B=B, h8=h8, w8=w8, o8=o8: t[c * o8:c * (o8 + B * h8 * w8)].view(B, c, h8, w8))
-        with lg():
-            fcs = [ops.warp_grid(Hs, h, w) for Hs, (h, w) in zip(Hs_list, hw_list)]
-        with lg():
-            samples = [ops.grid_sample(I, fc) for I, fc in zip(Is_list, fcs)]
-        raw = self.feat.forward_group(samples, False)
-        with lg():
-            feats = [ops.l2norm(f) for f in raw]
-        if os.environ.get("RFX_CORR_BIDIR", "1") == "0":
-            cs = ops.corr_neigh_group([torch.cat((ft, fs), dim=0) for ft, fs in zip(featt_list, feats)],
-                                      [torch.cat((fs, ft), dim=0) for ft, fs in zip(featt_list, feats)])
-        else:
-            cs = [torch.empty((2 * ft.shape[0], 49, ft.shape[2], ft.shape[3]), dtype=torch.float32, device=dev) for ft in featt_list]
-            ops.corr_neigh_bidir_group(featt_list, feats, outs=cs)
-        fd8 = self.flow.forward_group([c[:c.shape[0] // 2] for c in cs], False, False, outs=[cut8[g](f8, 2) for g in range(G)])
-        md = self.match.trunk.forward_group(cs, False, halves_out=[(cut8[g](m12, 1), cut8[g](m21, 1)) for g in range(G)])
-        with lg():                                          # the resize reads match12Down8, compose_flow the /8 flow: independent
-            for g in range(G):
-                B, h, w = lay["shapes"][g][:3]
-                ops.resize_bilinear(md[g][0], (h, w), align_corners=False, out=cut[g](match12))
-            f12 = [ops.compose_flow(fd8[g], fcs[g], clamp=True, want_inb=True, inb_out=cut[g](inb).view(lay["shapes"][g][0], *hw_list[g]))[0]
-                   for g in range(G)]
-        match = torch.mul(match12, inb)                     # match12 * inb of all groups: one multiply over the packed buffers
-        if out is not None:
-            out.update(match=match, flowDown8=f8, match12Down8=m12, match21Down8=m21, layout=lay)
-        return [dict(flow12=f12[g], match=cut[g](match), flowDown8=fd8[g], match12Down8=md[g][0], match21Down8=md[g][1])
-                for g in range(G)]
+        features featt_list[g] (B_g,256,h/8,w/8), homographies Hs_list[g] (B_g,3,3), target size hw_list[g] = (h, w).  Returns one
+        dict per group with pred_flow_mask's keys, each tensor bit-identical to pred_flow_mask on that group alone; the packed
+        buffers and ``out``: pred_flow_mask_lists."""
+        fcs = self._stage(lambda Hs, hw: ops.warp_grid(Hs, hw[0], hw[1]), Hs_list, hw_list)
+        return self.pred_flow_mask_lists(self._sampled_features(Is_list, fcs), featt_list, fcs, out=out)
 
     def pred_flow_mask_kitti(self, IsSample, ItSample, flowCoarse, out_hw=None):
-        """evaluation/evalKITTI/evaluation.py:49-81: both images go through the FeatureExtractor here, and the
-        matchability is cycle-checked: match = match12 * grid_sample(match21, flowUp) * in-bounds(flow12).
-        ``out_hw``: resolution of the identity grid the reference passes (``grid``): the coarse grid's own by default; the
-        ORIGINAL image size in the full-resolution pass of the KITTI driver (:302), where flowCoarse has the fine size."""
-        B = IsSample.shape[0]
-        f = ops.l2norm(self.feat(torch.cat((IsSample, ItSample), dim=0)))
-        feats, featt = f[:B], f[B:]
-        c = self._corr_both(featt, feats)                                                        # corr12 | corr21, one launch
-        corr12 = c[:B]
-        flowDown8 = self.flow(corr12, False)
-        md = self.match(c, False)
-        match12Down8, match21Down8 = md[:B], md[B:]
-        H, W = (flowCoarse.shape[1], flowCoarse.shape[2]) if out_hw is None else out_hw
-        m = ops.resize_bilinear(md, (H, W), align_corners=False)
-        match12, match21 = m[:B], m[B:]
-        flow12, inb, flowUp = ops.compose_flow(flowDown8, flowCoarse, clamp=True, want_inb=True, want_flow_up=True, out_hw=(H, W))
-        # (match12 * cycle) * in-bounds, left to right like the reference expression (evalKITTI/evaluation.py:75-77), one kernel
-        match = ops.match_score(match12[:, 0], ops.grid_sample(match21, flowUp)[:, 0], inb).unsqueeze(1)
-        return dict(flow12=flow12, match=match, flowDown8=flowDown8, match12Down8=match12Down8,
-                    match21Down8=match21Down8)
+        """evaluation/evalKITTI/evaluation.py:49-81: both images go through the FeatureExtractor here (one batch), and the
+        matchability is cycle-checked.  ``out_hw``: resolution of the identity grid the reference passes (``grid``): the coarse
+        grid's own by default; the ORIGINAL image size in the full-resolution pass of the KITTI driver (:302), where flowCoarse has
+        the fine size."""
+        feats, featt = self._features_both([IsSample], [ItSample])
+        return self.pred_flow_mask_lists(feats, featt, [flowCoarse], cycle=True, out_hw=out_hw)[0]
 
     # ---------------------------------------------------------------- multi-homography driver (SURVEY 8f1)
     def multi_h(self, prep, b=0, maxCoarse=10, maskRegionTh=0.01, It_bg=None, feats=None, sample_fn=None):
@@ -892,20 +869,8 @@ class AlignPipeline:
     # ---------------------------------------------------------------- YFCC / Corr driver shape (variant C)
     def pred_flow_mask_cycle(self, IsTensor, featt, flowCoarse):
         """PredFlowMask of evaluation/evalYFCC/evaluation.py:32-58 (= evalCorr/evaluation.py:29-56) for a batch: the Hpatch form
-        (pred_flow_mask) with the CYCLE-CHECKED matchability -- match = match12 * grid_sample(match21, flowUp) * in-bounds(flow12)
-        -- all at the target's resolution, target features handed in."""
-        IsSample = ops.grid_sample(IsTensor, flowCoarse)
-        feats = ops.l2norm(self.feat(IsSample))
-        B = IsTensor.shape[0]
-        c = self._corr_both(featt, feats)                                  # corr12 | corr21 from one pass
-        flowDown8 = self.flow(c[:B], False)
-        md = self.match(c, False)
-        match12Down8, match21Down8 = md[:B], md[B:]
-        H, W = flowCoarse.shape[1], flowCoarse.shape[2]
-        m = ops.resize_bilinear(md, (H, W), align_corners=False)
-        flow12, inb, flowUp = ops.compose_flow(flowDown8, flowCoarse, clamp=True, want_inb=True, want_flow_up=True)
-        match = ops.match_score(m[:B, 0], ops.grid_sample(m[B:], flowUp)[:, 0], inb).unsqueeze(1)     # left to right, like the reference
-        return dict(flow12=flow12, match=match, flowDown8=flowDown8, match12Down8=match12Down8, match21Down8=match21Down8)
+        (pred_flow_mask) with the CYCLE-CHECKED matchability, all at the target's resolution, target features handed in."""
+        return self.pred_flow_mask_lists(self._sampled_features([IsTensor], [flowCoarse]), [featt], [flowCoarse], cycle=True)[0]
 
     def multi_h_variant_c(self, src_u8, tgt_candidates_u8, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None,
                           want_lists=True, pair_ids=None, draw_epoch=0):
@@ -1047,17 +1012,9 @@ class AlignPipeline:
             m2 = torch.stack((H2[valid], W2[valid], ones), dim=1)
             bestH, _, res = ops.ransac_h4(m1, m2, draw(n, self.nbIter).to(dev), self.tol,
                                           degenerate=self._degenerate_mode(sample_fn is not None or self.draw == "host"))
-            hom_d2 = ops.warp_grid(bestH[None], h_d2, w_d2)
-            hom_resize = ops.warp_grid(bestH[None], h_r, w_r)
-            Is_d2 = ops.grid_sample(tensor_s, hom_d2)
-            flow_d2 = self.pred_flow_mask_kitti(Is_d2, tensor_d2, hom_d2)["flowDown8"]
-            flowCoarse, _, _ = ops.compose_flow(flow_d2, hom_resize, clamp=True)
-            IsSample = ops.grid_sample(tensor_s, flowCoarse)
-            pm = self.pred_flow_mask_kitti(IsSample, tensor_resize, flowCoarse, out_hw=(h_org, w_org))
-            match = pm["match"][0, 0]
-            if cc_th > 0:                                                     # :321 -- on the device unless a host filter is injected
-                match = (ops.remove_small_cc(match, cc_th, 0.99) if remove_small_cc is None else
-                         torch.from_numpy(remove_small_cc(match.cpu().numpy(), 0.99, cc_th)).to(dev))
+            flow_d2, pm, match = self.kitti_fine_round(bestH[None], tensor_s, tensor_d2, tensor_resize, (h_org, w_org), cc_th,
+                                                       remove_small_cc)
+            match = match[0]
             stat = torch.stack((((match > 0.9999).float() * (1 - fg)).mean(), res[0].float()))
             gain, status = stat.cpu().tolist()                                # sync: acceptance statistic + status
             if status != 0:

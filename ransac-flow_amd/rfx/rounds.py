@@ -366,11 +366,8 @@ class RaggedGroup:
         self.have_featt = True
         pipe, ItT, ft = self.st.pipe, self.ItT, {}
         xs = [torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]] for mem in self.tgroups.values()]
-        if ops.fine_groups_enabled() and len(xs) > 1:
-            # all target shapes as one chain of grouped launches (no side streams: this lock-step group has a stream of its own)
-            raw = pipe.feat.forward_group(xs, False)
-            with ops.launch_group(pipe.dev, False):
-                fs = [ops.l2norm(f) for f in raw]
+        if ops.fine_groups_enabled():
+            fs = pipe.feat_l2norm(xs)                    # all target shapes as one chain of stages
         else:
             fs = [ops.l2norm(pipe.feat(x)) for x in xs]
         for f, mem in zip(fs, self.tgroups.values()):

@@ -1,6 +1,8 @@
 """Grouped forms of the fine-stage kernels (ops.launch_group over warp_grid, grid_sample, compose_flow, the FeatureExtractor stem,
 blurpool, l2norm, flow_head, resize_bilinear and the 7x7 correlation), the grouped forwards of the FeatureExtractor and the two
-heads, AlignPipeline.pred_flow_mask_groups / fine_quickstart_groups, and the RFX_FINE_GROUPS switch of the ragged drivers.
+heads, AlignPipeline.pred_flow_mask_groups / fine_quickstart_groups, and the RFX_FINE_GROUPS switch of the ragged drivers.  Every
+chain is one body over lists (ops.stage): the grouped calls are compared with the same body at list length one, which must launch
+eagerly (no grouped launch).
 
 Everything is compared bit for bit (no tolerance) with the same op / net / method called on each problem alone.  The grid-stride
 kernels get one problem whose own grid is above the 8192-block cap next to a tiny one: a body that strode by the launch's gridDim.x
@@ -208,6 +210,41 @@ def test_corr_bidir_inside_group_with_ragged_width_raises():
     assert _same(ops.corr_neigh_bidir_group([x], [y])[0], ops.corr_neigh_bidir(x, y))      # the recorder is usable again
 
 
+def test_corr_odd_width_alone_is_the_one_problem_group():
+    # width 10: padded to 12 and cropped by the ONE implementation; alone it launches eagerly
+    x, y = _rand(3, 8, 7, 10, seed=0), _rand(3, 8, 7, 10, seed=1)
+    n0 = ops.group_stats()
+    a1, g1 = ops.corr_neigh(x, y), ops.corr_neigh_group([x], [y])[0]
+    a2, g2 = ops.corr_neigh_bidir(x, y), ops.corr_neigh_bidir_group([x], [y])[0]
+    assert ops.group_stats() == n0
+    assert tuple(a1.shape) == (3, 49, 7, 10) and _bits(a1, g1) and _same(a2, g2)
+    assert _bits(a2[0], a1) and _bits(a2[1], ops.corr_neigh(y, x))
+
+
+# ------------------------------------------------------------------------------------------------ 2b. the stage helper
+def test_stage_one_row_is_eager_and_rows_are_one_group():
+    probs = [(_rand(1, 3, 9, 11, seed=6),), (_rand(2, 64, 7, 9, seed=7),), (_rand(3, 36, 9, 15, seed=5),)]
+    calls = []
+
+    def fn(x):
+        calls.append(ops.launch_group.recording())
+        return ops.l2norm(x)
+    n0 = ops.group_stats()
+    one = ops.stage(fn, [probs[1][0]], device=DEV, side_streams=False)
+    assert ops.group_stats() == n0 and calls == [False]                    # no group opened, no grouped launch
+    assert len(one) == 1 and _bits(one[0], ops.l2norm(probs[1][0]))
+    alone, ref, n_ref = _grouped(ops.l2norm, probs)
+    n0 = ops.group_stats()
+    got = ops.stage(fn, [p[0] for p in probs], device=DEV, side_streams=False)
+    n1 = ops.group_stats()
+    torch.cuda.synchronize()
+    assert calls[1:] == [True] * 3
+    assert n1[0] - n0[0] == 1 and n1[1] - n0[1] == n_ref == 2, (n0, n1, n_ref)       # the one- and the four-wavefront kernel
+    assert all(_bits(a, g) for a, g in zip(alone, got))
+    with pytest.raises(ValueError):
+        ops.stage(lambda a, b: a, [1, 2], [1], device=DEV)
+
+
 # ------------------------------------------------------------------------------------------------ 3. nets
 NET_IN = [(2, 3, 48, 64), (1, 3, 64, 80), (1, 3, 80, 48), (3, 3, 56, 72)]
 
@@ -235,6 +272,22 @@ def test_heads_forward_group(up8X):
         torch.cuda.synchronize()
         for i, (a, g) in enumerate(zip(alone, got)):
             assert _bits(a, g), (type(net).__name__, i)
+
+
+def test_forward_group_of_one_input_is_the_eager_call():
+    x = _rand(*NET_IN[0], seed=0)
+    v = _rand(NET_IN[0][0], 49, NET_IN[0][2] // 8, NET_IN[0][3] // 8, seed=0)
+    feat = FeatureExtractorNet(weights.feature_extractor_sd(1), DEV)
+    flow = NetFlowCoarseNet(weights.net_flow_coarse_sd(2), 7, DEV)
+    match = NetMatchabilityNet(weights.net_matchability_sd(3, last_std=3.0), 7, DEV)
+    n0 = ops.group_stats()
+    got = feat.forward_group([x])
+    assert len(got) == 1 and _bits(got[0], feat(x))
+    for net in (flow, match):
+        for up8X in (False, True):
+            got = net.forward_group([v], up8X)
+            assert len(got) == 1 and _bits(got[0], net(v, up8X)), (type(net).__name__, up8X)
+    assert ops.group_stats() == n0
 
 
 # ------------------------------------------------------------------------------------------------ 4. pipeline
@@ -292,6 +345,39 @@ def test_pred_flow_mask_groups(pipe):
     # one group: pred_flow_mask itself
     one = pipe.pred_flow_mask_groups(Is[3:], featt[3:], Hs[3:], hw[3:])
     assert all(_bits(one[0][key], alone[3][key]) for key in alone[3])
+
+
+def test_pred_flow_mask_groups_one_group_packs_its_own_tensors(pipe):
+    from rfx.pipeline import packed_group_offsets
+    Is, It, Hs, hw = _fine_inputs(pipe)
+    for g in (0, 3):                                                       # /8 widths 8 and 9 (padded correlation)
+        featt = ops.l2norm(pipe.feat(It[g]))
+        alone = pipe.pred_flow_mask(Is[g], featt, ops.warp_grid(Hs[g], *hw[g]))
+        packed = {}
+        n0 = ops.group_stats()
+        got = pipe.pred_flow_mask_groups([Is[g]], [featt], [Hs[g]], [hw[g]], out=packed)
+        assert ops.group_stats() == n0                                     # zero grouped launches
+        torch.cuda.synchronize()
+        assert len(got) == 1 and set(got[0]) == set(alone) and all(_bits(got[0][key], alone[key]) for key in alone)
+        for key in ("match", "flowDown8", "match12Down8", "match21Down8"):
+            assert packed[key].dim() == 1 and _bits(packed[key], alone[key].reshape(-1)), (g, key)
+        assert packed["layout"] == packed_group_offsets([(FINE[g][0],) + hw[g] + tuple(featt.shape[2:])])
+
+
+def test_cycle_forms_take_one_group(pipe):
+    Is, It, Hs, hw = _fine_inputs(pipe)
+    sub = [0, 1]
+    fcs = [ops.warp_grid(Hs[g], *hw[g]) for g in sub]
+    featt = [ops.l2norm(pipe.feat(It[g])) for g in sub]
+    feats = [ops.l2norm(pipe.feat(ops.grid_sample(Is[g], fcs[g]))) for g in sub]
+    with pytest.raises(ValueError, match="one shape group"):               # pred_flow_mask_cycle's form
+        pipe.pred_flow_mask_lists(feats, featt, fcs, cycle=True)
+    with pytest.raises(ValueError, match="one shape group"):               # pred_flow_mask_kitti's form
+        pipe.pred_flow_mask_lists(feats, featt, fcs, cycle=True, out_hw=(90, 70))
+    # one group through the list form is the named method, bit for bit
+    one = pipe.pred_flow_mask_lists(feats[:1], featt[:1], fcs[:1], cycle=True)[0]
+    ref = pipe.pred_flow_mask_cycle(Is[0], featt[0], fcs[0])
+    assert set(one) == set(ref) and all(_bits(one[key], ref[key]) for key in ref)
 
 
 def test_fine_quickstart_groups(pipe):
