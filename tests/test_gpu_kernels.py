@@ -4,7 +4,9 @@ inputs, plus the reference golden vectors.  Needs a real MI355X: run with ``-m g
 Tolerances: integer / index outputs bit exact; float32 outputs within round-off of the value range
 (stated per test).  Where a float near-tie could flip an arg-max the test verifies that every
 disagreement IS such a near-tie (margin check in float64) and bounds their rate.
-The warp / pool / resize / seg kernels are held to float64 at their edges in tests/test_gpu_pointwise_exact.py."""
+The warp / pool / resize / seg kernels are held to float64 at their edges in tests/test_gpu_pointwise_exact.py; the correlation
+and mutual-NN kernels -- every tile variant, short channel counts, the plain fallback, exact ties of the arg-max, the dense batched
+and ragged entries -- bit for bit in tests/test_gpu_match_exact.py (the near-tie allowance of ``_mnn_check`` below is for random data)."""
 import os
 
 import numpy as np
