@@ -358,6 +358,23 @@ size_t rfx_remove_small_cc_ragged_ws_bytes(long long total_px);
 int rfx_remove_small_cc_ragged_f32(const float* in, float* out, const long long* match_off, const int32_t* dims, int n_active,
                                    long long total_px, long long max_hw, float match_th, void* ws, void* stream);
 
+/* The nearest-explained-pixel fill of the KITTI scripts' --interpolate option (evaluation/evalKITTI/getResults.py:87-93,
+ * interpolate_flow_match: scipy.ndimage.distance_transform_edt(~binary, return_indices=True) on the host there, then flow[idx]).
+ * values, out (N,H,W,C) float32, channels last -- the layout of flowGlobal; explained (N,H,W) bytes (a torch.bool), non-zero = the
+ * pixel keeps its value.  out[n,r,x,:] = values[n,r',c',:] with (r',c') scipy's index for pixel (r,x), INDEX FOR INDEX: the
+ * explained pixel of map n that minimises (r'-r)^2 + (c'-x)^2 (an exact integer), among equals the smallest column c', among those
+ * the smallest row r'.  A map without any explained pixel: scipy's index is (-1, 0) everywhere, which numpy's indexing reads as
+ * pixel (H-1, 0); out takes that pixel's values.  index, if not NULL, receives the index pairs (N,2,H,W) int32 -- scipy's layout
+ * per map, row plane first; (-1, 0) for such an empty map.  Values move as 32-bit words: NaN payloads and -0.0 arrive bit for bit.
+ * Two launches (a sweep per column, then a search per row over the columns' nearest rows, staged in 32 KB of LDS).
+ * ws: rfx_nearest_fill_ws_bytes(N,H,W) bytes = one int32 per pixel (0 for a non-positive size).
+ * RFX_E_ARG: a null pointer other than index, a non-positive N, H, W or C, out == values (the kernel reads other pixels while it
+ * writes).  RFX_E_LIMIT: W > 8192 (the staged row), H > 31728 (distances stay int32 below the no-pixel sentinel 2^30), C > 8.
+ * All of these are checked before any HIP call. */
+size_t rfx_nearest_fill_ws_bytes(int N, int H, int W);
+int rfx_nearest_fill_f32(const float* values, const unsigned char* explained, float* out, int32_t* index, int N, int H, int W, int C,
+                         void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * All-pairs correlation + mutual nearest neighbours (utils/outil.py:32-45, mutualMatching).
  * featA: (C, nA) and featB: (C, nB), column = one cell ("K-major": element (k,i) at k*ld+i).

@@ -35,8 +35,15 @@ def _wrap(fn):
     return call
 
 
+def _kitti_getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate, device="cuda"):
+    """evalKITTI/getResults.py:95-141 with the reference's argument list.  RFX_KITTI_FILL=host|device (default host) says where
+    the nearest-neighbour fill of ``interpolate`` runs (rfx.assemble.interpolate_flow_match); the result is the same tensor."""
+    return _a.kitti_getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate, device,
+                                fill=os.environ.get("RFX_KITTI_FILL", "host"))
+
+
 hpatch = types.SimpleNamespace(getFlow_all=_wrap(_a.hpatch_getFlow_all),
                                getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse))
 corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse))
-kitti = types.SimpleNamespace(getFlow_all=_wrap(_a.kitti_getFlow_all),
+kitti = types.SimpleNamespace(getFlow_all=_wrap(_kitti_getFlow_all),
                               getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse))

@@ -9,7 +9,9 @@ ONE dense flow (and confidence) at the evaluation resolution:
 Reference: evaluation/evalHpatch/getResults.py:16-63, evaluation/evalCorr/getResults.py:78-136,
 evaluation/evalKITTI/getResults.py:95-141.  Device work = librfx kernels (rfx_warp_grid_f32, rfx_compose_flow_f32,
 rfx_resize_bilinear_f32, rfx_grid_sample_f32, rfx_match_score_f32, rfx_merge_multi_h_f32); reading the ``.npy`` files
-KITTI's connected-component filter runs on the device (rfx_remove_small_cc_f32); its nearest-neighbour fill stays on the host like in the reference (scipy).
+KITTI's connected-component filter runs on the device (rfx_remove_small_cc_f32).  Its nearest-neighbour fill (--interpolate) runs
+where ``fill`` says: "host" (the default) copies flow and mask to the host and calls scipy like the reference; "device" is
+rfx_nearest_fill_f32, scipy's indices reproduced index for index, with no host transfer and no sync.
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
@@ -59,8 +61,20 @@ def remove_small_cc(score, cc_th, match_th=0.99):
     return ops.remove_small_cc(score, cc_th, match_th)
 
 
-def interpolate_flow_match(flowGlobal, binary):
-    """evalKITTI/getResults.py:87-93 on the host."""
+FILLS = ("host", "device")
+
+
+def _check_fill(fill):
+    if fill not in FILLS:
+        raise ValueError("fill must be one of %s, got %r" % (FILLS, fill))
+
+
+def interpolate_flow_match(flowGlobal, binary, fill="host"):
+    """evalKITTI/getResults.py:87-93: every pixel takes the flow of its nearest explained pixel.  fill="host": scipy on the host,
+    like the reference; fill="device": ops.nearest_fill (the same indices, ties included), asynchronous on the current stream."""
+    _check_fill(fill)
+    if fill == "device":
+        return ops.nearest_fill(flowGlobal, binary)
     from scipy import ndimage
     idx = ndimage.distance_transform_edt((~binary[0]).cpu().numpy(), return_distances=False, return_indices=True)
     f = flowGlobal[0].cpu().numpy()[tuple(idx)]
@@ -68,7 +82,8 @@ def interpolate_flow_match(flowGlobal, binary):
 
 
 def assemble_kitti(flowd2Down, flowDown, param, matchDown, out_hw, th, multiH, cc_th=0.0, interpolate=False,
-                   device="cuda"):
+                   device="cuda", fill="host"):
+    _check_fill(fill)
     H, W = int(out_hw[0]), int(out_hw[1])
     d2d, fd = _to_dev(flowd2Down, device), _to_dev(flowDown, device)
     pm, md = _to_dev(param, device), _to_dev(matchDown, device)
@@ -83,7 +98,7 @@ def assemble_kitti(flowd2Down, flowDown, param, matchDown, out_hw, th, multiH, c
         score = remove_small_cc(ops.match_score(m[:, 0], cyc=cyc, inb=inb), cc_th)
         fg, mg, binary = ops.merge_multi_h(flow, score, th, multiH)
     if interpolate:
-        fg = interpolate_flow_match(fg, binary)
+        fg = interpolate_flow_match(fg, binary, fill)
     return fg, mg, binary
 
 
@@ -141,14 +156,15 @@ def corr_getFlow_Coarse(pairID, flowList, finePath, coarsePath, device="cuda"):
 
 
 def kitti_getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate,
-                      device="cuda"):
-    """evalKITTI/getResults.py:95-141; the output size is that of ``grid_org`` (1,H,W,2), as in the reference."""
+                      device="cuda", fill="host"):
+    """evalKITTI/getResults.py:95-141; the output size is that of ``grid_org`` (1,H,W,2), as in the reference.  ``fill``: where the
+    nearest-neighbour fill of ``interpolate`` runs (interpolate_flow_match)."""
     param = _load(os.path.join(predDir, "Homograpy_{}_{}.npy".format(pairID, nbH)))
     flowd2 = _load(os.path.join(predDir, "{}_D2_{}_{}.npy".format(res_name, pairID, nbH)))
     flow = _load(os.path.join(predDir, "{}_{}_{}.npy".format(res_name, pairID, nbH)))
     match = _load(os.path.join(predDir, "{}_Mask_{}_{}.npy".format(res_name, pairID, nbH)))
     H, W = int(grid_org.shape[1]), int(grid_org.shape[2])
-    return assemble_kitti(flowd2, flow, param, match, (H, W), th, multiH, cc_th, interpolate, device)[0]
+    return assemble_kitti(flowd2, flow, param, match, (H, W), th, multiH, cc_th, interpolate, device, fill)[0]
 
 
 def kitti_getFlow_onlyCoarse(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate,

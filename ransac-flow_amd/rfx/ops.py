@@ -1086,6 +1086,29 @@ def remove_small_cc_ragged(match, match_off, hw, cc_th, match_th=0.99, inplace=F
     return out
 
 
+def nearest_fill(values, explained, want_index=False):
+    """evaluation/evalKITTI/getResults.py:87-93 on the device (rfx_nearest_fill_f32): every pixel takes the values of its nearest
+    explained pixel -- scipy.ndimage.distance_transform_edt(~explained, return_indices=True) index for index, ties included (the
+    smallest column, then the smallest row; a map without explained pixel reads pixel (H-1, 0)).  values (N,H,W,C) or (H,W,C)
+    float32, C <= 8; explained (N,H,W) or (H,W) bool.  Returns a new tensor, with want_index also scipy's indices (N,2,H,W) int32
+    ((2,H,W) for a single map)."""
+    v = _dev(values, "values")
+    e = _dev(explained, "explained", torch.bool)
+    squeeze = v.dim() == 3
+    if v.dim() not in (3, 4) or e.dim() != v.dim() - 1 or tuple(e.shape) != tuple(v.shape[:-1]):
+        raise RuntimeError("nearest_fill: values (N,H,W,C) / (H,W,C) with explained (N,H,W) / (H,W) expected, got %s and %s"
+                           % (tuple(v.shape), tuple(e.shape)))
+    v4, e3 = (v[None], e[None]) if squeeze else (v, e)
+    N, H, W, C = v4.shape
+    out = torch.empty_like(v4)
+    idx = torch.empty((N, 2, H, W), dtype=torch.int32, device=v4.device) if want_index else None
+    ws = torch.empty(_lib.load().rfx_nearest_fill_ws_bytes(N, H, W), dtype=torch.uint8, device=v4.device)
+    _call("rfx_nearest_fill_f32", _one_device(v4, e3), _p(v4), _p(e3), _p(out), _p(idx), N, H, W, C, _p(ws))
+    if squeeze:
+        out, idx = out[0], (idx[0] if want_index else None)
+    return (out, idx) if want_index else out
+
+
 _HOST_KC = None
 
 
