@@ -45,9 +45,10 @@ const char* rfx_version(void);
  * multi-homography round kernels, rfx_filter_matches_ragged_f32 and rfx_multih_accept_ragged_f32; 13:
  * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
  * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32; 16:
- * rfx_group_stats, and the fine-stage entry points record inside a group).  A binding
+ * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
+ * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
-#define RFX_ABI_VERSION 16
+#define RFX_ABI_VERSION 17
 int rfx_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -470,19 +471,16 @@ int rfx_ransac_h4_batched(const float* match1, const float* match2, const int32_
  * can be bit-exact there.  The DLT kernel therefore FLAGS such hypotheses (sigma_8 < 1e-8 * max|bidiagonal|, one Sturm count on
  * the bidiagonal dgebd2 leaves; csrc/dlt.h) and the search can be run in two stages around a host re-solve:
  *   rfx_ransac_h4_batched_stage(..., stages = 1)   pack + DLT: hypotheses and flags into ws (bestH / inlier / result untouched)
- *   rfx_ransac_degenerate_list(ws, ...)            idx (batch,kcap) int32 = flagged hypotheses that survived the duplicate
- *                                                  filter, ascending; count (batch) int32 (may exceed kcap: list truncated)
- *   [host: numpy's LAPACK on exactly those systems -- what the reference itself computes on this host]
- *   rfx_ransac_patch_h(ws, ..., idx, count, Hpatch (batch,kcap,9))   re-solved homographies in, det gate re-evaluated
+ *   rfx_ransac_degenerate_gather(ws, ...)          the flagged hypotheses that survived the duplicate filter, ascending per pair, and
+ *                                                  the point coordinates of their samples, one row each (below)
+ *   [host: LAPACK on exactly those systems -- what the reference itself computes on this host]
+ *   rfx_ransac_patch_h_rows(ws, ..., H_rows)       re-solved homographies in, det gate re-evaluated
  *   rfx_ransac_h4_batched_stage(..., stages = 2)   count + select on the patched hypotheses
  * stages = 3 is rfx_ransac_h4_batched.  cap / N / batch / ws as for rfx_ransac_h4_batched (same workspace across the calls). */
 int rfx_ransac_h4_batched_stage(const float* match1, const float* match2, const int32_t* n, int cap, const int64_t* samples,
                                 int N, float tol, float* bestH, uint8_t* inlier, int32_t* result, void* ws, int batch,
                                 int stages, void* stream);
-int rfx_ransac_degenerate_list(const void* ws, int cap, int N, int batch, int32_t* idx, int32_t* count, int kcap, void* stream);
-int rfx_ransac_patch_h(void* ws, int cap, int N, int batch, const int32_t* idx, const int32_t* count, const float* Hpatch,
-                       int kcap, void* stream);
-/* The same exchange in COMPACT form (round 6: what the exact mode runs on).  rfx_ransac_degenerate_gather, after stage 1: lists the
+/* The exchange (ABI 17: the only form; the (batch,kcap) lists of ABI 7-16 are gone).  rfx_ransac_degenerate_gather, after stage 1: lists the
  * flagged hypotheses of every pair (idx (batch,N) int32, count (batch) int32 -- device scratch), off (batch+1) int32 = exclusive
  * prefix of count with off[batch] = total (device; also stored to off_host when non-NULL), and writes ONE ROW PER FLAGGED
  * HYPOTHESIS at row off[b]+k of xy_rows: 16 floats = the sample's 4 source points (x, y) then its 4 target points (x, y), i.e.

@@ -66,7 +66,7 @@ RFX_HD double rfx_dlapy2(double x, double y) {
 // points collinear in BOTH images: common on the cell lattices) the null space is two-dimensional, a reflector is built from
 // a vector that is pure rounding noise, and which unit vector of the null space LAPACK returns depends on the summation order
 // inside the host BLAS -- it differs between LAPACK builds.  Those hypotheses are flagged so that a caller who needs the
-// host's answer bit for bit can re-solve exactly them with the host's LAPACK (rfx_ransac_degenerate_list).
+// host's answer bit for bit can re-solve exactly them with the host's LAPACK (rfx_ransac_degenerate_gather).
 RFX_HD bool rfx_bidiag_rank_deficient(const double bd[15], double rel) {
     double mx = 0.0;
 #pragma unroll

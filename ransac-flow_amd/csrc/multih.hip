@@ -89,11 +89,8 @@ __device__ __forceinline__ void filter_body(const int64_t* __restrict__ idx1, co
                                             const float* __restrict__ xb, const float* __restrict__ yb, float* __restrict__ m1,
                                             float* __restrict__ m2, int32_t* __restrict__ n_out, int32_t* __restrict__ kept, int k,
                                             int n, int cap, int h, int w, int ct, float sh, float sw) {
-    __shared__ int wsum[16];
-    __shared__ int base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base = 0;
-    __syncthreads();
+    const int t = threadIdx.x;
+    RfxOrderedCompact oc = rfx_ordered_compact_begin();
     for (int s = 0; s < n; s += 1024) {
         const int i = s + t;
         bool keep = false;
@@ -103,25 +100,15 @@ __device__ __forceinline__ void filter_body(const int64_t* __restrict__ idx1, co
             const int r = (int)(cell / ct), c = (int)(cell - (int64_t)r * ct);
             keep = keep_cell(mask, bg, h, w, sh, sw, r, c);
         }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const int cq = wsum[q]; if (q < wave) woff += cq; tot += cq; }
-        const int b0 = base;
+        const int pos = oc.place(keep);
         if (keep) {
-            const size_t o = (size_t)(b0 + woff + before) * 3;
+            const size_t o = (size_t)pos * 3;
             m1[o] = xa[a]; m1[o + 1] = ya[a]; m1[o + 2] = 1.0f;
             m2[o] = xb[cell]; m2[o + 1] = yb[cell]; m2[o + 2] = 1.0f;
-            if (kept) kept[b0 + woff + before] = i;
+            if (kept) kept[pos] = i;
         }
-        __syncthreads();
-        if (t == 0) base = b0 + tot;
-        __syncthreads();
     }
-    const int ntot = base;
+    const int ntot = oc.total();
     for (int i = ntot + t; i < cap; i += 1024) {
         const size_t o = (size_t)i * 3;
         m1[o] = m1[o + 1] = m1[o + 2] = 0.0f;

@@ -487,11 +487,8 @@ __device__ __forceinline__ void mnn_compact_body(const MnnArgs& a) {
     int64_t* idx1 = a.idx1 + (size_t)blockIdx.x * a.idxStride;
     int64_t* idx2 = a.idx2 + (size_t)blockIdx.x * a.idxStride;
     int32_t* count = a.count + blockIdx.x;
-    __shared__ int wsum[16];
-    __shared__ int base;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base = 0;
-    __syncthreads();
+    const int t = threadIdx.x;
+    RfxOrderedCompact oc = rfx_ordered_compact_begin();
     for (int s = 0; s < nA; s += 1024) {
         const int i = s + t;
         bool keep = false;
@@ -501,26 +498,13 @@ __device__ __forceinline__ void mnn_compact_body(const MnnArgs& a) {
             const float v = rowVal[i];
             keep = ((unsigned)j < (unsigned)nB) && (colIdx[j] == i) && (v * v > 0.0f);
         }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int c = wsum[w];
-            if (w < wave) woff += c;
-            tot += c;
-        }
-        const int b = base;
+        const int pos = oc.place(keep);
         if (keep) {
-            idx1[b + woff + before] = i;
-            idx2[b + woff + before] = j;
+            idx1[pos] = i;
+            idx2[pos] = j;
         }
-        __syncthreads();
-        if (t == 0) base = b + tot;
-        __syncthreads();
     }
-    if (t == 0) count[0] = base;
+    if (t == 0) count[0] = oc.total();
 }
 
 __global__ __launch_bounds__(1024) void mnn_compact_kernel(MnnArgs a) { mnn_compact_body(a); }
@@ -528,18 +512,17 @@ __global__ __launch_bounds__(1024) void mnn_compact_kernel(MnnArgs a) { mnn_comp
 struct WsLayout {
     size_t rowPartVal, rowPartIdx, colPartVal, colPartIdx, rowVal, rowIdx, colIdx, total;
 };
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 inline WsLayout layout(int nA, int nB) {
     const size_t tA = (nA + BM - 1) / BM, tB = (nB + BN - 1) / BN;
     WsLayout L;
     size_t o = 0;
-    L.rowPartVal = o; o += al(tB * nA * 4);
-    L.rowPartIdx = o; o += al(tB * nA * 4);
-    L.colPartVal = o; o += al(tA * nB * 4);
-    L.colPartIdx = o; o += al(tA * nB * 4);
-    L.rowVal = o; o += al((size_t)nA * 4);
-    L.rowIdx = o; o += al((size_t)nA * 4);
-    L.colIdx = o; o += al((size_t)nB * 4);
+    L.rowPartVal = o; o += rfx_al256(tB * nA * 4);
+    L.rowPartIdx = o; o += rfx_al256(tB * nA * 4);
+    L.colPartVal = o; o += rfx_al256(tA * nB * 4);
+    L.colPartIdx = o; o += rfx_al256(tA * nB * 4);
+    L.rowVal = o; o += rfx_al256((size_t)nA * 4);
+    L.rowIdx = o; o += rfx_al256((size_t)nA * 4);
+    L.colIdx = o; o += rfx_al256((size_t)nB * 4);
     L.total = o;
     return L;
 }

@@ -83,8 +83,6 @@ SIGNATURES = {
     "rfx_ransac_batched_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rfx_ransac_h4_batched_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_void_p] * 4
                                     + [c_int, c_int, c_void_p]),
-    "rfx_ransac_degenerate_list": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "rfx_ransac_patch_h": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "rfx_ransac_degenerate_gather": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
     "rfx_ransac_patch_h_rows": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p]),
     "rfx_dlt4_homography_flags": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
@@ -107,7 +105,7 @@ SIGNATURES = {
                                         + [c_void_p] * 12 + [c_longlong] + [c_int] * 3 + [c_void_p]),
 }
 
-ABI_VERSION = 16    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
+ABI_VERSION = 17    # RFX_ABI_VERSION of the include/rfx_api.h these prototypes mirror
 
 _lib = None
 

@@ -1351,16 +1351,9 @@ def gather_matches_ragged(idx1, idx2, n, xa, ya, offA, xb, yb, offB):
           _p(_dev(xa, "xa")), _p(_dev(ya, "ya")), _p(offA), _p(_dev(xb, "xb")), _p(_dev(yb, "yb")), _p(offB), _p(m1), _p(m2), B)
     return m1, m2
 
-def ransac_h4_batched(match1, match2, n, samples, tol, degenerate="device", info=None):
-    """match1/match2 (B,cap,3), n (B,) int32 device, samples (B,N,4) int64 -> bestH (B,3,3), inlier (B,cap) bool,
-    result (B,4) int32 [status (3 = fewer than 4 matches), count, winner, nUnique] -- all device tensors.
-    ``degenerate``: what to do with 4-point samples whose 8x9 DLT system is rank deficient (three matched points collinear in
-    both images; ~1 % of the draws on the cell lattices).  "device" (default, no host round trip): the Householder sweep's
-    own null vector -- a valid unit vector of the 2-D null space, but not the one the host LAPACK's rounding noise picks.
-    "lapack": the search runs in two stages around ONE sync: the flagged hypotheses (rfx_ransac_degenerate_list) are re-solved
-    with the host's LAPACK (lapack_dlt: utils/outil.py:68-87 itself) and patched in before counting, so that inlier counts,
-    the winner and its inlier indices equal a CPU run of the reference on this host bit for bit even when such a sample wins
-    (late multi-homography rounds with a handful of matches left).  ``info`` (dict) receives n_degenerate per pair."""
+def _ransac_batched_buffers(match1, match2, n, samples):
+    """The validated inputs of a batched search and its freshly allocated outputs: (match1, match2, n, samples), (bestH (B,3,3) f32,
+    inl (B,cap) uint8, res (B,4) int32, ws)."""
     match1, match2 = _dev(match1, "match1"), _dev(match2, "match2")
     n = _dev(n, "n", torch.int32)
     samples = _dev(samples, "samples", torch.int64)
@@ -1368,18 +1361,31 @@ def ransac_h4_batched(match1, match2, n, samples, tol, degenerate="device", info
     N = samples.shape[1]
     if samples.shape[0] != B or n.shape[0] != B:
         raise ValueError("batch sizes differ")
-    lib = _lib.load()
     dev = match1.device
     bestH = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
     inl = torch.empty((B, cap), dtype=torch.uint8, device=dev)
     res = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.rfx_ransac_batched_ws_bytes(cap, N, B), dtype=torch.uint8, device=dev)
-    odev = _one_device(match1, match2, n, samples)
-    if degenerate != "lapack":
-        _call("rfx_ransac_h4_batched", odev, _p(match1), _p(match2), _p(n), cap, _p(samples), N, float(tol), _p(bestH), _p(inl),
-              _p(res), _p(ws), B)
-        return bestH, inl.bool(), res
-    return ransac_h4_batched_finish(ransac_h4_batched_begin(match1, match2, n, samples, tol, _out=(bestH, inl, res, ws)), info=info)
+    ws = torch.empty(_lib.load().rfx_ransac_batched_ws_bytes(cap, N, B), dtype=torch.uint8, device=dev)
+    return (match1, match2, n, samples), (bestH, inl, res, ws)
+
+
+def ransac_h4_batched(match1, match2, n, samples, tol, degenerate="device", info=None):
+    """match1/match2 (B,cap,3), n (B,) int32 device, samples (B,N,4) int64 -> bestH (B,3,3), inlier (B,cap) bool,
+    result (B,4) int32 [status (3 = fewer than 4 matches), count, winner, nUnique] -- all device tensors.
+    ``degenerate``: what to do with 4-point samples whose 8x9 DLT system is rank deficient (three matched points collinear in
+    both images; ~1 % of the draws on the cell lattices).  "device" (default, no host round trip): the Householder sweep's
+    own null vector -- a valid unit vector of the 2-D null space, but not the one the host LAPACK's rounding noise picks.
+    "lapack": the search runs in two stages around ONE sync: the flagged hypotheses (rfx_ransac_degenerate_gather) are re-solved
+    with the host's LAPACK (lapack_dlt: utils/outil.py:68-87 itself) and patched in before counting, so that inlier counts,
+    the winner and its inlier indices equal a CPU run of the reference on this host bit for bit even when such a sample wins
+    (late multi-homography rounds with a handful of matches left).  ``info`` (dict) receives n_degenerate per pair."""
+    if degenerate == "lapack":
+        return ransac_h4_batched_finish(ransac_h4_batched_begin(match1, match2, n, samples, tol), info=info)
+    (match1, match2, n, samples), (bestH, inl, res, ws) = _ransac_batched_buffers(match1, match2, n, samples)
+    (B, cap, _), N = match1.shape, samples.shape[1]
+    _call("rfx_ransac_h4_batched", _one_device(match1, match2, n, samples), _p(match1), _p(match2), _p(n), cap, _p(samples), N,
+          float(tol), _p(bestH), _p(inl), _p(res), _p(ws), B)
+    return bestH, inl.bool(), res
 
 
 # ---- the exact mode's search, split at its one host wait so that a caller can put other work between the halves -------------
@@ -1407,30 +1413,16 @@ class _ExactSearch:
     __slots__ = ("odev", "args", "bestH", "inl", "res", "ws", "idx", "cnt", "off", "buf", "event", "B", "N", "cap", "gather_args", "t_begin")
 
 
-def ransac_h4_batched_begin(match1, match2, n, samples, tol, _out=None):
+def ransac_h4_batched_begin(match1, match2, n, samples, tol):
     """First half of ransac_h4_batched(degenerate="lapack"): stage 1 (pack + DLT with rank flags) and rfx_ransac_degenerate_gather --
     the flagged samples of all pairs, one 64-byte row each, written by the device straight into pinned host memory -- then an event
     on the launch stream.  Nothing waits here: the caller may enqueue more device work (or run another batch's host work) before
     ransac_h4_batched_finish."""
-    match1, match2 = _dev(match1, "match1"), _dev(match2, "match2")
-    n = _dev(n, "n", torch.int32)
-    samples = _dev(samples, "samples", torch.int64)
-    B, cap, _ = match1.shape
-    N = samples.shape[1]
-    if samples.shape[0] != B or n.shape[0] != B:
-        raise ValueError("batch sizes differ")
+    c = _ExactSearch()
+    (match1, match2, n, samples), (c.bestH, c.inl, c.res, c.ws) = _ransac_batched_buffers(match1, match2, n, samples)
     from . import _lapack
     _lapack.load()
-    lib = _lib.load()
-    dev = match1.device
-    c = _ExactSearch()
-    if _out is None:
-        c.bestH = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-        c.inl = torch.empty((B, cap), dtype=torch.uint8, device=dev)
-        c.res = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        c.ws = torch.empty(lib.rfx_ransac_batched_ws_bytes(cap, N, B), dtype=torch.uint8, device=dev)
-    else:
-        c.bestH, c.inl, c.res, c.ws = _out
+    (B, cap, _), N, dev = match1.shape, samples.shape[1], match1.device
     c.odev = _one_device(match1, match2, n, samples)
     c.B, c.N, c.cap = B, N, cap
     c.args = (_p(match1), _p(match2), _p(n), cap, _p(samples), N, float(tol), _p(c.bestH), _p(c.inl), _p(c.res), _p(c.ws), B)

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_abi_16_and_group_stats_prototype():
     hdr = open(os.path.join(ROOT, "include", "rfx_api.h")).read()
-    assert int(re.search(r"#define RFX_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 16
+    assert int(re.search(r"#define RFX_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 17
     assert re.search(r"int rfx_group_stats\(long long\* groups, long long\* launches\);", hdr)
     assert _lib.SIGNATURES["rfx_group_stats"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p])
 

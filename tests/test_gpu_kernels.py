@@ -687,7 +687,7 @@ def test_ransac_sentinels_and_many_seeds(dev):
     assert rel.max() <= 1e-3 and (rel <= 4e-7).float().mean() > 0.95  # host BLAS may round the K=3 chain differently
 
 
-def _lattice_few_matches(seed, n=13, n_line=6):
+def _lattice_few_matches(seed, n=13, n_line=6, N=600):
     """A late multi-homography round in miniature: a handful of matches left on the 30x40 cell lattice -- ``n_line`` of them on
     ONE lattice row that maps to a shifted row (collinear in both images, same spacing), the rest unrelated.  A sample with three
     points of that line has a rank-7 DLT system, and such samples WIN here (they are the only ones that can explain the line):
@@ -702,7 +702,7 @@ def _lattice_few_matches(seed, n=13, n_line=6):
     m1 = torch.cat((cells[row + 1, cols + 2], flat[torch.randperm(1200, generator=g)[:n_out]]))
     m2 = torch.cat((cells[row, cols], flat[torch.randperm(1200, generator=g)[:n_out]]))
     p = torch.randperm(n, generator=g)
-    return m1[p].clone(), m2[p].clone(), torch.randint(n, (600, 4), generator=g)
+    return m1[p].clone(), m2[p].clone(), torch.randint(n, (N, 4), generator=g)
 
 
 def test_rank_deficient_winners_equal_the_host_lapack_in_exact_mode(dev):
@@ -761,6 +761,105 @@ def test_rank_deficient_winners_equal_the_host_lapack_in_exact_mode(dev):
     for b, (a, c, sm) in enumerate(cases):
         h1, i1, r1 = ops.ransac_h4(a.to(dev), c.to(dev), (sm % len(a)).to(dev), 0.05, degenerate="lapack")
         assert torch.equal(bH[b], h1) and torch.equal(bI[b, :len(a)], i1) and torch.equal(bR[b], r1)
+
+
+def _rank7(m1, m2, s):
+    """Per sample of s: no repeated index and sigma_8 / sigma_1 < 1e-10 of its DLT system (the host's float64 SVD)."""
+    sv = np.linalg.svd(restate.dlt_matrix(m1[s].numpy(), m2[s].numpy()), compute_uv=False)
+    srt = s.sort(1)[0]
+    return ((srt[:, 1:] != srt[:, :-1]).all(1).numpy()) & (sv[:, 7] / sv[:, 0] < 1e-10)
+
+
+def test_search_compacts_across_1024_hypothesis_blocks(dev):
+    """The select and the flag-list kernels walk the hypotheses in trips of 1024 and carry the rank in the filtered order (and the list
+    position) from trip to trip.  N = 2 * 1024 + 64 + 37: three trips, the last one partial and no multiple of a wavefront; ~40 % of the
+    lattice samples repeat an index, so rank and index differ and ranks cross 1024; rank-7 samples sit in all three trips; two seeds
+    are won beyond the first trip.  Exact mode against the oracle, bit for bit; then the batched form against the single-pair calls."""
+    N = 2 * 1024 + 64 + 37
+    winners, spans = [], np.zeros(3, dtype=np.int64)
+    for seed in range(12):
+        m1, m2, s = _lattice_few_matches(seed, N=N)
+        Hb, cnt, inl_ref, _ = restate.ransac(m1, m2, 0.05, s)                  # raises TypeError / returns None: the test fails
+        assert Hb is not None, seed
+        uniq = restate.filter_samples(s)
+        assert 1024 < len(uniq) < N
+        flagged = _rank7(m1, m2, s)
+        per_trip = [int(flagged[a:b].sum()) for a, b in ((0, 1024), (1024, 2048), (2048, N))]
+        assert min(per_trip) >= 1, (seed, per_trip)
+        spans += per_trip
+        info = {}
+        bestH, inl, res = ops.ransac_h4(m1.to(dev), m2.to(dev), s.to(dev), 0.05, degenerate="lapack", info=info)
+        r = res.cpu().tolist()
+        assert [r[0], r[1], r[3]] == [0, int(cnt), len(uniq)], (seed, r, int(cnt), len(uniq))
+        assert np.array_equal(inl.cpu().numpy(), inl_ref), seed
+        assert np.array_equal(bestH.cpu().numpy(), Hb), (seed, np.abs(bestH.cpu().numpy() - Hb).max())
+        assert info["n_degenerate"][0] >= int(flagged.sum()), (seed, info["n_degenerate"], int(flagged.sum()))
+        winners.append(r[2])
+        # the single-pair entry point (match count from the host): the part of its record that no null vector decides
+        r1 = ops.ransac_h4(m1.to(dev), m2.to(dev), s.to(dev), 0.05)[2].cpu().tolist()
+        assert r1[0] == 0 and r1[3] == len(uniq), (seed, r1)
+    assert max(winners) >= 1024, winners
+    assert (spans > 0).all()
+    cases = [_lattice_few_matches(sd, n=nn, N=N) for sd, nn in ((3, 13), (8, 30), (11, 9))]
+    cap = max(len(c[0]) for c in cases)
+    M1 = torch.zeros((3, cap, 3)); M2 = torch.zeros((3, cap, 3))
+    for b, (a, c, _) in enumerate(cases):
+        M1[b, :len(a)], M2[b, :len(a)] = a, c
+    nd = torch.tensor([len(c[0]) for c in cases], dtype=torch.int32, device=dev)
+    S = torch.stack([c[2] for c in cases]).to(dev)
+    bH, bI, bR = ops.ransac_h4_batched(M1.to(dev), M2.to(dev), nd, S, 0.05, degenerate="lapack")
+    for b, (a, c, sm) in enumerate(cases):
+        h1, i1, r1 = ops.ransac_h4(a.to(dev), c.to(dev), sm.to(dev), 0.05, degenerate="lapack")
+        assert torch.equal(bH[b], h1) and torch.equal(bI[b, :len(a)], i1) and not bool(bI[b, len(a):].any()) and torch.equal(bR[b], r1)
+
+
+def test_zero_chunk_abort_beyond_rank_1024(dev):
+    """utils/outil.py:145-146 gives up when a whole chunk of 100 surviving hypotheses counts nothing.  Here that chunk is ranks
+    1100 .. 1199 of the filtered order, the second trip of the select kernel's loop: 100 permutations of four extra matches whose system
+    has full rank (sigma_8 / sigma_1 ~ 1.5e-4: no rank flag) but |det H| ~ 6e-8, sixteen times below the gate.  The same list without
+    those rows finds all 40 good matches."""
+    rows, cols, tol, eps = 15, 20, 0.02, 1e-4
+    xs = ((torch.arange(cols) + 0.5) / cols - 0.5) * 2
+    ys = ((torch.arange(rows) + 0.5) / rows - 0.5) * 2
+    xb = xs.repeat(rows); yb = ys.repeat_interleave(cols)
+    Hm = torch.tensor([[1.05, .02, .03], [-.01, .97, -.02], [.01, .02, 1.]])          # test_batched_ransac_equals_per_pair's
+    pts = torch.stack((xb, yb, torch.ones_like(xb)), 1) @ Hm.T
+    xa, ya = pts[:, 0] / pts[:, 2], pts[:, 1] / pts[:, 2]
+    g = torch.Generator().manual_seed(3)
+    cells = torch.randperm(rows * cols, generator=g)[:40]
+    m1 = torch.cat((torch.stack((xa[cells], ya[cells], torch.ones(40)), 1),
+                    torch.tensor([[-.5, -.5, 1.], [.5, -.5, 1.], [.5, .5, 1.], [-.5, .5, 1.]])))
+    m2 = torch.cat((torch.stack((xb[cells], yb[cells], torch.ones(40)), 1),
+                    torch.tensor([[-.6, eps, 1.], [-.1, -2 * eps, 1.], [.3, 3 * eps, 1.], [.7, -eps, 1.]])))
+    head, n_unique = [], 0
+    while n_unique < 1100:                                                             # duplicate rows stay in place: rank != index
+        head.append(torch.randint(40, (1, 4), generator=g))
+        n_unique += len(set(head[-1][0].tolist())) == 4
+    head = torch.cat(head)
+    perms = torch.stack([40 + torch.randperm(4, generator=g) for _ in range(100)])
+    tail = torch.randint(40, (37, 4), generator=g)
+    S = torch.cat((head, perms, tail))
+    S0 = torch.cat((head, torch.zeros_like(perms), tail))                               # the 100 rows replaced by rows the filter drops
+    n_filtered = len(restate.filter_samples(S))
+    # the oracle on exactly these inputs
+    assert len(head) > 1100 and len(restate.filter_samples(head)) == 1100 and n_filtered >= 1200
+    assert int(restate.score_ransac(m1, m2, tol, perms)[1].max()) == 0 and not _rank7(m1, m2, perms).any()
+    assert restate.ransac(m1, m2, tol, S)[:2] == (None, 0)
+    assert int(restate.ransac(m1[:40], m2[:40], tol, S0)[1]) == 40
+
+    def aborted(H, inl, r, n):
+        return r == [1, 0, -1, n_filtered] and not bool(inl[:n].any()) and not bool(H.any())
+    H, inl, res = ops.ransac_h4(m1.to(dev), m2.to(dev), S.to(dev), tol, degenerate="lapack")
+    assert aborted(H, inl, res.cpu().tolist(), 44), res
+    H, inl, res = ops.ransac_h4(m1.to(dev), m2.to(dev), S.to(dev), tol)                # the single-pair entry point
+    assert aborted(H, inl, res.cpu().tolist(), 44), res
+    M1, M2 = torch.stack((m1, m1)), torch.stack((m2, m2))
+    M1[0, 40:] = 0; M2[0, 40:] = 0
+    nd = torch.tensor([40, 44], dtype=torch.int32, device=dev)
+    bH, bI, bR = ops.ransac_h4_batched(M1.to(dev), M2.to(dev), nd, torch.stack((S0, S)).to(dev), tol, degenerate="lapack")
+    bR = bR.cpu().tolist()
+    assert aborted(bH[1], bI[1], bR[1], 44), bR
+    assert bR[0][:2] == [0, 40] and bR[0][3] == n_filtered - 100 and bool(bI[0, :40].all()) and not bool(bI[0, 40:].any()), bR
 
 
 # ------------------------------------------------------------------ whole networks

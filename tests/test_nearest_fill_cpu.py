@@ -89,7 +89,7 @@ def test_tie_rule_is_scipys():
 
 def test_header_and_binding_declare_the_entry_points():
     hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "rfx_api.h")).read(), flags=re.S)
-    assert int(re.search(r"#define RFX_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 16
+    assert int(re.search(r"#define RFX_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 17
     assert re.search(r"\bsize_t\s+rfx_nearest_fill_ws_bytes\s*\(\s*int\s+N\s*,\s*int\s+H\s*,\s*int\s+W\s*\)\s*;", hdr)
     args = re.search(r"\bint\s+rfx_nearest_fill_f32\s*\(([^;{]*?)\)\s*;", hdr, flags=re.S).group(1).split(",")
     assert [ctypes.c_void_p if "*" in a else ctypes.c_int for a in args] == _lib.SIGNATURES["rfx_nearest_fill_f32"][1]

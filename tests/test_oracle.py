@@ -424,6 +424,20 @@ def test_library_exports_every_declared_symbol():
     assert lib.rfx_mutual_nn_ws_bytes(8531, 1200) > 0 and lib.rfx_ransac_ws_bytes(900, 1000) > 0
 
 
+def test_ransac_workspace_is_five_arrays_on_256_byte_boundaries():
+    """The per-pair RANSAC workspace (ransac_args in csrc/ransac.hip, host only): n float4 + n float32 packed matches, N x 9 float32
+    hypotheses, N flag bytes, N int32 counts, each padded to 256 bytes; a batch takes that stride once per pair; no size for a
+    non-positive argument."""
+    lib = _lib.load()
+    al = lambda x: (x + 255) // 256 * 256
+    for n, N in ((1, 1), (13, 2149), (44, 1427), (900, 1000), (8531, 50000), (16, 64), (17, 65)):
+        one = al(16 * n) + al(4 * n) + al(36 * N) + al(N) + al(4 * N)
+        assert lib.rfx_ransac_ws_bytes(n, N) == one, (n, N)
+        for batch in (1, 3, 64):
+            assert lib.rfx_ransac_batched_ws_bytes(n, N, batch) == one * batch, (n, N, batch)
+    assert lib.rfx_ransac_ws_bytes(0, 10) == lib.rfx_ransac_ws_bytes(10, 0) == lib.rfx_ransac_batched_ws_bytes(10, 10, 0) == 0
+
+
 def test_ops_refuse_cpu_tensors():
     from rfx import ops
     with pytest.raises(RuntimeError):
