@@ -376,6 +376,34 @@ size_t rfx_nearest_fill_ws_bytes(int N, int H, int W);
 int rfx_nearest_fill_f32(const float* values, const unsigned char* explained, float* out, int32_t* index, int N, int H, int W, int C,
                          void* ws, void* stream);
 
+/* The pixel correspondences of all explained pixels of an assembled flow (evaluation/evalYFCC/getResults.py:53-71,
+ * matches_from_flow: numpy boolean indexing of the flow and of np.rot90(gridB, k) on the host there).
+ * flow (N,H,W,2) float32, keep (N,H,W) bytes, non-zero = explained; bg (N,H,W) bytes or NULL, ANDed with keep (the script's
+ * match_binary * matchBG).  k in 0..3 = (angle / 90) mod 4; (wA, hA) the source size, (wB, hB) the UNROTATED target size: the maps
+ * are (hB, wB) for even k and (wB, hB) for odd k.  Rows come map after map, row-major over the pixels (i, j) of a map:
+ *     pts1 (rows,2) float32:  t = x + 1; t = t * (float)(wA - 1); t = t / 2, each step rounded to float32; y with hA - 1;
+ *     pts2 (rows,2) int64:    np.rot90(gridB, k)[i, j] = (j, i) | (wB-1-i, j) | (wB-1-j, hB-1-i) | (i, hB-1-j) for k = 0 | 1 | 2 | 3;
+ *     offsets (N+1) int64:    the exclusive prefix of the per-map row counts, offsets[N] = rows; stays on the device.
+ * pts1 and pts2 must have room for N*H*W rows; rows beyond offsets[N] are not written.  Deterministic: three stream-ordered launches
+ * (count per 1024-pixel tile, one-workgroup scan of the tile counts, scatter by recomputed ballots), no atomics, no workgroup waits
+ * on another; flow is read only where kept.  ws: rfx_flow_points_ws_bytes(N,H,W) bytes = one int32 per tile, ceil(H*W / 1024) tiles
+ * per map (0 for a non-positive size).
+ * RFX_E_ARG: a null pointer other than bg, a non-positive N, H or W, k outside 0..3, wA or hA < 1, a map shape that is not the
+ * one k and (wB, hB) give, flow / pts1 / offsets not 8-byte or pts2 not 16-byte aligned.  RFX_E_LIMIT: N*H*W > 2^31 - 1.
+ * All of these are checked before any HIP call. */
+size_t rfx_flow_points_ws_bytes(int N, int H, int W);
+int rfx_flow_points_f32(const float* flow, const unsigned char* keep, const unsigned char* bg, int N, int H, int W, int k, int wA,
+                        int hA, int wB, int hB, float* pts1, long long* pts2, long long* offsets, void* ws, void* stream);
+
+/* The keypoint transfer of evaluation/evalCorr/getResults.py:15-31 (alignmentError: the whole maps go to the host there): for K
+ * target pixels (xb[q], yb[q]) (int32, device) of ONE map, flow (H,W,2), match (H,W) float32,
+ *     xa[q] = ((flow[yb,xb,0] + 1) * 0.5f) * (float)(wA - 1),  ya[q] with channel 1 and hA - 1 (float32, in that order),
+ *     keep[q] = match[yb,xb] > 0.5f  (a byte).
+ * A pixel outside the map reads nothing and gives 0, 0, 0 (the Python mirror refuses it on the host).
+ * RFX_E_ARG: a null pointer, a non-positive K, H or W, wA or hA < 1, flow not 8-byte aligned; RFX_E_LIMIT: H*W > 2^31 - 1. */
+int rfx_sample_points_f32(const float* flow, const float* match, const int32_t* xb, const int32_t* yb, int K, int H, int W, int wA,
+                          int hA, float* xa, float* ya, unsigned char* keep, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * All-pairs correlation + mutual nearest neighbours (utils/outil.py:32-45, mutualMatching).
  * featA: (C, nA) and featB: (C, nB), column = one cell ("K-major": element (k,i) at k*ld+i).

@@ -1,14 +1,17 @@
-"""Drop-in for the flow-assembly functions of the reference's three ``getResults.py`` scripts (which are scripts,
+"""Drop-in for the flow-assembly functions of the reference's four ``getResults.py`` scripts (which are scripts,
 not modules: their bodies parse argv and walk dataset folders that are out of scope).  Same names, argument lists
 and return conventions (CPU tensors, ``[]`` sentinels); the arithmetic runs in librfx on the HIP device:
 
-    from getResults import hpatch, corr, kitti
+    from getResults import hpatch, corr, kitti, yfcc
     flow = hpatch.getFlow_all(pairID, finePath, coarsePath, flowList, multiH, warper, grid, th, outW, outH)
     flow, match = corr.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)
     flow = kitti.getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate)
+    counts, nbAlign = corr.alignmentError(wB, hB, wA, hA, XA, YA, XB, YB, flow, match, pixelGrid)
+    flow, binary = yfcc.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)        # numpy, like the script
+    pts1, pts2 = yfcc.matches_from_flow(flow, binary, sizeA, sizeB, angle)                             # numpy float32 / int64
 
-Reference: evaluation/evalHpatch/getResults.py:16-80, evaluation/evalCorr/getResults.py:78-164,
-evaluation/evalKITTI/getResults.py:95-152.
+Reference: evaluation/evalHpatch/getResults.py:16-80, evaluation/evalCorr/getResults.py:15-38,78-164,
+evaluation/evalKITTI/getResults.py:95-152, evaluation/evalYFCC/getResults.py:53-71,132-190.
 """
 import os
 import sys
@@ -42,8 +45,33 @@ def _kitti_getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_
                                 fill=os.environ.get("RFX_KITTI_FILL", "host"))
 
 
+def _np(x):
+    if isinstance(x, tuple):
+        return tuple(_np(v) for v in x)
+    return x.cpu().numpy() if hasattr(x, "cpu") else x
+
+
+def _yfcc_getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th, device="cuda"):
+    """evalYFCC/getResults.py:132-148 -> numpy (flowGlobal (H,W,2) float32, match_binary (H,W) bool), or ([], [])."""
+    fg, binary = _a.yfcc_getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th, device)
+    return (fg, binary) if isinstance(fg, list) else (fg[0].cpu().numpy(), binary[0].cpu().numpy())
+
+
+def _yfcc__getFlow(flow, param, match, matchBG, multiH, th, device="cuda"):
+    """evalYFCC/getResults.py:150-190, the reference's argument order (multiH before th) -> numpy, squeezed like the reference."""
+    fg, binary = _a.assemble_yfcc(flow, param, match, matchBG, th, multiH, device)
+    return fg[0].cpu().numpy(), binary[0].cpu().numpy()
+
+
+def _yfcc_matches_from_flow(flowFine, matchBinary, sizeA, sizeB, angle):
+    """evalYFCC/getResults.py:53-71 -> numpy (pts1 (n,2) float32, pts2 (n,2) int64)."""
+    return _np(_a.yfcc_matches(flowFine, matchBinary, sizeA, sizeB, angle))
+
+
 hpatch = types.SimpleNamespace(getFlow_all=_wrap(_a.hpatch_getFlow_all),
                                getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse))
-corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse))
+corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse),
+                             alignmentError=_a.corr_alignment_error)
 kitti = types.SimpleNamespace(getFlow_all=_wrap(_kitti_getFlow_all),
                               getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse))
+yfcc = types.SimpleNamespace(getFlow=_yfcc_getFlow, _getFlow=_yfcc__getFlow, matches_from_flow=_yfcc_matches_from_flow)

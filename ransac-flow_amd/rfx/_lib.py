@@ -69,6 +69,9 @@ SIGNATURES = {
     "rfx_remove_small_cc_ragged_f32": (c_int, [c_void_p] * 4 + [c_int, c_longlong, c_longlong, c_float, c_void_p, c_void_p]),
     "rfx_nearest_fill_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_nearest_fill_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "rfx_flow_points_ws_bytes": (c_size_t, [c_int] * 3),
+    "rfx_flow_points_f32": (c_int, [c_void_p] * 3 + [c_int] * 8 + [c_void_p] * 5),
+    "rfx_sample_points_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4),
     "rfx_mutual_nn_ws_bytes": (c_size_t, [c_int, c_int]),
     "rfx_mutual_nn_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p]),
     "rfx_mutual_nn_batched_f32": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_int, c_longlong, c_int]

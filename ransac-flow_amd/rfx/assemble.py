@@ -7,17 +7,21 @@ ONE dense flow (and confidence) at the evaluation resolution:
     owner(p) = 0 if score_0(p) >= th else first i >= 1 with score_i(p) >= th (multiH) else 0
 
 Reference: evaluation/evalHpatch/getResults.py:16-63, evaluation/evalCorr/getResults.py:78-136,
-evaluation/evalKITTI/getResults.py:95-141.  Device work = librfx kernels (rfx_warp_grid_f32, rfx_compose_flow_f32,
+evaluation/evalKITTI/getResults.py:95-141, evaluation/evalYFCC/getResults.py:132-190.  Device work = librfx kernels (rfx_warp_grid_f32, rfx_compose_flow_f32,
 rfx_resize_bilinear_f32, rfx_grid_sample_f32, rfx_match_score_f32, rfx_merge_multi_h_f32); reading the ``.npy`` files
 KITTI's connected-component filter runs on the device (rfx_remove_small_cc_f32).  Its nearest-neighbour fill (--interpolate) runs
 where ``fill`` says: "host" (the default) copies flow and mask to the host and calls scipy like the reference; "device" is
 rfx_nearest_fill_f32, scipy's indices reproduced index for index, with no host transfer and no sync.
+What the YFCC and Corr scripts then READ off the assembled maps stays on the device as well: the correspondences of all explained
+pixels (yfcc_matches: rfx_flow_points_f32, evalYFCC/getResults.py:53-71) and the transfer of annotated keypoints
+(corr_alignment_error: rfx_sample_points_f32, evalCorr/getResults.py:15-38; 3 K values cross the bus, not the maps).
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
     <fine>/mask_{id}_{n}H.npy   (n,2,h/8,w/8) float   matchability 1->2 | 2->1
     <coarse>/flow_{id}_{n}H.npy (n,3,3)        float   homographies
-    <mask>/maskBG_{id}_{n}H.npy (h,w) bool              background mask (loaded by evalCorr, unused in the assembly)
+    <mask>/maskBG_{id}_{n}H.npy (h,w) bool              background mask (loaded by evalCorr, unused in its assembly; YFCC ANDs it
+                                                        with the explained mask)
     KITTI: Homograpy_{id}_{n}.npy, {res}_D2_{id}_{n}.npy, {res}_{id}_{n}.npy, {res}_Mask_{id}_{n}.npy, BG_{id}_{n}H.npy
 """
 import os
@@ -54,6 +58,47 @@ def assemble(flowDown, param, matchDown, out_hw, th, multiH, cycle, device="cuda
     m = ops.resize_bilinear(md, (H, W), align_corners=False)
     cyc = ops.grid_sample(m[:, 1:2].contiguous(), fup)[:, 0] if cycle else None
     return ops.merge_multi_h(flow, m[:, 0], th, multiH, cyc=cyc, inb=inb)
+
+
+def assemble_yfcc(flowDown, param, matchDown, matchBG, th, multiH, device="cuda"):
+    """evalYFCC/getResults.py:150-190 (_getFlow): assemble(..., cycle=True) at 8h x 8w, the explained mask ANDed with the background
+    mask matchBG (8h,8w) -> (flowGlobal (1,H,W,2), binary (1,H,W) bool) device tensors."""
+    h, w = int(flowDown.shape[2]), int(flowDown.shape[3])
+    fg, _, binary = assemble(flowDown, param, matchDown, (h * 8, w * 8), th, multiH, True, device)
+    bg = matchBG if torch.is_tensor(matchBG) else torch.from_numpy(np.ascontiguousarray(np.asarray(matchBG) != 0))
+    return fg, binary & (bg.to(fg.device) != 0).reshape(1, h * 8, w * 8)
+
+
+def yfcc_matches(flowGlobal, binary, sizeA, sizeB, angle):
+    """evalYFCC/getResults.py:53-71 (matches_from_flow) on the maps assemble_yfcc returns, (1,H,W,2) and (1,H,W), or on single
+    (H,W,2) / (H,W) maps; numpy arrays are uploaded.  sizeA = (wA, hA), sizeB = (wB, hB) before the rotation by ``angle``.
+    -> (pts1 (n,2) float32, pts2 (n,2) int64) device tensors, in numpy's boolean-indexing order."""
+    dev = next((t.device for t in (flowGlobal, binary) if torch.is_tensor(t) and t.is_cuda), "cuda")
+    f = _to_dev(flowGlobal, dev)
+    b = binary.to(dev) if torch.is_tensor(binary) else torch.from_numpy(np.ascontiguousarray(np.asarray(binary))).to(dev)
+    b = b if b.dtype in (torch.bool, torch.uint8) else b != 0
+    if f.dim() == 4 and f.shape[0] == 1:
+        f, b = f[0], b.reshape(f.shape[1], f.shape[2])
+    return ops.matches_from_flow(f, b, sizeA, sizeB, angle)[:2]
+
+
+def corr_alignment_error(wB, hB, wA, hA, XA, YA, XB, YB, flow, match2, pixelGrid, device="cuda"):
+    """evalCorr/getResults.py:15-38 (alignmentError): flow (1,hB,wB,2) and match2 (1,hB,wB,1) as corr_getFlow returns them (or
+    arrays), keypoints XA, YA (source) and XB, YB (target) as numpy arrays -- floats are truncated toward zero, like the reference's
+    astype(np.int64) --, pixelGrid (1,T).  The maps are read on the device at the K target keypoints (ops.sample_points); the
+    distances of the kept keypoints and their tally under the T thresholds are numpy float64 on the host, where the reference
+    promotes too.  -> (counts (T,), nbAlign), zeros when no keypoint is kept."""
+    dev = next((t.device for t in (flow, match2) if torch.is_tensor(t) and t.is_cuda), device)
+    f = _to_dev(flow, dev).reshape(int(hB), int(wB), 2)
+    m = _to_dev(match2, dev).reshape(int(hB), int(wB))
+    xa, ya = np.asarray(XA).astype(np.int64), np.asarray(YA).astype(np.int64)
+    xaH, yaH, keep = (t.cpu().numpy() for t in ops.sample_points(f, m, XB, YB, (wA, hA)))
+    index = np.where(keep)[0]
+    nbAlign = len(index)
+    if nbAlign == 0:
+        return np.zeros(pixelGrid.shape[1]), nbAlign
+    pixelDiff = ((xaH[index] - xa[index]) ** 2 + (yaH[index] - ya[index]) ** 2) ** 0.5
+    return np.sum(pixelDiff.reshape((-1, 1)) <= pixelGrid, axis=0), nbAlign
 
 
 def remove_small_cc(score, cc_th, match_th=0.99):
@@ -141,6 +186,18 @@ def corr_getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th, d
     h, w = flow.shape[2], flow.shape[3]
     fg, mg, _ = assemble(flow, param, match, (h * 8, w * 8), th, multiH, True, device)
     return fg, mg.unsqueeze(3)
+
+
+def yfcc_getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th, device="cuda"):
+    """evalYFCC/getResults.py:132-148 -> (flowGlobal (1,8h,8w,2), binary (1,8h,8w) bool) or ([], [])."""
+    nbH = find_nbH(pairID, flowList)
+    if nbH is None:
+        return [], []
+    flow = _load(os.path.join(finePath, "flow_{:d}_{}H.npy".format(pairID, nbH)))
+    param = _load(os.path.join(coarsePath, "flow_{:d}_{}H.npy".format(pairID, nbH)))
+    match = _load(os.path.join(finePath, "mask_{:d}_{}H.npy".format(pairID, nbH)))
+    matchBG = np.load(os.path.join(maskPath, "maskBG_{:d}_{}H.npy".format(pairID, nbH)))
+    return assemble_yfcc(flow, param, match, matchBG, th, multiH, device)
 
 
 def corr_getFlow_Coarse(pairID, flowList, finePath, coarsePath, device="cuda"):

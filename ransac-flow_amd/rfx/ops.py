@@ -1109,6 +1109,99 @@ def nearest_fill(values, explained, want_index=False):
     return (out, idx) if want_index else out
 
 
+def _points_geometry(flow, keep, sizeA, sizeB, angle, bg):
+    """Shapes of a flow_points call, checked before anything touches a device -> (single map?, k, (wA, hA), (wB, hB))."""
+    for name, t in (("flow", flow), ("keep", keep), ("bg", bg)):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    (wA, hA), (wB, hB) = (int(sizeA[0]), int(sizeA[1])), (int(sizeB[0]), int(sizeB[1]))
+    k = (int(angle) // 90) % 4
+    single = flow.dim() == 3
+    if flow.dim() not in (3, 4) or flow.shape[-1] != 2 or tuple(keep.shape) != tuple(flow.shape[:-1]):
+        raise ValueError("flow_points: flow (N,H,W,2) / (H,W,2) with keep (N,H,W) / (H,W) expected, got %s and %s"
+                         % (tuple(flow.shape), tuple(keep.shape)))
+    if bg is not None and tuple(bg.shape) != tuple(keep.shape):
+        raise ValueError("flow_points: bg %s is not of keep's shape %s" % (tuple(bg.shape), tuple(keep.shape)))
+    want = (wB, hB) if k & 1 else (hB, wB)
+    if tuple(flow.shape[-3:-1]) != want or min(want) < 1 or (not single and flow.shape[0] < 1):
+        raise ValueError("flow_points: maps of shape %s do not fit sizeB = %s at angle %s (%s expected)"
+                         % (tuple(flow.shape[-3:-1]), (wB, hB), angle, want))
+    if wA < 1 or hA < 1:
+        raise ValueError("flow_points: sizeA = %s" % ((wA, hA),))
+    return single, k, (wA, hA), (wB, hB)
+
+
+def _mask_bytes(t, name):
+    """A bool or uint8 mask on a HIP device (non-zero = set), contiguous."""
+    return _dev(t, name, torch.uint8 if t.dtype == torch.uint8 else torch.bool)
+
+
+def flow_points(flow, keep, sizeA, sizeB, angle=0, bg=None):
+    """evaluation/evalYFCC/getResults.py:53-71 (matches_from_flow) on the device (rfx_flow_points_f32): the correspondences of all
+    pixels with keep (and bg, if given) set, map after map, row-major inside a map -- numpy's boolean indexing of the flow and of
+    np.rot90(gridB, angle // 90).  flow (N,H,W,2) / (H,W,2) float32, keep and bg (N,H,W) / (H,W) bool or uint8; sizeA = (wA, hA),
+    sizeB = (wB, hB) the unrotated target size.  No host sync: returns (pts1_buf (N*H*W,2) float32, pts2_buf (N*H*W,2) int64,
+    offsets (N+1,) int64), all on the device; only the first offsets[-1] rows of the buffers are written, map n's rows are
+    offsets[n]:offsets[n+1]."""
+    single, k, (wA, hA), (wB, hB) = _points_geometry(flow, keep, sizeA, sizeB, angle, bg)
+    f, m = _dev(flow, "flow"), _mask_bytes(keep, "keep")
+    b = _mask_bytes(bg, "bg") if bg is not None else None
+    N, (H, W) = (1 if single else f.shape[0]), f.shape[-3:-1]
+    lib = _lib.load()
+    pts1 = torch.empty((N * H * W, 2), dtype=torch.float32, device=f.device)
+    pts2 = torch.empty((N * H * W, 2), dtype=torch.int64, device=f.device)
+    offsets = torch.empty(N + 1, dtype=torch.int64, device=f.device)
+    ws = torch.empty(lib.rfx_flow_points_ws_bytes(N, H, W), dtype=torch.uint8, device=f.device)
+    _call("rfx_flow_points_f32", _one_device(f, m, b), _p(f), _p(m), _p(b), N, H, W, k, wA, hA, wB, hB, _p(pts1), _p(pts2),
+          _p(offsets), _p(ws))
+    return pts1, pts2, offsets
+
+
+def matches_from_flow(flow, keep, sizeA, sizeB, angle=0, bg=None):
+    """flow_points, exactly sized: ONE read of the offsets (the only host sync), then views of the first offsets[-1] rows.
+    A single (H,W,2) map -> (pts1 (n,2) float32, pts2 (n,2) int64); a batch (N,H,W,2) -> (pts1, pts2, offsets) with offsets the
+    (N+1,) int64 HOST copy just read: map n's points are rows offsets[n]:offsets[n+1].  The results are views of flow_points'
+    N*H*W-row buffers (no copy); ``.clone()`` them to let the buffers go."""
+    pts1, pts2, offsets = flow_points(flow, keep, sizeA, sizeB, angle, bg)
+    off = offsets.cpu()
+    total = int(off[-1])
+    if flow.dim() == 3:
+        return pts1[:total], pts2[:total]
+    return pts1[:total], pts2[:total], off
+
+
+def sample_points(flow, match, xb, yb, sizeA):
+    """evaluation/evalCorr/getResults.py:15-31 (alignmentError's reads of the assembled maps) on the device (rfx_sample_points_f32):
+    for K target pixels (xb, yb) -- host integers, or floats truncated toward zero like ``astype(np.int64)`` -- of ONE map,
+    xa = ((flow[yb,xb,0] + 1) * 0.5) * (wA - 1), ya likewise with channel 1 and hA - 1, keep = match[yb,xb] > 0.5.  flow (H,W,2) or
+    (1,H,W,2), match (H,W) with any number of size-1 axes around it, float32 on the device.  A pixel outside the map is a bad
+    argument (RfxError), found on the host before anything is launched.  Returns device tensors (xa, ya float32, keep bool) of K."""
+    import numpy as np
+    f = _dev(flow, "flow")
+    m = _dev(match, "match")
+    if f.dim() == 4 and f.shape[0] == 1:
+        f = f[0]
+    if f.dim() != 3 or f.shape[2] != 2 or m.numel() != f.shape[0] * f.shape[1]:
+        raise ValueError("sample_points: flow (H,W,2) with match (H,W) expected, got %s and %s" % (tuple(flow.shape), tuple(match.shape)))
+    H, W = int(f.shape[0]), int(f.shape[1])
+    wA, hA = int(sizeA[0]), int(sizeA[1])
+    x = np.asarray(xb.cpu() if isinstance(xb, torch.Tensor) else xb).astype(np.int64).reshape(-1)
+    y = np.asarray(yb.cpu() if isinstance(yb, torch.Tensor) else yb).astype(np.int64).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError("sample_points: %d xb for %d yb" % (x.size, y.size))
+    K = int(x.size)
+    if wA < 1 or hA < 1 or (K and (x.min() < 0 or x.max() >= W or y.min() < 0 or y.max() >= H)):
+        _lib.check(-1, "rfx_sample_points_f32 (a keypoint outside the %d x %d map, or sizeA = %s)" % (W, H, (wA, hA)))
+    xa = torch.empty(K, dtype=torch.float32, device=f.device)
+    ya = torch.empty(K, dtype=torch.float32, device=f.device)
+    keep = torch.empty(K, dtype=torch.bool, device=f.device)
+    if K:
+        xy = torch.from_numpy(np.stack((x, y)).astype(np.int32)).to(f.device)
+        _call("rfx_sample_points_f32", _one_device(f, m), _p(f), _p(m), _p(xy[0]), _p(xy[1]), K, H, W, wA, hA, _p(xa), _p(ya),
+              _p(keep))
+    return xa, ya, keep
+
+
 _HOST_KC = None
 
 
