@@ -46,7 +46,8 @@ const char* rfx_version(void);
  * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
  * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32; 16:
  * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
- * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows).  A binding
+ * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17:
+ * no existing entry point moved, and a binding that knows the new name refuses a library without it).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
 #define RFX_ABI_VERSION 17
 int rfx_abi_version(void);
@@ -616,6 +617,21 @@ int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t* idx2, cons
                                   const float* xa, const float* ya, const long long* offA, const float* xb, const float* yb,
                                   const long long* offB, float* match1, float* match2, int32_t* n_out, int32_t* kept,
                                   void* stream);
+
+/* rfx_keep_mask_f32 for ACTIVE PAIRS OF DIFFERENT SIZES, one launch: the keep map variant C's getCoarse multiplies the target features
+ * with before the mutual matching of EVERY round (evaluation/evalYFCC/coarseAlignFeatMatch.py:158-166).  mask / bg: the packed buffers
+ * above (pair b's h_b * w_b floats at moff[b], geometry in geom[b]); bg NULL = all foreground; mask NULL = nothing explained yet (the
+ * candidate search); both NULL = every cell kept.  For b = active[k] (k itself when active is NULL) the cell value is the one
+ * rfx_keep_mask_f32 computes for that pair alone -- same interpolation, same operation order, scales h_b / rt_b and w_b / ct_b rounded
+ * to float32 as the dense entry point forms them -- stored as 0.0 / 1.0 in keep[b * ldB + cell], cell < rt_b * ct_b: the pair's row
+ * sits at its own position b, the layout rfx_mutual_nn_ragged_f32 reads its maskB in.  Columns from rt_b * ct_b on and the rows of
+ * pairs that are not in the list are NOT written.  nB_round (batch int32, or NULL) receives rt_b * ct_b at the active pairs'
+ * positions only; zeroed by the caller and passed to rfx_mutual_nn_ragged_f32 as nB, it makes the matching skip every other pair
+ * (count 0, no work).  max_cells: the largest rt_b * ct_b among the active pairs, <= ldB; the grid is
+ * (ceil(max_cells / 256), n_active) workgroups of 256 threads, n_active <= 65535 (RFX_E_LIMIT).  A pair whose table row is not
+ * positive, or has more cells than ldB, gets no cell and nB_round 0. */
+int rfx_keep_mask_ragged_f32(const float* mask, const float* bg, const long long* moff, const int32_t* geom, const int32_t* active,
+                             int n_active, int ldB, int max_cells, float* keep, int32_t* nB_round, void* stream);
 
 /* rfx_multih_accept_ragged_f32 (evalHpatch/evaluation.py:225,238-239; mode 1: evalKITTI/evaluation.py:322,332-333): the accept rule,
  * mask update and record store of rfx_multih_accept_f32.  The round's per-pair inputs are packed PER ACTIVE PAIR (offsets per k, the

@@ -52,8 +52,10 @@ __device__ __forceinline__ float fg_px(float maskv, const float* __restrict__ bg
     return __fadd_rn(maskv, __fsub_rn(1.0f, bgv)) > 0.5f ? 1.0f : 0.0f;
 }
 
+// HAS_MASK = false: nothing is explained yet (the mask is all zero and is not read)
+template <bool HAS_MASK = true>
 __device__ __forceinline__ float keep_px(const float* __restrict__ mask, const float* __restrict__ bg, size_t o) {
-    return __fsub_rn(1.0f, fg_px(mask[o], bg, o));
+    return __fsub_rn(1.0f, fg_px(HAS_MASK ? mask[o] : 0.0f, bg, o));
 }
 
 __device__ __forceinline__ float src_index_nc(float scale, int dst) {   // ATen upsample_bilinear2d, align_corners=False
@@ -61,14 +63,15 @@ __device__ __forceinline__ float src_index_nc(float scale, int dst) {   // ATen 
     return s < 0.f ? 0.f : s;
 }
 
+template <bool HAS_MASK = true>
 __device__ __forceinline__ bool keep_cell(const float* __restrict__ mask, const float* __restrict__ bg, int h, int w, float sh,
                                           float sw, int r, int c) {
     const float fy = src_index_nc(sh, r), fx = src_index_nc(sw, c);
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
     const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float v00 = keep_px(mask, bg, (size_t)y0 * w + x0), v01 = keep_px(mask, bg, (size_t)y0 * w + x1);
-    const float v10 = keep_px(mask, bg, (size_t)y1 * w + x0), v11 = keep_px(mask, bg, (size_t)y1 * w + x1);
+    const float v00 = keep_px<HAS_MASK>(mask, bg, (size_t)y0 * w + x0), v01 = keep_px<HAS_MASK>(mask, bg, (size_t)y0 * w + x1);
+    const float v10 = keep_px<HAS_MASK>(mask, bg, (size_t)y1 * w + x0), v11 = keep_px<HAS_MASK>(mask, bg, (size_t)y1 * w + x1);
     // same operation order as resize_bilinear_kernel (pool.hip), which is pinned against ATen
     const float r0 = fmaf(v01, lx, __fmul_rn(v00, hx));
     const float r1 = fmaf(v11, lx, __fmul_rn(v10, hx));
@@ -309,6 +312,33 @@ __global__ __launch_bounds__(1024) void filter_matches_ragged_kernel(
     filter_body(idx1, idx2, mask, bg, xa, ya, xb, yb, m1, m2, n_out, kept, k, n, cap, h, w, ct, sh, sw);
 }
 
+// keep_mask_kernel for active pairs of different sizes (the per-round re-matching of variant C,
+// evaluation/evalYFCC/coarseAlignFeatMatch.py:158-166): workgroup (x, k) computes cells [256 x, 256 x + 256) of pair b = active[k] with
+// the pair's own geometry and scales and writes them into ROW b of keep (ldB floats per row: the maskB layout of
+// rfx_mutual_nn_ragged_f32); workgroups past the pair's own cell count leave at once.  One thread per active pair stores rt * ct into
+// nB_round[b].  mask == nullptr: nothing explained yet; mask == bg == nullptr: every cell is kept.  A pair with a broken table row, or
+// more cells than a row holds, gets no cell and nB_round 0.
+__global__ __launch_bounds__(256) void keep_mask_ragged_kernel(const float* __restrict__ mask, const float* __restrict__ bg,
+                                                               const long long* __restrict__ moff, const int32_t* __restrict__ geom,
+                                                               const int32_t* __restrict__ active, int ldB, float* __restrict__ keep,
+                                                               int32_t* __restrict__ nB_round) {
+    const int k = blockIdx.y, b = active ? active[k] : k;
+    const int h = geom[b * RG], w = geom[b * RG + 1], rt = geom[b * RG + 2], ct = geom[b * RG + 3];
+    const bool sane = h > 0 && w > 0 && rt > 0 && ct > 0 && (long long)rt * ct <= (long long)ldB;
+    const int cells = sane ? rt * ct : 0;
+    const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (nB_round && cell == 0) nB_round[b] = cells;
+    if (cell >= cells) return;
+    float* out = keep + (size_t)b * ldB + cell;
+    if (!mask && !bg) { *out = 1.0f; return; }
+    // the dense entry point's host-side (float)h / (float)rt: the double quotient of two 24-bit integers rounds to the same float
+    const float sh = (float)((double)h / (double)rt), sw = (float)((double)w / (double)ct);
+    const int r = cell / ct, c = cell % ct;
+    const bool kept = mask ? keep_cell<true>(mask + moff[b], bg ? bg + moff[b] : nullptr, h, w, sh, sw, r, c)
+                           : keep_cell<false>(nullptr, bg + moff[b], h, w, sh, sw, r, c);
+    *out = kept ? 1.0f : 0.0f;
+}
+
 // match: packed per ACTIVE pair, pair k of the round at element offset match_off[k]; mask / bg: pair b at moff[b]
 __global__ __launch_bounds__(256) void accept_partial_ragged_kernel(const float* __restrict__ match,
                                                                     const long long* __restrict__ match_off,
@@ -438,6 +468,23 @@ extern "C" int rfx_filter_matches_ragged_f32(const int64_t* idx1, const int64_t*
         return RFX_E_ARG;
     hipLaunchKernelGGL(filter_matches_ragged_kernel, dim3(n_active), dim3(1024), 0, rfx_stream(stream), idx1, idx2, count, cap, active,
                        mask, bg, moff, geom, xa, ya, offA, xb, yb, offB, match1, match2, n_out, kept);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+// rfx_keep_mask_f32 for active pairs of different sizes, one launch (evaluation/evalYFCC/coarseAlignFeatMatch.py:158-166): mask / bg are
+// the packed buffers of the ragged rounds (pair b's h * w floats at moff[b]; geom[b] = h, w, rt, ct, h8, w8); bg may be null (all
+// foreground), mask may be null (nothing explained yet), both null = every cell kept.  For b = active[k] (k when active is null) the
+// first rt * ct floats of row b of keep (ldB floats per row) receive 0 / 1; the rest of the row and the rows of the other pairs are not
+// written.  nB_round (or null) receives rt * ct at the active pairs' positions only: zeroed by the caller, it makes
+// rfx_mutual_nn_ragged_f32 skip every other pair.  max_cells: the largest rt * ct among the active pairs (sizes the grid).
+extern "C" int rfx_keep_mask_ragged_f32(const float* mask, const float* bg, const long long* moff, const int32_t* geom,
+                                        const int32_t* active, int n_active, int ldB, int max_cells, float* keep, int32_t* nB_round,
+                                        void* stream) {
+    if (!moff || !geom || !keep || n_active <= 0 || ldB <= 0 || max_cells <= 0 || max_cells > ldB) return RFX_E_ARG;
+    if (n_active > 65535) return RFX_E_LIMIT;
+    hipLaunchKernelGGL(keep_mask_ragged_kernel, dim3((max_cells + 255) / 256, n_active), dim3(256), 0, rfx_stream(stream), mask, bg,
+                       moff, geom, active, ldB, keep, nB_round);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

@@ -101,6 +101,7 @@ SIGNATURES = {
     "rfx_multih_accept_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3 + [c_double, c_int] + [c_void_p] * 7
                               + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_longlong] + [c_int] * 5 + [c_void_p]),
     "rfx_filter_matches_ragged_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 15),
+    "rfx_keep_mask_ragged_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3),
     "rfx_multih_accept_ragged_ws_bytes": (c_size_t, [c_int]),
     "rfx_multih_accept_ragged_f32": (c_int, [c_void_p] * 7 + [c_int, c_longlong] + [c_void_p] * 3 + [c_double, c_int]
                                      + [c_void_p] * 9 + [c_longlong] + [c_int] * 3 + [c_void_p]),

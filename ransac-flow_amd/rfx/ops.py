@@ -1661,6 +1661,42 @@ def keep_mask(mask, bg, active, rt, ct, n=None, hw=None, device=None):
     return keep
 
 
+def keep_mask_ragged(mask, bg, moff, geom, active, ldB, max_cells, keep=None, nB_round=None):
+    """keep_mask for active pairs of DIFFERENT sizes (rfx_keep_mask_ragged_f32, one launch): ``mask`` / ``bg`` are the packed 1-D
+    float32 buffers of the ragged rounds (pair b's h*w values at element ``moff[b]`` ((B,) int64), ``geom`` (B,6) int32 = h, w, rt, ct,
+    h8, w8 per pair); ``bg`` None = all foreground, ``mask`` None = nothing explained yet, both None = every cell kept.  ``active``:
+    (a,) int32 device tensor or None (all pairs).  -> ``keep`` (B, ldB) float32: row b of an ACTIVE pair holds its 0/1 keep map in
+    its first rt*ct columns (what mutual_nn_ragged takes as maskB); everything else is left as it was (a new tensor: zero).
+    ``nB_round`` ((B,) int32, zeroed by the caller, or None) receives rt*ct at the active pairs' positions: the nB with which
+    mutual_nn_ragged matches the active pairs only.  ``max_cells``: the largest rt*ct among the active pairs (<= ldB)."""
+    m = _dev(mask, "mask") if mask is not None else None
+    bgd = _dev(bg, "bg") if bg is not None else None
+    act = _dev(active, "active", torch.int32) if active is not None else None
+    moff, geom = _dev(moff, "moff", torch.int64), _dev(geom, "geom", torch.int32)
+    B, ldB, max_cells = moff.numel(), int(ldB), int(max_cells)
+    if geom.shape != (B, 6) or B == 0:
+        raise ValueError("geom must be (B,6) and moff hold one offset per pair")
+    if any(t is not None and t.dim() != 1 for t in (m, bgd)) or (m is not None and bgd is not None and m.shape != bgd.shape):
+        raise ValueError("mask / bg of a ragged batch are packed 1-D buffers of one size")
+    if not 0 < max_cells <= ldB:
+        raise ValueError("max_cells = %d must lie in [1, ldB = %d]" % (max_cells, ldB))
+    if keep is None:
+        keep = torch.zeros((B, ldB), dtype=torch.float32, device=moff.device)
+    elif not isinstance(keep, torch.Tensor) or keep.dtype != torch.float32 or tuple(keep.shape) != (B, ldB) or not keep.is_contiguous():
+        raise ValueError("keep must be a contiguous float32 (B, ldB) tensor (written in place)")
+    if nB_round is not None and (not isinstance(nB_round, torch.Tensor) or nB_round.dtype != torch.int32 or nB_round.numel() != B or
+                                 not nB_round.is_contiguous()):
+        raise ValueError("nB_round must be a contiguous int32 (B,) tensor (written in place)")
+    keep = _dev(keep, "keep")
+    nbr = _dev(nB_round, "nB_round", torch.int32) if nB_round is not None else None
+    a = B if act is None else act.numel()
+    if a == 0:
+        raise ValueError("no active pair")
+    _call("rfx_keep_mask_ragged_f32", _one_device(keep, m, bgd, moff, geom, act, nbr), _p(m), _p(bgd), _p(moff), _p(geom), _p(act), a,
+          ldB, max_cells, _p(keep), _p(nbr))
+    return keep
+
+
 class MultiHRecords:
     """The fixed-size per-pair result records of the multi-homography drivers (what
     evaluation/evalHpatch/evaluation.py:254-260 saves per pair), one float32 row per pair so that ONE all_gather moves them:

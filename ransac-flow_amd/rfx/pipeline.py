@@ -157,6 +157,37 @@ def ragged_multih_tables(plan):
     return dict(moff=moff, geom=geom, total=pos)
 
 
+def ragged_candidate_plan(src_sizes, cand_sizes, min_size, scales, mode="min"):
+    """ragged_plan for pairs with K candidate targets each (the YFCC driver's rotations): ``cand_sizes[k][b]`` = (w, h) of candidate k
+    of pair b.  Image index i < nS is pyramid level i of the source, nS + k is candidate k.  Returns ragged_plan's dict with
+    levels[b] / cells[b] of nS + K entries, nB[k][b] (per candidate), ldB over all candidates, cap = max over (b, k) of
+    min(nA[b], nB[k][b]), K, and buckets over ALL images (sources first, then targets by pair and candidate).  With K = 1 every
+    entry but nB (one more list level) equals ragged_plan's.  Pure function of the sizes."""
+    K = len(cand_sizes)
+    plans = [ragged_plan(src_sizes, ts, min_size, scales, mode) for ts in cand_sizes]
+    p0, nS, B = plans[0], plans[0]["nS"], plans[0]["B"]
+    levels = [p0["levels"][b][:nS] + [p["levels"][b][nS] for p in plans] for b in range(B)]
+    cells = [p0["cells"][b][:nS] + [p["cells"][b][nS] for p in plans] for b in range(B)]
+    nB = [p["nB"] for p in plans]
+    buckets = collections.OrderedDict()
+    for lv in levels:
+        for shp in lv:
+            buckets.setdefault(shp, [])
+    for shp in buckets:
+        mem = [(b, i) for b, lv in enumerate(levels) for i, x in enumerate(lv) if x == shp]
+        buckets[shp] = sorted(mem, key=lambda m: (m[1] >= nS, m[0], m[1]))
+    return dict(levels=levels, cells=cells, nA=p0["nA"], nB=nB, offs=p0["offs"], ldA=p0["ldA"], ldB=max(p["ldB"] for p in plans),
+                cap=max(p["cap"] for p in plans), buckets=buckets, nS=nS, B=B, K=K)
+
+
+def ragged_variant_c_tables(plan, chosen):
+    """ragged_multih_tables for a ragged_candidate_plan and the candidate ``chosen[b]`` of every pair: the packed-mask tables of the
+    YFCC driver's rounds (moff, geom = (h, w, rt, ct, h8, w8) of the CHOSEN candidate's resized image, total)."""
+    nS = plan["nS"]
+    pick = lambda key: [plan[key][b][:nS] + [plan[key][b][nS + c]] for b, c in enumerate(chosen)]
+    return ragged_multih_tables(dict(plan, levels=pick("levels"), cells=pick("cells")))
+
+
 def resize_img_dims(w, h, stride, min_size):
     """outil.resizeImg (utils/outil.py:6-19): smaller side -> min_size, each side ROUNDED to a multiple of stride."""
     ratio = min(w / min_size, h / min_size)
@@ -873,7 +904,7 @@ class AlignPipeline:
         return self.pred_flow_mask_lists(self._sampled_features([IsTensor], [flowCoarse]), [featt], [flowCoarse], cycle=True)[0]
 
     def multi_h_variant_c(self, src_u8, tgt_candidates_u8, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None,
-                          want_lists=True, pair_ids=None, draw_epoch=0):
+                          want_lists=True, pair_ids=None, draw_epoch=0, split=None):
         """The driver of evaluation/evalYFCC/evaluation.py:176-292 for a batch of B pairs in lock-step, everything on the device.
 
         ``src_u8`` (B,H,W,3) uint8: the sources; ``tgt_candidates_u8``: K tensors (B,Hk,Wk,3) -- candidate k of every pair (the
@@ -891,7 +922,19 @@ class AlignPipeline:
         target size, or None (all ones).  ``sample_fn(b, n, nbIter)``: explicit draws (parity mode), called per pair in ascending
         order, first for the candidates k = 0..K-1 with >= 4 matches, then per round.  Device draws are keyed by (seed, pair id,
         candidate / round) with their own driver tags.
+        Lists of images -- ``src_u8``: B uint8 (H,W,3) device tensors, ``tgt_candidates_u8``: K lists of B uint8 (Hk_b,Wk_b,3) tensors
+        (YFCC100M images come in arbitrary sizes, and the rotations swap height and width): all sources of one shape and, per
+        candidate, all targets of one shape are stacked and take the dense path unchanged; otherwise the ragged path
+        (_multi_h_variant_c_ragged) -- per pair the results are, bit for bit, the pair's alone.  ``It_bg`` is then K lists (or None)
+        of B per-pair (h,w) tensors at the candidates' resized sizes (None entries = all ones); ``split``: lock-step groups of the
+        rounds as in multi_h_batched (default 1; the dense path runs its shape groups one after the other).  The ragged path fills
+        no ``records`` (their geometry depends on the chosen candidate, known only after the search) and always returns the lists.
         Returns a list of B dicts: H / flowDown8 / matchDown8 lists, mask, nbH, candidate (the chosen k), nbInlier (K counts)."""
+        if isinstance(src_u8, (list, tuple)) or any(isinstance(c, (list, tuple)) for c in tgt_candidates_u8):
+            src_l, cands, It_bg, ragged = self._variant_c_lists(src_u8, tgt_candidates_u8, It_bg, records, want_lists)
+            if ragged:
+                return self._multi_h_variant_c_ragged(src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split)
+            src_u8, tgt_candidates_u8 = src_l, cands
         dev = self.dev
         B, K = src_u8.shape[0], len(tgt_candidates_u8)
         host_draw = sample_fn is not None or self.draw == "host"
@@ -961,6 +1004,192 @@ class AlignPipeline:
 
         rounds.drive_rounds(self, [shape_groups()])
         return st.close(lambda b: masks[b])
+
+    # ---------------------------------------------------------------- the YFCC driver on pairs of different sizes
+    def _variant_c_lists(self, src, cands, It_bg, records, want_lists):
+        """The list inputs of multi_h_variant_c, checked -> (src, cands, It_bg, ragged).  Same shapes throughout (``ragged`` False):
+        everything stacked into the dense driver's tensors.  Otherwise per-pair lists, It_bg as K lists of B entries or None."""
+        dev = self.dev
+        src_l = list(src)
+        cands = [list(c) for c in cands]
+        B, K = len(src_l), len(cands)
+        if B == 0 or K == 0:
+            raise ValueError("one source per pair and at least one list of candidate targets")
+        if any(len(c) != B for c in cands):
+            raise ValueError("every pair needs the same number K of candidates: K lists of B = %d targets each, got lengths %s"
+                             % (B, [len(c) for c in cands]))
+        imgs = src_l + [x for c in cands for x in c]
+        if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 for x in imgs):
+            raise ValueError("sources and candidate targets are uint8 (H,W,3) tensors, one per pair")
+        ragged = len({tuple(x.shape) for x in src_l}) > 1 or any(len({tuple(x.shape) for x in c}) > 1 for c in cands)
+        if It_bg is not None:
+            if len(It_bg) != K or any(g is not None and len(g) != B for g in It_bg):
+                raise ValueError("It_bg: one entry per candidate (K = %d), each None or B = %d per-pair maps" % (K, B))
+            mode = "max" if self.variant == "A" else "min"
+            for k, g in enumerate(It_bg):
+                for b, x in enumerate(g if g is not None else ()):
+                    nw, nh = resize_dims(cands[k][b].shape[1], cands[k][b].shape[0], self.minSize, mode)
+                    if x is not None and tuple(x.shape) != (nh, nw):
+                        raise ValueError("It_bg[%d][%d] of shape %s for a candidate resized to %s" % (k, b, tuple(x.shape), (nh, nw)))
+        if ragged and records is not None:
+            raise ValueError("multi_h_variant_c on pairs of different sizes fills no records: their geometry depends on the chosen "
+                             "candidate, which is known only after the search")
+        if ragged and not want_lists:
+            raise ValueError("multi_h_variant_c on pairs of different sizes has no records to fill, so want_lists=False would return "
+                             "nothing")
+        if any(not x.is_cuda or x.device != imgs[0].device for x in imgs):
+            raise ValueError("sources and candidate targets must live on one HIP device (no CPU fallback)")
+        if ragged:
+            return src_l, cands, It_bg, True
+        if It_bg is not None:                                # per-pair maps -> the dense driver's (B,h,w) tensor per candidate
+            dense_bg = []
+            for g in It_bg:
+                if g is None or isinstance(g, torch.Tensor) or all(x is None for x in g):
+                    dense_bg.append(g if isinstance(g, torch.Tensor) else None)
+                    continue
+                hw = next(tuple(x.shape) for x in g if x is not None)
+                dense_bg.append(torch.stack([torch.ones(hw, device=dev) if x is None else x.to(dev).float() for x in g]))
+            It_bg = dense_bg
+        return torch.stack(src_l), [torch.stack(c) for c in cands], It_bg, False
+
+    def prepare_candidates_device(self, src_list, cands):
+        """prepare_ragged_device for pairs with K candidate targets each (cands[k][b]: uint8 (H,W,3) device tensors): the LANCZOS
+        pyramid and the float conversions run once per input shape and level, whatever pair or candidate an image belongs to.  Returns a
+        ragged prep over a ragged_candidate_plan: bucket_x, IsTensor[b], ItTensor[k][b] (raw, (1,3,h,w))."""
+        mode = "max" if self.variant == "A" else "min"
+        size = lambda x: (x.shape[1], x.shape[0])
+        plan = ragged_candidate_plan([size(x) for x in src_list], [[size(x) for x in c] for c in cands], self.minSize, self.scaleList, mode)
+        nS, mid, B, K = plan["nS"], plan["nS"] // 2, plan["B"], plan["K"]
+        norm, IsT, ItT = {}, [None] * B, [[None] * B for _ in range(K)]
+        groups = collections.OrderedDict()
+        for b, x in enumerate(src_list):
+            groups.setdefault(("src", tuple(x.shape)), []).append((b, None))
+        for k, c in enumerate(cands):
+            for b, x in enumerate(c):
+                groups.setdefault(("tgt", tuple(x.shape)), []).append((b, k))
+        for (kind, _), mem in groups.items():
+            u8 = torch.stack([src_list[b] if k is None else cands[k][b] for b, k in mem])
+            b0, k0 = mem[0]
+            for i in (range(nS) if kind == "src" else [nS + k0]):
+                nh, nw = plan["levels"][b0][i]
+                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid or i >= nS))
+                for j, (b, k) in enumerate(mem):
+                    norm[(b, i if k is None else nS + k)] = nrm[j:j + 1]
+                    if k is not None:
+                        ItT[k][b] = raw[j:j + 1]
+                    elif i == mid:
+                        IsT[b] = raw[j:j + 1]
+        xs = [torch.cat([norm[m] for m in mem], dim=0) for mem in plan["buckets"].values()]
+        return dict(ragged=True, plan=plan, B=B, K=K, bucket_x=xs, IsTensor=IsT, ItTensor=ItT)
+
+    def _features_candidates(self, prep):
+        """_features_ragged for a prep of prepare_candidates_device: ONE grouped trunk pass over all buckets -- the sources' pyramid
+        levels and all B * K candidate targets -- then the normalised features scattered into featA (B,1024,ldA) and featB
+        (K,B,1024,ldB).  The targets' tables are packed candidate after candidate, pair after pair: nB_dev / offB are (K,B)."""
+        plan, B, K, dev = prep["plan"], prep["B"], prep["K"], self.dev
+        nS, ldA, ldB = plan["nS"], plan["ldA"], plan["ldB"]
+        featA = torch.zeros((B, 1024, ldA), dtype=torch.float32, device=dev)
+        featB = torch.zeros((K, B, 1024, ldB), dtype=torch.float32, device=dev)
+        fs = self.trunk.forward_group(prep["bucket_x"])
+        offs_host, spans = [], []
+        for mem in plan["buckets"].values():
+            k = sum(1 for m in mem if m[1] < nS)
+            spans.append((k, len(offs_host), len(mem)))
+            offs_host += [b * 1024 * ldA + plan["offs"][b][i] for b, i in mem[:k]] + [((i - nS) * B + b) * 1024 * ldB for b, i in mem[k:]]
+        nB_flat = [n for per_k in plan["nB"] for n in per_k]
+        offA = np.cumsum([0] + plan["nA"][:-1]).tolist()
+        offB = np.cumsum([0] + nB_flat[:-1]).tolist()
+        tab = torch.tensor(offs_host + offA + offB, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        for f, (k, o, n) in zip(fs, spans):
+            if k:
+                ops.l2norm_scatter(f[:k], featA, tab[o:o + k], ldA)
+            if k < n:
+                ops.l2norm_scatter(f[k:], featB, tab[o + k:o + n], ldB)
+        coords = lambda cells: [torch.cat(t) for t in zip(*[cell_coords_cached(r, c, dev) for r, c in cells])]
+        WA, HA = coords([rc for b in range(B) for rc in plan["cells"][b][:nS]])
+        Wt, Ht = coords([plan["cells"][b][nS + k] for k in range(K) for b in range(B)])
+        no = len(offs_host)
+        sizes = torch.tensor(plan["nA"] + nB_flat, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        return dict(ragged=True, featA=featA, featB=featB, ldA=ldA, ldB=ldB, nA=plan["nA"], nB=plan["nB"], cap=plan["cap"],
+                    nA_dev=sizes[:B], nB_dev=sizes[B:].view(K, B), WA=WA, HA=HA, Wt=Wt, Ht=Ht, offA=tab[no:no + B],
+                    offB=tab[no + B:].view(K, B), _refs=(fs, tab))
+
+    def _multi_h_variant_c_ragged(self, src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split):
+        """multi_h_variant_c for pairs of different sizes (src_l[b], cands[k][b]: uint8 (H,W,3) device tensors).
+        *Search*: the source pyramids and all B * K candidate targets through ONE grouped trunk pass (_features_candidates); per
+        candidate index k, for all pairs at once: keep map of the candidate's background (rfx_keep_mask_ragged_f32, mask null) ->
+        masked ragged mutual matching -> match gather -> draws (tag variant_c_select, round k) -> RANSAC search; ONE host sync, the
+        (B,K) inlier-count table.  *Rounds*: rounds.RaggedVariantCGroup on the CHOSEN candidates' features and packed masks
+        (ragged_variant_c_tables) under the lock-step machinery of the other ragged drivers."""
+        dev, B, K = self.dev, len(src_l), len(cands)
+        host_draw = sample_fn is not None or self.draw == "host"
+        degen = self._degenerate_mode(host_draw)
+        prep = self.prepare_candidates_device(src_l, cands)
+        plan, feats = prep["plan"], self._features_candidates(prep)
+        nS, ldB, maxNA = plan["nS"], plan["ldB"], max(plan["nA"])
+        ones = lambda hw: torch.ones(hw[0] * hw[1], dtype=torch.float32, device=dev)
+        flat = lambda x, hw: ones(hw) if x is None else x.to(dev).float().reshape(-1)
+        up64 = lambda v: torch.tensor(v, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+
+        def tables(chosen):
+            tabs = ragged_variant_c_tables(plan, chosen)
+            tab = up64(tabs["moff"] + [v for g in tabs["geom"] for v in g])
+            return tabs, tab[:B], tab[B:].to(torch.int32).view(B, 6)
+
+        ids, ep_sel = self._draw_epoch(pair_ids, "variant_c_select", draw_epoch)
+        all_b = list(range(B))
+        counts = []
+        for k in range(K):
+            keep = None
+            if It_bg is not None and It_bg[k] is not None and any(x is not None for x in It_bg[k]):
+                tabs, moff, geom = tables([k] * B)
+                bg = torch.cat([flat(x, g[:2]) for x, g in zip(It_bg[k], tabs["geom"])])
+                keep = ops.keep_mask_ragged(None, bg, moff, geom, None, ldB, max(plan["nB"][k]))
+            idx1, idx2, n_k = ops.mutual_nn_ragged(feats["featA"], feats["featB"][k], feats["nA_dev"], feats["nB_dev"][k], maxNA,
+                                                   max(plan["nB"][k]), maskB=keep, score_chunk=self.score_chunk, cap=plan["cap"])
+            M1, M2 = ops.gather_matches_ragged(idx1, idx2, n_k, feats["HA"], feats["WA"], feats["offA"], feats["Ht"], feats["Wt"],
+                                               feats["offB"][k])
+            smp = self._round_draws(all_b, n_k, sample_fn, None, ids, ep_sel, k)
+            _, _, res = ops.ransac_h4_batched(M1, M2, n_k, smp, self.tol, degenerate=degen)
+            counts.append(torch.where((res[:, 0] == 0) & (n_k >= 4), res[:, 1], torch.zeros_like(res[:, 1])))
+        table = torch.stack(counts, dim=1).cpu()                          # the ONE sync of the search: (B,K) inlier counts
+        chosen = [int(max(range(K), key=lambda k: (int(table[b, k]), -k))) for b in range(B)]     # first maximum (np.argmax)
+        outs = [dict(H=[], flowDown8=[], matchDown8=[], nbH=0, candidate=chosen[b], nbInlier=table[b].tolist()) for b in range(B)]
+        # the rounds: the chosen candidates' features, sizes and tables as ONE ragged batch
+        tabs, moff, geom = tables(chosen)
+        pick = up64([c * B + b for b, c in enumerate(chosen)])
+        bg = None
+        if It_bg is not None and any(It_bg[c] is not None and It_bg[c][b] is not None for b, c in enumerate(chosen)):
+            bg = torch.cat([flat(None if It_bg[c] is None else It_bg[c][b], g[:2]) for (b, c), g in zip(enumerate(chosen), tabs["geom"])])
+        rf = dict(feats, featB=feats["featB"].view(K * B, 1024, ldB).index_select(0, pick), nB=[plan["nB"][c][b] for b, c in enumerate(chosen)],
+                  nB_dev=feats["nB_dev"].reshape(-1).index_select(0, pick), offB=feats["offB"].reshape(-1).index_select(0, pick))
+        st = rounds.RoundState(self, outs, "variant_c", (), split, sample_fn, None, True, None, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
+        batch = dict(prep=dict(IsTensor=prep["IsTensor"], ItTensor=[prep["ItTensor"][c][b] for b, c in enumerate(chosen)]), feats=rf,
+                     tabs=tabs, idx1=None, idx2=None, cnt=None, bg=bg, moff=moff, geom=geom,
+                     Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev))
+        rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedVariantCGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
+
+        def mask_of(b):
+            o, (h, w) = tabs["moff"][b], tabs["geom"][b][:2]
+            return batch["Mask"][o:o + h * w].view(h, w)
+        return st.close(mask_of)
+
+    def multi_h_variant_c_pairs(self, pairs, angles=(0, 90, 180, 270), maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None,
+                                records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None):
+        """multi_h_variant_c on pairs of PIL images, the candidates being the target turned by ``angles`` (multiples of 90 degrees,
+        counter-clockwise: evaluation/evalYFCC/evaluation.py:189).  Every image is uploaded once; a candidate is torch.rot90 of the
+        uploaded target, byte-identical to PIL's rotate(angle, expand=True) for right angles.  All sources of one size and all targets
+        of one size: the dense path on stacked tensors (``It_bg``: K tensors (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise the
+        ragged path on lists (``It_bg``: K lists of per-pair maps; no records)."""
+        if any(int(a) % 90 for a in angles):
+            raise ValueError("candidate angles are multiples of 90 degrees, got %s" % (tuple(angles),))
+        up = lambda im: torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(self.dev)
+        src, tgt = [up(p[0]) for p in pairs], [up(p[1]) for p in pairs]
+        cands = [[torch.rot90(t, int(a) // 90 % 4, (0, 1)).contiguous() for t in tgt] for a in angles]
+        if len({p[0].size for p in pairs}) == 1 and len({p[1].size for p in pairs}) == 1:
+            src, cands = torch.stack(src), [torch.stack(c) for c in cands]
+        return self.multi_h_variant_c(src, cands, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
+                                      records=records, want_lists=want_lists, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
 
     # ---------------------------------------------------------------- KITTI two-resolution driver (SURVEY 8f1, BASELINE config 5)
     resize_img_dims = staticmethod(resize_img_dims)     # outil.resizeImg's sizes (module level: ragged_kitti_tables uses it too)
@@ -1189,8 +1418,8 @@ class AlignPipeline:
         """coarse() + fine_quickstart() of a prep from prepare / prepare_device or, for pairs of different sizes, prepare_ragged /
         prepare_ragged_device.  A ragged batch gives every pair, bit for bit, what it gives alone (same ``pair_ids`` / draws); it
         runs eagerly (no HIP-graph capture).  multi_h_batched takes ragged preps too (multi_h_pairs), and multi_h_kitti_batched takes
-        lists of images of different sizes (multi_h_kitti_pairs).  Not covered for ragged batches: multi_h_variant_c and the drop-in
-        modules."""
+        lists of images of different sizes (multi_h_kitti_pairs), and so does multi_h_variant_c (multi_h_variant_c_pairs; without
+        records).  Not covered for ragged batches: the drop-in modules."""
         res = self.coarse(prep, feats=feats, samples=samples, pair_ids=pair_ids, draw_epoch=draw_epoch)
         if fine:
             eye = torch.eye(3, device=self.dev)

@@ -7,7 +7,8 @@ flags) -> per-pair outputs and stop rule.  It is a generator that yields a HIP e
 one generator per lock-step group, each under its own stream, and resumes the group whose event is due.  What the drivers differ
 in -- where a round's matches come from, the fine stage, how a pair's outputs are cut out of the round's tensors, when a pair
 stops -- is the group class: DenseGroup (Hpatch), KittiGroup, RaggedGroup (Hpatch, pairs of different sizes), RaggedKittiGroup
-(KITTI, pairs of different sizes), VariantCGroup (one target-shape group of the YFCC driver).  ``split_policy`` decides how many groups a batch is cut into, RoundState holds what the
+(KITTI, pairs of different sizes), VariantCGroup (one target-shape group of the YFCC driver), RaggedVariantCGroup (YFCC, pairs and
+chosen candidates of different sizes).  ``split_policy`` decides how many groups a batch is cut into, RoundState holds what the
 groups of one call share.
 """
 import collections
@@ -326,9 +327,9 @@ class RaggedGroup:
                                  Is=torch.cat([IsT[m] for m in mem]) if len(mem) > 1 else IsT[mem[0]]) for mem in fine.values()]
         self.have_featt = False
 
-    def matches(self, A, active):
-        # the round's layout: fine groups in order, each with its active members; pair k of the active list sits at
-        # match_off[k] of the packed matchability and at off8[k] of the packed /8 maps
+    def round_layout(self, active):
+        """The round's layout: fine groups in order, each with its active members; pair k of the active list sits at match_off[k] of
+        the packed matchability and at off8[k] of the packed /8 maps.  One pinned table goes up."""
         a = len(active)
         kpos = {m: k for k, m in enumerate(active)}
         rg, table, m_off, o8 = [], [0] * (2 * a), 0, 0
@@ -352,6 +353,9 @@ class RaggedGroup:
         self.x0 = len(table)
         table += self.extra_table(rg, kpos, a)
         self.rg, self.table, self.T = rg, table, torch.tensor(table, dtype=torch.int64).pin_memory().to(self.st.pipe.dev, non_blocking=True)
+
+    def matches(self, A, active):
+        self.round_layout(active)
         f = self.feats
         return ops.filter_matches_ragged(self.idx1, self.idx2, self.cnt, A, self.Mask, self.bg, self.moff, self.geom, f["HA"], f["WA"],
                                          self.offA, f["Ht"], f["Wt"], self.offB)
@@ -376,10 +380,16 @@ class RaggedGroup:
         for g in self.fine_groups:
             g["featt"] = torch.cat([ft[m] for m in g["members"]]) if len(g["members"]) > 1 else ft[g["members"][0]]
 
+    grouped_fine = True                  # all fine groups of a round as one chain of grouped launches (where RFX_FINE_GROUPS is on)
+
+    def pred_group(self, Is, featt, flowCoarse):
+        """The fine pass of one fine group's active members (the per-group form)."""
+        return self.st.pipe.pred_flow_mask(Is, featt, flowCoarse)
+
     def fine(self, A, active, Hs, bestH, res, n_dev):
         rg, T, a, gm = self.rg, self.T, len(active), self.gm
         take = lambda ent, t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
-        if ops.fine_groups_enabled():
+        if self.grouped_fine and ops.fine_groups_enabled():
             # fine stage: all fine groups as ONE chain of grouped launches; its packed outputs are in fine-group order, which is the
             # order matches() laid the round's offsets out in -- they go to the accept kernel as they are
             packed = {}
@@ -393,8 +403,8 @@ class RaggedGroup:
             for ent in rg:
                 g = ent["g"]
                 h, w = g["hw"]
-                ent["pm"] = self.st.pipe.pred_flow_mask(take(ent, g["Is"], "sel"), take(ent, g["featt"], "sel"),
-                                                        ops.warp_grid(take(ent, Hs, "kidx"), h, w))
+                ent["pm"] = self.pred_group(take(ent, g["Is"], "sel"), take(ent, g["featt"], "sel"),
+                                            ops.warp_grid(take(ent, Hs, "kidx"), h, w))
             pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
         accept, gain = ops.multih_accept_ragged(pack("match"), T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
                                                 self.st.maskRegionTh, 0, max(gm[m][0] * gm[m][1] for m in active), bestH=bestH,
@@ -422,6 +432,42 @@ class RaggedGroup:
 
     def goes_on(self, b):
         return self.st.nb[b] <= self.st.maxCoarse
+
+
+class RaggedVariantCGroup(RaggedGroup):
+    """Pairs [lo, hi) of a ragged batch of the YFCC driver (pairs -- and chosen candidate targets -- of different sizes): RaggedGroup
+    with the differences VariantCGroup has over DenseGroup.  Every round RE-MATCHES: ONE rfx_keep_mask_ragged_f32 for the active pairs
+    (keep map of the explained-region mask + background, written into each pair's own row, and the round's nB table: rt * ct at the
+    active positions, 0 elsewhere), ONE masked ragged mutual matching that skips the inactive pairs on that table, ONE gather of the
+    active pairs' matches.  The fine stage is the cycle-checked PredFlowMask, once per fine group of active pairs (no grouped chain);
+    its matchability maps are packed in fine-group order for the ragged accept kernel (mode 0).  ``batch``: RaggedGroup's (idx1 /
+    idx2 / cnt None: nothing is cached) with ``feats`` = the CHOSEN candidates' featB / nB / offB and the tables of
+    pipeline.ragged_variant_c_tables."""
+    grouped_fine = False
+
+    def __init__(self, st, batch, lo, hi):
+        super().__init__(st, batch, lo, hi)
+        f, dev = self.feats, st.pipe.dev
+        self.fA, self.fB, self.nA_dev = f["featA"][lo:hi], f["featB"][lo:hi], f["nA_dev"][lo:hi]
+        self.nA, self.nB, self.ldB, self.cap = f["nA"][lo:hi], f["nB"][lo:hi], f["ldB"], f["cap"]
+        self.keep = torch.zeros((hi - lo, self.ldB), dtype=torch.float32, device=dev)
+        self.nB_round = torch.zeros(hi - lo, dtype=torch.int32, device=dev)
+
+    def matches(self, A, active):
+        self.round_layout(active)
+        f = self.feats
+        self.nB_round.zero_()
+        max_nB = max(self.nB[m] for m in active)
+        ops.keep_mask_ragged(self.Mask, self.bg, self.moff, self.geom, A, self.ldB, max_nB, keep=self.keep, nB_round=self.nB_round)
+        idx1, idx2, cnt = ops.mutual_nn_ragged(self.fA, self.fB, self.nA_dev, self.nB_round, max(self.nA[m] for m in active), max_nB,
+                                               maskB=self.keep, score_chunk=self.st.pipe.score_chunk, cap=self.cap)
+        n_dev = _rows(cnt, A)
+        M1, M2 = ops.gather_matches_ragged(_rows(idx1, A), _rows(idx2, A), n_dev, f["HA"], f["WA"], _rows(self.offA, A), f["Ht"], f["Wt"],
+                                           _rows(self.offB, A))
+        return M1, M2, n_dev
+
+    def pred_group(self, Is, featt, flowCoarse):
+        return self.st.pipe.pred_flow_mask_cycle(Is, featt, flowCoarse)
 
 
 class RaggedKittiGroup(RaggedGroup):
