@@ -212,9 +212,11 @@ __global__ __launch_bounds__(256) void merge_multi_h_kernel(const float* __restr
             }
         }
         const float2 f = reinterpret_cast<const float2*>(flow)[(long long)best * HW + p];
+        // torch.clamp: a NaN stays a NaN (fminf / fmaxf would drop it).  A degenerate homography (z' = 0 inside the image) puts
+        // one into its coarse grid, and the reference hands it on to whoever reads the flow
         float2 o;
-        o.x = fminf(fmaxf(f.x, -1.0f), 1.0f);
-        o.y = fminf(fmaxf(f.y, -1.0f), 1.0f);
+        o.x = f.x < -1.0f ? -1.0f : (f.x > 1.0f ? 1.0f : f.x);
+        o.y = f.y < -1.0f ? -1.0f : (f.y > 1.0f ? 1.0f : f.y);
         reinterpret_cast<float2*>(flowG)[p] = o;
         if (matchG) matchG[p] = mbest;
         if (binary) binary[p] = found ? 1 : 0;

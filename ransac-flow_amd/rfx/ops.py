@@ -768,7 +768,8 @@ _LANCZOS_MAX = 64                                # must not grow it for ever (a 
 
 
 def lanczos_resize_u8(img, out_w, out_h):
-    """PIL.Image.resize((out_w, out_h), LANCZOS) for a uint8 (N,H,W,3) device tensor -- bit-identical to Pillow."""
+    """PIL.Image.resize((out_w, out_h), LANCZOS) for a uint8 (N,H,W,C) device tensor, C in 1..4 (3 on the product path; every
+    channel is resampled on its own, as Pillow does for L and RGB) -- bit-identical to Pillow.  Another C is refused (RfxError)."""
     from . import lanczos
     img = _dev(img, "image", torch.uint8)
     N, H, W, C = img.shape
