@@ -46,8 +46,9 @@ const char* rfx_version(void);
  * rfx_conv1x1_split_tile_channels; 14: the ragged forms of the KITTI round kernels, rfx_remove_small_cc_ragged_f32 and
  * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32; 16:
  * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
- * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17:
- * no existing entry point moved, and a binding that knows the new name refuses a library without it).  A binding
+ * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17,
+ * and so were rfx_epe_ws_bytes, rfx_epe_homography_f32 and rfx_epe_flow_f32: no existing entry point moved, and a binding that knows
+ * a new name refuses a library without it).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
 #define RFX_ABI_VERSION 17
 int rfx_abi_version(void);
@@ -404,6 +405,38 @@ int rfx_flow_points_f32(const float* flow, const unsigned char* keep, const unsi
  * RFX_E_ARG: a null pointer, a non-positive K, H or W, wA or hA < 1, flow not 8-byte aligned; RFX_E_LIMIT: H*W > 2^31 - 1. */
 int rfx_sample_points_f32(const float* flow, const float* match, const int32_t* xb, const int32_t* yb, int K, int H, int W, int wA,
                           int hA, float* xa, float* ya, unsigned char* keep, void* stream);
+
+/* The end-point error of an assembled flow, reduced on the device to one float64 sum and one count per map (ADDED under ABI 17, like
+ * rfx_keep_mask_ragged_f32: nothing existing moves).  Both entry points below share the outputs and the reduction:
+ *     sum (N) float64:    the counted pixels' errors added in float64, in an order fixed by the pixel's place in its map;
+ *     count (N) int32:    the number of counted pixels;
+ *     err (N,H,W) or NULL: the per-pixel error, NaN (the quiet NaN 0x7fc00000 / 0x7ff8000000000000) where the pixel is not counted.
+ * Two stream-ordered launches, no floating-point atomics, no workgroup waits on another: a workgroup adds a tile of 1024 consecutive
+ * pixels of ONE map (a thread its four pixels in order, a wavefront by a fixed tree, the four wavefronts in order) and writes the
+ * tile's sum and count to ws; one wavefront per map then adds the map's tile sums in index order.  A pixel that is not counted adds
+ * +0.0.  A map's sum therefore has the same bits run after run, alone or at any position of a batch; a single counted pixel gives its
+ * own error exactly.  ws: rfx_epe_ws_bytes(N,H,W) bytes = one float64 and one int32 per tile, ceil(H*W / 1024) tiles per map (0 for a
+ * non-positive size).
+ *
+ * rfx_epe_homography_f32: evaluation/evalHpatch/getResults.py:83-144 (getGT), :147-156 (epe) and the statements :221-250 that mask
+ * and un-normalise the two maps.  flow (N,Sh,Sw,2) float32, Hinv (N,9) float64 row-major (the inverse of the scaled ground-truth
+ * homography).  Per pixel (i, j): (xw, yw, zw) = Hinv (j, i, 1) in float64, each row as (h0 * j + h1 * i) + h2 without a fused step,
+ * rounded to float32; gx = ((2 * xw) / (zw + 1e-8f)) / (float)(Sw - 1) - 1 in float32 steps, gy with yw and Sh - 1; counted iff
+ * -1 <= gx <= 1 and -1 <= gy <= 1; both maps to pixels by t = v + 1, t = t * (float)(S - 1), t = t / 2 (Sw for x, Sh for y);
+ * err = sqrtf(fmaf(dy, dy, dx * dx)) -- what torch.norm(p=2, dim=1) gives a two-element row on the CPU.  err is float32.
+ *
+ * rfx_epe_flow_f32: evaluation/evalKITTI/getResults.py:221-228.  flow (N,H,W,2) float32 (absolute, in [-1,1]), u, v (N,H,W) float32
+ * (KITTI's (uint16 - 32768) / 64 is exact in float32), valid (N,H,W) bytes, non-zero = counted.
+ * up = ((fx - linspace(-1,1,W)[j]) * (float)(W - 1)) / 2 in float32 steps, vp with H; err = sqrt(dx * dx + dy * dy) in float64 with
+ * dx = (double)up - (double)u.  err is float64.
+ *
+ * RFX_E_ARG: a null pointer other than err, a non-positive N, H or W, Sh or Sw < 2, flow / Hinv / sum / ws / a float64 err not
+ * 8-byte aligned.  RFX_E_LIMIT: N*H*W > 2^31 - 1.  All of these are checked before any HIP call. */
+size_t rfx_epe_ws_bytes(int N, int H, int W);
+int rfx_epe_homography_f32(const float* flow, const double* Hinv, int N, int Sh, int Sw, double* sum, int32_t* count, float* err,
+                           void* ws, void* stream);
+int rfx_epe_flow_f32(const float* flow, const float* u, const float* v, const unsigned char* valid, int N, int H, int W, double* sum,
+                     int32_t* count, double* err, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * All-pairs correlation + mutual nearest neighbours (utils/outil.py:32-45, mutualMatching).

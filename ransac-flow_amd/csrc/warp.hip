@@ -9,6 +9,7 @@
 // the thread so the 4 corner offsets / weights are computed once per pixel.
 #include "common.h"
 #include "group.h"
+#include "linspace.h"
 #include <math.h>
 
 namespace {
@@ -17,13 +18,6 @@ inline int grid_for(long long total, int block) {
     long long g = (total + block - 1) / block;
     const long long cap = 256LL * 32;
     return (int)(g < cap ? g : cap);
-}
-
-// torch.linspace(-1, 1, n)[i] as ATen computes it (symmetric about the midpoint).
-__device__ __forceinline__ float lin(int i, int n) {
-    if (n <= 1) return -1.0f;
-    const float step = 2.0f / (float)(n - 1);
-    return i < n / 2 ? -1.0f + step * (float)i : 1.0f - step * (float)(n - 1 - i);
 }
 
 __device__ __forceinline__ float unnormalize(float g, int size, int align) {
@@ -77,7 +71,7 @@ __device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsi
         const int y = (int)(r % h);
         const int b = (int)(r / h);
         const float* M = Hm + b * 9;
-        const float px = lin(x, w), py = lin(y, h);
+        const float px = rfx_lin(x, w), py = rfx_lin(y, h);
         // (x', y', z') = M (px, py, 1): k-ordered fma chain like a K=3 sgemm
         const float xs = fmaf(1.0f, M[2], fmaf(py, M[1], px * M[0]));
         const float ys = fmaf(1.0f, M[5], fmaf(py, M[4], px * M[3]));
@@ -156,7 +150,7 @@ __device__ __forceinline__ void compose_flow_body(const ComposeFlowArgs& a, cons
             u[c] = hy * (hx * s[(size_t)y0 * wd + x0] + lx * s[(size_t)y0 * wd + x1]) +
                    ly * (hx * s[(size_t)y1 * wd + x0] + lx * s[(size_t)y1 * wd + x1]);
         }
-        float gx = u[0] + lin(x, W), gy = u[1] + lin(y, H);
+        float gx = u[0] + rfx_lin(x, W), gy = u[1] + rfx_lin(y, H);
         if (clampf) {
             gx = fminf(fmaxf(gx, -1.0f), 1.0f);
             gy = fminf(fmaxf(gy, -1.0f), 1.0f);

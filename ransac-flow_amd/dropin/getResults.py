@@ -9,9 +9,11 @@ and return conventions (CPU tensors, ``[]`` sentinels); the arithmetic runs in l
     counts, nbAlign = corr.alignmentError(wB, hB, wA, hA, XA, YA, XB, YB, flow, match, pixelGrid)
     flow, binary = yfcc.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)        # numpy, like the script
     pts1, pts2 = yfcc.matches_from_flow(flow, binary, sizeA, sizeB, angle)                             # numpy float32 / int64
+    aepe = hpatch.epe_from_homography(flow_est, Hinv)                  # a float; Hinv: rfx.assemble.hpatch_gt_homography(...)[1]
+    avg_error = kitti.epe(flow, u, v, valid)                           # a float; u, v, valid as readFlow returns them
 
-Reference: evaluation/evalHpatch/getResults.py:16-80, evaluation/evalCorr/getResults.py:15-38,78-164,
-evaluation/evalKITTI/getResults.py:95-152, evaluation/evalYFCC/getResults.py:53-71,132-190.
+Reference: evaluation/evalHpatch/getResults.py:16-80,83-156,218-250, evaluation/evalCorr/getResults.py:15-38,78-164,
+evaluation/evalKITTI/getResults.py:95-152,221-228, evaluation/evalYFCC/getResults.py:53-71,132-190.
 """
 import os
 import sys
@@ -69,9 +71,9 @@ def _yfcc_matches_from_flow(flowFine, matchBinary, sizeA, sizeB, angle):
 
 
 hpatch = types.SimpleNamespace(getFlow_all=_wrap(_a.hpatch_getFlow_all),
-                               getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse))
+                               getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse), epe_from_homography=_a.hpatch_epe)
 corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse),
                              alignmentError=_a.corr_alignment_error)
 kitti = types.SimpleNamespace(getFlow_all=_wrap(_kitti_getFlow_all),
-                              getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse))
+                              getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse), epe=_a.kitti_epe)
 yfcc = types.SimpleNamespace(getFlow=_yfcc_getFlow, _getFlow=_yfcc__getFlow, matches_from_flow=_yfcc_matches_from_flow)

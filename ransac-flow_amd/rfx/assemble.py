@@ -15,6 +15,9 @@ rfx_nearest_fill_f32, scipy's indices reproduced index for index, with no host t
 What the YFCC and Corr scripts then READ off the assembled maps stays on the device as well: the correspondences of all explained
 pixels (yfcc_matches: rfx_flow_points_f32, evalYFCC/getResults.py:53-71) and the transfer of annotated keypoints
 (corr_alignment_error: rfx_sample_points_f32, evalCorr/getResults.py:15-38; 3 K values cross the bus, not the maps).
+The end-point error the HPatches and KITTI scripts end in is reduced on the device too (hpatch_epe: rfx_epe_homography_f32,
+evalHpatch/getResults.py:83-156,221-250 -- the ground-truth map is formed per pixel from the nine numbers of hpatch_gt_homography;
+kitti_epe: rfx_epe_flow_f32, evalKITTI/getResults.py:221-228); one float64 sum and one count per map cross the bus.
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
@@ -99,6 +102,91 @@ def corr_alignment_error(wB, hB, wA, hA, XA, YA, XB, YB, flow, match2, pixelGrid
         return np.zeros(pixelGrid.shape[1]), nbAlign
     pixelDiff = ((xaH[index] - xa[index]) ** 2 + (yaH[index] - ya[index]) ** 2) ** 0.5
     return np.sum(pixelDiff.reshape((-1, 1)) <= pixelGrid, axis=0), nbAlign
+
+
+def identity_grid(h, w, device="cuda"):
+    """The grid the scripts fall back to when a pair has no saved flow (evalHpatch/getResults.py:191-193,218;
+    evalKITTI/getResults.py:209-214): torch.linspace(-1, 1, w) along x and (-1, 1, h) along y, (1,h,w,2).  ops.warp_grid of the
+    identity homography gives it exactly (x * 1 + y * 0 + 0, divided by 1)."""
+    return ops.warp_grid(torch.eye(3, dtype=torch.float32, device=device)[None], int(h), int(w))
+
+
+def hpatch_gt_homography(H, ref_hw, trg_hw, size):
+    """evalHpatch/getResults.py:107-117 (getGT): the ground-truth homography H (3,3), given for the original images of (h, w) =
+    ref_hw and trg_hw, mapped to size x size images (size: an int, the script's minSize, or (h_scale, w_scale)) -- the product
+    S2 H inv(S1) with the diagonal scale matrices S1 (source) and S2 (target) -- and its inverse.  numpy float64 on the host, the
+    reference's own calls in its order, so the same nine numbers.  -> (H_scale, Hinv)."""
+    h_scale, w_scale = (size, size) if np.ndim(size) == 0 else (size[0], size[1])
+    (h_ref, w_ref), (h_trg, w_trg) = ref_hw, trg_hw
+    S1 = np.array([[w_scale / w_ref, 0, 0], [0, h_scale / h_ref, 0], [0, 0, 1]])
+    S2 = np.array([[w_scale / w_trg, 0, 0], [0, h_scale / h_trg, 0], [0, 0, 1]])
+    H_scale = np.dot(np.dot(S2, np.asarray(H, dtype=np.float64).reshape(3, 3)), np.linalg.inv(S1))
+    return H_scale, np.linalg.inv(H_scale)
+
+
+def _mean(total, count, as_float32):
+    """sum / count per map on the host, after ONE read of both -> a list of Python floats; NaN for a map without a counted pixel
+    (the mean of nothing)."""
+    both = torch.stack((total.reshape(-1), count.reshape(-1).to(torch.float64))).cpu().tolist()    # a count is exact in float64
+    out = []
+    for s, c in zip(*both):
+        m = s / int(c) if c else float("nan")
+        out.append(float(np.float32(m)) if as_float32 else m)
+    return out
+
+
+def hpatch_epe(flow_est, Hinv, size=None, device="cuda"):
+    """evalHpatch/getResults.py:218-250: the average end-point error of flow_est -- the (1,S,S,2) device tensor hpatch_getFlow_all
+    returns, or its [] for a pair without a saved flow, which stands for the identity grid of ``size`` x ``size`` -- against the
+    ground truth Hinv defines (hpatch_gt_homography's second result), over the pixels the ground truth keeps inside [-1,1]^2.  The
+    map stays on the device (ops.epe_homography); a sum and a count come back.  -> float32(sum / count) as a Python float, NaN when
+    no pixel is inside.  A batch -- flow_est (N,S,S,2) with Hinv (N,3,3) -- gives a list of N."""
+    h = np.asarray(Hinv.cpu() if torch.is_tensor(Hinv) else Hinv, dtype=np.float64)
+    batch = h.ndim == 3
+    h = h.reshape(-1, 9)
+    if not torch.is_tensor(flow_est) and len(flow_est) == 0:
+        if size is None:
+            raise ValueError("hpatch_epe: a pair without a saved flow needs size (the identity grid's)")
+        sh, sw = (size, size) if np.ndim(size) == 0 else (size[0], size[1])
+        flow_est = identity_grid(sh, sw, device).expand(len(h), -1, -1, -1)
+    dev = flow_est.device if torch.is_tensor(flow_est) and flow_est.is_cuda else device
+    f = _to_dev(flow_est, dev)
+    f = f[None] if f.dim() == 3 else f
+    total, count = ops.epe_homography(f, torch.from_numpy(h).to(f.device))
+    out = _mean(total, count, True)
+    return out if batch else out[0]
+
+
+def _exact_f32(a, name):
+    """A ground-truth array or tensor as a float32 tensor, refused if that changes a value (KITTI's (uint16 - 32768) / 64 never
+    does)."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
+    t32 = t.to(torch.float32)
+    if t.dtype != torch.float32 and not torch.equal(t32.to(torch.float64), t.to(torch.float64)):
+        raise ValueError("kitti_epe: %s has values that float32 does not hold exactly" % name)
+    return t32
+
+
+def kitti_epe(flowGlobal, u, v, valid, device="cuda"):
+    """evalKITTI/getResults.py:221-228: the average end-point error of the assembled flow -- the (1,H,W,2) device tensor
+    assemble_kitti / kitti_getFlow_all return, or [] for a pair without prediction (the identity grid) -- against the ground truth
+    u, v (H,W) of readFlow (:17-24; arrays or tensors whose values float32 holds exactly: anything else is refused) over the pixels with
+    valid set.  The flow stays on the device (ops.epe_flow); u, v, valid go up, a sum and a count come back.  -> sum / count in
+    float64 as a Python float, NaN when nothing is valid.  A batch -- (N,H,W,2) with (N,H,W) arrays -- gives a list of N."""
+    uh, vh = _exact_f32(u, "u"), _exact_f32(v, "v")                    # refused here, before the flow is touched
+    batch = uh.dim() == 3
+    H, W = int(uh.shape[-2]), int(uh.shape[-1])
+    if not torch.is_tensor(flowGlobal) and len(flowGlobal) == 0:
+        flowGlobal = identity_grid(H, W, device).expand(uh.shape[0] if batch else 1, -1, -1, -1)
+    dev = flowGlobal.device if torch.is_tensor(flowGlobal) and flowGlobal.is_cuda else device
+    f = _to_dev(flowGlobal, dev)
+    f = f[None] if f.dim() == 3 else f
+    m = valid if torch.is_tensor(valid) else torch.from_numpy(np.ascontiguousarray(np.asarray(valid)))
+    m = (m if m.dtype in (torch.bool, torch.uint8) else m != 0).to(dev)
+    shape = (f.shape[0], H, W)
+    total, count = ops.epe_flow(f, uh.to(dev).reshape(shape).contiguous(), vh.to(dev).reshape(shape).contiguous(), m.reshape(shape))
+    out = _mean(total, count, False)
+    return out if batch else out[0]
 
 
 def remove_small_cc(score, cc_th, match_th=0.99):

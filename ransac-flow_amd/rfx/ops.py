@@ -1203,6 +1203,63 @@ def sample_points(flow, match, xb, yb, sizeA):
     return xa, ya, keep
 
 
+def _epe_outputs(name, N, H, W, err_dtype, want_err, *operands):
+    """The shared tail of the two end-point-error ops: outputs, workspace, the call."""
+    dev = _one_device(*operands)
+    total = torch.empty(N, dtype=torch.float64, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    err = torch.empty((N, H, W), dtype=err_dtype, device=dev) if want_err else None
+    ws = torch.empty(_lib.load().rfx_epe_ws_bytes(N, H, W), dtype=torch.uint8, device=dev)
+    _call(name, dev, *[_p(t) for t in operands], N, H, W, _p(total), _p(count), _p(err), _p(ws))
+    return total, count, err
+
+
+def epe_homography(flow, Hinv, want_err=False):
+    """evaluation/evalHpatch/getResults.py:83-156,221-250 on the device (rfx_epe_homography_f32): the end-point error of an estimated
+    correspondence map against the map ONE inverse ground-truth homography defines, over the pixels that homography keeps inside
+    [-1,1]^2.  flow (N,Sh,Sw,2) float32 with Hinv (N,3,3) or (N,9) float64, or a single map (Sh,Sw,2) with Hinv (3,3) or (9,).  No
+    host sync: returns device tensors (sum (N,) float64, count (N,) int32[, err (N,Sh,Sw) float32, NaN outside]) -- 0-dim and (Sh,Sw)
+    for a single map; the average is sum / count.  A map's sum has the same bits alone or anywhere in a batch."""
+    for name, t in (("flow", flow), ("Hinv", Hinv)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    single = flow.dim() == 3
+    n = 1 if single else (flow.shape[0] if flow.dim() == 4 else -1)
+    if flow.dim() not in (3, 4) or flow.shape[-1] != 2 or n < 1 or Hinv.numel() != 9 * n or \
+            tuple(Hinv.shape) not in (((3, 3), (9,)) if single else ((n, 3, 3), (n, 9))):
+        raise ValueError("epe_homography: flow (N,Sh,Sw,2) with Hinv (N,3,3) / (N,9), or (Sh,Sw,2) with (3,3) / (9,), expected, got "
+                         "%s and %s" % (tuple(flow.shape), tuple(Hinv.shape)))
+    Sh, Sw = int(flow.shape[-3]), int(flow.shape[-2])
+    if Sh < 2 or Sw < 2:
+        raise ValueError("epe_homography: maps of %d x %d pixels (the rule divides by size - 1)" % (Sh, Sw))
+    f, h = _dev(flow, "flow"), _dev(Hinv, "Hinv", torch.float64)
+    total, count, err = _epe_outputs("rfx_epe_homography_f32", n, Sh, Sw, torch.float32, want_err, f, h)
+    if single:
+        total, count, err = total[0], count[0], (err[0] if want_err else None)
+    return (total, count, err) if want_err else (total, count)
+
+
+def epe_flow(flow, u, v, valid, want_err=False):
+    """evaluation/evalKITTI/getResults.py:221-228 on the device (rfx_epe_flow_f32): the flow minus the identity grid, scaled to
+    pixels in float32 steps, its float64 distance to the ground truth (u, v) over the pixels with valid set.  flow (N,H,W,2) float32,
+    u, v (N,H,W) float32, valid (N,H,W) bool or uint8 -- or single maps (H,W,2) / (H,W).  No host sync: returns device tensors
+    (sum (N,) float64, count (N,) int32[, err (N,H,W) float64, NaN where not valid]) -- 0-dim and (H,W) for single maps."""
+    for name, t in (("flow", flow), ("u", u), ("v", v), ("valid", valid)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    single = flow.dim() == 3
+    maps = tuple(flow.shape[:-1])
+    if flow.dim() not in (3, 4) or flow.shape[-1] != 2 or min(maps) < 1 or any(tuple(t.shape) != maps for t in (u, v, valid)):
+        raise ValueError("epe_flow: flow (N,H,W,2) / (H,W,2) with u, v, valid (N,H,W) / (H,W) expected, got %s, %s, %s and %s"
+                         % tuple(tuple(t.shape) for t in (flow, u, v, valid)))
+    f, uu, vv, m = _dev(flow, "flow"), _dev(u, "u"), _dev(v, "v"), _mask_bytes(valid, "valid")
+    n, (H, W) = (1 if single else int(f.shape[0])), (int(x) for x in f.shape[-3:-1])
+    total, count, err = _epe_outputs("rfx_epe_flow_f32", n, H, W, torch.float64, want_err, f, uu, vv, m)
+    if single:
+        total, count, err = total[0], count[0], (err[0] if want_err else None)
+    return (total, count, err) if want_err else (total, count)
+
+
 _HOST_KC = None
 
 
