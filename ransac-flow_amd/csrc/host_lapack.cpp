@@ -6,14 +6,13 @@
 // std::threads.  Plain host C++: no HIP, no Python.  Compiled with -ffp-contract=off: the float32 products of the system
 // must round exactly like the reference's elementwise float32 multiplications.
 #include "../../include/rfx_host_api.h"
+#include "host_pool.h"
 
 #include <dlfcn.h>
 
 #include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -106,75 +105,7 @@ inline int64_t solve_one(const float* r, Scratch& S, float* Hf, double* Hd) {
     return info;
 }
 
-// ---------------------------------------------------------------- a small persistent pool: parallel_for over item blocks
-class Pool {
-  public:
-    explicit Pool(int n) { resize(n); }
-    ~Pool() { stop(); }
-    int size() const { return (int)workers_.size() + 1; }
-    void resize(int n) {
-        if (n < 1) n = 1;
-        if (n == size()) return;
-        stop();
-        quit_ = false;
-        for (int i = 0; i < n - 1; ++i) workers_.emplace_back([this] { loop(); });
-    }
-    // fn(begin, end) over [0, total) in blocks of `block`, dealt dynamically; the caller works too and returns when all is done
-    void run(int64_t total, int64_t block, const std::function<void(int64_t, int64_t)>& fn) {
-        if (total <= 0) return;
-        std::lock_guard<std::mutex> serial(run_mutex_);            // one parallel region at a time
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            fn_ = &fn; total_ = total; block_ = block; next_.store(0); pending_ = (int)workers_.size(); ++gen_;
-        }
-        cv_.notify_all();
-        work();
-        std::unique_lock<std::mutex> lk(m_);
-        done_cv_.wait(lk, [this] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-  private:
-    void work() {
-        for (;;) {
-            const int64_t b = next_.fetch_add(block_);
-            if (b >= total_) break;
-            (*fn_)(b, b + block_ < total_ ? b + block_ : total_);
-        }
-    }
-    void loop() {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return quit_ || gen_ != seen; });
-                if (quit_) return;
-                seen = gen_;
-            }
-            work();
-            std::lock_guard<std::mutex> lk(m_);
-            if (--pending_ == 0) done_cv_.notify_one();
-        }
-    }
-    void stop() {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            quit_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : workers_) t.join();
-        workers_.clear();
-    }
-    std::vector<std::thread> workers_;
-    std::mutex m_, run_mutex_;
-    std::condition_variable cv_, done_cv_;
-    const std::function<void(int64_t, int64_t)>* fn_ = nullptr;
-    std::atomic<int64_t> next_{0};
-    int64_t total_ = 0, block_ = 1;
-    int pending_ = 0;
-    uint64_t gen_ = 0;
-    bool quit_ = false;
-};
+using rfxhost::Pool;                 // host_pool.h: a small persistent pool, parallel_for over item blocks
 
 Pool* g_pool = nullptr;
 std::mutex g_pool_mutex;

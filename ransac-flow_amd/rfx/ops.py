@@ -12,6 +12,7 @@ import threading
 import torch
 
 from . import _lib
+from .cache import BoundedCache
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 
@@ -763,8 +764,8 @@ def resize_bilinear(x, size, align_corners=False, out=None):
     return out
 
 
-_LANCZOS_TABLES = collections.OrderedDict()      # (sizes, device) -> coefficient tables, LRU-bounded: a stream of variable-size images
-_LANCZOS_MAX = 64                                # must not grow it for ever (a table set is a few KB)
+_LANCZOS_TABLES = BoundedCache(64)      # (sizes, device) -> coefficient tables, LRU-bounded: a stream of variable-size images must
+                                        # not grow it for ever (a table set is a few KB)
 
 
 def lanczos_resize_u8(img, out_w, out_h):
@@ -776,18 +777,10 @@ def lanczos_resize_u8(img, out_w, out_h):
     p = lanczos.plan(W, H, out_w, out_h)
     if p is None:
         return img.clone()
-    key = (W, H, out_w, out_h, str(img.device))
-    tabs = _LANCZOS_TABLES.get(key)
-    if tabs is None:
-        tabs = {k: torch.from_numpy(p[k]).to(img.device) for k in ("bounds_h", "kk_h", "bounds_v", "kk_v")}
-        _LANCZOS_TABLES[key] = tabs
-        while len(_LANCZOS_TABLES) > _LANCZOS_MAX:
-            # the evicted tensors stay alive for as long as a kernel that reads them is queued (stream-ordered allocator); a captured
-            # HIP graph that baked their addresses in holds its own references (trunk_pass.graphed keeps `prep` in the cache entry)
-            _LANCZOS_TABLES.popitem(last=False)
-    else:
-        _LANCZOS_TABLES.move_to_end(key)
-    lib = _lib.load()
+    # evicted tables stay alive for as long as a kernel that reads them is queued (stream-ordered allocator); a captured HIP graph
+    # that baked their addresses in holds them by lease (trunk_pass.graphed)
+    tabs = _LANCZOS_TABLES.get((W, H, out_w, out_h, str(img.device)),
+                               lambda: {k: torch.from_numpy(p[k]).to(img.device) for k in ("bounds_h", "kk_h", "bounds_v", "kk_v")})
     cur, curH = img, H
     if p["need_h"]:
         tmp = torch.empty((N, p["rows_h"], out_w, C), dtype=torch.uint8, device=img.device)
@@ -1541,23 +1534,40 @@ def ransac_h4_batched(match1, match2, n, samples, tol, degenerate="device", info
 
 # ---- the exact mode's search, split at its one host wait so that a caller can put other work between the halves -------------
 
-_PINNED = {}           # (device index, stream) -> dict(off, xy, H): pinned exchange buffers of the exact mode, LRU-bounded
+def _alloc_exchange(n_off, rows):
+    """One set of pinned exchange buffers of the exact mode: off (n_off) int32, xy (rows,16) f32, H (rows,9) f32 -- written by the
+    gather kernel / read by the patch kernel in place (device-visible, coherent memory)."""
+    return dict(off=torch.zeros(n_off, dtype=torch.int32).pin_memory(), xy=torch.empty((rows, 16), dtype=torch.float32).pin_memory(),
+                H=torch.empty((rows, 9), dtype=torch.float32).pin_memory())
 
 
-def _exact_buffers(dev, B, rows):
-    """Pinned host buffers of one (device, stream): off (B+1) int32, xy (rows,16) f32, H (rows,9) f32 -- written by the gather kernels /
-    read by the patch kernel in place (device-visible, coherent memory), grown on demand, at most 8 sets kept."""
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    ent = _PINNED.pop(key, None)
-    if ent is None or ent["off"].numel() < B + 1 or ent["xy"].shape[0] < rows:
-        rows = max(rows, ent["xy"].shape[0] if ent is not None else 0)
-        nb = max(B + 1, ent["off"].numel() if ent is not None else 0)
-        ent = dict(off=torch.zeros(nb, dtype=torch.int32).pin_memory(), xy=torch.empty((rows, 16), dtype=torch.float32).pin_memory(),
-                   H=torch.empty((rows, 9), dtype=torch.float32).pin_memory())
-    _PINNED[key] = ent                       # most recently used last
-    while len(_PINNED) > 8:
-        _PINNED.pop(next(iter(_PINNED)))
-    return ent
+class _ExchangePool:
+    """The free list of exchange sets.  A search owns the set it took until it gives it back together with an event recorded behind
+    its last launch (rfx_ransac_patch_h_rows reads H asynchronously, and the next owner's host solve writes H): a set is handed out
+    again only once that event has completed, to a taker on any stream.  Beyond MAX_IDLE idle sets the oldest whose event has
+    completed are dropped; a set still being read is never freed."""
+    MAX_IDLE = 8
+
+    def __init__(self):
+        self.lock, self.idle, self.allocations = threading.Lock(), [], 0
+
+    def take(self, n_off, rows):
+        with self.lock:
+            for k, (s, ev) in enumerate(self.idle):
+                if s["off"].shape[0] >= n_off and s["xy"].shape[0] >= rows and ev.query():
+                    del self.idle[k]
+                    return s
+            self.allocations += 1
+        return _alloc_exchange(n_off, rows)
+
+    def give(self, s, event):
+        with self.lock:
+            self.idle.append((s, event))
+            over = self.idle[:-self.MAX_IDLE]
+            self.idle = [e for e in over if not e[1].query()] + self.idle[len(over):]
+
+
+_EXCHANGE = _ExchangePool()
 
 
 class _ExactSearch:
@@ -1567,8 +1577,9 @@ class _ExactSearch:
 def ransac_h4_batched_begin(match1, match2, n, samples, tol):
     """First half of ransac_h4_batched(degenerate="lapack"): stage 1 (pack + DLT with rank flags) and rfx_ransac_degenerate_gather --
     the flagged samples of all pairs, one 64-byte row each, written by the device straight into pinned host memory -- then an event
-    on the launch stream.  Nothing waits here: the caller may enqueue more device work (or run another batch's host work) before
-    ransac_h4_batched_finish."""
+    on the launch stream.  Nothing waits here: the caller may enqueue more device work, run another batch's host work or begin
+    another search, on this stream or another, before ransac_h4_batched_finish: every search owns its exchange buffers, and
+    searches may finish in any order."""
     c = _ExactSearch()
     (match1, match2, n, samples), (c.bestH, c.inl, c.res, c.ws) = _ransac_batched_buffers(match1, match2, n, samples)
     from . import _lapack
@@ -1582,7 +1593,7 @@ def ransac_h4_batched_begin(match1, match2, n, samples, tol):
     c.idx = torch.empty((B, N), dtype=torch.int32, device=dev)
     c.cnt = torch.empty(B, dtype=torch.int32, device=dev)
     c.off = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    c.buf = _exact_buffers(dev, B, min(B * N, max(1 << 16, B * N // 8)))
+    c.buf = _EXCHANGE.take(B + 1, min(B * N, max(1 << 16, B * N // 8)))      # the search's own until finish gives it back
     _exact_gather(c)
     return c
 
@@ -1607,7 +1618,8 @@ def ransac_h4_batched_finish(c, info=None):
     off = c.buf["off"].numpy()
     total = int(off[B])
     if total > c.buf["xy"].shape[0]:                                          # more flagged samples than rows: grow, gather again
-        c.buf = _exact_buffers(c.odev, B, total)
+        _EXCHANGE.give(c.buf, c.event)
+        c.buf = _EXCHANGE.take(B + 1, total)
         _exact_gather(c)
         c.event.synchronize()
         off = c.buf["off"].numpy()
@@ -1622,7 +1634,10 @@ def ransac_h4_batched_finish(c, info=None):
         info["n_solved"] = n_solved
         info["host_ms"] = (time.perf_counter() - t0) * 1e3
     _call("rfx_ransac_h4_batched_stage", c.odev, *c.args, 2)
-    c.gather_args = None
+    c.event = torch.cuda.Event()
+    c.event.record(torch.cuda.current_stream(c.odev))
+    _EXCHANGE.give(c.buf, c.event)
+    c.gather_args = c.buf = None
     return c.bestH, c.inl.bool(), c.res
 
 

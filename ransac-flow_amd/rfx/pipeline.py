@@ -19,6 +19,7 @@ import torch
 import PIL.Image as Image
 
 from . import ops, rounds, trunk_pass
+from .cache import BoundedCache
 from .nets import ResNet50Trunk, FeatureExtractorNet, NetFlowCoarseNet, NetMatchabilityNet
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -47,25 +48,14 @@ def pil_to_tensor(pil):
     return torch.from_numpy(arr.copy()).permute(2, 0, 1).contiguous().float().div(255)
 
 
-_CELL_COORDS = collections.OrderedDict()
-_CELL_COORDS_MAX = 64
+_CELL_COORDS = BoundedCache(64)
 
 
 def cell_coords_cached(n_rows, n_cols, device):
     """cell_coords() memoised per (shape, device): the grids are constants of the map size (a dozen tiny ATen launches per
-    pyramid level and step otherwise).  LRU-bounded (64 shapes: a stream of variable-size pairs must not grow it for ever).
-    Captured HIP graphs (trunk_pass.graphed) bake these tensors' addresses into their kernels: the feature
-    dict a capture returns carries the tensors it read (``_coord_refs``), so an evicted entry stays alive for as long as a graph
-    that replays against it does."""
-    key = (n_rows, n_cols, str(device))
-    v = _CELL_COORDS.get(key)
-    if v is None:
-        v = _CELL_COORDS[key] = cell_coords(n_rows, n_cols, device)
-        while len(_CELL_COORDS) > _CELL_COORDS_MAX:
-            _CELL_COORDS.popitem(last=False)
-    else:
-        _CELL_COORDS.move_to_end(key)
-    return v
+    pyramid level and step otherwise).  LRU-bounded (64 shapes: a stream of variable-size pairs must not grow it for ever); a
+    captured HIP graph that read an entry holds it by lease (trunk_pass.graphed)."""
+    return _CELL_COORDS.get((n_rows, n_cols, str(device)), lambda: cell_coords(n_rows, n_cols, device))
 
 
 def cell_coords(n_rows, n_cols, device):
@@ -260,6 +250,18 @@ class AlignPipeline:
         self.std = torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
         self._capture = trunk_pass.CapturePolicy(self.MAX_GRAPHS)       # which trunk-pass shapes replay a HIP graph
         self._graphs = self._capture.entries
+        self._ids_cache = BoundedCache(16)      # pair-id tuple -> its device tensor (_draw_epoch)
+        self._stream_pools = {}                 # purpose -> the side streams of _side_streams
+
+    def _side_streams(self, purpose, n, exact=False):
+        """``n`` pipeline-owned side streams for ``purpose``, the same ones call after call.  A pool grows on demand; with
+        ``exact`` one of another size is rebuilt."""
+        pool = self._stream_pools.setdefault(purpose, [])
+        if exact and len(pool) != n:
+            del pool[:]
+        while len(pool) < n:
+            pool.append(torch.cuda.Stream(device=self.dev))
+        return pool[:n]
 
     def _degenerate_mode(self, host_draw):
         if self.degenerate == "auto":
@@ -293,12 +295,7 @@ class AlignPipeline:
             self._draw_calls += 1
             return None, self._draw_calls
         key = tuple(int(i) for i in pair_ids)
-        cache = self.__dict__.setdefault("_ids_cache", {})
-        ids = cache.get(key)
-        if ids is None:
-            if len(cache) >= 16:
-                cache.pop(next(iter(cache)))
-            ids = cache[key] = torch.tensor(key, dtype=torch.int32).pin_memory().to(self.dev, non_blocking=True)
+        ids = self._ids_cache.get(key, lambda: torch.tensor(key, dtype=torch.int32).pin_memory().to(self.dev, non_blocking=True))
         return ids, int(draw_epoch) * 16 + self.DRAW_TAG[driver]
 
     def _device_draw(self, n_dev, ids=None, epoch=0, rnd=0):

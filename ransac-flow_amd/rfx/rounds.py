@@ -76,15 +76,9 @@ def drive_rounds(pipe, gens):
     stream for k = 0, pipeline-owned side streams after), yields a HIP event whenever it needs the host to see device results,
     and is resumed once that event has completed -- whichever group is ready first.  One generator: the plain sequential loop."""
     main = torch.cuda.current_stream(pipe.dev)
-    if len(gens) > 1:
-        pool = pipe.__dict__.setdefault("_round_streams", [])
-        while len(pool) < len(gens) - 1:
-            pool.append(torch.cuda.Stream(device=pipe.dev))
-        streams = [main] + pool[:len(gens) - 1]
-        for s in streams[1:]:
-            s.wait_stream(main)
-    else:
-        streams = [main]
+    streams = [main] + pipe._side_streams("round", max(len(gens) - 1, 0))
+    for s in streams[1:]:
+        s.wait_stream(main)
     live = [(g, s, None) for g, s in zip(gens, streams)]
     while live:
         # the group whose event has already completed goes first (its host work -- the LAPACK stage, the next round's

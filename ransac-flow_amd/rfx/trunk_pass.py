@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import ops
+from .cache import lease
 
 
 def graph_eligible(B):
@@ -65,12 +66,15 @@ def graphed(pipe, key, inputs, body, what="trunk pass"):
         return body(inputs)
     with torch.cuda.device(pipe.dev):
         if step == "capture":
-            body(inputs)                                # warm-up: lazily built state (packed weights ...) must exist
-            torch.cuda.synchronize(pipe.dev)
-            static = [x.clone() for x in inputs]
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                prep, out = body(static)
+            # whatever the captured kernels read from a bounded cache (Lanczos tables, cell coordinates: addresses baked into the
+            # graph) is held by the lease list, which lives and dies with the cache entry
+            with lease() as held:
+                body(inputs)                            # warm-up: lazily built state (packed weights ...) must exist
+                torch.cuda.synchronize(pipe.dev)
+                static = [x.clone() for x in inputs]
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    prep, out = body(static)
             # an empty capture (kernels launched outside the captured stream) would replay stale features for ever:
             # check once that a replay really rewrites the outputs
             out["featA"].zero_()
@@ -78,8 +82,9 @@ def graphed(pipe, key, inputs, body, what="trunk pass"):
             torch.cuda.synchronize(pipe.dev)
             if not bool(out["featA"].abs().sum() > 0):
                 raise RuntimeError("HIP-graph capture of the %s is empty (kernels did not go to the capture stream)" % what)
-            pipe._capture.store(key, (g, static, prep, out))
-        g, static, prep, out = pipe._capture.entries[key]
+            held = list({id(v): v for v in held}.values())      # warm-up and capture read the same values: keep each once
+            pipe._capture.store(key, (g, static, prep, out, held))
+        g, static, prep, out, _ = pipe._capture.entries[key]
         for d, x in zip(static, inputs):
             d.copy_(x)
         g.replay()
@@ -200,11 +205,9 @@ def _levels_grouped(pipe, prep, lay):
         # instances serial on its stream.
         # (side streams inside a chain, shared or one pool per chain, crash the process on ROCm 7.2: chains stay serial)
         chains = [idxs for idxs in balance_chains([x.numel() for x in xs], nch) if idxs]
-        if getattr(pipe, "_chain_streams", None) is None or len(pipe._chain_streams) != nch - 1:
-            pipe._chain_streams = [torch.cuda.Stream(device=pipe.dev) for _ in range(nch - 1)]
         main = torch.cuda.current_stream(pipe.dev)
-        outs = fork_join(main, [(main if k == 0 else pipe._chain_streams[k - 1], functools.partial(chain, idxs, side_streams=False))
-                                for k, idxs in enumerate(chains)])
+        streams = [main] + pipe._side_streams("chain", nch - 1, exact=True)
+        outs = fork_join(main, [(streams[k], functools.partial(chain, idxs, side_streams=False)) for k, idxs in enumerate(chains)])
         fs = [None] * len(xs)
         for idxs, out in zip(chains, outs):
             for i, f in zip(idxs, out):
@@ -224,10 +227,9 @@ def _levels_streamed(pipe, prep, lay, nstream):
     B, tgt = lay.B, prep["tgt"]
     pair = pair_level_with_target([x.shape for x in prep["src"]], tgt.shape)
     main = torch.cuda.current_stream(pipe.dev)
-    if nstream > 1 and (getattr(pipe, "_streams", None) is None or len(pipe._streams) != nstream):
-        # (stream priorities for the largest levels -- the critical path of a small-batch pass -- were measured: 7.7 ->
-        # 9.1-9.2 ms with one or two high-priority queues; all queues stay equal)
-        pipe._streams = [torch.cuda.Stream(device=pipe.dev) for _ in range(nstream)]
+    # (stream priorities for the largest levels -- the critical path of a small-batch pass -- were measured: 7.7 ->
+    # 9.1-9.2 ms with one or two high-priority queues; all queues stay equal)
+    streams = pipe._side_streams("level", nstream, exact=True) if nstream > 1 else [main]
 
     def level(i):
         x = prep["src"][i]
@@ -238,8 +240,7 @@ def _levels_streamed(pipe, prep, lay, nstream):
         _l2norm_level(lay, i, f2[:B])
         return f2[B:]
 
-    outs = fork_join(main, [(pipe._streams[i % nstream] if nstream > 1 else main, functools.partial(level, i))
-                            for i in range(len(lay.dims))])
+    outs = fork_join(main, [(streams[i % len(streams)], functools.partial(level, i)) for i in range(len(lay.dims))])
     ft_raw = None if pair is None else outs[pair]
     if ft_raw is not None and nstream > 1:
         ft_raw.record_stream(main)
@@ -247,14 +248,13 @@ def _levels_streamed(pipe, prep, lay, nstream):
 
 
 def _finish(pipe, prep, lay, ft_raw):
-    """The target's normalised features (from its own trunk pass when no form has run it yet) and the feature dict.  ``_coord_refs``
-    keeps the cell-coordinate tensors a captured graph read alive (pipeline.cell_coords_cached)."""
+    """The target's normalised features (from its own trunk pass when no form has run it yet) and the feature dict."""
     B = lay.B
     ft = ops.l2norm(ft_raw if ft_raw is not None else pipe.trunk(prep["tgt"]))
     rt, ct = ft.shape[2], ft.shape[3]
     Wt, Ht = pipe._cell_coords(rt, ct)
     return dict(featA=lay.featA, featB=ft.view(B, 1024, rt * ct), nA=lay.nA, ldA=lay.ldA, nB=rt * ct, WA=torch.cat(lay.Ws),
-                HA=torch.cat(lay.Hs), Wt=Wt, Ht=Ht, rt=rt, ct=ct, _coord_refs=(lay.Ws, lay.Hs))
+                HA=torch.cat(lay.Hs), Wt=Wt, Ht=Ht, rt=rt, ct=ct)
 
 
 def features_eager(pipe, prep):

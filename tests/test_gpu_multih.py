@@ -217,6 +217,114 @@ def test_graph_from_raw_images_equals_the_eager_calls(dev, monkeypatch):
     assert len(res) == 1
 
 
+def _tensors(v):
+    if isinstance(v, torch.Tensor):
+        return [v]
+    return [t for x in (v.values() if isinstance(v, dict) else v) for t in _tensors(x)]
+
+
+def test_graph_keeps_the_tables_it_read(dev, monkeypatch):
+    """A captured graph bakes in the addresses of the Lanczos tables and cell coordinates it read from the bounded caches; a replay
+    never asks the caches again.  The graph entry's lease list (trunk_pass.graphed) must hold those tensors: alive after both
+    caches are emptied -- asserted BEFORE the replay, so that a missing lease fails here and no graph runs against freed memory --
+    the replay then equals the eager calls bit for bit, and the tensors die with the entry."""
+    import gc
+    import weakref
+    from rfx import lanczos, pipeline
+
+    def cached(cache, key):
+        def missing():
+            raise AssertionError("%r is not in the cache" % (key,))
+        return cache.get(key, missing)
+    ops._LANCZOS_TABLES.clear()             # earlier tests' graphs hold tensors of these shapes too: start from tensors of our own
+    pipeline._CELL_COORDS.clear()
+    pipe = AlignPipeline(dict(trunk=weights.resnet50_trunk_sd(0)), nbScale=3, nbIter=10, tolerance=0.05, minSize=160, scaleR=1.2,
+                         device=dev)
+    raws = [pipe.upload_raw([synth.make_pair(128, 160, seed=s)]) for s in (7, 8)]
+    monkeypatch.setenv("RFX_GRAPH", "0")
+    p = pipe.prepare_device(*raws[1])
+    f = pipe.features(p)
+    ref = [t.clone() for t in (p["IsTensor"], p["ItTensor"], f["featA"], f["featB"])]
+    monkeypatch.setenv("RFX_GRAPH", "1")
+    for _ in range(2):                      # first sighting: eager; second: capture + replay
+        p, f = pipe.prepare_and_features(*raws[0])
+    (key, entry), = pipe._graphs.items()
+    assert key[0] == "raw"
+    held = _tensors(entry[-1])
+    assert held
+    sizes = [pipeline.resize_dims(160, 128, int(160 * sc), "max") for sc in pipe.scaleList] + [pipeline.resize_dims(160, 128, 160, "max")]
+    resized = [(nw, nh) for nw, nh in sizes if lanczos.plan(160, 128, nw, nh) is not None]
+    assert len(resized) == 2                # the two pyramid levels beside scale 1 (scale 1 and the target keep their size)
+    for nw, nh in resized:
+        tabs = cached(ops._LANCZOS_TABLES, (160, 128, nw, nh, str(pipe.dev)))
+        assert sorted(tabs) == ["bounds_h", "bounds_v", "kk_h", "kk_v"]
+        for t in tabs.values():
+            assert any(t is h for h in held)
+    for nw, nh in sizes:
+        for t in cached(pipeline._CELL_COORDS, (nh // 16, nw // 16, str(pipe.dev))):
+            assert any(t is h for h in held)
+    alive = [weakref.ref(t) for t in held]
+    del p, f, entry, held, tabs, t
+    ops._LANCZOS_TABLES.clear()
+    pipeline._CELL_COORDS.clear()
+    gc.collect()
+    assert all(r() is not None for r in alive)
+    p, f = pipe.prepare_and_features(*raws[1])              # only now: the replay
+    assert len(pipe._graphs) == 1
+    for got, want in zip((p["IsTensor"], p["ItTensor"], f["featA"], f["featB"]), ref):
+        assert torch.equal(got, want)
+    del p, f, got
+    pipe._graphs.clear()
+    gc.collect()
+    assert all(r() is None for r in alive)                  # the lease does not leak: it dies with the graph entry
+
+
+def _lattice_search(seed, dev, B=2, N=64):
+    """B pairs with matches on the 4 x 4 cell lattice (restate.get_wh, as the exact-mode tests of test_gpu_kernels.py build theirs),
+    the source a shift of the target by one lattice column or row (collinear stays collinear: rank-7 samples in quantity) with three
+    mismatches; 16 and 13 matches; N index draws each.  -> (match1, match2, n, samples) on the device."""
+    import restate
+    W, Hh = restate.get_wh(4, 4)
+    cells = torch.stack((Hh, W, torch.ones_like(W)), 1)
+    g = torch.Generator().manual_seed(seed)
+    M1, M2, ns, S = torch.zeros((B, 16, 3)), torch.zeros((B, 16, 3)), [], []
+    for b in range(B):
+        n = 16 - 3 * b
+        src = cells.clone()
+        src[:, b % 2] += 2 / 4.0
+        p = torch.randperm(16, generator=g)[:n]
+        M1[b, :n], M2[b, :n] = src[p], cells[p]
+        M1[b, :3] = src[torch.randperm(16, generator=g)[:3]]
+        ns.append(n)
+        S.append(torch.randint(n, (N, 4), generator=g))
+    return M1.to(dev), M2.to(dev), torch.tensor(ns, dtype=torch.int32, device=dev), torch.stack(S).to(dev)
+
+
+def test_exact_searches_may_overlap_on_one_stream(dev, monkeypatch):
+    """Two searches of the exact mode begun on ONE stream before either is finished: each owns its pinned exchange buffers (the second
+    gather used to overwrite the systems of the first), so both equal their own sequential run bit for bit, finished in either
+    order; the sets are recycled afterwards."""
+    monkeypatch.setattr(ops, "_EXCHANGE", ops._ExchangePool())
+    searches = [_lattice_search(1, dev), _lattice_search(2, dev)]
+    refs = []
+    for s in searches:
+        info = {}
+        refs.append(ops.ransac_h4_batched(*s, 0.05, degenerate="lapack", info=info))
+        assert min(info["n_degenerate"]) > 0, info                  # the pinned rows really carry systems
+    torch.cuda.synchronize(dev)
+    assert not all(torch.equal(a, b) for a, b in zip(*refs))
+    for order in ((0, 1), (1, 0)):
+        begun = [ops.ransac_h4_batched_begin(*s, 0.05) for s in searches]
+        assert begun[0].buf is not begun[1].buf
+        got = {k: ops.ransac_h4_batched_finish(begun[k]) for k in order}
+        for k in (0, 1):
+            for g, r, what in zip(got[k], refs[k], ("bestH", "inlier", "res")):
+                assert torch.equal(g, r), (order, k, what)
+    again = ops.ransac_h4_batched(*searches[0], 0.05, degenerate="lapack")
+    assert all(torch.equal(g, r) for g, r in zip(again, refs[0]))
+    assert ops._EXCHANGE.allocations == 2
+
+
 TRUNK_SWITCHES = ("RFX_GRAPH", "RFX_GROUPED", "RFX_GROUP_CHAINS", "RFX_TRUNK_STREAMS")
 # (batch, calls, one environment per run): the launch forms of the trunk pass besides the default small-batch ones
 TRUNK_FORMS = {
