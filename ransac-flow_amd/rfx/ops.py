@@ -1854,6 +1854,19 @@ class MultiHRecordsRagged:
             r.hd2, r.wd2, r.off_d2, r.d2dims = self.hd2[lo:hi], self.wd2[lo:hi], self.off_d2[lo:hi], self.d2dims[lo:hi]
         return r
 
+    @staticmethod
+    def require(records, sizes8, sizes_d2=None):
+        """ValueError unless ``records`` is a MultiHRecordsRagged built from a driver's own size lists: ``sizes8[b]`` = (h8, w8) of
+        pair b's fine pass and -- the KITTI driver -- ``sizes_d2[b]`` = (hd2, wd2) of its half-resolution pass."""
+        ok = isinstance(records, MultiHRecordsRagged) and list(zip(records.h8, records.w8)) == [tuple(s) for s in sizes8]
+        if ok and sizes_d2 is not None:
+            ok = records.hd2 is not None and list(zip(records.hd2, records.wd2)) == [tuple(s) for s in sizes_d2]
+        if not ok:
+            raise ValueError("a ragged batch fills an ops.MultiHRecordsRagged built from its pairs' own sizes: h8_list / w8_list = the /8 "
+                             "sizes of the fine pass %s%s" % ([tuple(s) for s in sizes8], "" if sizes_d2 is None else
+                                                              ", hd2_list / wd2_list = those of the half-resolution pass %s"
+                                                              % ([tuple(s) for s in sizes_d2],)))
+
     def views(self, b):
         """Pair b's (nbH, status, H (max_h,3,3), flowDown8 (max_h,2,h8,w8), matchDown8 (max_h,2,h8,w8)[, flowD2 (max_h,2,hd2,wd2):
         records built with the d2 lists])."""

@@ -10,7 +10,6 @@ hypotheses.  Semantics per pair are the reference's (variant A: ResizeMaxSize, o
 Host-side work that stays on the CPU: PIL LANCZOS pyramid + ToTensor/Normalize.
 ``prepare()`` does it and uploads; everything after runs on the device.
 """
-import collections
 import functools
 import os
 
@@ -18,9 +17,11 @@ import numpy as np
 import torch
 import PIL.Image as Image
 
-from . import ops, rounds, trunk_pass
+from . import ops, ragged, rounds, trunk_pass
 from .cache import BoundedCache
 from .nets import ResNet50Trunk, FeatureExtractorNet, NetFlowCoarseNet, NetMatchabilityNet
+from .ragged import (packed_group_offsets, ragged_candidate_plan, ragged_kitti_tables, ragged_multih_tables,      # noqa: F401
+                     ragged_plan, ragged_variant_c_tables, resize_dims, resize_img_dims)     # importable from here by name too
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -32,15 +33,6 @@ def scale_list(nb_scale, scale_r):
         return [1]
     half = nb_scale // 2 + 1
     return np.linspace(scale_r, 1, half).tolist() + np.linspace(1, 1 / scale_r, half).tolist()[1:]
-
-
-def resize_dims(w, h, min_size, mode, stride=16):
-    """ResizeMaxSize (quick_start/coarseAlignFeatMatch.py:80-90) / ResizeMinSize
-    (evaluation/evalHpatch/coarseAlignFeatMatch.py:90-100)."""
-    f = max if mode == "max" else min
-    ratio = f(w / float(min_size), h / float(min_size))
-    nw, nh = int(round(w / ratio)), int(round(h / ratio))
-    return nw // stride * stride, nh // stride * stride
 
 
 def pil_to_tensor(pil):
@@ -70,144 +62,6 @@ def cell_coords(n_rows, n_cols, device):
     W = r.view(-1, 1).expand(n_rows, n_cols).reshape(-1)
     Hh = c.view(1, -1).expand(n_rows, n_cols).reshape(-1)
     return ((W - 0.5) * 2).to(device), ((Hh - 0.5) * 2).to(device)
-
-
-
-def packed_group_offsets(bhw_list):
-    """Where the shape groups of a grouped fine stage sit in its packed buffers.  ``bhw_list``: one (B, h, w[, h8, w8]) per group, in
-    group order (h8, w8: the /8 map size, default h // 8, w // 8).  Returns dict(off, off8, total, total8, shapes): group g's full-
-    resolution maps start at element off[g] (B*h*w elements, one plane per pair), its /8 maps at off8[g] (B*h8*w8; the two-channel
-    /8 flow at 2 * off8[g]); total / total8 are the buffer sizes.  Pure Python: no device involved."""
-    off, off8, shapes, t, t8 = [], [], [], 0, 0
-    for e in bhw_list:
-        B, h, w = int(e[0]), int(e[1]), int(e[2])
-        h8, w8 = (int(e[3]), int(e[4])) if len(e) > 3 else (h // 8, w // 8)
-        if B <= 0 or h <= 0 or w <= 0 or h8 <= 0 or w8 <= 0:
-            raise ValueError("packed_group_offsets: empty group %r" % (tuple(e),))
-        off.append(t)
-        off8.append(t8)
-        shapes.append((B, h, w, h8, w8))
-        t += B * h * w
-        t8 += B * h8 * w8
-    return dict(off=off, off8=off8, total=t, total8=t8, shapes=shapes)
-
-
-def ragged_plan(src_sizes, tgt_sizes, min_size, scales, mode="max"):
-    """Bucket / offset plan of a ragged batch: pair b's source of size src_sizes[b] = (w, h) gives len(scales) pyramid levels and its
-    target of size tgt_sizes[b] one more image, each resized by resize_dims exactly as the one-pair path does (multiples of 16).
-    Images of EQUAL shape -- any level, any pair, sources and targets alike -- form one bucket: one dense problem of the grouped trunk
-    pass.  Level index len(scales) stands for the target.  Pure function of the sizes (no tensors).
-    Returns dict(levels[b][i] = (h, w) of image i of pair b, cells[b][i] = (h // 16, w // 16), nA[b], nB[b], offs[b][i] = column
-    of level i in pair b's (C, nA) block, ldA / ldB = the largest nA / nB padded to a multiple of 4, cap = max_b min(nA, nB),
-    buckets = {(h, w): [(b, i), ...]} in order of first appearance, members ordered sources first (by pair, level), then targets)."""
-    nS = len(scales)
-    levels, cells, nA, nB, offs = [], [], [], [], []
-    for (sw, sh), (tw, th) in zip(src_sizes, tgt_sizes):
-        lv = []
-        for sc in scales:
-            nw, nh = resize_dims(sw, sh, int(min_size * sc), mode)
-            lv.append((nh, nw))
-        nw, nh = resize_dims(tw, th, min_size, mode)
-        lv.append((nh, nw))
-        cl = [(h // 16, w // 16) for h, w in lv]
-        o, off = [], 0
-        for r, c in cl[:nS]:
-            o.append(off)
-            off += r * c
-        levels.append(lv)
-        cells.append(cl)
-        offs.append(o)
-        nA.append(off)
-        nB.append(cl[nS][0] * cl[nS][1])
-    buckets = collections.OrderedDict()
-    for b, lv in enumerate(levels):
-        for i, shp in enumerate(lv):
-            buckets.setdefault(shp, [])
-    for shp in buckets:
-        mem = [(b, i) for b, lv in enumerate(levels) for i, x in enumerate(lv) if x == shp]
-        buckets[shp] = sorted(mem, key=lambda m: (m[1] == nS, m[0], m[1]))
-    pad4 = lambda n: (n + 3) // 4 * 4
-    return dict(levels=levels, cells=cells, nA=nA, nB=nB, offs=offs, ldA=pad4(max(nA)), ldB=pad4(max(nB)),
-                cap=max(min(a, b) for a, b in zip(nA, nB)), buckets=buckets, nS=nS, B=len(levels))
-
-
-def ragged_multih_tables(plan):
-    """The packed-mask tables of a ragged batch's multi-homography rounds, a pure function of the plan: pair b's explained-region mask
-    (and background map) are the h*w floats at element ``moff[b]`` of one buffer of ``total`` floats, pair after pair without gaps,
-    and ``geom[b]`` = (h, w, rt, ct, h8, w8): the resized target image (plan["levels"][b][nS]), its feature map
-    (plan["cells"][b][nS]) and the /8 maps of the fine stage.  What rfx_filter_matches_ragged_f32 / rfx_multih_accept_ragged_f32 read."""
-    nS = plan["nS"]
-    moff, geom, pos = [], [], 0
-    for b in range(plan["B"]):
-        h, w = plan["levels"][b][nS]
-        rt, ct = plan["cells"][b][nS]
-        moff.append(pos)
-        geom.append((h, w, rt, ct, h // 8, w // 8))
-        pos += h * w
-    return dict(moff=moff, geom=geom, total=pos)
-
-
-def ragged_candidate_plan(src_sizes, cand_sizes, min_size, scales, mode="min"):
-    """ragged_plan for pairs with K candidate targets each (the YFCC driver's rotations): ``cand_sizes[k][b]`` = (w, h) of candidate k
-    of pair b.  Image index i < nS is pyramid level i of the source, nS + k is candidate k.  Returns ragged_plan's dict with
-    levels[b] / cells[b] of nS + K entries, nB[k][b] (per candidate), ldB over all candidates, cap = max over (b, k) of
-    min(nA[b], nB[k][b]), K, and buckets over ALL images (sources first, then targets by pair and candidate).  With K = 1 every
-    entry but nB (one more list level) equals ragged_plan's.  Pure function of the sizes."""
-    K = len(cand_sizes)
-    plans = [ragged_plan(src_sizes, ts, min_size, scales, mode) for ts in cand_sizes]
-    p0, nS, B = plans[0], plans[0]["nS"], plans[0]["B"]
-    levels = [p0["levels"][b][:nS] + [p["levels"][b][nS] for p in plans] for b in range(B)]
-    cells = [p0["cells"][b][:nS] + [p["cells"][b][nS] for p in plans] for b in range(B)]
-    nB = [p["nB"] for p in plans]
-    buckets = collections.OrderedDict()
-    for lv in levels:
-        for shp in lv:
-            buckets.setdefault(shp, [])
-    for shp in buckets:
-        mem = [(b, i) for b, lv in enumerate(levels) for i, x in enumerate(lv) if x == shp]
-        buckets[shp] = sorted(mem, key=lambda m: (m[1] >= nS, m[0], m[1]))
-    return dict(levels=levels, cells=cells, nA=p0["nA"], nB=nB, offs=p0["offs"], ldA=p0["ldA"], ldB=max(p["ldB"] for p in plans),
-                cap=max(p["cap"] for p in plans), buckets=buckets, nS=nS, B=B, K=K)
-
-
-def ragged_variant_c_tables(plan, chosen):
-    """ragged_multih_tables for a ragged_candidate_plan and the candidate ``chosen[b]`` of every pair: the packed-mask tables of the
-    YFCC driver's rounds (moff, geom = (h, w, rt, ct, h8, w8) of the CHOSEN candidate's resized image, total)."""
-    nS = plan["nS"]
-    pick = lambda key: [plan[key][b][:nS] + [plan[key][b][nS + c]] for b, c in enumerate(chosen)]
-    return ragged_multih_tables(dict(plan, levels=pick("levels"), cells=pick("cells")))
-
-
-def resize_img_dims(w, h, stride, min_size):
-    """outil.resizeImg (utils/outil.py:6-19): smaller side -> min_size, each side ROUNDED to a multiple of stride."""
-    ratio = min(w / min_size, h / min_size)
-    return int(round(w / ratio / stride) * stride), int(round(h / ratio / stride) * stride)
-
-
-def ragged_kitti_tables(plan, tgt_sizes, fineSize):
-    """The tables of a ragged batch's KITTI rounds, a pure function of the plan, the targets' ORIGINAL sizes ``tgt_sizes[b]`` = (w, h)
-    and ``fineSize``: per pair org[b] = (h_org, w_org), resize[b] = (h_r, w_r) and half[b] = (h_d2, w_d2) = resize_img_dims at fineSize
-    and fineSize // 2 (stride 8), d2[b] = (h_d2 // 8, w_d2 // 8) = the size of the half-resolution /8 flow.  The explained-region
-    masks (and background maps) live at the ORIGINAL target size: pair b's h_org * w_org floats at ``moff[b]`` of one buffer of
-    ``total`` floats, and geom[b] = (h_org, w_org, rt, ct, h_r // 8, w_r // 8) -- the mask's size, the coarse target feature map
-    (plan["cells"][b][nS]) and the /8 maps of the full-resolution pass: what rfx_filter_matches_ragged_f32 /
-    rfx_multih_accept_ragged_d2_f32 read."""
-    nS = plan["nS"]
-    out = dict(moff=[], geom=[], org=[], resize=[], half=[], d2=[])
-    pos = 0
-    for b, (w_org, h_org) in enumerate(tgt_sizes):
-        w_r, h_r = resize_img_dims(w_org, h_org, 8, fineSize)
-        w_d2, h_d2 = resize_img_dims(w_org, h_org, 8, fineSize // 2)
-        rt, ct = plan["cells"][b][nS]
-        out["moff"].append(pos)
-        out["geom"].append((h_org, w_org, rt, ct, h_r // 8, w_r // 8))
-        out["org"].append((h_org, w_org))
-        out["resize"].append((h_r, w_r))
-        out["half"].append((h_d2, w_d2))
-        out["d2"].append((h_d2 // 8, w_d2 // 8))
-        pos += h_org * w_org
-    out["total"] = pos
-    return out
 
 
 class AlignPipeline:
@@ -323,6 +177,16 @@ class AlignPipeline:
         return dict(src=[norm(s) for s in src], tgt=norm(tgt), IsTensor=torch.stack(IsT).to(self.dev),
                     ItTensor=torch.stack(tgt).to(self.dev), B=len(pairs))
 
+    @staticmethod
+    def _mixed_sizes(pairs):
+        """Pairs of PIL images: do the sources, or the targets, come in more than one size?  (Then the ragged path.)"""
+        return ragged.mixed([p[0].size for p in pairs], [p[1].size for p in pairs])
+
+    def _upload_lists(self, pairs):
+        """Pairs of PIL images -> (sources, targets): per side a list of uint8 (H,W,3) device tensors, every image uploaded once."""
+        up = lambda im: torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(self.dev)
+        return [up(p[0]) for p in pairs], [up(p[1]) for p in pairs]
+
     def upload_raw(self, pairs):
         """Raw uint8 images of a batch -> device (N,H,W,3) tensors (what a decoder would leave in HBM)."""
         src = torch.from_numpy(np.stack([np.asarray(p[0].convert("RGB"), dtype=np.uint8) for p in pairs])).to(self.dev)
@@ -356,9 +220,9 @@ class AlignPipeline:
 
     # ---------------------------------------------------------------- ragged batches (pairs of different sizes)
     def _ragged_prep(self, plan, norm, IsT, ItT):
-        """norm[(b, i)]: (1,3,h,w) normalised image i of pair b (i = nS: the target) -> the ragged prep: one (N,3,h,w) tensor per
+        """norm[(b, i)]: (1,3,h,w) normalised image i of pair b (i >= nS: the targets) -> the ragged prep: one (N,3,h,w) tensor per
         bucket of the plan (members in the plan's order), the per-pair raw IsTensor / ItTensor (1,3,h,w) of the fine stage."""
-        xs = [torch.cat([norm[m] for m in mem], dim=0) for mem in plan["buckets"].values()]
+        xs = [torch.cat([norm[m] for m in mem], dim=0) for mem in plan["buckets"].values()]         # always a copy: a bucket of its own
         return dict(ragged=True, plan=plan, B=plan["B"], bucket_x=xs, IsTensor=IsT, ItTensor=ItT)
 
     def _ragged_plan(self, src_sizes, tgt_sizes):
@@ -383,70 +247,82 @@ class AlignPipeline:
             ItT.append(t.to(self.dev))
         return self._ragged_prep(plan, norm, IsT, ItT)
 
+    def _prepare_lists_device(self, plan, src_list, cands):
+        """The device pre-processing of B sources and K lists of B targets (uint8 (H,W,3) device tensors) over ``plan`` (image nS + k
+        of a pair = its target k): the LANCZOS pyramid and the float conversions run once per input shape and level -- one
+        rfx_lanczos_pass_u8 / rfx_u8_to_f32_chw chain for all images that share both, whatever pair or list they belong to.
+        Returns (norm[(b, i)], IsTensor[b], ItTensor[k][b]): the normalised images and the raw ones of the fine stage, (1,3,h,w)."""
+        nS, mid, B = plan["nS"], plan["nS"] // 2, plan["B"]
+        norm, IsT, ItT = {}, [None] * B, [[None] * B for _ in cands]
+        imgs = [(x, b, None) for b, x in enumerate(src_list)] + [(x, b, k) for k, c in enumerate(cands) for b, x in enumerate(c)]
+        for (is_tgt, _), mem in ragged.by_shape([(k is not None, tuple(x.shape)) for x, _, k in imgs]).items():
+            u8 = torch.stack([imgs[j][0] for j in mem])
+            who = [imgs[j][1:] for j in mem]
+            for i in ([nS + who[0][1]] if is_tgt else range(nS)):
+                nh, nw = plan["levels"][who[0][0]][i]
+                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid or is_tgt))
+                ragged.hand_back(norm, [(b, i if k is None else nS + k) for b, k in who], nrm)
+                if is_tgt:
+                    for j, (b, k) in enumerate(who):
+                        ItT[k][b] = raw[j:j + 1]
+                elif i == mid:
+                    ragged.hand_back(IsT, [b for b, _ in who], raw)
+        return norm, IsT, ItT
+
     def prepare_ragged_device(self, src_list, tgt_list):
-        """prepare_device() for pairs of different sizes: src_list / tgt_list = uint8 (H,W,3) device tensors, one per pair.  The
-        LANCZOS pyramid and the float conversions run per (input shape, output shape) bucket -- one rfx_lanczos_pass_u8 /
-        rfx_u8_to_f32_chw chain for all images that share both -- and equal prepare_ragged() bit for bit."""
+        """prepare_device() for pairs of different sizes: src_list / tgt_list = uint8 (H,W,3) device tensors, one per pair
+        (_prepare_lists_device with one list of targets); equals prepare_ragged() bit for bit."""
         plan = self._ragged_plan([(x.shape[1], x.shape[0]) for x in src_list], [(x.shape[1], x.shape[0]) for x in tgt_list])
-        nS, mid = plan["nS"], plan["nS"] // 2
-        norm, IsT, ItT = {}, [None] * plan["B"], [None] * plan["B"]
-        groups = collections.OrderedDict()
-        for b, x in enumerate(src_list):
-            groups.setdefault(("src", tuple(x.shape)), []).append(b)
-        for b, x in enumerate(tgt_list):
-            groups.setdefault(("tgt", tuple(x.shape)), []).append(b)
-        for (kind, _), bs in groups.items():
-            u8 = torch.stack([(src_list if kind == "src" else tgt_list)[b] for b in bs])
-            lv = range(nS) if kind == "src" else [nS]
-            for i in lv:
-                nh, nw = plan["levels"][bs[0]][i]
-                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD,
-                                         want_raw=(i == mid or i == nS))
-                for k, b in enumerate(bs):
-                    norm[(b, i)] = nrm[k:k + 1]
-                    if i == mid and kind == "src":
-                        IsT[b] = raw[k:k + 1]
-                    elif i == nS:
-                        ItT[b] = raw[k:k + 1]
-        return self._ragged_prep(plan, norm, IsT, ItT)
+        norm, IsT, ItT = self._prepare_lists_device(plan, src_list, [tgt_list])
+        return self._ragged_prep(plan, norm, IsT, ItT[0])
+
+    def prepare_candidates_device(self, src_list, cands):
+        """prepare_ragged_device for pairs with K candidate targets each (cands[k][b]: uint8 (H,W,3) device tensors).  Returns a
+        ragged prep over a ragged_candidate_plan: bucket_x, K, IsTensor[b], ItTensor[k][b] (raw, (1,3,h,w))."""
+        size = lambda x: (x.shape[1], x.shape[0])
+        plan = ragged_candidate_plan([size(x) for x in src_list], [[size(x) for x in c] for c in cands], self.minSize, self.scaleList,
+                                     "max" if self.variant == "A" else "min")
+        return dict(self._ragged_prep(plan, *self._prepare_lists_device(plan, src_list, cands)), K=plan["K"])
 
     def _features_ragged(self, prep):
         """features() of a ragged prep: ONE grouped trunk pass over all buckets (nets.forward_group: one launch per kernel instance
-        and layer for up to RFX_MAX_GROUP buckets), then one rfx_l2norm_nchw_scatter_f32 per bucket and destination (sources into
-        the padded featA (B,1024,ldA), targets into featB (B,1024,ldB)).  Cell coordinates: per pair, the tables of the one-pair
-        path, packed pair after pair (offA / offB = where pair b's begin)."""
-        plan, B, dev = prep["plan"], prep["B"], self.dev
+        and layer for up to RFX_MAX_GROUP buckets) -- the sources' pyramid levels and every target -- then one
+        rfx_l2norm_nchw_scatter_f32 per bucket and destination: sources into the padded featA (B,1024,ldA), target k of pair b into
+        featB (K,B,1024,ldB).  Cell coordinates: per image, the tables of the one-pair path, packed pair after pair for the sources
+        and list after list, pair after pair for the targets (offA / offB = where they begin, nB_dev / offB (K,B)).  A prep of two
+        images per pair (no ``K``) is the K = 1 case with featB / nB / nB_dev / offB of its one list."""
+        plan, B, K, dev = prep["plan"], prep["B"], prep.get("K", 1), self.dev
         nS, ldA, ldB = plan["nS"], plan["ldA"], plan["ldB"]
+        nB = plan["nB"] if "K" in prep else [plan["nB"]]
         featA = torch.zeros((B, 1024, ldA), dtype=torch.float32, device=dev)
-        featB = torch.zeros((B, 1024, ldB), dtype=torch.float32, device=dev)
+        featB = torch.zeros((K, B, 1024, ldB), dtype=torch.float32, device=dev)
         fs = self.trunk.forward_group(prep["bucket_x"])
         # all destination tables in one upload
         offs_host, spans = [], []
         for mem in plan["buckets"].values():
             k = sum(1 for m in mem if m[1] < nS)
-            src = [b * 1024 * ldA + plan["offs"][b][i] for b, i in mem[:k]]
-            tgt = [b * 1024 * ldB for b, _ in mem[k:]]
             spans.append((k, len(offs_host), len(mem)))
-            offs_host += src + tgt
+            offs_host += [b * 1024 * ldA + plan["offs"][b][i] for b, i in mem[:k]] + [((i - nS) * B + b) * 1024 * ldB for b, i in mem[k:]]
+        nB_flat = [n for per_k in nB for n in per_k]
         offA = np.cumsum([0] + plan["nA"][:-1]).tolist()
-        offB = np.cumsum([0] + plan["nB"][:-1]).tolist()
+        offB = np.cumsum([0] + nB_flat[:-1]).tolist()
         tab = torch.tensor(offs_host + offA + offB, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         for f, (k, o, n) in zip(fs, spans):
             if k:
                 ops.l2norm_scatter(f[:k], featA, tab[o:o + k], ldA)
             if k < n:
                 ops.l2norm_scatter(f[k:], featB, tab[o + k:o + n], ldB)
-        WA, HA, Wt, Ht = [], [], [], []
-        for b in range(B):
-            for i, (r, c) in enumerate(plan["cells"][b]):
-                W, Hh = cell_coords_cached(r, c, dev)
-                (WA if i < nS else Wt).append(W)
-                (HA if i < nS else Ht).append(Hh)
+        coords = lambda cells: [torch.cat(t) for t in zip(*[cell_coords_cached(r, c, dev) for r, c in cells])]
+        WA, HA = coords([rc for b in range(B) for rc in plan["cells"][b][:nS]])
+        Wt, Ht = coords([plan["cells"][b][nS + k] for k in range(K) for b in range(B)])
         no = len(offs_host)
-        sizes = torch.tensor(plan["nA"] + plan["nB"], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        return dict(ragged=True, featA=featA, featB=featB, ldA=ldA, ldB=ldB, nA=plan["nA"], nB=plan["nB"], cap=plan["cap"],
-                    nA_dev=sizes[:B], nB_dev=sizes[B:], WA=torch.cat(WA), HA=torch.cat(HA), Wt=torch.cat(Wt), Ht=torch.cat(Ht),
-                    offA=tab[no:no + B], offB=tab[no + B:no + 2 * B], offA_host=offA, offB_host=offB, _refs=(fs, tab))
+        sizes = torch.tensor(plan["nA"] + nB_flat, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        out = dict(ragged=True, featA=featA, featB=featB, ldA=ldA, ldB=ldB, nA=plan["nA"], nB=nB, cap=plan["cap"], nA_dev=sizes[:B],
+                   nB_dev=sizes[B:].view(K, B), WA=WA, HA=HA, Wt=Wt, Ht=Ht, offA=tab[no:no + B], offB=tab[no + B:].view(K, B),
+                   offA_host=offA, offB_host=offB, _refs=(fs, tab))
+        if "K" not in prep:
+            out.update({key: out[key][0] for key in ("featB", "nB", "nB_dev", "offB")})
+        return out
 
     def _mutual_ragged(self, feats, maskB=None):
         mask = None
@@ -468,20 +344,17 @@ class AlignPipeline:
         """fine_quickstart of a ragged prep: the pairs grouped by (source, target) image shape, each group through today's dense
         batch kernels -- all groups as one chain of grouped launches (fine_quickstart_groups) with RFX_FINE_GROUPS on, one chain per
         group otherwise.  Returns one dict per pair, every tensor with a leading batch dimension of 1."""
-        groups = collections.OrderedDict()
-        for b in range(prep["B"]):
-            groups.setdefault((tuple(prep["IsTensor"][b].shape), tuple(prep["ItTensor"][b].shape)), []).append(b)
+        IsT, ItT = prep["IsTensor"], prep["ItTensor"]
+        groups = list(ragged.by_shape([(tuple(s.shape), tuple(t.shape)) for s, t in zip(IsT, ItT)]).values())
         out = [None] * prep["B"]
-        subs = [dict(IsTensor=torch.cat([prep["IsTensor"][b] for b in bs]), ItTensor=torch.cat([prep["ItTensor"][b] for b in bs]))
-                for bs in groups.values()]
-        hs = [Hs[bs] for bs in groups.values()]
+        subs = [dict(IsTensor=torch.cat([IsT[b] for b in bs]), ItTensor=torch.cat([ItT[b] for b in bs])) for bs in groups]
+        hs = [Hs[bs] for bs in groups]
         if ops.fine_groups_enabled():
             fs = self.fine_quickstart_groups(subs, hs)
         else:
             fs = [self.fine_quickstart(sub, h) for sub, h in zip(subs, hs)]
-        for bs, f in zip(groups.values(), fs):
-            for k, b in enumerate(bs):
-                out[b] = {key: v[k:k + 1] for key, v in f.items()}
+        for bs, f in zip(groups, fs):
+            ragged.hand_back(out, bs, f)
         return out
 
     # ---------------------------------------------------------------- coarse stage
@@ -860,39 +733,21 @@ class AlignPipeline:
                                 draw_epoch, split):
         """multi_h_batched for a ragged prep.  One grouped trunk pass (_features_ragged), one ragged mutual matching, then the
         lock-step rounds of rounds.RaggedGroup under the dense driver's coroutine / stream machinery (rounds.drive_rounds, ``split``).
-        The explained-region masks (and background maps) of all pairs live in ONE packed buffer (ragged_multih_tables: offsets and
-        geometry uploaded once), so a round is one filter launch, one draw, one RANSAC search and one accept launch for all active
+        The explained-region masks (and background maps) of all pairs live in ONE packed buffer (ragged_multih_tables, ragged.PackedBatch:
+        offsets and geometry uploaded once), so a round is one filter launch, one draw, one RANSAC search and one accept launch for all active
         pairs of a group whatever their sizes, and one host readback.  Only the fine stage of a round (warp_grid, PredFlowMask)
         runs per group of active pairs that share (source shape, target shape), on the dense kernels."""
         feats = feats or self.features(prep)
-        dev, B, plan = self.dev, prep["B"], prep["plan"]
-        tabs = ragged_multih_tables(plan)
+        B, tabs = prep["B"], ragged_multih_tables(prep["plan"])
         idx1, idx2, cnt = self._mutual_ragged(feats)
         st = rounds.RoundState(self, [dict(H=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "multi_h", rounds.HPATCH_SPLIT, split,
                                sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
-        if records is not None and (not isinstance(records, ops.MultiHRecordsRagged) or
-                                    list(zip(records.h8, records.w8)) != [g[4:6] for g in tabs["geom"]]):
-            raise ValueError("a ragged batch fills an ops.MultiHRecordsRagged built from its pairs' own /8 sizes")
-        tab = torch.tensor(tabs["moff"] + [v for g in tabs["geom"] for v in g], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        bg = None
-        if It_bg is not None:
-            if len(It_bg) != B:
-                raise ValueError("It_bg of a ragged batch: one (h, w) tensor (or None) per pair")
-            parts = []
-            for x, g in zip(It_bg, tabs["geom"]):
-                if x is not None and tuple(x.shape) != g[:2]:
-                    raise ValueError("It_bg entry of shape %s for a target of %s" % (tuple(x.shape), g[:2]))
-                parts.append(torch.ones(g[0] * g[1], dtype=torch.float32, device=dev) if x is None else x.to(dev).float().reshape(-1))
-            bg = torch.cat(parts)
-        batch = dict(prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, bg=bg, tabs=tabs, moff=tab[:B],
-                     geom=tab[B:].to(torch.int32).view(B, 6), Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev),
-                     nbH=torch.zeros(B, dtype=torch.int32, device=dev))
+        if records is not None:
+            ops.MultiHRecordsRagged.require(records, [g[4:6] for g in tabs["geom"]])
+        pb = ragged.PackedBatch(tabs, It_bg, self.dev)
+        batch = dict(pb.fields(), prep=prep, feats=feats, idx1=idx1, idx2=idx2, cnt=cnt)
         rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
-
-        def mask_of(b):
-            o, (h, w) = tabs["moff"][b], tabs["geom"][b][:2]
-            return batch["Mask"][o:o + h * w].view(h, w)
-        return st.close(mask_of, (idx1, idx2, cnt))
+        return st.close(pb.mask_of, (idx1, idx2, cnt))
 
     # ---------------------------------------------------------------- YFCC / Corr driver shape (variant C; VERDICT r4 #4)
     def pred_flow_mask_cycle(self, IsTensor, featt, flowCoarse):
@@ -928,14 +783,12 @@ class AlignPipeline:
         no ``records`` (their geometry depends on the chosen candidate, known only after the search) and always returns the lists.
         Returns a list of B dicts: H / flowDown8 / matchDown8 lists, mask, nbH, candidate (the chosen k), nbInlier (K counts)."""
         if isinstance(src_u8, (list, tuple)) or any(isinstance(c, (list, tuple)) for c in tgt_candidates_u8):
-            src_l, cands, It_bg, ragged = self._variant_c_lists(src_u8, tgt_candidates_u8, It_bg, records, want_lists)
-            if ragged:
+            src_l, cands, It_bg, mixed = self._variant_c_lists(src_u8, tgt_candidates_u8, It_bg, records, want_lists)
+            if mixed:
                 return self._multi_h_variant_c_ragged(src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split)
             src_u8, tgt_candidates_u8 = src_l, cands
         dev = self.dev
         B, K = src_u8.shape[0], len(tgt_candidates_u8)
-        host_draw = sample_fn is not None or self.draw == "host"
-        degen = self._degenerate_mode(host_draw)
         prep = self.prepare_device(src_u8, tgt_candidates_u8[0])
         feats = self.features(prep)
         featA, nA, ldA = feats["featA"], feats["nA"], feats.get("ldA", feats["nA"])
@@ -959,23 +812,14 @@ class AlignPipeline:
             M1, M2 = ops.gather_matches(idx1, idx2, cnt, feats["HA"], feats["WA"], c["Ht"], c["Wt"])
             return M1, M2, cnt
 
-        ids, ep_sel = self._draw_epoch(pair_ids, "variant_c_select", draw_epoch)
-        all_b = list(range(B))
-        counts = []
-        for k, c in enumerate(cand):
+        def matches_of(k):
+            c = cand[k]
             keep = None if c["bg"] is None else ops.keep_mask(None, c["bg"], None, c["rt"], c["ct"])
-            M1, M2, n_k = matches(c, featA, c["featB"], keep, B)
-            smp = self._round_draws(all_b, n_k, sample_fn, None, ids, ep_sel, k)
-            _, _, res = ops.ransac_h4_batched(M1, M2, n_k, smp, self.tol, degenerate=degen)
-            counts.append(torch.where((res[:, 0] == 0) & (n_k >= 4), res[:, 1], torch.zeros_like(res[:, 1])))
-        table = torch.stack(counts, dim=1).cpu()                          # the ONE sync of the search: (B,K) inlier counts
-        chosen = [int(max(range(K), key=lambda k: (int(table[b, k]), -k))) for b in range(B)]     # first maximum (np.argmax)
-        outs = [dict(H=[], flowDown8=[], matchDown8=[], nbH=0, candidate=chosen[b], nbInlier=table[b].tolist()) for b in range(B)]
+            return matches(c, featA, c["featB"], keep, B)
+        chosen, _, outs = self._variant_c_select(K, B, matches_of, sample_fn, pair_ids, draw_epoch)
         if records is not None:
             records.rec[:, 3] = torch.tensor(chosen, dtype=torch.float32).to(dev)
-        groups = {}
-        for b in range(B):
-            groups.setdefault(tuple(cand[chosen[b]]["ItT"].shape[2:]), []).append(b)
+        groups = ragged.by_shape([tuple(cand[c]["ItT"].shape[2:]) for c in chosen])
         # the shape groups one after the other, each as ONE lock-step group of its own (no split, no trace)
         st = rounds.RoundState(self, outs, "variant_c", (), 1, sample_fn, records, want_lists, None, pair_ids, draw_epoch, maskRegionTh,
                                maxCoarse)
@@ -1002,9 +846,29 @@ class AlignPipeline:
         rounds.drive_rounds(self, [shape_groups()])
         return st.close(lambda b: masks[b])
 
+    def _variant_c_select(self, K, B, matches_of, sample_fn, pair_ids, draw_epoch):
+        """The candidate search of the YFCC driver (evaluation/evalYFCC/evaluation.py:191-210) for B pairs and K candidates:
+        ``matches_of(k)`` -> (M1, M2, n_k), the matches of every pair with its candidate k; per candidate the draws (tag
+        variant_c_select, round k), the RANSAC search and nbInlier = the winner's inlier count (0 unless the status is 0 and n >= 4);
+        ONE host sync, the (B,K) count table; the chosen candidate is the first maximum.  Returns (chosen, table, outs): outs[b] = the
+        pair's result dict with ``candidate`` and ``nbInlier`` filled in."""
+        degen = self._degenerate_mode(sample_fn is not None or self.draw == "host")
+        ids, ep_sel = self._draw_epoch(pair_ids, "variant_c_select", draw_epoch)
+        all_b = list(range(B))
+        counts = []
+        for k in range(K):
+            M1, M2, n_k = matches_of(k)
+            smp = self._round_draws(all_b, n_k, sample_fn, None, ids, ep_sel, k)
+            _, _, res = ops.ransac_h4_batched(M1, M2, n_k, smp, self.tol, degenerate=degen)
+            counts.append(torch.where((res[:, 0] == 0) & (n_k >= 4), res[:, 1], torch.zeros_like(res[:, 1])))
+        table = torch.stack(counts, dim=1).cpu()                          # the ONE sync of the search: (B,K) inlier counts
+        chosen = ragged.choose_candidates(table)
+        outs = [dict(H=[], flowDown8=[], matchDown8=[], nbH=0, candidate=chosen[b], nbInlier=table[b].tolist()) for b in range(B)]
+        return chosen, table, outs
+
     # ---------------------------------------------------------------- the YFCC driver on pairs of different sizes
     def _variant_c_lists(self, src, cands, It_bg, records, want_lists):
-        """The list inputs of multi_h_variant_c, checked -> (src, cands, It_bg, ragged).  Same shapes throughout (``ragged`` False):
+        """The list inputs of multi_h_variant_c, checked -> (src, cands, It_bg, mixed).  Same shapes throughout (``mixed`` False):
         everything stacked into the dense driver's tensors.  Otherwise per-pair lists, It_bg as K lists of B entries or None."""
         dev = self.dev
         src_l = list(src)
@@ -1018,7 +882,7 @@ class AlignPipeline:
         imgs = src_l + [x for c in cands for x in c]
         if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 for x in imgs):
             raise ValueError("sources and candidate targets are uint8 (H,W,3) tensors, one per pair")
-        ragged = len({tuple(x.shape) for x in src_l}) > 1 or any(len({tuple(x.shape) for x in c}) > 1 for c in cands)
+        mixed = ragged.mixed(*([tuple(x.shape) for x in lst] for lst in [src_l] + cands))
         if It_bg is not None:
             if len(It_bg) != K or any(g is not None and len(g) != B for g in It_bg):
                 raise ValueError("It_bg: one entry per candidate (K = %d), each None or B = %d per-pair maps" % (K, B))
@@ -1028,15 +892,15 @@ class AlignPipeline:
                     nw, nh = resize_dims(cands[k][b].shape[1], cands[k][b].shape[0], self.minSize, mode)
                     if x is not None and tuple(x.shape) != (nh, nw):
                         raise ValueError("It_bg[%d][%d] of shape %s for a candidate resized to %s" % (k, b, tuple(x.shape), (nh, nw)))
-        if ragged and records is not None:
+        if mixed and records is not None:
             raise ValueError("multi_h_variant_c on pairs of different sizes fills no records: their geometry depends on the chosen "
                              "candidate, which is known only after the search")
-        if ragged and not want_lists:
+        if mixed and not want_lists:
             raise ValueError("multi_h_variant_c on pairs of different sizes has no records to fill, so want_lists=False would return "
                              "nothing")
         if any(not x.is_cuda or x.device != imgs[0].device for x in imgs):
             raise ValueError("sources and candidate targets must live on one HIP device (no CPU fallback)")
-        if ragged:
+        if mixed:
             return src_l, cands, It_bg, True
         if It_bg is not None:                                # per-pair maps -> the dense driver's (B,h,w) tensor per candidate
             dense_bg = []
@@ -1049,127 +913,40 @@ class AlignPipeline:
             It_bg = dense_bg
         return torch.stack(src_l), [torch.stack(c) for c in cands], It_bg, False
 
-    def prepare_candidates_device(self, src_list, cands):
-        """prepare_ragged_device for pairs with K candidate targets each (cands[k][b]: uint8 (H,W,3) device tensors): the LANCZOS
-        pyramid and the float conversions run once per input shape and level, whatever pair or candidate an image belongs to.  Returns a
-        ragged prep over a ragged_candidate_plan: bucket_x, IsTensor[b], ItTensor[k][b] (raw, (1,3,h,w))."""
-        mode = "max" if self.variant == "A" else "min"
-        size = lambda x: (x.shape[1], x.shape[0])
-        plan = ragged_candidate_plan([size(x) for x in src_list], [[size(x) for x in c] for c in cands], self.minSize, self.scaleList, mode)
-        nS, mid, B, K = plan["nS"], plan["nS"] // 2, plan["B"], plan["K"]
-        norm, IsT, ItT = {}, [None] * B, [[None] * B for _ in range(K)]
-        groups = collections.OrderedDict()
-        for b, x in enumerate(src_list):
-            groups.setdefault(("src", tuple(x.shape)), []).append((b, None))
-        for k, c in enumerate(cands):
-            for b, x in enumerate(c):
-                groups.setdefault(("tgt", tuple(x.shape)), []).append((b, k))
-        for (kind, _), mem in groups.items():
-            u8 = torch.stack([src_list[b] if k is None else cands[k][b] for b, k in mem])
-            b0, k0 = mem[0]
-            for i in (range(nS) if kind == "src" else [nS + k0]):
-                nh, nw = plan["levels"][b0][i]
-                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid or i >= nS))
-                for j, (b, k) in enumerate(mem):
-                    norm[(b, i if k is None else nS + k)] = nrm[j:j + 1]
-                    if k is not None:
-                        ItT[k][b] = raw[j:j + 1]
-                    elif i == mid:
-                        IsT[b] = raw[j:j + 1]
-        xs = [torch.cat([norm[m] for m in mem], dim=0) for mem in plan["buckets"].values()]
-        return dict(ragged=True, plan=plan, B=B, K=K, bucket_x=xs, IsTensor=IsT, ItTensor=ItT)
-
-    def _features_candidates(self, prep):
-        """_features_ragged for a prep of prepare_candidates_device: ONE grouped trunk pass over all buckets -- the sources' pyramid
-        levels and all B * K candidate targets -- then the normalised features scattered into featA (B,1024,ldA) and featB
-        (K,B,1024,ldB).  The targets' tables are packed candidate after candidate, pair after pair: nB_dev / offB are (K,B)."""
-        plan, B, K, dev = prep["plan"], prep["B"], prep["K"], self.dev
-        nS, ldA, ldB = plan["nS"], plan["ldA"], plan["ldB"]
-        featA = torch.zeros((B, 1024, ldA), dtype=torch.float32, device=dev)
-        featB = torch.zeros((K, B, 1024, ldB), dtype=torch.float32, device=dev)
-        fs = self.trunk.forward_group(prep["bucket_x"])
-        offs_host, spans = [], []
-        for mem in plan["buckets"].values():
-            k = sum(1 for m in mem if m[1] < nS)
-            spans.append((k, len(offs_host), len(mem)))
-            offs_host += [b * 1024 * ldA + plan["offs"][b][i] for b, i in mem[:k]] + [((i - nS) * B + b) * 1024 * ldB for b, i in mem[k:]]
-        nB_flat = [n for per_k in plan["nB"] for n in per_k]
-        offA = np.cumsum([0] + plan["nA"][:-1]).tolist()
-        offB = np.cumsum([0] + nB_flat[:-1]).tolist()
-        tab = torch.tensor(offs_host + offA + offB, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        for f, (k, o, n) in zip(fs, spans):
-            if k:
-                ops.l2norm_scatter(f[:k], featA, tab[o:o + k], ldA)
-            if k < n:
-                ops.l2norm_scatter(f[k:], featB, tab[o + k:o + n], ldB)
-        coords = lambda cells: [torch.cat(t) for t in zip(*[cell_coords_cached(r, c, dev) for r, c in cells])]
-        WA, HA = coords([rc for b in range(B) for rc in plan["cells"][b][:nS]])
-        Wt, Ht = coords([plan["cells"][b][nS + k] for k in range(K) for b in range(B)])
-        no = len(offs_host)
-        sizes = torch.tensor(plan["nA"] + nB_flat, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        return dict(ragged=True, featA=featA, featB=featB, ldA=ldA, ldB=ldB, nA=plan["nA"], nB=plan["nB"], cap=plan["cap"],
-                    nA_dev=sizes[:B], nB_dev=sizes[B:].view(K, B), WA=WA, HA=HA, Wt=Wt, Ht=Ht, offA=tab[no:no + B],
-                    offB=tab[no + B:].view(K, B), _refs=(fs, tab))
-
     def _multi_h_variant_c_ragged(self, src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split):
         """multi_h_variant_c for pairs of different sizes (src_l[b], cands[k][b]: uint8 (H,W,3) device tensors).
-        *Search*: the source pyramids and all B * K candidate targets through ONE grouped trunk pass (_features_candidates); per
+        *Search*: the source pyramids and all B * K candidate targets through ONE grouped trunk pass (_features_ragged); per
         candidate index k, for all pairs at once: keep map of the candidate's background (rfx_keep_mask_ragged_f32, mask null) ->
         masked ragged mutual matching -> match gather -> draws (tag variant_c_select, round k) -> RANSAC search; ONE host sync, the
         (B,K) inlier-count table.  *Rounds*: rounds.RaggedVariantCGroup on the CHOSEN candidates' features and packed masks
         (ragged_variant_c_tables) under the lock-step machinery of the other ragged drivers."""
         dev, B, K = self.dev, len(src_l), len(cands)
-        host_draw = sample_fn is not None or self.draw == "host"
-        degen = self._degenerate_mode(host_draw)
         prep = self.prepare_candidates_device(src_l, cands)
-        plan, feats = prep["plan"], self._features_candidates(prep)
-        nS, ldB, maxNA = plan["nS"], plan["ldB"], max(plan["nA"])
-        ones = lambda hw: torch.ones(hw[0] * hw[1], dtype=torch.float32, device=dev)
-        flat = lambda x, hw: ones(hw) if x is None else x.to(dev).float().reshape(-1)
-        up64 = lambda v: torch.tensor(v, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        plan, feats = prep["plan"], self.features(prep)
+        ldB, maxNA = plan["ldB"], max(plan["nA"])
 
-        def tables(chosen):
-            tabs = ragged_variant_c_tables(plan, chosen)
-            tab = up64(tabs["moff"] + [v for g in tabs["geom"] for v in g])
-            return tabs, tab[:B], tab[B:].to(torch.int32).view(B, 6)
-
-        ids, ep_sel = self._draw_epoch(pair_ids, "variant_c_select", draw_epoch)
-        all_b = list(range(B))
-        counts = []
-        for k in range(K):
-            keep = None
+        def matches_of(k):
+            keep, max_nB = None, max(plan["nB"][k])
             if It_bg is not None and It_bg[k] is not None and any(x is not None for x in It_bg[k]):
-                tabs, moff, geom = tables([k] * B)
-                bg = torch.cat([flat(x, g[:2]) for x, g in zip(It_bg[k], tabs["geom"])])
-                keep = ops.keep_mask_ragged(None, bg, moff, geom, None, ldB, max(plan["nB"][k]))
-            idx1, idx2, n_k = ops.mutual_nn_ragged(feats["featA"], feats["featB"][k], feats["nA_dev"], feats["nB_dev"][k], maxNA,
-                                                   max(plan["nB"][k]), maskB=keep, score_chunk=self.score_chunk, cap=plan["cap"])
+                pb = ragged.PackedBatch(ragged_variant_c_tables(plan, [k] * B), It_bg[k], dev, masks=False)
+                keep = ops.keep_mask_ragged(None, pb.bg, pb.moff, pb.geom, None, ldB, max_nB)
+            idx1, idx2, n_k = ops.mutual_nn_ragged(feats["featA"], feats["featB"][k], feats["nA_dev"], feats["nB_dev"][k], maxNA, max_nB,
+                                                   maskB=keep, score_chunk=self.score_chunk, cap=plan["cap"])
             M1, M2 = ops.gather_matches_ragged(idx1, idx2, n_k, feats["HA"], feats["WA"], feats["offA"], feats["Ht"], feats["Wt"],
                                                feats["offB"][k])
-            smp = self._round_draws(all_b, n_k, sample_fn, None, ids, ep_sel, k)
-            _, _, res = ops.ransac_h4_batched(M1, M2, n_k, smp, self.tol, degenerate=degen)
-            counts.append(torch.where((res[:, 0] == 0) & (n_k >= 4), res[:, 1], torch.zeros_like(res[:, 1])))
-        table = torch.stack(counts, dim=1).cpu()                          # the ONE sync of the search: (B,K) inlier counts
-        chosen = [int(max(range(K), key=lambda k: (int(table[b, k]), -k))) for b in range(B)]     # first maximum (np.argmax)
-        outs = [dict(H=[], flowDown8=[], matchDown8=[], nbH=0, candidate=chosen[b], nbInlier=table[b].tolist()) for b in range(B)]
+            return M1, M2, n_k
+        chosen, _, outs = self._variant_c_select(K, B, matches_of, sample_fn, pair_ids, draw_epoch)
         # the rounds: the chosen candidates' features, sizes and tables as ONE ragged batch
-        tabs, moff, geom = tables(chosen)
-        pick = up64([c * B + b for b, c in enumerate(chosen)])
-        bg = None
-        if It_bg is not None and any(It_bg[c] is not None and It_bg[c][b] is not None for b, c in enumerate(chosen)):
-            bg = torch.cat([flat(None if It_bg[c] is None else It_bg[c][b], g[:2]) for (b, c), g in zip(enumerate(chosen), tabs["geom"])])
+        pb = ragged.PackedBatch(ragged_variant_c_tables(plan, chosen),
+                                None if It_bg is None else [None if It_bg[c] is None else It_bg[c][b] for b, c in enumerate(chosen)], dev)
+        pick = torch.tensor([c * B + b for b, c in enumerate(chosen)], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         rf = dict(feats, featB=feats["featB"].view(K * B, 1024, ldB).index_select(0, pick), nB=[plan["nB"][c][b] for b, c in enumerate(chosen)],
                   nB_dev=feats["nB_dev"].reshape(-1).index_select(0, pick), offB=feats["offB"].reshape(-1).index_select(0, pick))
         st = rounds.RoundState(self, outs, "variant_c", (), split, sample_fn, None, True, None, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
-        batch = dict(prep=dict(IsTensor=prep["IsTensor"], ItTensor=[prep["ItTensor"][c][b] for b, c in enumerate(chosen)]), feats=rf,
-                     tabs=tabs, idx1=None, idx2=None, cnt=None, bg=bg, moff=moff, geom=geom,
-                     Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev))
+        batch = dict(pb.fields(), prep=dict(IsTensor=prep["IsTensor"], ItTensor=[prep["ItTensor"][c][b] for b, c in enumerate(chosen)]),
+                     feats=rf, idx1=None, idx2=None, cnt=None)
         rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedVariantCGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
-
-        def mask_of(b):
-            o, (h, w) = tabs["moff"][b], tabs["geom"][b][:2]
-            return batch["Mask"][o:o + h * w].view(h, w)
-        return st.close(mask_of)
+        return st.close(pb.mask_of)
 
     def multi_h_variant_c_pairs(self, pairs, angles=(0, 90, 180, 270), maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None,
                                 records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None):
@@ -1180,10 +957,9 @@ class AlignPipeline:
         ragged path on lists (``It_bg``: K lists of per-pair maps; no records)."""
         if any(int(a) % 90 for a in angles):
             raise ValueError("candidate angles are multiples of 90 degrees, got %s" % (tuple(angles),))
-        up = lambda im: torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(self.dev)
-        src, tgt = [up(p[0]) for p in pairs], [up(p[1]) for p in pairs]
+        src, tgt = self._upload_lists(pairs)
         cands = [[torch.rot90(t, int(a) // 90 % 4, (0, 1)).contiguous() for t in tgt] for a in angles]
-        if len({p[0].size for p in pairs}) == 1 and len({p[1].size for p in pairs}) == 1:
+        if not self._mixed_sizes(pairs):
             src, cands = torch.stack(src), [torch.stack(c) for c in cands]
         return self.multi_h_variant_c(src, cands, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
                                       records=records, want_lists=want_lists, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
@@ -1306,7 +1082,7 @@ class AlignPipeline:
             src_l, tgt_l = [one(x) for x in src_u8], [one(x) for x in tgt_u8]
             if len(src_l) != len(tgt_l) or not src_l:
                 raise ValueError("one source and one target per pair")
-            if len({tuple(x.shape) for x in src_l}) > 1 or len({tuple(x.shape) for x in tgt_l}) > 1:
+            if ragged.mixed([tuple(x.shape) for x in src_l], [tuple(x.shape) for x in tgt_l]):
                 return self._multi_h_kitti_batched_ragged(src_l, tgt_l, fineSize, maskRegionTh, cc_th, It_bg, sample_fn, remove_small_cc,
                                                           records, want_lists, trace, pair_ids, draw_epoch, split)
             src_u8, tgt_u8 = torch.stack(src_l), torch.stack(tgt_l)
@@ -1342,70 +1118,40 @@ class AlignPipeline:
         and group ONE filter launch, ONE draw, ONE RANSAC search, ONE small-component filter (rfx_remove_small_cc_ragged_f32) and ONE
         accept launch (rfx_multih_accept_ragged_d2_f32) for all active pairs whatever their sizes, and one host readback; only the
         two PredFlowMask passes run per group of active pairs that share (source original shape, target original shape)."""
-        dev, B = self.dev, len(src_l)
+        B = len(src_l)
         prep = self.prepare_ragged_device(src_l, tgt_l)
         feats = self.features(prep)
         tabs = ragged_kitti_tables(prep["plan"], [(x.shape[1], x.shape[0]) for x in tgt_l], fineSize)
-        if records is not None and (not isinstance(records, ops.MultiHRecordsRagged) or records.hd2 is None or
-                                    list(zip(records.h8, records.w8, records.hd2, records.wd2)) !=
-                                    [g[4:6] + d for g, d in zip(tabs["geom"], tabs["d2"])]):
-            raise ValueError("a ragged KITTI batch fills an ops.MultiHRecordsRagged built from its pairs' own sizes: h8_list / w8_list = "
-                             "the /8 sizes of the full-resolution pass, hd2_list / wd2_list = those of the half-resolution pass "
-                             "(pipeline.ragged_kitti_tables: geom[b][4:6] and d2[b])")
+        if records is not None:
+            ops.MultiHRecordsRagged.require(records, [g[4:6] for g in tabs["geom"]], tabs["d2"])
         # the fine-stage images: sources at their ORIGINAL size, targets at fineSize and fineSize // 2 -- one chain per distinct shape
+        # (image 2 b = the source of pair b, 2 b + 1 its target)
         tensor_s, tensor_resize, tensor_d2 = [None] * B, [None] * B, [None] * B
-        groups = collections.OrderedDict()
-        for b in range(B):
-            groups.setdefault(("src", tuple(src_l[b].shape)), []).append(b)
-            groups.setdefault(("tgt", tuple(tgt_l[b].shape)), []).append(b)
-        for (kind, _), bs in groups.items():
-            u8 = torch.stack([(src_l if kind == "src" else tgt_l)[b] for b in bs])
-            if kind == "src":
-                outs = ((tensor_s, ops.u8_to_f32(u8)[0]),)
-            else:
+        imgs = [x for pair in zip(src_l, tgt_l) for x in pair]
+        for (is_tgt, _), mem in ragged.by_shape([(j % 2, tuple(x.shape)) for j, x in enumerate(imgs)]).items():
+            u8, bs = torch.stack([imgs[j] for j in mem]), [j // 2 for j in mem]
+            if is_tgt:
                 (h_r, w_r), (h_d2, w_d2) = tabs["resize"][bs[0]], tabs["half"][bs[0]]
-                outs = ((tensor_resize, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_r, h_r))[0]),
-                        (tensor_d2, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_d2, h_d2))[0]))
-            for dst, t in outs:
-                for k, b in enumerate(bs):
-                    dst[b] = t[k:k + 1]
+                ragged.hand_back(tensor_resize, bs, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_r, h_r))[0])
+                ragged.hand_back(tensor_d2, bs, ops.u8_to_f32(ops.lanczos_resize_u8(u8, w_d2, h_d2))[0])
+            else:
+                ragged.hand_back(tensor_s, bs, ops.u8_to_f32(u8)[0])
         idx1, idx2, cnt = self._mutual_ragged(feats)
         st = rounds.RoundState(self, [dict(H=[], flowD2=[], flowDown8=[], matchDown8=[]) for _ in range(B)], "kitti", rounds.KITTI_SPLIT,
                                split, sample_fn, records, want_lists, trace, pair_ids, draw_epoch, maskRegionTh,
                                host_filter=remove_small_cc is not None)
-        tab = torch.tensor(tabs["moff"] + [v for g in tabs["geom"] for v in g] + [v for d in tabs["d2"] for v in d],
-                           dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        bg = None
-        if It_bg is not None:
-            if len(It_bg) != B:
-                raise ValueError("It_bg of a ragged batch: one (h_org, w_org) tensor (or None) per pair")
-            parts = []
-            for x, hw in zip(It_bg, tabs["org"]):
-                if x is not None and tuple(x.shape) != hw:
-                    raise ValueError("It_bg entry of shape %s for a target of %s" % (tuple(x.shape), hw))
-                parts.append(torch.ones(hw[0] * hw[1], dtype=torch.float32, device=dev) if x is None else x.to(dev).float().reshape(-1))
-            bg = torch.cat(parts)
-        batch = dict(feats=feats, tabs=tabs, idx1=idx1, idx2=idx2, cnt=cnt, bg=bg, moff=tab[:B],
-                     geom=tab[B:7 * B].to(torch.int32).view(B, 6), d2dims=tab[7 * B:].to(torch.int32).view(B, 2), d2=tabs["d2"],
-                     Mask=torch.zeros(tabs["total"], dtype=torch.float32, device=dev), nbH=torch.zeros(B, dtype=torch.int32, device=dev),
-                     tensor_s=tensor_s, tensor_d2=tensor_d2, tensor_resize=tensor_resize, cc_th=cc_th, remove_small_cc=remove_small_cc)
+        pb = ragged.PackedBatch(tabs, It_bg, self.dev, extra_rows=tabs["d2"])
+        batch = dict(pb.fields(), feats=feats, idx1=idx1, idx2=idx2, cnt=cnt, d2dims=pb.extra, d2=tabs["d2"], tensor_s=tensor_s,
+                     tensor_d2=tensor_d2, tensor_resize=tensor_resize, cc_th=cc_th, remove_small_cc=remove_small_cc)
         rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedKittiGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
-
-        def mask_of(b):
-            o, (h, w) = tabs["moff"][b], tabs["org"][b]
-            return batch["Mask"][o:o + h * w].view(h, w)
-        return st.close(mask_of, (idx1, idx2, cnt))
+        return st.close(pb.mask_of, (idx1, idx2, cnt))
 
     def multi_h_kitti_pairs(self, pairs, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, sample_fn=None, remove_small_cc=None,
                             records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None):
         """multi_h_kitti_batched on pairs of PIL images.  All sources of one size and all targets of one size: upload_raw(), today's
         dense path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise per-pair uploads and the ragged path (``It_bg`` a
         list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged with the d2 lists)."""
-        if len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1:
-            up = lambda im: torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(self.dev)
-            src, tgt = [up(p[0]) for p in pairs], [up(p[1]) for p in pairs]
-        else:
-            src, tgt = self.upload_raw(pairs)
+        src, tgt = self._upload_lists(pairs) if self._mixed_sizes(pairs) else self.upload_raw(pairs)
         return self.multi_h_kitti_batched(src, tgt, fineSize=fineSize, maskRegionTh=maskRegionTh, cc_th=cc_th, It_bg=It_bg,
                                           sample_fn=sample_fn, remove_small_cc=remove_small_cc, records=records, want_lists=want_lists,
                                           trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
@@ -1435,17 +1181,15 @@ class AlignPipeline:
     def align_pairs(self, pairs, fine=True, samples=None, pair_ids=None):
         """Pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense path.  Otherwise the
         ragged path (prepare_ragged)."""
-        if len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1:
-            return self.align_prepared(self.prepare_ragged(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
-        return self.align_prepared(self.prepare(pairs), fine=fine, samples=samples, pair_ids=pair_ids)
+        prep = self.prepare_ragged(pairs) if self._mixed_sizes(pairs) else self.prepare(pairs)
+        return self.align_prepared(prep, fine=fine, samples=samples, pair_ids=pair_ids)
 
     def multi_h_pairs(self, pairs, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None, want_lists=True,
                       trace=None, pair_ids=None, draw_epoch=0, split=None):
         """multi_h_batched on pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense
         path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise prepare_ragged() and the ragged path (``It_bg`` a
         list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged)."""
-        ragged = len({p[0].size for p in pairs}) > 1 or len({p[1].size for p in pairs}) > 1
-        prep = self.prepare_ragged(pairs) if ragged else self.prepare(pairs)
+        prep = self.prepare_ragged(pairs) if self._mixed_sizes(pairs) else self.prepare(pairs)
         return self.multi_h_batched(prep, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
                                     records=records, want_lists=want_lists, trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch,
                                     split=split)

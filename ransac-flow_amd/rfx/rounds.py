@@ -11,12 +11,11 @@ stops -- is the group class: DenseGroup (Hpatch), KittiGroup, RaggedGroup (Hpatc
 chosen candidates of different sizes).  ``split_policy`` decides how many groups a batch is cut into, RoundState holds what the
 groups of one call share.
 """
-import collections
 import os
 
 import torch
 
-from . import ops
+from . import ops, ragged
 
 # default number of lock-step groups: (from this many pairs on, groups), largest first.
 # Hpatch (measured, profiles/r06_stream_sweep.txt: config 3, 64 pairs: 1 / 2 / 3 / 4 / 6 groups = 110.2 / 112.7 / 115.3 / 115.4 / 115.6
@@ -288,14 +287,14 @@ class VariantCGroup(DenseGroup):
 
 class RaggedGroup:
     """Pairs [lo, hi) of a ragged batch of the Hpatch driver (pairs of different sizes).  The explained-region masks (and
-    background maps) of all pairs live in ONE packed buffer (pipeline.ragged_multih_tables), so the filter and the accept kernel
+    background maps) of all pairs live in ONE packed buffer (ragged.ragged_multih_tables), so the filter and the accept kernel
     of a round are one launch each for all active pairs of the group.  Pairs of the slice that share (source shape, target shape)
     form a fine group: their raw images are stacked once, the target features are computed once per target shape, and every round
     runs warp_grid + PredFlowMask over the active members of all fine groups as one chain of grouped launches
     (AlignPipeline.pred_flow_mask_groups; RFX_FINE_GROUPS off: once per fine group, packed with one torch.cat each).  The round's
     matchability and /8 maps are packed in fine-group order and handed to rfx_multih_accept_ragged_f32 with per-active-pair offsets; those offsets
-    and the groups' gather indices go up in ONE pinned table per round.  ``batch``: prep, feats, tabs, idx1, idx2, cnt, the packed
-    Mask / bg, nbH (B,), moff (B,), geom (B,6)."""
+    and the groups' gather indices go up in ONE pinned table per round.  ``batch``: prep, feats, idx1, idx2, cnt and the fields of a
+    ragged.PackedBatch: tabs, the packed Mask / bg, nbH (B,), moff (B,), geom (B,6)."""
 
     def __init__(self, st, batch, lo, hi):
         cut = lambda t: None if t is None else t[lo:hi]
@@ -312,14 +311,16 @@ class RaggedGroup:
     def fine_setup(self, batch, lo, hi):
         """The fine groups of the slice and their stacked images."""
         IsT, self.ItT = batch["prep"]["IsTensor"][lo:hi], batch["prep"]["ItTensor"][lo:hi]
-        # fine groups: members in ascending order; target-shape groups for the FeatureExtractor pass of the targets
-        fine, self.tgroups = collections.OrderedDict(), collections.OrderedDict()
-        for m in range(hi - lo):
-            fine.setdefault((tuple(IsT[m].shape), tuple(self.ItT[m].shape)), []).append(m)
-            self.tgroups.setdefault(tuple(self.ItT[m].shape), []).append(m)
-        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2], hw8=self.gm[mem[0]][4:6],
-                                 Is=torch.cat([IsT[m] for m in mem]) if len(mem) > 1 else IsT[mem[0]]) for mem in fine.values()]
+        self.make_fine_groups([(tuple(s.shape), tuple(t.shape)) for s, t in zip(IsT, self.ItT)], Is=IsT)
+        self.tgroups = ragged.by_shape([tuple(t.shape) for t in self.ItT])      # the FeatureExtractor pass of the targets: per target shape
         self.have_featt = False
+
+    def make_fine_groups(self, keys, **images):
+        """The fine groups: the pairs of the slice that share ``keys[m]``, members ascending, each with its members' ``images``
+        (name -> per-pair (1,3,.,.) list) stacked once."""
+        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2], hw8=self.gm[mem[0]][4:6],
+                                 **{name: ragged.rows(ts, mem) for name, ts in images.items()})
+                            for mem in ragged.by_shape(keys).values()]
 
     def round_layout(self, active):
         """The round's layout: fine groups in order, each with its active members; pair k of the active list sits at match_off[k] of
@@ -363,16 +364,15 @@ class RaggedGroup:
             return
         self.have_featt = True
         pipe, ItT, ft = self.st.pipe, self.ItT, {}
-        xs = [torch.cat([ItT[m] for m in mem]) if len(mem) > 1 else ItT[mem[0]] for mem in self.tgroups.values()]
+        xs = [ragged.rows(ItT, mem) for mem in self.tgroups.values()]
         if ops.fine_groups_enabled():
             fs = pipe.feat_l2norm(xs)                    # all target shapes as one chain of stages
         else:
             fs = [ops.l2norm(pipe.feat(x)) for x in xs]
         for f, mem in zip(fs, self.tgroups.values()):
-            for j, m in enumerate(mem):
-                ft[m] = f[j:j + 1]
+            ragged.hand_back(ft, mem, f)
         for g in self.fine_groups:
-            g["featt"] = torch.cat([ft[m] for m in g["members"]]) if len(g["members"]) > 1 else ft[g["members"][0]]
+            g["featt"] = ragged.rows(ft, g["members"])
 
     grouped_fine = True                  # all fine groups of a round as one chain of grouped launches (where RFX_FINE_GROUPS is on)
 
@@ -380,9 +380,32 @@ class RaggedGroup:
         """The fine pass of one fine group's active members (the per-group form)."""
         return self.st.pipe.pred_flow_mask(Is, featt, flowCoarse)
 
+    def take(self, ent, t, key):
+        """The rows of ``t`` that round-group entry ``ent`` works on: key "sel" = its active members out of a fine group's stacked
+        tensor, "kidx" = its pairs out of a tensor over the round's active list (None: all rows, ``t`` itself)."""
+        return t if ent[key] is None else t.index_select(0, self.T[ent[key][0]:ent[key][0] + ent[key][1]])
+
+    @staticmethod
+    def pack(ts):
+        """Per-fine-group tensors -> ONE flat buffer in fine-group order (one group: a view of its own tensor)."""
+        return ragged.rows([t.reshape(-1) for t in ts], range(len(ts)))
+
+    def max_hw(self, active):
+        return max(self.gm[m][0] * self.gm[m][1] for m in active)
+
+    def where(self):
+        """After a round's fine stage: pair m -> (its round-group entry, its row there); with ``want_lists`` every entry gets ``md2``,
+        both matchability maps as the two channels of matchDown8."""
+        where = {}
+        for ent in self.rg:
+            if self.st.want_lists:
+                ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
+            for j, m in enumerate(ent["mem"]):
+                where[m] = (ent, j)
+        return where
+
     def fine(self, A, active, Hs, bestH, res, n_dev):
-        rg, T, a, gm = self.rg, self.T, len(active), self.gm
-        take = lambda ent, t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
+        rg, T, a, take = self.rg, self.T, len(active), self.take
         if self.grouped_fine and ops.fine_groups_enabled():
             # fine stage: all fine groups as ONE chain of grouped launches; its packed outputs are in fine-group order, which is the
             # order matches() laid the round's offsets out in -- they go to the accept kernel as they are
@@ -399,18 +422,12 @@ class RaggedGroup:
                 h, w = g["hw"]
                 ent["pm"] = self.pred_group(take(ent, g["Is"], "sel"), take(ent, g["featt"], "sel"),
                                             ops.warp_grid(take(ent, Hs, "kidx"), h, w))
-            pack = lambda key: (rg[0]["pm"][key].reshape(-1) if len(rg) == 1 else torch.cat([e["pm"][key].reshape(-1) for e in rg]))
+            pack = lambda key: self.pack([e["pm"][key] for e in rg])
         accept, gain = ops.multih_accept_ragged(pack("match"), T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
-                                                self.st.maskRegionTh, 0, max(gm[m][0] * gm[m][1] for m in active), bestH=bestH,
+                                                self.st.maskRegionTh, 0, self.max_hw(active), bestH=bestH,
                                                 flowDown8=pack("flowDown8"), match12Down8=pack("match12Down8"),
                                                 match21Down8=pack("match21Down8"), off8=T[a:2 * a], records=self.R)
-        where = {}                                                                  # pair m -> (its fine group's outputs, row)
-        for ent in rg:
-            if self.st.want_lists:
-                ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
-            for j, m in enumerate(ent["mem"]):
-                where[m] = (ent, j)
-        return dict(accept=accept, gain=gain, where=where)
+        return dict(accept=accept, gain=gain, where=self.where())
 
     def mask_rows(self, A, active):
         return [self.Mask[self.mo[m]:self.mo[m] + self.gm[m][0] * self.gm[m][1]].view(self.gm[m][:2]).clone() for m in active]
@@ -436,7 +453,7 @@ class RaggedVariantCGroup(RaggedGroup):
     active pairs' matches.  The fine stage is the cycle-checked PredFlowMask, once per fine group of active pairs (no grouped chain);
     its matchability maps are packed in fine-group order for the ragged accept kernel (mode 0).  ``batch``: RaggedGroup's (idx1 /
     idx2 / cnt None: nothing is cached) with ``feats`` = the CHOSEN candidates' featB / nB / offB and the tables of
-    pipeline.ragged_variant_c_tables."""
+    ragged.ragged_variant_c_tables."""
     grouped_fine = False
 
     def __init__(self, st, batch, lo, hi):
@@ -468,7 +485,7 @@ class RaggedKittiGroup(RaggedGroup):
     """Pairs [lo, hi) of a ragged batch of the KITTI driver: RaggedGroup with the differences KittiGroup has over DenseGroup -- the
     two-resolution fine pass, the small-component filter, accept mode 1, no cached target features, the reference's ``while True``
     with the capacity stop, flowD2 collected and traced.  The packed masks live at the ORIGINAL target sizes
-    (pipeline.ragged_kitti_tables).  A fine group is the pairs of the slice that share (source ORIGINAL shape, target ORIGINAL shape):
+    (ragged.ragged_kitti_tables).  A fine group is the pairs of the slice that share (source ORIGINAL shape, target ORIGINAL shape):
     the source is sampled at its original size and the outputs live at the original target size, so two pairs whose resized shapes
     coincide but whose originals differ are two groups.  A round runs pipeline.kitti_fine_round (without its dense filter) once per
     fine group over its active members, packs the matchability maps in fine-group order, then ONE rfx_remove_small_cc_ragged_f32 in
@@ -482,12 +499,7 @@ class RaggedKittiGroup(RaggedGroup):
         Ts, Td2, Tr = batch["tensor_s"][lo:hi], batch["tensor_d2"][lo:hi], batch["tensor_resize"][lo:hi]
         self.cc_th, self.remove_small_cc = batch["cc_th"], batch["remove_small_cc"]
         self.d2, self.d2dims = batch["d2"][lo:hi], batch["d2dims"][lo:hi]
-        fine = collections.OrderedDict()
-        for m in range(hi - lo):
-            fine.setdefault((tuple(Ts[m].shape), self.gm[m][:2]), []).append(m)
-        stack = lambda ts, mem: torch.cat([ts[m] for m in mem]) if len(mem) > 1 else ts[mem[0]]
-        self.fine_groups = [dict(members=mem, pos={m: j for j, m in enumerate(mem)}, hw=self.gm[mem[0]][:2], hw8=self.gm[mem[0]][4:6],
-                                 Is=stack(Ts, mem), d2=stack(Td2, mem), resize=stack(Tr, mem)) for mem in fine.values()]
+        self.make_fine_groups([(tuple(t.shape), hw[:2]) for t, hw in zip(Ts, self.gm)], Is=Ts, d2=Td2, resize=Tr)
 
     def target_features(self):
         pass                                             # both PredFlowMask passes of a round compute their own
@@ -505,17 +517,16 @@ class RaggedKittiGroup(RaggedGroup):
         return offd2 + dims
 
     def fine(self, A, active, Hs, bestH, res, n_dev):
-        rg, T, a, gm, x0 = self.rg, self.T, len(active), self.gm, self.x0
+        rg, T, a, gm, x0, take = self.rg, self.T, len(active), self.gm, self.x0, self.take
         pipe = self.st.pipe
         for ent in rg:
             g = ent["g"]
-            take = lambda t, key: t if ent[key] is None else t.index_select(0, T[ent[key][0]:ent[key][0] + ent[key][1]])
-            ent["flow_d2"], ent["pm"], ent["match"] = pipe.kitti_fine_round(take(Hs, "kidx"), take(g["Is"], "sel"), take(g["d2"], "sel"),
-                                                                            take(g["resize"], "sel"), g["hw"], cc_th=0)
-        cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]) if len(ts) > 1 else ts[0].reshape(-1)
-        pack = lambda key: cat([e["pm"][key] for e in rg])
-        max_hw = max(gm[m][0] * gm[m][1] for m in active)
-        match = cat([e["match"] for e in rg])
+            ent["flow_d2"], ent["pm"], ent["match"] = pipe.kitti_fine_round(take(ent, Hs, "kidx"), take(ent, g["Is"], "sel"),
+                                                                            take(ent, g["d2"], "sel"), take(ent, g["resize"], "sel"),
+                                                                            g["hw"], cc_th=0)
+        pack = lambda key: self.pack([e["pm"][key] for e in rg])
+        max_hw = self.max_hw(active)
+        match = self.pack([e["match"] for e in rg])
         if self.cc_th > 0:                                                              # evalKITTI/evaluation.py:321
             if self.remove_small_cc is None:
                 if len(rg) == 1:
@@ -531,15 +542,9 @@ class RaggedKittiGroup(RaggedGroup):
         accept, gain = ops.multih_accept_ragged(match, T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
                                                 self.st.maskRegionTh, self.accept_mode, max_hw, bestH=bestH, flowDown8=pack("flowDown8"),
                                                 match12Down8=pack("match12Down8"), match21Down8=pack("match21Down8"), off8=T[a:2 * a],
-                                                records=self.R, flowD2=cat([e["flow_d2"] for e in rg]), offd2=T[x0:x0 + a],
+                                                records=self.R, flowD2=self.pack([e["flow_d2"] for e in rg]), offd2=T[x0:x0 + a],
                                                 d2dims=self.d2dims if self.R is None else None)
-        where = {}
-        for ent in rg:
-            if self.st.want_lists:
-                ent["md2"] = torch.cat((ent["pm"]["match12Down8"], ent["pm"]["match21Down8"]), dim=1)
-            for j, m in enumerate(ent["mem"]):
-                where[m] = (ent, j)
-        return dict(accept=accept, gain=gain, where=where, match=match)
+        return dict(accept=accept, gain=gain, where=self.where(), match=match)
 
     def trace_entry(self, rd, active):
         where, tab, gm = rd["where"], self.table, self.gm

@@ -4,8 +4,8 @@
     timeout -k 10 600 python scripts/entry_trace.py [--tree PATH] --out profiles/NAME.json
 
 Wraps ops._call (every kernel entry call of the Python side goes through it) and reads ops.group_stats().  Per scenario the record
-holds ``calls``: the ordered entry names, one string, a leading "+" = recorded in a group; ``groups`` / ``grouped_launches``: the launch_group
-blocks that ended and the kernel launches they issued; ``sha256``: a digest of every tensor (and number) the call returned, by its
+holds ``calls``: the ordered entry names, one string, a leading "+" = recorded in a group, a block of calls repeated n times in a
+row written once, as "name*n" or "[name name ...]*n" (fold()); ``groups`` / ``grouped_launches``: the launch_group blocks that ended and the kernel launches they issued; ``sha256``: a digest of every tensor (and number) the call returned, by its
 path in the result (of the cached match lists: the rows below the count).  The calls recorded in ONE group are listed sorted by name: a group launches per kernel instance when it ends,
 so the order in which its problems were recorded is not an order of launches.  Fixed seed, device draws keyed by pair id, split=1,
 RFX_GRAPH=0 (the trunk pass is traced as launches, not replayed as a graph), degenerate="device" (no host stage).  ``--tree``: the
@@ -19,6 +19,26 @@ import os
 import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def fold(names):
+    """A list of entry names with every immediate repetition written once: at each position the block (up to 300 names) whose
+    repeats cover most is taken, "[a b c]*n" (one name: "a*n"), blocks folded in turn.  Names hold no space, bracket or asterisk, so
+    two lists fold to the same strings only if they are equal."""
+    out, i = [], 0
+    while i < len(names):
+        best = (0, 1, 1)                                                    # (names saved, block length, repeats)
+        for L in range(1, min(300, (len(names) - i) // 2) + 1):
+            r = 1
+            while names[i + r * L:i + (r + 1) * L] == names[i:i + L]:
+                r += 1
+            if (r - 1) * L > best[0]:
+                best = ((r - 1) * L, L, r)
+        _, L, r = best
+        block = fold(names[i:i + L]) if L > 1 else names[i:i + 1]
+        out.append(block[0] if r == 1 else ("%s*%d" % (block[0], r) if L == 1 else "[%s]*%d" % (" ".join(block), r)))
+        i += L * r
+    return out
 
 
 def digest(obj, path, out):
@@ -52,7 +72,7 @@ def main():
     import numpy as np
     import torch
     from rfx import ops, synth, weights
-    from rfx.pipeline import AlignPipeline
+    from rfx.pipeline import AlignPipeline, resize_dims
 
     dev = torch.device("cuda:0")
     sds = dict(trunk=weights.resnet50_trunk_sd(0), feat=weights.feature_extractor_sd(1), flow=weights.net_flow_coarse_sd(2),
@@ -69,6 +89,19 @@ def main():
     m_src, m_tgt = [up(p[0]) for p in mixed], [up(p[1]) for p in mixed]
     kitti = dict(fineSize=200, maskRegionTh=0.005, cc_th=0.01)
     ids4, ids3 = [11, 12, 13, 14], [21, 22, 23]
+    # the YFCC driver: a variant-C pipeline, K = 2 candidates per pair (the target and its quarter turn)
+    pipe_c = AlignPipeline(sds, nbScale=3, nbIter=300, tolerance=0.05, minSize=240, scaleR=1.2, variant="C", device=dev, seed=5,
+                           degenerate="device")
+    m_cands = [m_tgt, [torch.rot90(t, 1, (0, 1)).contiguous() for t in m_tgt]]
+
+    def half_ones(t):
+        """A background map for the uint8 (H,W,3) target ``t`` at its resized size: ones in the left half."""
+        nw, nh = resize_dims(t.shape[1], t.shape[0], 240, "min")
+        m = torch.zeros((nh, nw), dtype=torch.float32, device=dev)
+        m[:, :nw // 2] = 1
+        return m
+    bg_b = [half_ones(m_tgt[0]), None, half_ones(m_tgt[2])]
+    bg_c = [[half_ones(m_cands[0][0]), None, half_ones(m_cands[0][2])], [None, half_ones(m_cands[1][1]), half_ones(m_cands[1][2])]]
 
     scenarios = [
         ("features_B1", lambda: pipe.features(pipe.prepare_device(d_src[:1], d_tgt[:1]))),
@@ -83,11 +116,16 @@ def main():
         ("multi_h_variant_c_one_candidate", lambda: pipe.multi_h_variant_c(d_src, [d_tgt], maxCoarse=3, pair_ids=ids4)),
         ("multi_h_one_pair", lambda: pipe.multi_h(pipe.prepare_device(d_src[:1], d_tgt[:1]), 0, maxCoarse=3)),
         ("multi_h_kitti_one_pair", lambda: pipe.multi_h_kitti(d_src[:1], d_tgt[:1], **kitti)),
+        ("multi_h_batched_ragged_bg", lambda: pipe.multi_h_batched(pipe.prepare_ragged_device(m_src, m_tgt), maxCoarse=3, It_bg=bg_b,
+                                                                   pair_ids=ids3, split=1)),
+        ("multi_h_variant_c_lists", lambda: pipe_c.multi_h_variant_c(m_src, m_cands, maxCoarse=3, pair_ids=ids3, split=1)),
+        ("multi_h_variant_c_lists_bg", lambda: pipe_c.multi_h_variant_c(m_src, m_cands, maxCoarse=3, It_bg=bg_c, pair_ids=ids3, split=1)),
     ]
     call0 = ops._call
     res = {}
     for name, fn in scenarios:
         pipe.reseed(5)
+        pipe_c.reseed(5)
         log = []
 
         def traced(entry, *args, **kw):
@@ -111,7 +149,7 @@ def main():
             i = j
         sha = {}
         digest(out, "out", sha)
-        res[name] = dict(calls=" ".join(calls), entry_calls=len(calls), groups=g1[0] - g0[0], grouped_launches=g1[1] - g0[1], sha256=sha)
+        res[name] = dict(calls=" ".join(fold(calls)), entry_calls=len(calls), groups=g1[0] - g0[0], grouped_launches=g1[1] - g0[1], sha256=sha)
         print("%-34s %5d entry calls (%4d recorded), %3d groups, %4d grouped launches, %3d results" %
               (name, len(calls), sum(1 for c in calls if c[0] == "+"), g1[0] - g0[0], g1[1] - g0[1], len(sha)), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
