@@ -787,6 +787,36 @@ int rfx_softmax_accum_f32(const float* logits, float* scores, int N, int C, long
 int rfx_argmax_mask_f32(const float* scores, int N, int C, long long HW, int id, int complement, float* mask, int32_t* pred,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sky masks for a batch of targets (ADDED under ABI 17: no existing entry point moved).
+ * ------------------------------------------------------------------------------------------ */
+/* segNet/segEval.py:27-43 after the network passes, in ONE kernel: per scale s = 0..S-1 in order
+ *     rfx_resize_bilinear_f32(logits[s], align_corners = 0) to (H, W) -> rfx_softmax_accum_f32(div) (scale 0 stores, the others add),
+ * then rfx_argmax_mask_f32(id, complement) -- bit for bit that chain's pred and mask, without the (N,C,H,W) up-sampled logits and
+ * scores: one thread per output pixel forms the taps of every scale once, then per scale the maximum and the sum of expf(v - mx)
+ * over the classes in class order, then ((p_0 + p_1) + ...) with p_s = expf(v - mx_s) / sum_s / div per class and the running
+ * first maximum (strict >, NaN wins like torch.max).  logits: HOST array of S device pointers, map s is (N, C, hs[s], ws[s])
+ * float32; hs, ws: HOST arrays; all three are read during the call and travel in the kernel's argument block.  mask (N,H,W) float32,
+ * pred (N,H,W) int32 or NULL.  Records inside a grouped launch like the other pointwise families.
+ * RFX_E_ARG: a null pointer other than pred, S outside 1..8, a non-positive size or div.  RFX_E_LIMIT: N*H*W or an hs[s]*ws[s]
+ * above 2^31 - 1.  All of these are checked before any HIP call. */
+int rfx_seg_vote_f32(const float* const* logits, const int32_t* hs, const int32_t* ws, int S, int N, int C, int H, int W, float div,
+                     int id, int complement, float* mask, int32_t* pred, void* stream);
+
+/* The byte image scipy.misc.imresize makes of a sky mask before it resizes it, turned k quarter turns
+ * (evaluation/evalYFCC/evaluation.py:193,200,212: np.rot90(It_bg, k), then imresize -> scipy 1.2.3 pilutil.bytescale; k = 0 for
+ * evalHpatch/evaluation.py:180, evalCorr/evaluation.py:187, evalKITTI/evaluation.py:247-248).  mask (N,H,W) float32 of 0 / 1 values:
+ * a pixel becomes 255 where the mask is non-zero, provided ITS map holds both a zero and a non-zero value; a constant map becomes all
+ * zeros (bytescale's cscale = (cmax - cmin) or 1).  out (N,Ho,Wo) bytes = np.rot90(bytes, k), (Ho, Wo) = (H, W) for even k and (W, H)
+ * for odd k.  ws: rfx_sky_bytes_ws_bytes(N) bytes = one flag word per map, zeroed by the call; only ORs of constants reach a word, so
+ * no result depends on the order in which workgroups run.  Three stream-ordered operations.
+ * RFX_E_ARG: a null pointer, a non-positive N, H or W, k outside 0..3.  RFX_E_LIMIT: N*H*W > 2^31 - 1. */
+size_t rfx_sky_bytes_ws_bytes(int N);
+int rfx_sky_bytes_u8(const float* mask, int N, int H, int W, int k, uint8_t* out, void* ws, void* stream);
+/* out[i] = in[i] < threshold ? 1.0f : 0.0f -- the scripts' ``(imresize(It_bg, (Ith, Itw)) < 128).astype(np.float32)``
+ * (evalHpatch/evaluation.py:180) on the resized bytes.  RFX_E_ARG: a null pointer or total <= 0. */
+int rfx_less_than_u8_f32(const uint8_t* in, long long total, int threshold, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,10 @@ SIGNATURES = {
     "rfx_adaptive_avgpool2d_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "rfx_softmax_accum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_float, c_int, c_void_p]),
     "rfx_argmax_mask_f32": (c_int, [c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfx_seg_vote_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfx_sky_bytes_ws_bytes": (c_size_t, [c_int]),
+    "rfx_sky_bytes_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3),
+    "rfx_less_than_u8_f32": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
     "rfx_conv2d_tile_variant": (c_int, [c_int] * 4),
     "rfx_conv2d_kernel_id": (c_int, [c_int] * 9),
     "rfx_conv3x3_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),

@@ -1,4 +1,5 @@
-"""Host-side coefficient tables for the GPU Lanczos-3 resampler.
+"""Host-side coefficient tables for the GPU resampler: Pillow's LANCZOS and BILINEAR (the sky network's input
+scales, segNet/segData.py:74, and the scripts' ``imresize`` of the sky mask).
 
 The reference resizes every pyramid level with ``PIL.Image.resize(..., resample=LANCZOS)`` on the host
 (quick_start/coarseAlignFeatMatch.py:80-90).  Pillow's resampler (libImaging/Resample.c) is a separable
@@ -31,14 +32,35 @@ def _lanczos(x):
     return 0.0
 
 
+def _bilinear(x):
+    """Pillow's ``bilinear_filter``: the triangle 1 - |x| on (-1, 1)."""
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return 1.0 - x
+    return 0.0
+
+
+# name -> (filter function, support), as the ``struct filter`` entries of Resample.c
+FILTERS = {"lanczos": (_lanczos, LANCZOS_SUPPORT), "bilinear": (_bilinear, 1.0)}
+
+
+def coeffs(in_size, out_size, filter="lanczos"):
+    """-> (bounds int32 (out_size, 2) [xmin, count], weights int32 (out_size, ksize), ksize); one cached object per
+    (sizes, filter), whether the default filter is spelled out or not."""
+    if filter not in FILTERS:
+        raise ValueError("unknown resampling filter %r (one of %s)" % (filter, sorted(FILTERS)))
+    return _coeffs(in_size, out_size, filter)
+
+
 @functools.lru_cache(maxsize=256)
-def coeffs(in_size, out_size):
-    """-> (bounds int32 (out_size, 2) [xmin, count], weights int32 (out_size, ksize), ksize)."""
+def _coeffs(in_size, out_size, filter):
+    fn, filter_support = FILTERS[filter]
     in0, in1 = 0.0, float(in_size)
     filterscale = scale = (in1 - in0) / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = LANCZOS_SUPPORT * filterscale
+    support = filter_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), dtype=np.int32)
     kk = np.zeros((out_size, ksize), dtype=np.int32)
@@ -52,7 +74,7 @@ def coeffs(in_size, out_size):
         if xmax > in_size:
             xmax = in_size
         xmax -= xmin
-        w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
@@ -64,14 +86,14 @@ def coeffs(in_size, out_size):
     return bounds, kk, ksize
 
 
-def plan(in_w, in_h, out_w, out_h):
+def plan(in_w, in_h, out_w, out_h, filter="lanczos"):
     """Pass plan of ImagingResample for a full-image box: which passes run, the row window of the horizontal
     pass and the (shifted) vertical bounds.  Returns dict or None when the size is unchanged (Pillow copies)."""
     if (in_w, in_h) == (out_w, out_h):
         return None
     need_h, need_v = out_w != in_w, out_h != in_h
-    bh, kh, ksh = coeffs(in_w, out_w)
-    bv, kv, ksv = coeffs(in_h, out_h)
+    bh, kh, ksh = coeffs(in_w, out_w, filter)
+    bv, kv, ksv = coeffs(in_h, out_h, filter)
     y_first = int(bv[0, 0])
     y_last = int(bv[out_h - 1, 0] + bv[out_h - 1, 1])
     bv2 = bv.copy()
@@ -81,11 +103,11 @@ def plan(in_w, in_h, out_w, out_h):
                 y_first=y_first if need_h else 0, rows_h=(y_last - y_first) if need_h else in_h)
 
 
-def apply_numpy(img, out_w, out_h):
+def apply_numpy(img, out_w, out_h, filter="lanczos"):
     """Integer two-pass resample of a uint8 HWC array with the tables above (CPU check of the tables against
     Pillow itself; the product path runs the same arithmetic in rfx_lanczos_pass_u8)."""
     h, w, c = img.shape
-    p = plan(w, h, out_w, out_h)
+    p = plan(w, h, out_w, out_h, filter)
     if p is None:
         return img.copy()
     cur = img.astype(np.int64)

@@ -712,6 +712,72 @@ def argmax_mask(scores, class_id, complement=False, want_pred=False):
     return (mask, pred) if want_pred else mask
 
 
+SEG_VOTE_MAX_SCALES = 8
+
+
+def seg_vote(logits_list, out_hw, class_id, complement=False, want_pred=False, div=None):
+    """resize_bilinear(align_corners=False) to ``out_hw`` -> softmax_accum(div) per logit map in list order -> argmax_mask, in one
+    kernel and bit for bit that chain, without the (N, C, H, W) up-sampled logits and scores (segNet/segEval.py:27-43 after the network
+    passes).  logits_list: 1..8 float32 (N, C, h_s, w_s) device tensors of one N and C; div defaults to their number.
+    -> mask (N, H, W) float32 [, pred (N, H, W) int32]."""
+    maps = [_dev(t, "logits[%d]" % i) for i, t in enumerate(logits_list)]
+    S = len(maps)
+    if not 1 <= S <= SEG_VOTE_MAX_SCALES:
+        raise ValueError("seg_vote takes 1..%d logit maps, got %d" % (SEG_VOTE_MAX_SCALES, S))
+    if any(t.dim() != 4 or t.shape[:2] != maps[0].shape[:2] for t in maps):
+        raise ValueError("seg_vote: every logit map must be (N, C, h, w) with the same N and C")
+    N, C = int(maps[0].shape[0]), int(maps[0].shape[1])
+    H, W = int(out_hw[0]), int(out_hw[1])
+    dev = _one_device(*maps)
+    mask = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    pred = torch.empty((N, H, W), dtype=torch.int32, device=dev) if want_pred else None
+    ptrs = (ctypes.c_void_p * S)(*[t.data_ptr() for t in maps])
+    hs = (ctypes.c_int32 * S)(*[int(t.shape[2]) for t in maps])
+    ws = (ctypes.c_int32 * S)(*[int(t.shape[3]) for t in maps])
+    launch_group.keep(maps)
+    _call("rfx_seg_vote_f32", dev, ptrs, hs, ws, S, N, C, H, W, float(S if div is None else div), int(class_id),
+          1 if complement else 0, _p(mask), _p(pred))
+    return (mask, pred) if want_pred else mask
+
+
+def sky_bytes(mask, k=0):
+    """The byte image the scripts' ``imresize`` makes of a 0 / 1 sky mask (scipy 1.2.3 bytescale: 255 where non-zero if the map holds
+    both values, a constant map -> zeros; per map), turned ``k`` quarter turns as np.rot90 (evaluation/evalYFCC/evaluation.py:193).
+    mask (N, H, W) float32 -> (N, Ho, Wo, 1) uint8, the one-channel layout pil_resize_u8 reads."""
+    mask = _dev(mask, "mask")
+    if mask.dim() != 3:
+        raise ValueError("sky_bytes expects (N, H, W) masks")
+    k = int(k)
+    if not 0 <= k <= 3:
+        raise ValueError("k must be a number of quarter turns in 0..3")
+    N, H, W = (int(v) for v in mask.shape)
+    Ho, Wo = (W, H) if k & 1 else (H, W)
+    out = torch.empty((N, Ho, Wo, 1), dtype=torch.uint8, device=mask.device)
+    ws = torch.empty((max(1, _lib.load().rfx_sky_bytes_ws_bytes(N) // 4),), dtype=torch.int32, device=mask.device)
+    _call("rfx_sky_bytes_u8", mask.device, _p(mask), N, H, W, k, _p(out), _p(ws))
+    return out
+
+
+def less_than_u8(img, threshold):
+    """(img < threshold) as float32 1.0 / 0.0 for a uint8 device tensor, same shape."""
+    img = _dev(img, "bytes", torch.uint8)
+    out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+    _call("rfx_less_than_u8_f32", img.device, _p(img), img.numel(), int(threshold), _p(out))
+    return out
+
+
+def sky_background(mask, out_hw, k=0):
+    """The scripts' ``(imresize(np.rot90(mask, k), (h, w)) < 128).astype(np.float32)`` (evaluation/evalYFCC/evaluation.py:193-200;
+    k = 0: evalHpatch/evaluation.py:180, evalKITTI/evaluation.py:247-248) for a batch of 0 / 1 masks (N, H, W) on the device, bit for
+    bit: byte form per map (sky_bytes), Pillow BILINEAR on the one-channel bytes (pil_resize_u8), threshold.  ``out_hw`` = (h, w) ->
+    (N, h, w) float32, or a list of such sizes -> a list of maps made from ONE byte map."""
+    many = len(out_hw) > 0 and hasattr(out_hw[0], "__len__")
+    sizes = [tuple(int(v) for v in s) for s in (out_hw if many else [out_hw])]
+    b = sky_bytes(mask, k)
+    outs = [less_than_u8(pil_resize_u8(b, w, h, "bilinear"), 128)[..., 0] for (h, w) in sizes]
+    return outs if many else outs[0]
+
+
 def l2norm(x, out=None, out_batch_stride=0, out_chan_stride=0):
     """F.normalize(x, dim=1) for (N,C,H,W) or (N,C,L).  With ``out`` (a float32 device tensor/view start) the
     result is scattered with the given strides (elements)."""
@@ -768,19 +834,21 @@ _LANCZOS_TABLES = BoundedCache(64)      # (sizes, device) -> coefficient tables,
                                         # not grow it for ever (a table set is a few KB)
 
 
-def lanczos_resize_u8(img, out_w, out_h):
-    """PIL.Image.resize((out_w, out_h), LANCZOS) for a uint8 (N,H,W,C) device tensor, C in 1..4 (3 on the product path; every
-    channel is resampled on its own, as Pillow does for L and RGB) -- bit-identical to Pillow.  Another C is refused (RfxError)."""
+def pil_resize_u8(img, out_w, out_h, resample="lanczos"):
+    """PIL.Image.resize((out_w, out_h), LANCZOS | BILINEAR) for a uint8 (N,H,W,C) device tensor, C in 1..4 (every channel is resampled
+    on its own, as Pillow does for L and RGB) -- bit-identical to Pillow: rfx_lanczos_pass_u8 is table-driven, only rfx/lanczos.py
+    knows the filter.  Another C is refused (RfxError), another filter is a ValueError."""
     from . import lanczos
     img = _dev(img, "image", torch.uint8)
     N, H, W, C = img.shape
-    p = lanczos.plan(W, H, out_w, out_h)
+    p = lanczos.plan(W, H, out_w, out_h, resample)
     if p is None:
         return img.clone()
     # evicted tables stay alive for as long as a kernel that reads them is queued (stream-ordered allocator); a captured HIP graph
-    # that baked their addresses in holds them by lease (trunk_pass.graphed)
-    tabs = _LANCZOS_TABLES.get((W, H, out_w, out_h, str(img.device)),
-                               lambda: {k: torch.from_numpy(p[k]).to(img.device) for k in ("bounds_h", "kk_h", "bounds_v", "kk_v")})
+    # that baked their addresses in holds them by lease (trunk_pass.graphed).  The Lanczos key is the one it always was; every other
+    # filter's carries its name.
+    key = (W, H, out_w, out_h, str(img.device)) + (() if resample == "lanczos" else (resample,))
+    tabs = _LANCZOS_TABLES.get(key, lambda: {k: torch.from_numpy(p[k]).to(img.device) for k in ("bounds_h", "kk_h", "bounds_v", "kk_v")})
     cur, curH = img, H
     if p["need_h"]:
         tmp = torch.empty((N, p["rows_h"], out_w, C), dtype=torch.uint8, device=img.device)
@@ -793,6 +861,12 @@ def lanczos_resize_u8(img, out_w, out_h):
                                            _p(tabs["kk_v"]), p["ks_v"], 1, 0)
         cur = out
     return cur
+
+
+def lanczos_resize_u8(img, out_w, out_h):
+    """PIL.Image.resize((out_w, out_h), LANCZOS): pil_resize_u8 with the filter of the image pyramid (3 channels on the product
+    path)."""
+    return pil_resize_u8(img, out_w, out_h, "lanczos")
 
 
 def u8_to_f32(img, mean=None, std=None, want_raw=True):

@@ -40,6 +40,31 @@ def pil_to_tensor(pil):
     return torch.from_numpy(arr.copy()).permute(2, 0, 1).contiguous().float().div(255)
 
 
+def backgrounds_of_masks(masks, out_hw_list, k_list=None):
+    """ops.sky_background per group of masks that share (shape, output size, turns) -> one (h, w) map per mask, in order."""
+    k_list = [0] * len(masks) if k_list is None else [int(k) % 4 for k in k_list]
+    keys = [(tuple(m.shape), (int(hw[0]), int(hw[1])), k) for m, hw, k in zip(masks, out_hw_list, k_list)]
+    out = [None] * len(masks)
+    for (_, hw, k), mem in ragged.by_shape(keys).items():
+        bg = ops.sky_background(torch.stack([masks[j] for j in mem]), hw, k)
+        for row, j in enumerate(mem):
+            out[j] = bg[row]
+    return out
+
+
+def sky_backgrounds(seg, tgt_u8_list, out_hw_list, k_list=None, max_batch=None):
+    """The scripts' --segNet step for a list of targets, on the device: ``It_bg = imresize(np.rot90(skyFromSeg(target), k), (h, w))
+    < 128`` (evaluation/evalHpatch/evaluation.py:177-180, evalYFCC/evaluation.py:185-200) per target.  seg: a segnet.SegNetDevice;
+    tgt_u8_list: (H, W, 3) uint8 device tensors (or PIL images); out_hw_list: the (h, w) of each map; k_list: quarter turns of
+    each mask before the resize (default none); max_batch: get_sky_batch's (default: its own).  get_sky_batch, then
+    ops.sky_background per (shape, size, turns) group: no host resize, no mask download, no (N, 150, H, W) tensor.
+    -> list of (h, w) float32 device maps, what the drivers take as It_bg."""
+    if len(out_hw_list) != len(tgt_u8_list) or (k_list is not None and len(k_list) != len(tgt_u8_list)):
+        raise ValueError("one output size (and one number of turns) per target")
+    masks = seg.get_sky_batch(tgt_u8_list) if max_batch is None else seg.get_sky_batch(tgt_u8_list, max_batch=max_batch)
+    return backgrounds_of_masks(masks, out_hw_list, k_list)
+
+
 _CELL_COORDS = BoundedCache(64)
 
 
@@ -217,6 +242,24 @@ class AlignPipeline:
         th, tw = tgt_u8.shape[1], tgt_u8.shape[2]
         nw, nh = resize_dims(tw, th, self.minSize, mode)
         return ops.u8_to_f32(ops.lanczos_resize_u8(tgt_u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD)
+
+    # ---------------------------------------------------------------- sky masks (the scripts' --segNet)
+    def _upload_targets(self, pairs):
+        return [torch.from_numpy(np.asarray(p[1].convert("RGB"), dtype=np.uint8).copy()).to(self.dev) for p in pairs]
+
+    def _target_resized_hw(self, h, w):
+        """(rows, columns) of a target of (h, w) pixels after setTarget's resize: the size the drivers' It_bg has."""
+        nw, nh = resize_dims(w, h, self.minSize, "max" if self.variant == "A" else "min")
+        return nh, nw
+
+    _backgrounds_of_masks = staticmethod(backgrounds_of_masks)
+    sky_backgrounds = staticmethod(sky_backgrounds)      # pipe.sky_backgrounds(seg, targets, sizes[, turns])
+
+    @staticmethod
+    def _seg_or_bg(seg, It_bg):
+        if seg is not None and It_bg is not None:
+            raise ValueError("give either seg (It_bg is formed from the targets) or It_bg, not both")
+        return seg is not None
 
     # ---------------------------------------------------------------- ragged batches (pairs of different sizes)
     def _ragged_prep(self, plan, norm, IsT, ItT):
@@ -949,18 +992,27 @@ class AlignPipeline:
         return st.close(pb.mask_of)
 
     def multi_h_variant_c_pairs(self, pairs, angles=(0, 90, 180, 270), maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None,
-                                records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None):
+                                records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None, seg=None):
         """multi_h_variant_c on pairs of PIL images, the candidates being the target turned by ``angles`` (multiples of 90 degrees,
         counter-clockwise: evaluation/evalYFCC/evaluation.py:189).  Every image is uploaded once; a candidate is torch.rot90 of the
         uploaded target, byte-identical to PIL's rotate(angle, expand=True) for right angles.  All sources of one size and all targets
         of one size: the dense path on stacked tensors (``It_bg``: K tensors (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise the
-        ragged path on lists (``It_bg``: K lists of per-pair maps; no records)."""
+        ragged path on lists (``It_bg``: K lists of per-pair maps; no records).  ``seg`` instead of ``It_bg``: one sky mask per target
+        (get_sky_batch), and candidate k gets it turned like the candidate, at that candidate's resized size
+        (evaluation/evalYFCC/evaluation.py:193-200)."""
         if any(int(a) % 90 for a in angles):
             raise ValueError("candidate angles are multiples of 90 degrees, got %s" % (tuple(angles),))
+        use_seg = self._seg_or_bg(seg, It_bg)
         src, tgt = self._upload_lists(pairs)
         cands = [[torch.rot90(t, int(a) // 90 % 4, (0, 1)).contiguous() for t in tgt] for a in angles]
+        if use_seg:
+            masks = seg.get_sky_batch(tgt)
+            It_bg = [self._backgrounds_of_masks(masks, [self._target_resized_hw(int(x.shape[0]), int(x.shape[1])) for x in c],
+                                                [int(a) // 90] * len(tgt)) for a, c in zip(angles, cands)]
         if not self._mixed_sizes(pairs):
             src, cands = torch.stack(src), [torch.stack(c) for c in cands]
+            if use_seg:
+                It_bg = [torch.stack(g) for g in It_bg]
         return self.multi_h_variant_c(src, cands, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
                                       records=records, want_lists=want_lists, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
 
@@ -1147,11 +1199,16 @@ class AlignPipeline:
         return st.close(pb.mask_of, (idx1, idx2, cnt))
 
     def multi_h_kitti_pairs(self, pairs, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, sample_fn=None, remove_small_cc=None,
-                            records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None):
+                            records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None, seg=None):
         """multi_h_kitti_batched on pairs of PIL images.  All sources of one size and all targets of one size: upload_raw(), today's
         dense path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise per-pair uploads and the ragged path (``It_bg`` a
-        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged with the d2 lists)."""
-        src, tgt = self._upload_lists(pairs) if self._mixed_sizes(pairs) else self.upload_raw(pairs)
+        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged with the d2 lists).  ``seg`` instead of ``It_bg``: It_bg at
+        (h_org, w_org) from the uploaded targets (evaluation/evalKITTI/evaluation.py:245-248; sky_backgrounds)."""
+        mixed = self._mixed_sizes(pairs)
+        src, tgt = self._upload_lists(pairs) if mixed else self.upload_raw(pairs)
+        if self._seg_or_bg(seg, It_bg):
+            bgs = self.sky_backgrounds(seg, list(tgt), [(int(t.shape[0]), int(t.shape[1])) for t in tgt])
+            It_bg = bgs if mixed else torch.stack(bgs)
         return self.multi_h_kitti_batched(src, tgt, fineSize=fineSize, maskRegionTh=maskRegionTh, cc_th=cc_th, It_bg=It_bg,
                                           sample_fn=sample_fn, remove_small_cc=remove_small_cc, records=records, want_lists=want_lists,
                                           trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
@@ -1185,11 +1242,16 @@ class AlignPipeline:
         return self.align_prepared(prep, fine=fine, samples=samples, pair_ids=pair_ids)
 
     def multi_h_pairs(self, pairs, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None, want_lists=True,
-                      trace=None, pair_ids=None, draw_epoch=0, split=None):
+                      trace=None, pair_ids=None, draw_epoch=0, split=None, seg=None):
         """multi_h_batched on pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense
         path (``It_bg`` (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise prepare_ragged() and the ragged path (``It_bg`` a
-        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged)."""
-        prep = self.prepare_ragged(pairs) if self._mixed_sizes(pairs) else self.prepare(pairs)
+        list of per-pair tensors, ``records`` an ops.MultiHRecordsRagged).  ``seg`` (a segnet.SegNetDevice) instead of ``It_bg``: the
+        scripts' --segNet, It_bg formed on the device from the targets at their resized size (sky_backgrounds)."""
+        mixed = self._mixed_sizes(pairs)
+        if self._seg_or_bg(seg, It_bg):
+            bgs = self.sky_backgrounds(seg, self._upload_targets(pairs), [self._target_resized_hw(p[1].size[1], p[1].size[0]) for p in pairs])
+            It_bg = bgs if mixed else torch.stack(bgs)
+        prep = self.prepare_ragged(pairs) if mixed else self.prepare(pairs)
         return self.multi_h_batched(prep, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
                                     records=records, want_lists=want_lists, trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch,
                                     split=split)

@@ -27,6 +27,7 @@ IMG_MAX_SIZE = 500
 PADDING_CONSTANT = 8
 MEAN = (0.485, 0.456, 0.406)              # segNet/segData.py:29-31
 STD = (0.229, 0.224, 0.225)
+DEFAULT_MAX_BATCH = 8                     # get_sky_batch: images of one shape per network pass
 
 
 def input_sizes(ori_width, ori_height, img_sizes=IMG_SIZES, img_max_size=IMG_MAX_SIZE, pad=PADDING_CONSTANT):
@@ -93,7 +94,15 @@ class SegDecoder:
         h, w = conv5.shape[2], conv5.shape[3]
         parts = [conv5]
         for scale, conv in zip(self.POOL_SCALES, self.ppm):
-            parts.append(ops.resize_bilinear(conv(ops.adaptive_avgpool2d(conv5, scale)), (h, w), align_corners=False))
+            pooled = ops.adaptive_avgpool2d(conv5, scale)
+            if pooled.shape[0] > 1 and scale * scale < 4:
+                # ppm.0 (the 1 x 1 pooled map, 2048 -> 512): a single image has fewer than 4 pixels there and runs as ONE fma chain on the
+                # implicit GEMM, a batch of 4 or more would take the k-major kernel's chunked sums (conv_decide: N * HW >= 4).  A batched
+                # pass keeps the batch-1 instance for this layer, image by image, so that a mask does not depend on its batch.
+                y = torch.cat([conv(pooled[i:i + 1]) for i in range(pooled.shape[0])], dim=0)
+            else:
+                y = conv(pooled)
+            parts.append(ops.resize_bilinear(y, (h, w), align_corners=False))
         return self.classify(self.conv_last(torch.cat(parts, dim=1)))
 
 
@@ -123,6 +132,46 @@ class SegNetDevice:
         """-> (mask (H, W) float32 device tensor[, pred (H, W) int32]): segEval.py:37-43."""
         out = ops.argmax_mask(self.scores(img), self.segId, complement=self.segFg, want_pred=want_pred)
         return (out[0][0], out[1][0]) if want_pred else out[0]
+
+    def scale_inputs(self, batch_u8):
+        """The network inputs of the five test scales for a batch (N, H, W, 3) of uint8 images on the device: per scale
+        ``img_transform(img.resize((tw, th), Image.BILINEAR))`` of every image, bit for bit (segNet/segData.py:57-77 -- Pillow's
+        fixed-point BILINEAR passes and ToTensor + Normalize as kernels, no host arithmetic) -> list of (N, 3, th, tw) float32."""
+        N, H, W, _ = batch_u8.shape
+        return [ops.u8_to_f32(ops.pil_resize_u8(batch_u8, tw, th, "bilinear"), MEAN, STD, want_raw=False)[1]
+                for (tw, th) in input_sizes(W, H)]
+
+    def get_sky_batch(self, images, max_batch=DEFAULT_MAX_BATCH, want_pred=False):
+        """``get_sky_device`` for a list of targets: (H, W, 3) uint8 device tensors, or PIL images (uploaded once).  Images of one
+        shape run the five scales as batches of at most ``max_batch``; the scales' logits go through ONE ops.seg_vote (no
+        (N, 150, H, W) tensor).  -> one (H, W) float32 device mask per image, in input order [, and the int32 pred maps]; per
+        image bit for bit what get_sky_device gives."""
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError("max_batch must be at least 1")
+        ims = []
+        for im in images:
+            if not isinstance(im, torch.Tensor):
+                im = torch.from_numpy(np.array(im.convert("RGB"))).to(self.dev)
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_cuda:
+                raise TypeError("get_sky_batch takes (H, W, 3) uint8 device tensors or PIL images")
+            ims.append(im)
+        by_shape = {}
+        for i, im in enumerate(ims):
+            by_shape.setdefault((int(im.shape[0]), int(im.shape[1])), []).append(i)
+        masks, preds = [None] * len(ims), [None] * len(ims)
+        for (H, W), idx in by_shape.items():
+            for c0 in range(0, len(idx), max_batch):
+                chunk = idx[c0:c0 + max_batch]
+                x = torch.stack([ims[i] for i in chunk], dim=0)
+                logits = [self.decoder(self.encoder(xin)) for xin in self.scale_inputs(x)]
+                out = ops.seg_vote(logits, (H, W), self.segId, complement=self.segFg, want_pred=want_pred)
+                m, p = out if want_pred else (out, None)
+                for j, i in enumerate(chunk):
+                    masks[i] = m[j]
+                    if want_pred:
+                        preds[i] = p[j]
+        return (masks, preds) if want_pred else masks
 
     def getSky(self, img_or_path):
         img = Image.open(img_or_path) if isinstance(img_or_path, (str, bytes)) or hasattr(img_or_path, "__fspath__") else img_or_path
