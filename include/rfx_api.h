@@ -338,6 +338,18 @@ int rfx_merge_multi_h_f32(const float* flow, const float* match12, long long mat
 int rfx_match_score_f32(const float* match12, long long match12_stride, const float* cyc, const float* inb, int n,
                         long long HW, float* score, void* stream);
 
+/* The tail of the cycle-checked PredFlowMask forms (evaluation/evalYFCC/evaluation.py:47-58, evaluation/evalKITTI/evaluation.py:66-81)
+ * as one kernel: per pixel what rfx_resize_bilinear_f32 (align_corners = 0) of both matchability maps, rfx_compose_flow_f32 with
+ * clamp = 1, inb and flowUp, rfx_grid_sample_f32 of the up-sampled match21 at flowUp and rfx_match_score_f32 compute, operation for
+ * operation and bit for bit, without the up-sampled maps, flowUp, inb and the sampled cycle map in memory.
+ * flowDown8 (N,2,hd,wd); match12Down8 / match21Down8: N planes of hd*wd floats, image i at + i*stride (the two halves of one
+ * (2N,1,hd,wd) tensor: stride hd*wd); coarseGrid (N,Hc,Wc,2); outputs at (H,W) -- (Hc,Wc) everywhere except in the KITTI
+ * full-resolution pass (evaluation/evalKITTI/evaluation.py:302) -- flow12 (N,H,W,2) and match (N,H,W) = (match12 * cycle) * inb,
+ * both caller-owned (views of packed buffers); no input may alias an output.  Records inside a group (rfx_group_begin). */
+int rfx_cycle_tail_f32(const float* flowDown8, const float* match12Down8, long long match12_stride, const float* match21Down8,
+                       long long match21_stride, const float* coarseGrid, float* flow12, float* match, int N, int hd, int wd,
+                       int Hc, int Wc, int H, int W, void* stream);
+
 /* The small-component filter of the KITTI scripts (evaluation/evalKITTI/evaluation.py:85-100 online -- remove_small_cc(match,
  * 0.99, cc_th) at :321 -- and evaluation/evalKITTI/getResults.py:66-84 offline, :122), which the reference runs on the host
  * with skimage.measure.label: out = in with every 8-connected component of (in > match_th) of at most max_area pixels set to

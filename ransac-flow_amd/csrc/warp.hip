@@ -231,6 +231,107 @@ __global__ __launch_bounds__(256) void match_score_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// cycle_tail: the tail of the cycle-checked PredFlowMask forms (evaluation/evalYFCC/evaluation.py:47-58, evalKITTI/evaluation.py:66-81),
+// what rfx_resize_bilinear_f32(align_corners = 0) of both matchability maps -> rfx_compose_flow_f32(clamp, inb, flowUp) ->
+// rfx_grid_sample_f32(up-sampled match21, flowUp) -> rfx_match_score_f32 give, per pixel, without the four full-resolution maps in
+// between (both up-sampled matchabilities, flowUp, inb, the sampled cycle map).  The /8 maps are a few KB per image and stay in cache.
+// Every float operation is the chain's, spelled out (__fmul_rn / __fadd_rn / fmaf) as the chain's kernels are compiled: the sums the
+// compiler contracts there are the fmaf calls here, so the result does not depend on what it would contract in this body.
+struct CycleTailArgs {
+    const float* flowDown; const float* m12; const float* m21; const float* coarse; float* flow12; float* match;
+    long long NP, m12_stride, m21_stride;    // N * H * W; floats between two images' planes of match12Down8 / match21Down8
+    int hd, wd, Hc, Wc, H, W; float sh, sw;
+};
+
+// the taps of resize_bilinear_body (align_corners = 0) at one output pixel: the upper left tap's offset inside a plane, the steps to
+// the clamped right and lower neighbours and the two fractions
+struct UpTap { int o00, dx, dy; float lx, ly; };
+
+__device__ __forceinline__ UpTap up_tap(float sh, float sw, int y, int x, int hd, int wd) {
+    UpTap t;
+    const float fy = src_index(sh, y), fx = src_index(sw, x);
+    int y0 = (int)fy, x0 = (int)fx;
+    y0 = y0 < hd - 1 ? y0 : hd - 1;          // (never taken by an index the rule above produces: keeps every read inside the plane)
+    x0 = x0 < wd - 1 ? x0 : wd - 1;
+    t.ly = fy - (float)y0;
+    t.lx = fx - (float)x0;
+    t.o00 = y0 * wd + x0;
+    t.dx = x0 < wd - 1 ? 1 : 0;
+    t.dy = y0 < hd - 1 ? wd : 0;
+    return t;
+}
+
+// resize_bilinear_body's per-sample expression, operation for operation
+__device__ __forceinline__ float up_resize(const float* __restrict__ plane, const UpTap& t) {
+    const float* q = plane + t.o00;
+    const float v00 = q[0], v01 = q[t.dx], v10 = q[t.dy], v11 = q[t.dy + t.dx];
+    const float hy = 1.f - t.ly, hx = 1.f - t.lx;
+    const float r0 = fmaf(v01, t.lx, __fmul_rn(v00, hx));
+    const float r1 = fmaf(v11, t.lx, __fmul_rn(v10, hx));
+    return fmaf(r1, t.ly, __fmul_rn(r0, hy));
+}
+
+// compose_flow_body's up-sampling of one residual-flow channel: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11), contracted
+// as compose_flow_kernel is (the second product of every sum fused)
+__device__ __forceinline__ float up_flow(const float* __restrict__ plane, const UpTap& t) {
+    const float* q = plane + t.o00;
+    const float v00 = q[0], v01 = q[t.dx], v10 = q[t.dy], v11 = q[t.dy + t.dx];
+    const float hy = 1.f - t.ly, hx = 1.f - t.lx;
+    const float top = fmaf(t.lx, v01, __fmul_rn(hx, v00));
+    const float bot = fmaf(t.lx, v11, __fmul_rn(hx, v10));
+    return fmaf(hy, top, __fmul_rn(t.ly, bot));
+}
+
+__device__ __forceinline__ void cycle_tail_body(const CycleTailArgs& a, const unsigned bx, const unsigned gx_) {
+    const float* __restrict__ flowDown = a.flowDown;
+    const float* __restrict__ m12 = a.m12;
+    const float* __restrict__ m21 = a.m21;
+    const float* __restrict__ coarse = a.coarse;
+    float* __restrict__ flow12 = a.flow12;
+    float* __restrict__ match = a.match;
+    const int hd = a.hd, wd = a.wd, Hc = a.Hc, Wc = a.Wc, H = a.H, W = a.W;
+    const float sh = a.sh, sw = a.sw;
+    const size_t HW = (size_t)H * W, hw = (size_t)hd * wd, HWc = (size_t)Hc * Wc;
+    for (long long p = (long long)bx * blockDim.x + threadIdx.x; p < a.NP; p += (long long)gx_ * blockDim.x) {
+        const long long n = p / (long long)HW;
+        const int px = (int)(p - n * (long long)HW);
+        const int y = px / W, x = px - y * W;
+        const UpTap t = up_tap(sh, sw, y, x, hd, wd);
+        // compose_flow (clamp = 1): the sampling grid, flow12, the in-bounds mask
+        const float* f = flowDown + (size_t)n * 2 * hw;
+        float gx = __fadd_rn(up_flow(f, t), rfx_lin(x, W)), gy = __fadd_rn(up_flow(f + hw, t), rfx_lin(y, H));
+        gx = fminf(fmaxf(gx, -1.0f), 1.0f);
+        gy = fminf(fmaxf(gy, -1.0f), 1.0f);
+        const Corners c = corners(gx, gy, Hc, Wc, 0);
+        const float2* cg = reinterpret_cast<const float2*>(coarse) + (size_t)n * HWc;
+        const long long o00 = (long long)c.y0 * Wc + c.x0;
+        float ox = 0.f, oy = 0.f;
+        if (c.m_nw) { const float2 v = cg[o00]; ox = fmaf(v.x, c.nw, ox); oy = fmaf(v.y, c.nw, oy); }
+        if (c.m_ne) { const float2 v = cg[o00 + 1]; ox = fmaf(v.x, c.ne, ox); oy = fmaf(v.y, c.ne, oy); }
+        if (c.m_sw) { const float2 v = cg[o00 + Wc]; ox = fmaf(v.x, c.sw, ox); oy = fmaf(v.y, c.sw, oy); }
+        if (c.m_se) { const float2 v = cg[o00 + Wc + 1]; ox = fmaf(v.x, c.se, ox); oy = fmaf(v.y, c.se, oy); }
+        float2 o; o.x = ox; o.y = oy;
+        reinterpret_cast<float2*>(flow12)[p] = o;
+        const float inb = (ox >= -1.0f && ox <= 1.0f && oy >= -1.0f && oy <= 1.0f) ? 1.0f : 0.0f;
+        // resize_bilinear of match12Down8 at the pixel
+        const float v12 = up_resize(m12 + n * a.m12_stride, t);
+        // grid_sample of the up-sampled match21 (H x W) at (gx, gy): each tap is the resize expression at that tap's integer pixel
+        const Corners k = corners(gx, gy, H, W, 0);
+        const float* s21 = m21 + n * a.m21_stride;
+        float cyc = 0.0f;
+        if (k.m_nw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, k.y0, k.x0, hd, wd)), k.nw, cyc);
+        if (k.m_ne) cyc = fmaf(up_resize(s21, up_tap(sh, sw, k.y0, k.x0 + 1, hd, wd)), k.ne, cyc);
+        if (k.m_sw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, k.y0 + 1, k.x0, hd, wd)), k.sw, cyc);
+        if (k.m_se) cyc = fmaf(up_resize(s21, up_tap(sh, sw, k.y0 + 1, k.x0 + 1, hd, wd)), k.se, cyc);
+        // match_score: (match12 * cycle) * in-bounds, left to right
+        match[p] = __fmul_rn(__fmul_rn(v12, cyc), inb);
+    }
+}
+
+using CycleTail = RfxFamily<CycleTailArgs, cycle_tail_body, 256>;
+__global__ __launch_bounds__(CycleTail::BLOCK) void cycle_tail_kernel(CycleTailArgs a) { cycle_tail_body(a, blockIdx.x, gridDim.x); }
+
 }  // namespace
 
 // predFlowCoarse's tail (model/model.py:333-340): flowGrad = || f[:, :, 1:, 1:] - f[:, :, :-1, :-1] ||_2 over the two flow
@@ -299,6 +400,22 @@ extern "C" int rfx_match_score_f32(const float* match12, long long match12_strid
                        match12_stride, cyc, inb, HW, total, score);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
+}
+
+extern "C" int rfx_cycle_tail_f32(const float* flowDown8, const float* match12Down8, long long match12_stride,
+                                  const float* match21Down8, long long match21_stride, const float* coarseGrid, float* flow12,
+                                  float* match, int N, int hd, int wd, int Hc, int Wc, int H, int W, void* stream) {
+    if (!flowDown8 || !match12Down8 || !match21Down8 || !coarseGrid || !flow12 || !match || N <= 0 || hd <= 0 || wd <= 0 || Hc <= 0 ||
+        Wc <= 0 || H <= 0 || W <= 0)
+        return RFX_E_ARG;
+    const long long hw = (long long)hd * wd;
+    // plane offsets inside one image are ints in the kernel; the strides may only matter where there is a second image
+    if (hw > 0x7fffffffLL || (long long)H * W > 0x7fffffffLL || (N > 1 && (match12_stride < hw || match21_stride < hw))) return RFX_E_ARG;
+    const long long NP = (long long)N * H * W;
+    const float sh = (float)hd / (float)H, sw = (float)wd / (float)W;
+    const CycleTailArgs a = {flowDown8, match12Down8, match21Down8, coarseGrid, flow12, match, NP, match12_stride, match21_stride,
+                             hd, wd, Hc, Wc, H, W, sh, sw};
+    return CycleTail::launch(cycle_tail_kernel, a, (unsigned)grid_for(NP, CycleTail::BLOCK), rfx_stream(stream));
 }
 
 extern "C" int rfx_flow_grad_clamp_f32(const float* flowCoarse, const float* grid, float* flowGrad, float* flow, int B, int H,

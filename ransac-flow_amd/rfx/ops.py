@@ -119,7 +119,7 @@ class Profiler:
 
 class launch_group:
     """``with ops.launch_group(device):`` -- the convolution ops and the fine-stage ops (stem_conv_maxblur, blurpool2d, l2norm,
-    flow_head, resize_bilinear, corr_neigh / corr_neigh_bidir, warp_grid, grid_sample, compose_flow) issued inside are RECORDED by
+    flow_head, resize_bilinear, corr_neigh / corr_neigh_bidir, warp_grid, grid_sample, compose_flow, cycle_tail) issued inside are RECORDED by
     the library and launched at exit as ONE launch per kernel instance (rfx_group_begin / rfx_group_end: blockIdx.y selects the
     problem).  For the same layer of several independent inputs of different sizes; chains use it through ``stage``, which also
     keeps the one rule: a recorded op may not READ an output of the same group, on the device or with an eager torch op.  Not used
@@ -225,8 +225,9 @@ FINE_GROUPS_DEFAULT = True
 
 def fine_groups_enabled(env=None):
     """RFX_FINE_GROUPS: the fine stage of the ragged drivers (rounds.RaggedGroup, AlignPipeline._fine_ragged) as ONE chain of grouped
-    launches over all shape groups (AlignPipeline.pred_flow_mask_groups / fine_quickstart_groups) instead of one chain per shape
-    group.  "1" / "0"; unset = FINE_GROUPS_DEFAULT.  Always off under a Profiler (grouped launches are not profiled)."""
+    launches over all shape groups (AlignPipeline.pred_flow_mask_groups / pred_flow_mask_cycle_groups / kitti_fine_round_groups /
+    fine_quickstart_groups) instead of one chain per shape group.  "1" / "0"; unset = FINE_GROUPS_DEFAULT (and, in the round drivers,
+    the driver's own ``grouped_fine``).  Always off under a Profiler (grouped launches are not profiled)."""
     env = os.environ if env is None else env
     v = str(env.get("RFX_FINE_GROUPS", "")).strip()
     on = FINE_GROUPS_DEFAULT if v == "" else v != "0"
@@ -1062,6 +1063,42 @@ def match_score(match12, cyc=None, inb=None):
     out = torch.empty((n, H, W), dtype=torch.float32, device=match12.device)
     _call("rfx_match_score_f32", _one_device(match12, c, b), match12.data_ptr(), stride, _p(c), _p(b), n, H * W, _p(out))
     return out
+
+
+def _down8_planes(m, B, hd, wd, name):
+    """A /8 matchability map (B,1,hd,wd) with contiguous planes (a batch slice of a larger tensor allowed) -> its batch stride."""
+    if not isinstance(m, torch.Tensor) or not m.is_cuda or m.dtype != torch.float32:
+        raise RuntimeError("%s must be a float32 tensor on a HIP device (no CPU fallback)" % name)
+    if tuple(m.shape) != (B, 1, hd, wd) or (hd * wd > 1 and (m.stride(3) != 1 or m.stride(2) != wd)) or \
+            (B > 1 and m.stride(0) < hd * wd):
+        raise ValueError("%s must be (%d,1,%d,%d) with contiguous planes, got %s" % (name, B, hd, wd, tuple(m.shape)))
+    return m.stride(0) if B > 1 else hd * wd
+
+
+def cycle_tail(flowDown8, match12Down8, match21Down8, coarseGrid, out_hw=None, flow12_out=None, match_out=None):
+    """The tail of the cycle-checked PredFlowMask forms in one kernel (rfx_cycle_tail_f32): bit for bit what
+    resize_bilinear(both matchability maps) -> compose_flow(clamp=True, want_inb, want_flow_up, out_hw) -> grid_sample(up-sampled
+    match21, flowUp) -> match_score give, without their full-resolution intermediates.  flowDown8 (B,2,hd,wd); match12Down8 /
+    match21Down8 (B,1,hd,wd), e.g. the two halves of one (2B,1,hd,wd) tensor; coarseGrid (B,Hc,Wc,2); ``out_hw``: the output size when
+    it is not the coarse grid's (KITTI full-resolution pass).  ``flow12_out`` (B,H,W,2) / ``match_out`` (B,H,W): where the results go
+    (views of packed buffers) instead of new tensors; they may not alias an input.  -> (flow12 (B,H,W,2), match (B,H,W))."""
+    flowDown8, coarseGrid = _dev(flowDown8, "flowDown8"), _dev(coarseGrid, "coarse grid")
+    if flowDown8.dim() != 4 or flowDown8.shape[1] != 2:
+        raise ValueError("flowDown8 must be (B,2,hd,wd), got %s" % (tuple(flowDown8.shape),))
+    B, _, hd, wd = flowDown8.shape
+    if coarseGrid.dim() != 4 or coarseGrid.shape[0] != B or coarseGrid.shape[3] != 2:
+        raise ValueError("coarse grid must be (%d,Hc,Wc,2), got %s" % (B, tuple(coarseGrid.shape)))
+    s12 = _down8_planes(match12Down8, B, hd, wd, "match12Down8")
+    s21 = _down8_planes(match21Down8, B, hd, wd, "match21Down8")
+    Hc, Wc = coarseGrid.shape[1], coarseGrid.shape[2]
+    H, W = (Hc, Wc) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    flow12 = _out_or_new(flow12_out, (B, H, W, 2), flowDown8, "cycle_tail flow12")
+    match = _out_or_new(match_out, (B, H, W), flowDown8, "cycle_tail match")
+    if flow12.data_ptr() % 8 or coarseGrid.data_ptr() % 8:
+        raise ValueError("cycle_tail: flow12 and the coarse grid are accessed as float2 and must be 8-byte aligned")
+    _call("rfx_cycle_tail_f32", _one_device(flowDown8, match12Down8, match21Down8, coarseGrid), _p(flowDown8), _p(match12Down8), s12,
+          _p(match21Down8), s21, _p(coarseGrid), _p(flow12), _p(match), B, hd, wd, Hc, Wc, H, W)
+    return flow12, match
 
 
 def merge_multi_h(flow, match12, th, multiH, cyc=None, inb=None):

@@ -582,6 +582,45 @@ class AlignPipeline:
         ops.corr_neigh_bidir_group(featt, feats, outs=cs)
         return cs
 
+    def _pred_heads(self, feats, featt, fcs, hw_list):
+        """The part of the PredFlowMask chain that the plain and the cycle-checked forms share, over G shape groups: both correlation
+        directions, the flow head and the matchability head (both matchability passes in one batch).  ``hw_list``: the size the
+        group's full-resolution outputs have.  Returns (layout, new, cut, packed /8 flow, its per-group views, the one group's whole
+        (2B,1,h/8,w/8) matchability or None, per-group (match12Down8, match21Down8), packed match12Down8, packed match21Down8);
+        ``new(n)`` makes a flat buffer, ``cut(t)`` the per-group (B,1,h,w) views of a packed full-resolution buffer."""
+        lay = packed_group_offsets([(fc.shape[0], hw[0], hw[1], ft.shape[2], ft.shape[3]) for fc, hw, ft in zip(fcs, hw_list, featt)])
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
+        cut = lambda t: [t[o:o + B * h * w].view(B, 1, h, w) for (B, h, w, _, _), o in zip(lay["shapes"], lay["off"])]
+        cut8 = lambda t, c=1: [t[c * o8:c * (o8 + B * h8 * w8)].view(B, c, h8, w8) for (B, _, _, h8, w8), o8 in zip(lay["shapes"], lay["off8"])]
+        cs = self._corr_both(featt, feats)
+        f8 = new(2 * lay["total8"])
+        fd8 = self.flow.forward_group([c[:c.shape[0] // 2] for c in cs], False, False, outs=cut8(f8, 2))
+        if len(fcs) == 1:
+            # one group's batch is written as a whole: the last convolution is one launch over its 2B volumes
+            md = self.match.forward_group(cs, False, False)[0]
+            halves = [(md[:md.shape[0] // 2], md[md.shape[0] // 2:])]
+            m12, m21 = halves[0][0].reshape(-1), halves[0][1].reshape(-1)
+        else:
+            md, m12, m21 = None, new(lay["total8"]), new(lay["total8"])
+            halves = self.match.trunk.forward_group(cs, False, halves_out=list(zip(cut8(m12), cut8(m21))))
+        return lay, new, cut, f8, fd8, md, halves, m12, m21
+
+    def _pred_flow_mask_cycle_lists(self, feats, featt, fcs, out_hw_list=None, out=None):
+        """The cycle-checked PredFlowMask chain after the features over G shape groups (pred_flow_mask_lists' ``cycle`` form takes one):
+        the shared heads, then ONE stage of ops.cycle_tail, which writes every group's match straight into the packed buffer.  Group g's
+        outputs live at out_hw_list[g] (default: its coarse grid's size).  Per group bit-identical to the one-group form; returns and
+        ``out`` as pred_flow_mask_lists' plain form."""
+        hws = [tuple(fc.shape[1:3]) if hw is None else (int(hw[0]), int(hw[1])) for fc, hw in zip(fcs, out_hw_list or [None] * len(fcs))]
+        lay, new, cut, f8, fd8, _, halves, m12, m21 = self._pred_heads(feats, featt, fcs, hws)
+        packed = new(lay["total"])
+        match = cut(packed)
+        tails = self._stage(lambda d, h, fc, hw, m_out: ops.cycle_tail(d, h[0], h[1], fc, out_hw=hw, match_out=m_out[:, 0]),
+                            fd8, halves, fcs, hws, match)
+        if out is not None:
+            out.update(match=packed, flowDown8=f8, match12Down8=m12, match21Down8=m21, layout=lay)
+        return [dict(flow12=tails[g][0], match=match[g], flowDown8=fd8[g], match12Down8=halves[g][0], match21Down8=halves[g][1])
+                for g in range(len(fcs))]
+
     def pred_flow_mask_lists(self, feats, featt, fcs, cycle=False, out_hw=None, out=None):
         """The PredFlowMask chain after the features, written once, over G shape groups: group g = normalised source features
         feats[g] and target features featt[g] (B_g,256,h/8,w/8) and the coarse grid fcs[g] (B_g,h,w,2).  Both correlation directions,
@@ -597,21 +636,7 @@ class AlignPipeline:
         G = len(fcs)
         if cycle and G > 1:
             raise ValueError("the cycle-checked PredFlowMask forms take one shape group per call, got %d" % G)
-        lay = packed_group_offsets([(fc.shape[0], fc.shape[1], fc.shape[2], ft.shape[2], ft.shape[3]) for fc, ft in zip(fcs, featt)])
-        new = lambda n: torch.empty(n, dtype=torch.float32, device=self.dev)
-        cut = lambda t: [t[o:o + B * h * w].view(B, 1, h, w) for (B, h, w, _, _), o in zip(lay["shapes"], lay["off"])]
-        cut8 = lambda t, c=1: [t[c * o8:c * (o8 + B * h8 * w8)].view(B, c, h8, w8) for (B, _, _, h8, w8), o8 in zip(lay["shapes"], lay["off8"])]
-        cs = self._corr_both(featt, feats)
-        f8 = new(2 * lay["total8"])
-        fd8 = self.flow.forward_group([c[:c.shape[0] // 2] for c in cs], False, False, outs=cut8(f8, 2))
-        if G == 1:
-            # one group's batch is written as a whole: the last convolution is one launch over its 2B volumes
-            md = self.match.forward_group(cs, False, False)[0]
-            halves = [(md[:md.shape[0] // 2], md[md.shape[0] // 2:])]
-            m12, m21 = halves[0][0].reshape(-1), halves[0][1].reshape(-1)
-        else:
-            m12, m21 = new(lay["total8"]), new(lay["total8"])
-            halves = self.match.trunk.forward_group(cs, False, halves_out=list(zip(cut8(m12), cut8(m21))))
+        lay, new, cut, f8, fd8, md, halves, m12, m21 = self._pred_heads(feats, featt, fcs, [fc.shape[1:3] for fc in fcs])
         if cycle:
             B = fcs[0].shape[0]
             H, W = fcs[0].shape[1:3] if out_hw is None else out_hw
@@ -656,6 +681,14 @@ class AlignPipeline:
         the fine size."""
         feats, featt = self._features_both([IsSample], [ItSample])
         return self.pred_flow_mask_lists(feats, featt, [flowCoarse], cycle=True, out_hw=out_hw)[0]
+
+    def pred_flow_mask_kitti_groups(self, IsSample_list, ItSample_list, fcs, out_hw_list=None, out=None):
+        """pred_flow_mask_kitti for G shape groups in one call: group g = sampled sources IsSample_list[g] and targets ItSample_list[g]
+        (B_g,3,h,w), coarse grid fcs[g] (B_g,h,w,2), outputs at out_hw_list[g] (None: the grid's size).  Every step is one ops.stage
+        over the groups and the tail is ops.cycle_tail.  Returns one dict per group with pred_flow_mask_kitti's keys, each tensor
+        bit-identical to pred_flow_mask_kitti on that group alone; the packed buffers and ``out``: pred_flow_mask_lists."""
+        feats, featt = self._features_both(IsSample_list, ItSample_list)
+        return self._pred_flow_mask_cycle_lists(feats, featt, fcs, out_hw_list, out)
 
     # ---------------------------------------------------------------- multi-homography driver (SURVEY 8f1)
     def multi_h(self, prep, b=0, maxCoarse=10, maskRegionTh=0.01, It_bg=None, feats=None, sample_fn=None):
@@ -797,6 +830,13 @@ class AlignPipeline:
         """PredFlowMask of evaluation/evalYFCC/evaluation.py:32-58 (= evalCorr/evaluation.py:29-56) for a batch: the Hpatch form
         (pred_flow_mask) with the CYCLE-CHECKED matchability, all at the target's resolution, target features handed in."""
         return self.pred_flow_mask_lists(self._sampled_features([IsTensor], [flowCoarse]), [featt], [flowCoarse], cycle=True)[0]
+
+    def pred_flow_mask_cycle_groups(self, Is_list, featt_list, Hs_list, hw_list, out=None):
+        """warp_grid + pred_flow_mask_cycle for G shape groups in one call (arguments as pred_flow_mask_groups): every step one ops.stage
+        over the groups, the tail ops.cycle_tail.  Returns one dict per group with pred_flow_mask_cycle's keys, each tensor
+        bit-identical to pred_flow_mask_cycle on that group alone; the packed buffers and ``out``: pred_flow_mask_lists."""
+        fcs = self._stage(lambda Hs, hw: ops.warp_grid(Hs, hw[0], hw[1]), Hs_list, hw_list)
+        return self._pred_flow_mask_cycle_lists(self._sampled_features(Is_list, fcs), featt_list, fcs, out=out)
 
     def multi_h_variant_c(self, src_u8, tgt_candidates_u8, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None,
                           want_lists=True, pair_ids=None, draw_epoch=0, split=None):
@@ -1109,6 +1149,27 @@ class AlignPipeline:
                 mh = match.cpu().numpy()
                 match = torch.from_numpy(np.stack([remove_small_cc(mh[k], 0.99, cc_th) for k in range(mh.shape[0])])).to(self.dev)
         return flow_d2, pm, match
+
+    def kitti_fine_round_groups(self, Hs_list, tensor_s_list, tensor_d2_list, tensor_resize_list, org_hw_list, out=None):
+        """kitti_fine_round(..., cc_th=0) for G shape groups in one call: group g = homographies Hs_list[g] (a_g,3,3), sources
+        tensor_s_list[g], targets at the half and the full fine resolution tensor_d2_list[g] / tensor_resize_list[g], original target
+        size org_hw_list[g].  Every step is one ops.stage over the groups: both warp_grids, the half-resolution warp, the KITTI form
+        there, compose_flow of its /8 flow with the full-resolution grid, the full-resolution warp, the KITTI form at the original
+        size.  Returns one (flow_d2, PredFlowMask dict of the full-resolution pass, match (a_g,h_org,w_org) -- unfiltered) per group,
+        bit-identical to kitti_fine_round on that group alone; ``out`` receives the packed buffers of the full-resolution pass
+        (pred_flow_mask_lists) and ``flowD2``, the half-resolution /8 flows packed in group order."""
+        st = self._stage
+        hom_d2 = st(lambda Hs, t: ops.warp_grid(Hs, t.shape[2], t.shape[3]), Hs_list, tensor_d2_list)
+        hom_resize = st(lambda Hs, t: ops.warp_grid(Hs, t.shape[2], t.shape[3]), Hs_list, tensor_resize_list)
+        Is_d2 = st(ops.grid_sample, tensor_s_list, hom_d2)
+        half = {}
+        flow_d2 = [pm["flowDown8"] for pm in self.pred_flow_mask_kitti_groups(Is_d2, tensor_d2_list, hom_d2, out=half)]
+        flowCoarse = st(lambda d, fc: ops.compose_flow(d, fc, clamp=True)[0], flow_d2, hom_resize)
+        IsSample = st(ops.grid_sample, tensor_s_list, flowCoarse)
+        pms = self.pred_flow_mask_kitti_groups(IsSample, tensor_resize_list, flowCoarse, out_hw_list=org_hw_list, out=out)
+        if out is not None:
+            out["flowD2"] = half["flowDown8"]
+        return [(d2, pm, pm["match"][:, 0]) for d2, pm in zip(flow_d2, pms)]
 
     def multi_h_kitti_batched(self, src_u8, tgt_u8, fineSize=650, maskRegionTh=0.005, cc_th=0.01, It_bg=None, sample_fn=None,
                               remove_small_cc=None, records=None, want_lists=True, trace=None, pair_ids=None, draw_epoch=0, split=None):

@@ -374,11 +374,23 @@ class RaggedGroup:
         for g in self.fine_groups:
             g["featt"] = ragged.rows(ft, g["members"])
 
-    grouped_fine = True                  # all fine groups of a round as one chain of grouped launches (where RFX_FINE_GROUPS is on)
+    # all fine groups of a round as one chain of grouped launches: the driver's default where RFX_FINE_GROUPS is unset (a driver whose
+    # grouped chain measured slower keeps False here; RFX_FINE_GROUPS=1 / 0 selects either way)
+    grouped_fine = True
+
+    def use_groups(self):
+        """Whether this round's fine stage runs as one grouped chain: RFX_FINE_GROUPS where set, else the driver's ``grouped_fine``;
+        never under a Profiler (ops.fine_groups_enabled)."""
+        unset = str(os.environ.get("RFX_FINE_GROUPS", "")).strip() == ""
+        return ops.fine_groups_enabled() and (self.grouped_fine or not unset)
 
     def pred_group(self, Is, featt, flowCoarse):
         """The fine pass of one fine group's active members (the per-group form)."""
         return self.st.pipe.pred_flow_mask(Is, featt, flowCoarse)
+
+    def pred_groups(self, Is_list, featt_list, Hs_list, hw_list, out):
+        """The fine pass of all fine groups' active members as one chain of grouped launches."""
+        return self.st.pipe.pred_flow_mask_groups(Is_list, featt_list, Hs_list, hw_list, out=out)
 
     def take(self, ent, t, key):
         """The rows of ``t`` that round-group entry ``ent`` works on: key "sel" = its active members out of a fine group's stacked
@@ -406,12 +418,12 @@ class RaggedGroup:
 
     def fine(self, A, active, Hs, bestH, res, n_dev):
         rg, T, a, take = self.rg, self.T, len(active), self.take
-        if self.grouped_fine and ops.fine_groups_enabled():
+        if self.use_groups():
             # fine stage: all fine groups as ONE chain of grouped launches; its packed outputs are in fine-group order, which is the
             # order matches() laid the round's offsets out in -- they go to the accept kernel as they are
             packed = {}
-            pms = self.st.pipe.pred_flow_mask_groups([take(e, e["g"]["Is"], "sel") for e in rg], [take(e, e["g"]["featt"], "sel") for e in rg],
-                                                     [take(e, Hs, "kidx") for e in rg], [e["g"]["hw"] for e in rg], out=packed)
+            pms = self.pred_groups([take(e, e["g"]["Is"], "sel") for e in rg], [take(e, e["g"]["featt"], "sel") for e in rg],
+                                   [take(e, Hs, "kidx") for e in rg], [e["g"]["hw"] for e in rg], packed)
             for ent, pm in zip(rg, pms):
                 ent["pm"] = pm
             pack = lambda key: packed[key]
@@ -450,12 +462,11 @@ class RaggedVariantCGroup(RaggedGroup):
     with the differences VariantCGroup has over DenseGroup.  Every round RE-MATCHES: ONE rfx_keep_mask_ragged_f32 for the active pairs
     (keep map of the explained-region mask + background, written into each pair's own row, and the round's nB table: rt * ct at the
     active positions, 0 elsewhere), ONE masked ragged mutual matching that skips the inactive pairs on that table, ONE gather of the
-    active pairs' matches.  The fine stage is the cycle-checked PredFlowMask, once per fine group of active pairs (no grouped chain);
-    its matchability maps are packed in fine-group order for the ragged accept kernel (mode 0).  ``batch``: RaggedGroup's (idx1 /
+    active pairs' matches.  The fine stage is the cycle-checked PredFlowMask over the active members of all fine groups as one chain
+    of grouped launches (AlignPipeline.pred_flow_mask_cycle_groups; RFX_FINE_GROUPS off: once per fine group); its matchability maps
+    are packed in fine-group order for the ragged accept kernel (mode 0).  ``batch``: RaggedGroup's (idx1 /
     idx2 / cnt None: nothing is cached) with ``feats`` = the CHOSEN candidates' featB / nB / offB and the tables of
     ragged.ragged_variant_c_tables."""
-    grouped_fine = False
-
     def __init__(self, st, batch, lo, hi):
         super().__init__(st, batch, lo, hi)
         f, dev = self.feats, st.pipe.dev
@@ -480,6 +491,9 @@ class RaggedVariantCGroup(RaggedGroup):
     def pred_group(self, Is, featt, flowCoarse):
         return self.st.pipe.pred_flow_mask_cycle(Is, featt, flowCoarse)
 
+    def pred_groups(self, Is_list, featt_list, Hs_list, hw_list, out):
+        return self.st.pipe.pred_flow_mask_cycle_groups(Is_list, featt_list, Hs_list, hw_list, out=out)
+
 
 class RaggedKittiGroup(RaggedGroup):
     """Pairs [lo, hi) of a ragged batch of the KITTI driver: RaggedGroup with the differences KittiGroup has over DenseGroup -- the
@@ -487,9 +501,10 @@ class RaggedKittiGroup(RaggedGroup):
     with the capacity stop, flowD2 collected and traced.  The packed masks live at the ORIGINAL target sizes
     (ragged.ragged_kitti_tables).  A fine group is the pairs of the slice that share (source ORIGINAL shape, target ORIGINAL shape):
     the source is sampled at its original size and the outputs live at the original target size, so two pairs whose resized shapes
-    coincide but whose originals differ are two groups.  A round runs pipeline.kitti_fine_round (without its dense filter) once per
-    fine group over its active members, packs the matchability maps in fine-group order, then ONE rfx_remove_small_cc_ragged_f32 in
-    place for all active pairs and ONE ragged accept (mode 1) with the flowD2 store.  ``batch``: RaggedGroup's plus tensor_s /
+    coincide but whose originals differ are two groups.  A round runs the two-resolution fine pass over the active members of all fine
+    groups as one chain of grouped launches (pipeline.kitti_fine_round_groups; RFX_FINE_GROUPS off: pipeline.kitti_fine_round, without
+    its dense filter, once per fine group, the matchability maps packed in fine-group order), then ONE rfx_remove_small_cc_ragged_f32
+    on a copy of the packed maps for all active pairs and ONE ragged accept (mode 1) with the flowD2 store.  ``batch``: RaggedGroup's plus tensor_s /
     tensor_d2 / tensor_resize (per-pair (1,3,.,.) lists), d2 (per-pair (hd2, wd2) of the half-resolution /8 flow), d2dims (B,2) on the
     device, cc_th / remove_small_cc."""
     accept_mode = 1
@@ -519,18 +534,28 @@ class RaggedKittiGroup(RaggedGroup):
     def fine(self, A, active, Hs, bestH, res, n_dev):
         rg, T, a, gm, x0, take = self.rg, self.T, len(active), self.gm, self.x0, self.take
         pipe = self.st.pipe
-        for ent in rg:
-            g = ent["g"]
-            ent["flow_d2"], ent["pm"], ent["match"] = pipe.kitti_fine_round(take(ent, Hs, "kidx"), take(ent, g["Is"], "sel"),
-                                                                            take(ent, g["d2"], "sel"), take(ent, g["resize"], "sel"),
-                                                                            g["hw"], cc_th=0)
-        pack = lambda key: self.pack([e["pm"][key] for e in rg])
+        if self.use_groups():
+            # both resolutions' fine passes: all fine groups as ONE chain of grouped launches, packed in fine-group order
+            packed = {}
+            per_group = pipe.kitti_fine_round_groups([take(e, Hs, "kidx") for e in rg], [take(e, e["g"]["Is"], "sel") for e in rg],
+                                                     [take(e, e["g"]["d2"], "sel") for e in rg], [take(e, e["g"]["resize"], "sel") for e in rg],
+                                                     [e["g"]["hw"] for e in rg], out=packed)
+            for ent, r in zip(rg, per_group):
+                ent["flow_d2"], ent["pm"], ent["match"] = r
+            pack, match, flow_d2, shared = (lambda key: packed[key]), packed["match"], packed["flowD2"], True
+        else:
+            for ent in rg:
+                g = ent["g"]
+                ent["flow_d2"], ent["pm"], ent["match"] = pipe.kitti_fine_round(take(ent, Hs, "kidx"), take(ent, g["Is"], "sel"),
+                                                                                take(ent, g["d2"], "sel"), take(ent, g["resize"], "sel"),
+                                                                                g["hw"], cc_th=0)
+            pack = lambda key: self.pack([e["pm"][key] for e in rg])
+            match, flow_d2, shared = self.pack([e["match"] for e in rg]), self.pack([e["flow_d2"] for e in rg]), len(rg) == 1
         max_hw = self.max_hw(active)
-        match = self.pack([e["match"] for e in rg])
         if self.cc_th > 0:                                                              # evalKITTI/evaluation.py:321
             if self.remove_small_cc is None:
-                if len(rg) == 1:
-                    match = match.clone()            # a view of the fine group's own map: keep PredFlowMask's output (trace) as it is
+                if shared:
+                    match = match.clone()            # the storage of PredFlowMask's own maps: keep its output (trace) as it is
                 ops.remove_small_cc_ragged(match, T[:a], T[x0 + a:x0 + 4 * a].to(torch.int32).view(a, 3), self.cc_th, 0.99,
                                            inplace=True, max_hw=max_hw)
             else:                                    # an injected host filter, called in pair order: one round trip
@@ -542,7 +567,7 @@ class RaggedKittiGroup(RaggedGroup):
         accept, gain = ops.multih_accept_ragged(match, T[:a], self.Mask, self.bg, self.moff, self.geom, A, res, n_dev, self.nbH,
                                                 self.st.maskRegionTh, self.accept_mode, max_hw, bestH=bestH, flowDown8=pack("flowDown8"),
                                                 match12Down8=pack("match12Down8"), match21Down8=pack("match21Down8"), off8=T[a:2 * a],
-                                                records=self.R, flowD2=self.pack([e["flow_d2"] for e in rg]), offd2=T[x0:x0 + a],
+                                                records=self.R, flowD2=flow_d2, offd2=T[x0:x0 + a],
                                                 d2dims=self.d2dims if self.R is None else None)
         return dict(accept=accept, gain=gain, where=self.where(), match=match)
 
