@@ -350,6 +350,28 @@ int rfx_cycle_tail_f32(const float* flowDown8, const float* match12Down8, long l
                        long long match21_stride, const float* coarseGrid, float* flow12, float* match, int N, int hd, int wd,
                        int Hc, int Wc, int H, int W, void* stream);
 
+/* The offline flow assembly of the HPatches, Corr and YFCC scripts (evaluation/evalHpatch/getResults.py:16-63,
+ * evaluation/evalCorr/getResults.py:78-136, evaluation/evalYFCC/getResults.py:150-190) for EVERY pair of a batch, straight from the
+ * result records of the multi-homography drivers, in ONE launch (ADDED under ABI 17: nothing existing moves).  Per pair b with
+ * n = nbH read from its record ON THE DEVICE (clamped to max_h; only homography 0 when multiH == 0) the outputs are, bit for bit,
+ * those of rfx_warp_grid_f32(H[:n]) -> rfx_compose_flow_f32(flowDown8[:n], clamp = 1, inb[, flowUp]) -> rfx_resize_bilinear_f32(
+ * matchDown8[:n], align_corners = 0) [-> cycle != 0: rfx_grid_sample_f32(up-sampled match21, flowUp)] -> rfx_merge_multi_h_f32(th,
+ * multiH) -- without any (n,H,W) intermediate: a thread walks the homographies of its pixel in the merge's order, stops at the owner,
+ * and forms a tap of a homography's coarse grid (H x W, the output size) from the nine numbers.  A pair with nbH == 0 gets zeros.
+ * rec: rec_elems floats, rows of `width` floats laid out as rfx_multih_accept_f32 / rfx_multih_accept_ragged_f32 fill them: [0] nbH,
+ * H (max_h,9) from off_H, flowDown8 (max_h,2,h8,w8) from off_flow, matchDown8 (max_h,2,h8,w8) (channel 0: 1->2, channel 1: 2->1)
+ * from the pair's off_match.  table (B,8) int64 on the device, row b: element offset of the pair's row in rec | h8 | w8 | off_match |
+ * H | W (output size) | pixel offset of the pair's maps in the packed outputs | 0 -- a pure function of the batch's size lists.
+ * A row that does not describe a record inside rec and a map inside the outputs is skipped.  max_hw = the largest H * W (sizes the
+ * grid; 8192 workgroups per pair at the most, larger maps take several trips).  bg: total_px bytes laid out like binary, or NULL;
+ * binary &= bg != 0 (YFCC), nothing else changes.  Outputs, total_px pixels each: flowGlobal (total_px,2) 8-byte aligned = the
+ * owner's flow clamped to [-1,1] with NaN kept, matchGlobal = the owner's score (score_0 where nobody reaches th), binary u8.
+ * No output may alias rec.  KITTI's two-level composition and component filter are not covered. */
+int rfx_assemble_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                             const long long* table, int B, long long max_hw, float th, int multiH, int cycle,
+                             const uint8_t* bg, float* flowGlobal, float* matchGlobal, uint8_t* binary, long long total_px,
+                             void* stream);
+
 /* The small-component filter of the KITTI scripts (evaluation/evalKITTI/evaluation.py:85-100 online -- remove_small_cc(match,
  * 0.99, cc_th) at :321 -- and evaluation/evalKITTI/getResults.py:66-84 offline, :122), which the reference runs on the host
  * with skimage.measure.label: out = in with every 8-connected component of (in > match_th) of at most max_area pixels set to

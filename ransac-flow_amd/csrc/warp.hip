@@ -59,6 +59,19 @@ struct ComposeFlowArgs {
     long long NP; int hd, wd, Hc, Wc, H, W; float sh, sw; int clampf;
 };
 
+// kornia's warp_grid at integer pixel (x, y) of an h x w grid: M (px, py, 1) divided by its third component
+__device__ __forceinline__ float2 warp_point(const float* __restrict__ M, int x, int y, int h, int w) {
+    const float px = rfx_lin(x, w), py = rfx_lin(y, h);
+    // (x', y', z') = M (px, py, 1): k-ordered fma chain like a K=3 sgemm
+    const float xs = fmaf(1.0f, M[2], fmaf(py, M[1], __fmul_rn(px, M[0])));
+    const float ys = fmaf(1.0f, M[5], fmaf(py, M[4], __fmul_rn(px, M[3])));
+    const float zs = fmaf(1.0f, M[8], fmaf(py, M[7], __fmul_rn(px, M[6])));
+    float2 o;
+    o.x = xs / zs;
+    o.y = ys / zs;
+    return o;
+}
+
 __device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsigned bx, const unsigned gx) {
     const float* __restrict__ Hm = a.Hm;
     float* __restrict__ grid = a.grid;
@@ -71,14 +84,7 @@ __device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsi
         const int y = (int)(r % h);
         const int b = (int)(r / h);
         const float* M = Hm + b * 9;
-        const float px = rfx_lin(x, w), py = rfx_lin(y, h);
-        // (x', y', z') = M (px, py, 1): k-ordered fma chain like a K=3 sgemm
-        const float xs = fmaf(1.0f, M[2], fmaf(py, M[1], px * M[0]));
-        const float ys = fmaf(1.0f, M[5], fmaf(py, M[4], px * M[3]));
-        const float zs = fmaf(1.0f, M[8], fmaf(py, M[7], px * M[6]));
-        float2 o;
-        o.x = xs / zs;
-        o.y = ys / zs;
+        const float2 o = warp_point(M, x, y, h, w);
         reinterpret_cast<float2*>(grid)[idx] = o;
     }
 }
@@ -332,6 +338,98 @@ __device__ __forceinline__ void cycle_tail_body(const CycleTailArgs& a, const un
 using CycleTail = RfxFamily<CycleTailArgs, cycle_tail_body, 256>;
 __global__ __launch_bounds__(CycleTail::BLOCK) void cycle_tail_kernel(CycleTailArgs a) { cycle_tail_body(a, blockIdx.x, gridDim.x); }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// assemble_records: the offline flow assembly (evaluation/evalHpatch/getResults.py:16-63, evalCorr/getResults.py:78-136,
+// evalYFCC/getResults.py:150-190) of EVERY pair of a batch straight from the drivers' result records -- what, per pair,
+// rfx_warp_grid_f32 -> rfx_compose_flow_f32(clamp, inb[, flowUp]) -> rfx_resize_bilinear_f32 [-> rfx_grid_sample_f32] ->
+// rfx_merge_multi_h_f32 give on the record's first nbH entries, bit for bit, in one launch: nbH is read here, nothing of size (n,H,W)
+// is stored.  blockIdx.y = the pair, blockIdx.x strides over the pair's own H x W pixels; a thread walks the homographies in the
+// merge's order and stops at the owner, so homography i >= 1 is evaluated only at the pixels that reach it.  The coarse grid of a
+// homography is not stored either: a tap of its bilinear sample is warp_grid_body's expression at the tap's integer pixel.
+// Float operations are spelled out as in cycle_tail_body.
+struct AssembleRecArgs {
+    const float* rec; const long long* table; const uint8_t* bg; float* flowG; float* matchG; uint8_t* binary;
+    long long rec_elems, total_px;           // floats in rec; pixels in each of the packed outputs (and in bg)
+    int width, max_h, off_H, off_flow, multiH, cycle; float th;
+};
+
+__global__ __launch_bounds__(256) void assemble_records_kernel(AssembleRecArgs a) {
+    // row blockIdx.y of the table: row offset in rec | h8 | w8 | off_match | H | W | offset of the pair's pixels in the outputs | 0
+    const long long* __restrict__ T = a.table + (long long)blockIdx.y * 8;
+    const long long row_off = T[0], h8l = T[1], w8l = T[2], off_match = T[3], Hl = T[4], Wl = T[5], out_off = T[6];
+    // a row that does not describe a record inside rec and a map inside the outputs is skipped: no read or write leaves the buffers
+    if (row_off < 0 || row_off + a.width > a.rec_elems || h8l <= 0 || w8l <= 0 || h8l > a.width || w8l > a.width || Hl <= 0 ||
+        Wl <= 0 || Hl > 0x7fffffffLL || Wl > 0x7fffffffLL || Hl * Wl > 0x7fffffffLL)
+        return;
+    const long long n8 = 2 * h8l * w8l * a.max_h, HWl = Hl * Wl;
+    if (off_match < a.off_flow + n8 || off_match + n8 > a.width || out_off < 0 || out_off + HWl > a.total_px) return;
+    const int hd = (int)h8l, wd = (int)w8l, H = (int)Hl, W = (int)Wl, HW = (int)HWl, hw = hd * wd;
+    const float* __restrict__ row = a.rec + row_off;
+    const float* __restrict__ Hm = row + a.off_H;
+    const float* __restrict__ flowDown = row + a.off_flow;
+    const float* __restrict__ matchDown = row + off_match;
+    const uint8_t* __restrict__ bg = a.bg ? a.bg + out_off : nullptr;
+    float2* __restrict__ flowG = reinterpret_cast<float2*>(a.flowG) + out_off;
+    float* __restrict__ matchG = a.matchG + out_off;
+    uint8_t* __restrict__ binary = a.binary + out_off;
+    const float nf = row[0];                                   // nbH, a small integer held as a float
+    const int nb = nf >= 1.0f ? (nf < (float)a.max_h ? (int)nf : a.max_h) : 0;
+    const int last = a.multiH ? nb : (nb < 1 ? nb : 1);
+    const float sh = (float)hd / (float)H, sw = (float)wd / (float)W, th = a.th;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < HW; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
+        const int y = p / W, x = p - y * W;
+        const UpTap t = up_tap(sh, sw, y, x, hd, wd);
+        float2 fbest;
+        fbest.x = 0.0f; fbest.y = 0.0f;
+        float mbest = 0.0f;
+        bool found = false;
+        for (int i = 0; i < last; ++i) {
+            // compose_flow (clamp = 1) on homography i's grid: the sampling point, flow_i, the in-bounds mask
+            const float* f = flowDown + (size_t)i * 2 * hw;
+            float gx = __fadd_rn(up_flow(f, t), rfx_lin(x, W)), gy = __fadd_rn(up_flow(f + hw, t), rfx_lin(y, H));
+            gx = fminf(fmaxf(gx, -1.0f), 1.0f);
+            gy = fminf(fmaxf(gy, -1.0f), 1.0f);
+            const Corners c = corners(gx, gy, H, W, 0);
+            const float* M = Hm + i * 9;
+            float ox = 0.f, oy = 0.f;
+            if (c.m_nw) { const float2 v = warp_point(M, c.x0, c.y0, H, W); ox = fmaf(v.x, c.nw, ox); oy = fmaf(v.y, c.nw, oy); }
+            if (c.m_ne) { const float2 v = warp_point(M, c.x0 + 1, c.y0, H, W); ox = fmaf(v.x, c.ne, ox); oy = fmaf(v.y, c.ne, oy); }
+            if (c.m_sw) { const float2 v = warp_point(M, c.x0, c.y0 + 1, H, W); ox = fmaf(v.x, c.sw, ox); oy = fmaf(v.y, c.sw, oy); }
+            if (c.m_se) { const float2 v = warp_point(M, c.x0 + 1, c.y0 + 1, H, W); ox = fmaf(v.x, c.se, ox); oy = fmaf(v.y, c.se, oy); }
+            const float inb = (ox >= -1.0f && ox <= 1.0f && oy >= -1.0f && oy <= 1.0f) ? 1.0f : 0.0f;
+            // resize_bilinear of match12Down8 at the pixel; with the cycle check, grid_sample of the up-sampled match21 at (gx, gy):
+            // the map has the grid's size, so the taps and weights are c's, each tap the resize expression at its integer pixel
+            const float* m12 = matchDown + (size_t)i * 2 * hw;
+            float v = up_resize(m12, t);
+            if (a.cycle) {
+                const float* s21 = m12 + hw;
+                float cyc = 0.0f;
+                if (c.m_nw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0, c.x0, hd, wd)), c.nw, cyc);
+                if (c.m_ne) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0, c.x0 + 1, hd, wd)), c.ne, cyc);
+                if (c.m_sw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0 + 1, c.x0, hd, wd)), c.sw, cyc);
+                if (c.m_se) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0 + 1, c.x0 + 1, hd, wd)), c.se, cyc);
+                v = __fmul_rn(v, cyc);
+            }
+            v = __fmul_rn(v, inb);                             // score_i = match12 (* cycle) * in-bounds, left to right
+            // merge_multi_h_kernel's rule: 0 owns the pixel unless a later homography is the first to reach th
+            if (i == 0) { mbest = v; fbest.x = ox; fbest.y = oy; }
+            if (v >= th) {
+                mbest = v; fbest.x = ox; fbest.y = oy;
+                found = true;
+                break;
+            }
+        }
+        // torch.clamp: a NaN stays a NaN (merge_multi_h_kernel)
+        float2 o;
+        o.x = fbest.x < -1.0f ? -1.0f : (fbest.x > 1.0f ? 1.0f : fbest.x);
+        o.y = fbest.y < -1.0f ? -1.0f : (fbest.y > 1.0f ? 1.0f : fbest.y);
+        flowG[p] = o;
+        matchG[p] = mbest;
+        binary[p] = (found && (!bg || bg[p] != 0)) ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 // predFlowCoarse's tail (model/model.py:333-340): flowGrad = || f[:, :, 1:, 1:] - f[:, :, :-1, :-1] ||_2 over the two flow
@@ -416,6 +514,21 @@ extern "C" int rfx_cycle_tail_f32(const float* flowDown8, const float* match12Do
     const CycleTailArgs a = {flowDown8, match12Down8, match21Down8, coarseGrid, flow12, match, NP, match12_stride, match21_stride,
                              hd, wd, Hc, Wc, H, W, sh, sw};
     return CycleTail::launch(cycle_tail_kernel, a, (unsigned)grid_for(NP, CycleTail::BLOCK), rfx_stream(stream));
+}
+
+extern "C" int rfx_assemble_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                                        const long long* table, int B, long long max_hw, float th, int multiH, int cycle,
+                                        const uint8_t* bg, float* flowGlobal, float* matchGlobal, uint8_t* binary,
+                                        long long total_px, void* stream) {
+    if (!rec || !table || !flowGlobal || !matchGlobal || !binary || B <= 0 || B > 65535 || width <= 0 || max_h <= 0 || off_H < 1 ||
+        off_flow < off_H + 9 * max_h || off_flow > width || rec_elems < (long long)B * width || max_hw <= 0 ||
+        max_hw > 0x7fffffffLL || total_px < max_hw || ((uintptr_t)flowGlobal & 7))
+        return RFX_E_ARG;
+    const AssembleRecArgs a = {rec, table, bg, flowGlobal, matchGlobal, binary, rec_elems, total_px,
+                               width, max_h, off_H, off_flow, multiH ? 1 : 0, cycle ? 1 : 0, th};
+    hipLaunchKernelGGL(assemble_records_kernel, dim3(grid_for(max_hw, 256), B), dim3(256), 0, rfx_stream(stream), a);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
 }
 
 extern "C" int rfx_flow_grad_clamp_f32(const float* flowCoarse, const float* grid, float* flowGrad, float* flow, int B, int H,

@@ -18,6 +18,10 @@ pixels (yfcc_matches: rfx_flow_points_f32, evalYFCC/getResults.py:53-71) and the
 The end-point error the HPatches and KITTI scripts end in is reduced on the device too (hpatch_epe: rfx_epe_homography_f32,
 evalHpatch/getResults.py:83-156,221-250 -- the ground-truth map is formed per pixel from the nine numbers of hpatch_gt_homography;
 kitti_epe: rfx_epe_flow_f32, evalKITTI/getResults.py:221-228); one float64 sum and one count per map cross the bus.
+A whole BATCH whose arrays still lie on the device as the drivers' records (ops.MultiHRecords / ops.MultiHRecordsRagged) is assembled
+by assemble_records / assemble_yfcc_records in ONE launch (rfx_assemble_records_f32): per pair bit for bit what assemble /
+assemble_yfcc give on the record's first nbH entries, with nbH read on the device, no (n,H,W) intermediate and no host sync -- the
+HPatches, Corr and YFCC forms; KITTI's two-level composition and component filter stay with assemble_kitti, pair by pair.
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
@@ -70,6 +74,28 @@ def assemble_yfcc(flowDown, param, matchDown, matchBG, th, multiH, device="cuda"
     fg, _, binary = assemble(flowDown, param, matchDown, (h * 8, w * 8), th, multiH, True, device)
     bg = matchBG if torch.is_tensor(matchBG) else torch.from_numpy(np.ascontiguousarray(np.asarray(matchBG) != 0))
     return fg, binary & (bg.to(fg.device) != 0).reshape(1, h * 8, w * 8)
+
+
+def assemble_records(records, th, multiH, cycle, out_hw=None, bg=None):
+    """assemble() for every pair of a batch of device records at once (ops.assemble_records): cycle=False at any ``out_hw`` is the
+    HPatches form (evalHpatch/getResults.py:16-63), cycle=True at the default 8x size the Corr form (evalCorr/getResults.py:78-136).
+    -> (flowGlobal, matchGlobal, binary, valid): (B,H,W,2), (B,H,W), (B,H,W) bool for dense records, lists of per-pair maps for
+    ragged ones; valid (B,) bool on the device = the pair has a homography -- where the scripts return [] the maps are zero."""
+    return ops.assemble_records(records, th, multiH, cycle, out_hw=out_hw, bg=bg)
+
+
+def assemble_yfcc_records(records, bg, th, multiH):
+    """assemble_yfcc() for every pair of a batch of device records at once: cycle=True at 8h x 8w, the explained mask ANDed with the
+    background maps ``bg`` -- (B,8h,8w) for dense records, one (8h_b,8w_b) map per pair for ragged ones; tensors on the records'
+    device (bool / uint8; anything else counts as != 0) or numpy arrays, which are uploaded.  -> (flowGlobal, binary, valid)."""
+    dev = records.rec.device
+
+    def mask(m):
+        t = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(np.asarray(m) != 0)).to(dev)
+        return t if t.dtype in (torch.bool, torch.uint8) else t != 0
+    bg = [mask(m) for m in bg] if isinstance(bg, (list, tuple)) else mask(bg)
+    fg, _, binary, valid = ops.assemble_records(records, th, multiH, True, bg=bg)
+    return fg, binary, valid
 
 
 def yfcc_matches(flowGlobal, binary, sizeA, sizeB, angle):

@@ -1991,6 +1991,96 @@ class MultiHRecordsRagged:
         return v
 
 
+def assemble_records_table(records, out_hw=None):
+    """The size table of rfx_assemble_records_f32 for a MultiHRecords / MultiHRecordsRagged, on the host: a pure function of the
+    records' size lists and ``out_hw`` -- None (8x each pair's /8 size), one (H, W) for a dense batch, a list of one (H, W) per pair
+    for a ragged one.  -> (rows, max_hw, total_px): row b = (element offset of pair b's row | h8 | w8 | off_match | H | W | offset
+    of the pair's pixels in the packed outputs | 0), the largest H * W, the pixels of all pairs together."""
+    B, ragged = records.B, isinstance(records, MultiHRecordsRagged)
+    if (records.hd2 is not None) if ragged else bool(records.hd2):
+        raise ValueError("assemble_records: records with a flowD2 part (the KITTI driver's) are not covered; use assemble_kitti per pair")
+    h8 = records.h8 if ragged else [records.h8] * B
+    w8 = records.w8 if ragged else [records.w8] * B
+    offm = records.off_match if ragged else [records.off_match] * B
+    if out_hw is None:
+        sizes = [(8 * a, 8 * b) for a, b in zip(h8, w8)]
+    elif ragged:
+        sizes = [tuple(s) if hasattr(s, "__len__") else () for s in out_hw]
+        if len(sizes) != B or any(len(s) != 2 for s in sizes):
+            raise ValueError("assemble_records: out_hw of a ragged batch is a list of one (H, W) per pair (%d pairs), got %r" % (B, out_hw))
+    else:
+        if len(out_hw) != 2 or any(hasattr(s, "__len__") for s in out_hw):
+            raise ValueError("assemble_records: out_hw of a dense batch is ONE (H, W), got %r" % (out_hw,))
+        sizes = [tuple(out_hw)] * B
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    if any(H <= 0 or W <= 0 or H * W > 0x7fffffff for H, W in sizes):
+        raise ValueError("assemble_records: output sizes must be positive (and below 2^31 pixels), got %r" % (sizes,))
+    rows, off = [], 0
+    for b, (H, W) in enumerate(sizes):
+        rows.append((b * records.width, h8[b], w8[b], offm[b], H, W, off, 0))
+        off += H * W
+    return rows, max(H * W for H, W in sizes), off
+
+
+def assemble_records(records, th, multiH, cycle, out_hw=None, bg=None, out=None):
+    """The offline flow assembly (rfx.assemble.assemble: evalHpatch / evalCorr / evalYFCC getResults.py) of EVERY pair of a batch from
+    the drivers' records, in one launch (rfx_assemble_records_f32): per pair bit for bit what assemble.assemble gives on the first
+    nbH entries of its record -- nbH is read on the device, no (n,H,W) intermediate exists, nothing syncs with the host.
+    records: MultiHRecords or MultiHRecordsRagged (not the KITTI form with flowD2).  out_hw: see assemble_records_table.  bg: the
+    background maps ANDed into ``binary`` (YFCC), bool or uint8 -- (B,H,W) for dense records; for ragged ones a list of one (H_b,W_b)
+    map per pair or a packed 1-D buffer in the outputs' layout.  out: (flow (total_px,2) float32, match (total_px,) float32, binary
+    (total_px,) bool) packed buffers to fill instead of new ones (flow 8-byte aligned); they may not alias the records.
+    -> (flowGlobal, matchGlobal, binary, valid): dense records (B,H,W,2), (B,H,W), (B,H,W) bool; ragged records lists of per-pair
+    views (H_b,W_b,2), (H_b,W_b), (H_b,W_b) of packed buffers; valid (B,) bool = nbH > 0, on the device (a pair without a homography
+    has zeros in all three maps)."""
+    if not isinstance(records, (MultiHRecords, MultiHRecordsRagged)):
+        raise TypeError("records must be an ops.MultiHRecords or ops.MultiHRecordsRagged")
+    ragged = isinstance(records, MultiHRecordsRagged)
+    rows, max_hw, total = assemble_records_table(records, out_hw)
+    B, dev = records.B, records.rec.device
+    sizes = [(r[4], r[5]) for r in rows]
+    if bg is not None:
+        if ragged and isinstance(bg, (list, tuple)):
+            if len(bg) != B or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s for t, s in zip(bg, sizes)):
+                raise ValueError("assemble_records: bg of a ragged batch is one (H, W) map per pair of the sizes %r" % (sizes,))
+            parts = bg
+        else:
+            want = (total,) if ragged else (B,) + sizes[0]
+            if not isinstance(bg, torch.Tensor) or tuple(bg.shape) != want:
+                raise ValueError("assemble_records: bg must have the shape %r" % (want,))
+            parts = [bg]
+        if any(t.device != dev for t in parts):
+            raise ValueError("assemble_records: bg must live on the records' device %s" % dev)
+        if any(t.dtype not in (torch.bool, torch.uint8) for t in parts):
+            raise ValueError("assemble_records: bg must be bool or uint8")
+        bg = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]) if len(parts) > 1 else parts[0]
+    if out is not None:
+        fg, mg, binary = out
+        for t, shape, dts, name in ((fg, (total, 2), (torch.float32,), "flow"), (mg, (total,), (torch.float32,), "match"),
+                                    (binary, (total,), (torch.bool,), "binary")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype not in dts or not t.is_contiguous() or t.device != dev:
+                raise ValueError("assemble_records: out %s must be a contiguous %s %s tensor on %s" % (name, shape, dts[0], dev))
+        if fg.data_ptr() % 8:
+            raise ValueError("assemble_records: the flow output is accessed as float2 and must be 8-byte aligned")
+    rec = _dev(records.rec, "records")
+    if out is None:
+        fg = torch.empty((total, 2), dtype=torch.float32, device=dev)
+        mg = torch.empty(total, dtype=torch.float32, device=dev)
+        binary = torch.empty(total, dtype=torch.bool, device=dev)
+    b8 = _mask_bytes(bg, "bg") if bg is not None else None
+    table = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    _call("rfx_assemble_records_f32", _one_device(rec, b8, fg, mg, binary), _p(rec), rec.numel(), records.width, records.max_h,
+          records.off_H, records.off_flow, _p(table), B, max_hw, float(th), 1 if multiH else 0, 1 if cycle else 0, _p(b8), _p(fg),
+          _p(mg), _p(binary), total)
+    valid = rec[:, 0] >= 1                                    # the kernel's own test of nbH
+    if not ragged:
+        H, W = sizes[0]
+        return fg.view(B, H, W, 2), mg.view(B, H, W), binary.view(B, H, W), valid
+    views = [(r[6], r[4], r[5]) for r in rows]
+    return ([fg[o:o + H * W].view(H, W, 2) for o, H, W in views], [mg[o:o + H * W].view(H, W) for o, H, W in views],
+            [binary[o:o + H * W].view(H, W) for o, H, W in views], valid)
+
+
 def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode, bestH=None, flowDown8=None, match12Down8=None,
                   match21Down8=None, flowD2=None, records=None):
     """Accept rule + mask update + record store of one round (rfx_multih_accept_f32) -> (accept (a,) int32, gain (a,) f32),
