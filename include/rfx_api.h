@@ -47,7 +47,8 @@ const char* rfx_version(void);
  * rfx_multih_accept_ragged_d2_f32; 15: rfx_conv1x1_expand64_f32 and rfx_conv1x1_expand64_dual_f32; 16:
  * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
  * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17,
- * and so were rfx_epe_ws_bytes, rfx_epe_homography_f32 and rfx_epe_flow_f32: no existing entry point moved, and a binding that knows
+ * and so were rfx_epe_ws_bytes, rfx_epe_homography_f32, rfx_epe_flow_f32, rfx_assemble_records_f32, rfx_assemble_kitti_records_f32
+ * and rfx_kitti_scores_records_f32: no existing entry point moved, and a binding that knows
  * a new name refuses a library without it).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
 #define RFX_ABI_VERSION 17
@@ -371,6 +372,43 @@ int rfx_assemble_records_f32(const float* rec, long long rec_elems, int width, i
                              const long long* table, int B, long long max_hw, float th, int multiH, int cycle,
                              const uint8_t* bg, float* flowGlobal, float* matchGlobal, uint8_t* binary, long long total_px,
                              void* stream);
+
+/* The KITTI form of the assembly above (evaluation/evalKITTI/getResults.py:95-141, getFlow_all) for EVERY pair of a batch, from the
+ * records of the KITTI drivers, which carry the half-resolution flowD2 (both ADDED under ABI 17: nothing existing moves).  Per pair
+ * with n = nbH read on the device the outputs are, bit for bit, those of rfx_warp_grid_f32(H[:n]) -> rfx_compose_flow_f32(flowD2[:n],
+ * clamp = 1) -> rfx_compose_flow_f32(flowDown8[:n], that grid, clamp = 1, inb, flowUp) -> rfx_resize_bilinear_f32(matchDown8[:n]) ->
+ * rfx_grid_sample_f32(up-sampled match21, flowUp) -> [rfx_match_score_f32 -> rfx_remove_small_cc_f32 ->] rfx_merge_multi_h_f32:
+ * a tap of the fine flow's sample is the d2 flow at the tap's integer pixel, itself a four-tap sample of the homography grid formed
+ * from the nine numbers; neither d2, flowUp, inb nor an up-sampled map is stored.
+ * rec, width, max_h, off_H, off_flow: as for rfx_assemble_records_f32; a row also holds flowD2 (max_h,2,hd2,wd2) from the pair's
+ * off_d2.  table (B,12) int64 on the device, row b:
+ *     [0] element offset of the pair's row in rec | [1] h8 | [2] w8 | [3] off_match | [4] off_d2 | [5] hd2 | [6] wd2 | [7] H | [8] W
+ *     (output size) | [9] pixel offset of the pair's maps in the packed outputs | [10] element offset of the pair's score map 0 in
+ *     the batch's packed scores (map i at + i * H * W, max_h maps per pair) | [11] max_area of the component filter for H * W
+ * -- a pure function of the batch's size lists and cc_th.  A row that does not describe a record inside rec, a map inside the outputs
+ * and (where scores are used) max_h maps inside the score buffer is skipped.  max_hw = the largest H * W (8192 workgroups per pair at
+ * the most, larger maps take further trips).  The score buffer `scores` holds the elements [score_base, score_base + score_elems) of
+ * the batch's packed scores: a call on a chunk of consecutive pairs passes the chunk's first table row, its B and its own base.
+ * Limits (RFX_E_LIMIT): max_hw, total_px, score_elems <= 2^31 - 1, B * max_h <= 65535.  Both take a stream, allocate nothing and do
+ * not sync.
+ *
+ * rfx_kitti_scores_records_f32 (only with a component filter, cc_th > 0): score_i = (up(match12_i) * sample(up(match21_i), flowUp_i))
+ * * inb_i -- rfx_match_score_f32's map -- for every i < last of every pair (last = nbH with multiH, else min(nbH, 1)) into scores,
+ * and row b * max_h + i of dims (B * max_h, 3) int32, the table rfx_remove_small_cc_ragged_f32 reads: (H, W, max_area) for i < last,
+ * (0, 0, 0) -- a map the filter skips -- otherwise.  The filter's match_off is the host's: table[b][10] - score_base + i * H * W.
+ *
+ * rfx_assemble_kitti_records_f32: scores == NULL (cc_th == 0): a thread walks the homographies of its pixel in the merge's order and
+ * stops at the owner -- ONE launch for the batch.  scores != NULL: the thread finds the owner on the FILTERED scores by the same
+ * rule and evaluates the owner's flow only; matchGlobal is the owner's filtered score, or filtered score_0 where nobody reaches th.
+ * Outputs as rfx_assemble_records_f32 (flowGlobal 8-byte aligned, NaN kept by the clamp); a pair with nbH == 0 gets zeros.  No
+ * output may alias rec or scores. */
+int rfx_kitti_scores_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                                 const long long* table, int B, long long max_hw, int multiH, float* scores, long long score_base,
+                                 long long score_elems, int32_t* dims, long long total_px, void* stream);
+int rfx_assemble_kitti_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                                   const long long* table, int B, long long max_hw, float th, int multiH, const float* scores,
+                                   long long score_base, long long score_elems, float* flowGlobal, float* matchGlobal,
+                                   uint8_t* binary, long long total_px, void* stream);
 
 /* The small-component filter of the KITTI scripts (evaluation/evalKITTI/evaluation.py:85-100 online -- remove_small_cc(match,
  * 0.99, cc_th) at :321 -- and evaluation/evalKITTI/getResults.py:66-84 offline, :122), which the reference runs on the host

@@ -430,6 +430,190 @@ __global__ __launch_bounds__(256) void assemble_records_kernel(AssembleRecArgs a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// assemble_kitti_records: the KITTI form of the assembly above (evaluation/evalKITTI/getResults.py:95-141, getFlow_all) from records
+// that carry the half-resolution flowD2 -- per pair what rfx_warp_grid_f32 -> rfx_compose_flow_f32(flowD2, clamp) ->
+// rfx_compose_flow_f32(flowDown8, clamp, inb, flowUp) -> rfx_resize_bilinear_f32 -> rfx_grid_sample_f32 -> [rfx_match_score_f32 ->
+// rfx_remove_small_cc_f32 ->] rfx_merge_multi_h_f32 give on the record's first nbH entries, bit for bit.  The flow is a two-level
+// composition: a tap of the fine flow's bilinear sample is the d2 flow at that tap's integer pixel, itself a four-tap sample of the
+// homography grid, so a pixel costs up to 16 warp_points per homography and neither d2, flowUp, inb nor an up-sampled map is stored.
+// Row blockIdx.y of the (B,12) table: row offset in rec | h8 | w8 | off_match | off_d2 | hd2 | wd2 | H | W | offset of the pair's
+// pixels in the outputs | element offset of the pair's score map 0 | max_area of the component filter.
+struct KittiRecArgs {
+    const float* rec; const long long* table; float* scores; int32_t* dims; float* flowG; float* matchG; uint8_t* binary;
+    long long rec_elems, total_px, score_base, score_elems;   // floats in rec; pixels in each packed output; the score buffer holds
+                                                              // the elements [score_base, score_base + score_elems) of the batch's
+    int width, max_h, off_H, off_flow, multiH; float th;
+};
+
+constexpr int KITTI_COLS = 12;
+
+// one pair of the table, checked: nothing is read or written for a row with ok == false
+struct KittiPair {
+    const float* Hm; const float* flowDown; const float* matchDown; const float* flowD2;
+    long long out_off, score_off;            // score_off: relative to the score buffer
+    int hd, wd, hd2, wd2, H, W, HW, nb, last, max_area;
+    float sh8, sw8, sh2, sw2;
+    bool ok;
+};
+
+__device__ __forceinline__ KittiPair kitti_pair(const KittiRecArgs& a, const int b, const bool need_scores) {
+    const long long* __restrict__ T = a.table + (long long)b * KITTI_COLS;
+    const long long row_off = T[0], h8l = T[1], w8l = T[2], off_match = T[3], off_d2 = T[4], hd2l = T[5], wd2l = T[6], Hl = T[7],
+                    Wl = T[8], out_off = T[9], score_off = T[10] - a.score_base, area = T[11];
+    KittiPair k;
+    k.ok = false;
+    if (row_off < 0 || row_off + a.width > a.rec_elems || h8l <= 0 || w8l <= 0 || h8l > a.width || w8l > a.width || h8l * w8l > a.width ||
+        hd2l <= 0 || wd2l <= 0 || hd2l > a.width || wd2l > a.width || hd2l * wd2l > a.width || Hl <= 0 || Wl <= 0 ||
+        Hl > 0x7fffffffLL || Wl > 0x7fffffffLL || Hl * Wl > 0x7fffffffLL || area < 0 || area > 0x7fffffffLL)
+        return k;
+    const long long n8 = 2 * h8l * w8l * a.max_h, n2 = 2 * hd2l * wd2l * a.max_h, HWl = Hl * Wl;
+    if (off_match < a.off_flow + n8 || off_d2 < off_match + n8 || off_d2 + n2 > a.width || out_off < 0 || out_off + HWl > a.total_px)
+        return k;
+    if (need_scores && (score_off < 0 || score_off + HWl * a.max_h > a.score_elems)) return k;
+    const float* __restrict__ row = a.rec + row_off;
+    k.Hm = row + a.off_H; k.flowDown = row + a.off_flow; k.matchDown = row + off_match; k.flowD2 = row + off_d2;
+    k.out_off = out_off; k.score_off = score_off;
+    k.hd = (int)h8l; k.wd = (int)w8l; k.hd2 = (int)hd2l; k.wd2 = (int)wd2l; k.H = (int)Hl; k.W = (int)Wl; k.HW = (int)HWl;
+    k.max_area = (int)area;
+    const float nf = row[0];                                   // nbH, a small integer held as a float
+    k.nb = nf >= 1.0f ? (nf < (float)a.max_h ? (int)nf : a.max_h) : 0;
+    k.last = a.multiH ? k.nb : (k.nb < 1 ? k.nb : 1);
+    k.sh8 = (float)k.hd / (float)k.H; k.sw8 = (float)k.wd / (float)k.W;
+    k.sh2 = (float)k.hd2 / (float)k.H; k.sw2 = (float)k.wd2 / (float)k.W;
+    k.ok = true;
+    return k;
+}
+
+// level 1: d2 = compose_flow(flowD2_i, warp_grid(H_i), clamp) at the integer pixel (x, y) of the H x W grid
+__device__ __forceinline__ float2 kitti_d2_point(const KittiPair& k, const int i, const int x, const int y) {
+    const int hw2 = k.hd2 * k.wd2, H = k.H, W = k.W;
+    const UpTap t = up_tap(k.sh2, k.sw2, y, x, k.hd2, k.wd2);
+    const float* f = k.flowD2 + (size_t)i * 2 * hw2;
+    float gx = __fadd_rn(up_flow(f, t), rfx_lin(x, W)), gy = __fadd_rn(up_flow(f + hw2, t), rfx_lin(y, H));
+    gx = fminf(fmaxf(gx, -1.0f), 1.0f);
+    gy = fminf(fmaxf(gy, -1.0f), 1.0f);
+    const Corners c = corners(gx, gy, H, W, 0);
+    const float* M = k.Hm + i * 9;
+    float2 o;
+    o.x = 0.f; o.y = 0.f;
+    if (c.m_nw) { const float2 v = warp_point(M, c.x0, c.y0, H, W); o.x = fmaf(v.x, c.nw, o.x); o.y = fmaf(v.y, c.nw, o.y); }
+    if (c.m_ne) { const float2 v = warp_point(M, c.x0 + 1, c.y0, H, W); o.x = fmaf(v.x, c.ne, o.x); o.y = fmaf(v.y, c.ne, o.y); }
+    if (c.m_sw) { const float2 v = warp_point(M, c.x0, c.y0 + 1, H, W); o.x = fmaf(v.x, c.sw, o.x); o.y = fmaf(v.y, c.sw, o.y); }
+    if (c.m_se) { const float2 v = warp_point(M, c.x0 + 1, c.y0 + 1, H, W); o.x = fmaf(v.x, c.se, o.x); o.y = fmaf(v.y, c.se, o.y); }
+    return o;
+}
+
+// flow_i and score_i of homography i at the output pixel (x, y) of a pair, from the record alone.  t = the pixel's /8 taps.
+// level 2: flow = compose_flow(flowDown8_i, d2, clamp, inb, flowUp); score = (up(match12) * sample(up(match21), flowUp)) * inb
+struct FlowScore { float2 flow; float score; };
+
+__device__ __forceinline__ FlowScore kitti_flow_score(const KittiPair& k, const int i, const int x, const int y, const UpTap& t,
+                                                      const bool want_score) {
+    const int hw = k.hd * k.wd, H = k.H, W = k.W;
+    const float* f = k.flowDown + (size_t)i * 2 * hw;
+    float gx = __fadd_rn(up_flow(f, t), rfx_lin(x, W)), gy = __fadd_rn(up_flow(f + hw, t), rfx_lin(y, H));
+    gx = fminf(fmaxf(gx, -1.0f), 1.0f);
+    gy = fminf(fmaxf(gy, -1.0f), 1.0f);
+    const Corners c = corners(gx, gy, H, W, 0);
+    float ox = 0.f, oy = 0.f;
+    if (c.m_nw) { const float2 v = kitti_d2_point(k, i, c.x0, c.y0); ox = fmaf(v.x, c.nw, ox); oy = fmaf(v.y, c.nw, oy); }
+    if (c.m_ne) { const float2 v = kitti_d2_point(k, i, c.x0 + 1, c.y0); ox = fmaf(v.x, c.ne, ox); oy = fmaf(v.y, c.ne, oy); }
+    if (c.m_sw) { const float2 v = kitti_d2_point(k, i, c.x0, c.y0 + 1); ox = fmaf(v.x, c.sw, ox); oy = fmaf(v.y, c.sw, oy); }
+    if (c.m_se) { const float2 v = kitti_d2_point(k, i, c.x0 + 1, c.y0 + 1); ox = fmaf(v.x, c.se, ox); oy = fmaf(v.y, c.se, oy); }
+    FlowScore r;
+    r.flow.x = ox; r.flow.y = oy;
+    r.score = 0.0f;
+    if (want_score) {
+        const float inb = (ox >= -1.0f && ox <= 1.0f && oy >= -1.0f && oy <= 1.0f) ? 1.0f : 0.0f;
+        const float* m12 = k.matchDown + (size_t)i * 2 * hw;
+        const float* s21 = m12 + hw;
+        const float v12 = up_resize(m12, t);
+        float cyc = 0.0f;
+        if (c.m_nw) cyc = fmaf(up_resize(s21, up_tap(k.sh8, k.sw8, c.y0, c.x0, k.hd, k.wd)), c.nw, cyc);
+        if (c.m_ne) cyc = fmaf(up_resize(s21, up_tap(k.sh8, k.sw8, c.y0, c.x0 + 1, k.hd, k.wd)), c.ne, cyc);
+        if (c.m_sw) cyc = fmaf(up_resize(s21, up_tap(k.sh8, k.sw8, c.y0 + 1, c.x0, k.hd, k.wd)), c.sw, cyc);
+        if (c.m_se) cyc = fmaf(up_resize(s21, up_tap(k.sh8, k.sw8, c.y0 + 1, c.x0 + 1, k.hd, k.wd)), c.se, cyc);
+        r.score = __fmul_rn(__fmul_rn(v12, cyc), inb);         // (match12 * cycle) * in-bounds, left to right
+    }
+    return r;
+}
+
+// Kernel A.  blockIdx.y = the pair, blockIdx.x strides over its pixels.  scores == NULL (cc_th == 0): the fused walk of
+// assemble_records_kernel.  scores != NULL: the owner is found on the pair's FILTERED scores (kitti_scores_records_kernel, then the
+// component filter in place), and only the owner's flow is evaluated.
+__global__ __launch_bounds__(256) void assemble_kitti_records_kernel(KittiRecArgs a) {
+    const KittiPair k = kitti_pair(a, blockIdx.y, a.scores != nullptr);
+    if (!k.ok) return;
+    const int W = k.W, HW = k.HW, last = k.last;
+    float2* __restrict__ flowG = reinterpret_cast<float2*>(a.flowG) + k.out_off;
+    float* __restrict__ matchG = a.matchG + k.out_off;
+    uint8_t* __restrict__ binary = a.binary + k.out_off;
+    const float* __restrict__ sc = a.scores ? a.scores + k.score_off : nullptr;
+    const float th = a.th;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < HW; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
+        const int y = p / W, x = p - y * W;
+        const UpTap t = up_tap(k.sh8, k.sw8, y, x, k.hd, k.wd);
+        float2 fbest;
+        fbest.x = 0.0f; fbest.y = 0.0f;
+        float mbest = 0.0f;
+        bool found = false;
+        if (sc) {
+            int best = 0;
+            for (int i = 0; i < last; ++i) {
+                const float v = sc[(size_t)i * HW + p];
+                if (i == 0) mbest = v;
+                if (v >= th) {
+                    best = i; mbest = v;
+                    found = true;
+                    break;
+                }
+            }
+            if (last > 0) fbest = kitti_flow_score(k, best, x, y, t, false).flow;
+        } else {
+            for (int i = 0; i < last; ++i) {
+                const FlowScore r = kitti_flow_score(k, i, x, y, t, true);
+                // merge_multi_h_kernel's rule: 0 owns the pixel unless a later homography is the first to reach th
+                if (i == 0) { mbest = r.score; fbest = r.flow; }
+                if (r.score >= th) {
+                    mbest = r.score; fbest = r.flow;
+                    found = true;
+                    break;
+                }
+            }
+        }
+        // torch.clamp: a NaN stays a NaN (merge_multi_h_kernel)
+        float2 o;
+        o.x = fbest.x < -1.0f ? -1.0f : (fbest.x > 1.0f ? 1.0f : fbest.x);
+        o.y = fbest.y < -1.0f ? -1.0f : (fbest.y > 1.0f ? 1.0f : fbest.y);
+        flowG[p] = o;
+        matchG[p] = mbest;
+        binary[p] = found ? 1 : 0;
+    }
+}
+
+// Kernel B (cc_th > 0).  blockIdx.y = pair * max_h + homography: score_i of every map the merge reads (i < last) into the packed
+// score buffer, and the map's row (H, W, max_area) of the component filter's table -- (0, 0, 0), which the filter skips, for every
+// other map and for a pair whose table row is refused.
+__global__ __launch_bounds__(256) void kitti_scores_records_kernel(KittiRecArgs a) {
+    const int b = blockIdx.y / a.max_h, i = blockIdx.y - b * a.max_h;
+    const KittiPair k = kitti_pair(a, b, true);
+    const bool used = k.ok && i < k.last;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int32_t* d = a.dims + 3 * (long long)blockIdx.y;
+        d[0] = used ? k.H : 0; d[1] = used ? k.W : 0; d[2] = used ? k.max_area : 0;
+    }
+    if (!used) return;
+    const int W = k.W, HW = k.HW;
+    float* __restrict__ sc = a.scores + k.score_off + (size_t)i * HW;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < HW; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
+        const int y = p / W, x = p - y * W;
+        sc[p] = kitti_flow_score(k, i, x, y, up_tap(k.sh8, k.sw8, y, x, k.hd, k.wd), true).score;
+    }
+}
+
 }  // namespace
 
 // predFlowCoarse's tail (model/model.py:333-340): flowGrad = || f[:, :, 1:, 1:] - f[:, :, :-1, :-1] ||_2 over the two flow
@@ -527,6 +711,51 @@ extern "C" int rfx_assemble_records_f32(const float* rec, long long rec_elems, i
     const AssembleRecArgs a = {rec, table, bg, flowGlobal, matchGlobal, binary, rec_elems, total_px,
                                width, max_h, off_H, off_flow, multiH ? 1 : 0, cycle ? 1 : 0, th};
     hipLaunchKernelGGL(assemble_records_kernel, dim3(grid_for(max_hw, 256), B), dim3(256), 0, rfx_stream(stream), a);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+namespace {
+
+// the argument checks both KITTI entry points share, before any HIP call
+int kitti_records_check(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow, const long long* table,
+                        int B, long long max_hw, long long total_px) {
+    if (!rec || !table || B <= 0 || width <= 0 || max_h <= 0 || off_H < 1 || off_flow < (long long)off_H + 9LL * max_h ||
+        off_flow > width || rec_elems < (long long)B * width || max_hw <= 0 || total_px < max_hw)
+        return RFX_E_ARG;
+    if (max_hw > 0x7fffffffLL || total_px > 0x7fffffffLL || (long long)B * max_h > 65535) return RFX_E_LIMIT;
+    return RFX_OK;
+}
+
+}  // namespace
+
+extern "C" int rfx_kitti_scores_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                                            const long long* table, int B, long long max_hw, int multiH, float* scores,
+                                            long long score_base, long long score_elems, int32_t* dims, long long total_px,
+                                            void* stream) {
+    if (!scores || !dims || score_base < 0 || score_elems <= 0) return RFX_E_ARG;
+    const int rc = kitti_records_check(rec, rec_elems, width, max_h, off_H, off_flow, table, B, max_hw, total_px);
+    if (rc != RFX_OK) return rc;
+    if (score_elems > 0x7fffffffLL) return RFX_E_LIMIT;
+    const KittiRecArgs a = {rec, table, scores, dims, nullptr, nullptr, nullptr, rec_elems, total_px, score_base, score_elems,
+                            width, max_h, off_H, off_flow, multiH ? 1 : 0, 0.0f};
+    hipLaunchKernelGGL(kitti_scores_records_kernel, dim3(grid_for(max_hw, 256), B * max_h), dim3(256), 0, rfx_stream(stream), a);
+    RFX_LAUNCH_CHECK();
+    return RFX_OK;
+}
+
+extern "C" int rfx_assemble_kitti_records_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                                              const long long* table, int B, long long max_hw, float th, int multiH,
+                                              const float* scores, long long score_base, long long score_elems, float* flowGlobal,
+                                              float* matchGlobal, uint8_t* binary, long long total_px, void* stream) {
+    if (!flowGlobal || !matchGlobal || !binary || ((uintptr_t)flowGlobal & 7) || score_base < 0 || (scores && score_elems <= 0))
+        return RFX_E_ARG;
+    const int rc = kitti_records_check(rec, rec_elems, width, max_h, off_H, off_flow, table, B, max_hw, total_px);
+    if (rc != RFX_OK) return rc;
+    if (scores && score_elems > 0x7fffffffLL) return RFX_E_LIMIT;
+    const KittiRecArgs a = {rec, table, const_cast<float*>(scores), nullptr, flowGlobal, matchGlobal, binary, rec_elems, total_px,
+                            score_base, score_elems, width, max_h, off_H, off_flow, multiH ? 1 : 0, th};
+    hipLaunchKernelGGL(assemble_kitti_records_kernel, dim3(grid_for(max_hw, 256), B), dim3(256), 0, rfx_stream(stream), a);
     RFX_LAUNCH_CHECK();
     return RFX_OK;
 }

@@ -71,6 +71,10 @@ SIGNATURES = {
                            [c_void_p]),
     "rfx_assemble_records_f32": (c_int, [c_void_p, c_longlong] + [c_int] * 4 + [c_void_p, c_int, c_longlong, c_float, c_int, c_int] +
                                  [c_void_p] * 4 + [c_longlong, c_void_p]),
+    "rfx_kitti_scores_records_f32": (c_int, [c_void_p, c_longlong] + [c_int] * 4 + [c_void_p, c_int, c_longlong, c_int, c_void_p,
+                                             c_longlong, c_longlong, c_void_p, c_longlong, c_void_p]),
+    "rfx_assemble_kitti_records_f32": (c_int, [c_void_p, c_longlong] + [c_int] * 4 + [c_void_p, c_int, c_longlong, c_float, c_int,
+                                               c_void_p, c_longlong, c_longlong] + [c_void_p] * 3 + [c_longlong, c_void_p]),
     "rfx_remove_small_cc_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_remove_small_cc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "rfx_remove_small_cc_ragged_ws_bytes": (c_size_t, [c_longlong]),

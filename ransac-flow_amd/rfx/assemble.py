@@ -21,7 +21,9 @@ kitti_epe: rfx_epe_flow_f32, evalKITTI/getResults.py:221-228); one float64 sum a
 A whole BATCH whose arrays still lie on the device as the drivers' records (ops.MultiHRecords / ops.MultiHRecordsRagged) is assembled
 by assemble_records / assemble_yfcc_records in ONE launch (rfx_assemble_records_f32): per pair bit for bit what assemble /
 assemble_yfcc give on the record's first nbH entries, with nbH read on the device, no (n,H,W) intermediate and no host sync -- the
-HPatches, Corr and YFCC forms; KITTI's two-level composition and component filter stay with assemble_kitti, pair by pair.
+HPatches, Corr and YFCC forms.  KITTI's records (with flowD2) go through assemble_kitti_records (rfx_assemble_kitti_records_f32, with
+cc_th > 0 also rfx_kitti_scores_records_f32 and the ragged component filter): the two-level composition is evaluated per pixel, the
+filter runs on one packed score buffer per chunk of pairs, and the --interpolate fill is ops.nearest_fill on the batch.
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
@@ -259,6 +261,13 @@ def assemble_kitti(flowd2Down, flowDown, param, matchDown, out_hw, th, multiH, c
     if interpolate:
         fg = interpolate_flow_match(fg, binary, fill)
     return fg, mg, binary
+
+
+def assemble_kitti_records(records, out_hw, th, multiH, cc_th=0.0, interpolate=False):
+    """assemble_kitti(..., fill="device") for every pair of a batch of KITTI device records at once (ops.assemble_kitti_records):
+    ``out_hw`` one (H, W) for dense records, one per pair for ragged ones (None: 8x the /8 size).  -> (flowGlobal, matchGlobal,
+    binary, valid) as assemble_records returns them; a pair without a homography (valid False) has zeros in all three maps."""
+    return ops.assemble_kitti_records(records, th, multiH, cc_th=cc_th, interpolate=interpolate, out_hw=out_hw)
 
 
 # ---- file-level entry points with the reference's argument lists -------------------------------------------------

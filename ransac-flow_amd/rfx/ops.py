@@ -2081,6 +2081,166 @@ def assemble_records(records, th, multiH, cycle, out_hw=None, bg=None, out=None)
             [binary[o:o + H * W].view(H, W) for o, H, W in views], valid)
 
 
+KITTI_WS_BYTES = 1 << 30       # default workspace bound of assemble_kitti_records (scores + component-filter workspace of one chunk)
+KITTI_TABLE_COLS = 12
+
+
+def _kitti_records(records, what):
+    """(ragged?, per-pair hd2, wd2, off_d2) of records with a flowD2 part; TypeError / ValueError otherwise."""
+    if not isinstance(records, (MultiHRecords, MultiHRecordsRagged)):
+        raise TypeError("records must be an ops.MultiHRecords or ops.MultiHRecordsRagged")
+    ragged = isinstance(records, MultiHRecordsRagged)
+    if not ((records.hd2 is not None) if ragged else bool(records.hd2)):
+        raise ValueError("%s: records without a flowD2 part are not the KITTI drivers'; use assemble_records" % what)
+    B = records.B
+    if ragged:
+        return True, records.hd2, records.wd2, records.off_d2
+    return False, [records.hd2] * B, [records.wd2] * B, [records.off_d2] * B
+
+
+def assemble_kitti_records_table(records, out_hw=None, cc_th=0.0):
+    """The size table of rfx_assemble_kitti_records_f32 / rfx_kitti_scores_records_f32 for records of the KITTI drivers, on the host:
+    a pure function of the records' size lists, ``out_hw`` (None: 8x each pair's /8 size; one (H, W) for a dense batch; one (H, W)
+    per pair for a ragged one) and ``cc_th``.  -> (rows, max_hw, total_px): row b = (element offset of pair b's row | h8 | w8 |
+    off_match | off_d2 | hd2 | wd2 | H | W | offset of the pair's pixels in the packed outputs | element offset of the pair's score
+    map 0 in the batch's packed scores, max_h maps of H * W per pair | cc_max_area(H * W, cc_th))."""
+    what = "assemble_kitti_records"
+    ragged, hd2, wd2, offd2 = _kitti_records(records, what)
+    cc_th = float(cc_th)
+    if not cc_th >= 0:
+        raise ValueError("%s: cc_th must be >= 0, got %r" % (what, cc_th))
+    B = records.B
+    h8 = records.h8 if ragged else [records.h8] * B
+    w8 = records.w8 if ragged else [records.w8] * B
+    offm = records.off_match if ragged else [records.off_match] * B
+    if out_hw is None:
+        sizes = [(8 * a, 8 * b) for a, b in zip(h8, w8)]
+    elif ragged:
+        sizes = [tuple(s) if hasattr(s, "__len__") else () for s in out_hw]
+        if len(sizes) != B or any(len(s) != 2 for s in sizes):
+            raise ValueError("%s: out_hw of a ragged batch is a list of one (H, W) per pair (%d pairs), got %r" % (what, B, out_hw))
+    else:
+        if len(out_hw) != 2 or any(hasattr(s, "__len__") for s in out_hw):
+            raise ValueError("%s: out_hw of a dense batch is ONE (H, W), got %r" % (what, out_hw))
+        sizes = [tuple(out_hw)] * B
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    if any(H <= 0 or W <= 0 or H * W > 0x7fffffff for H, W in sizes):
+        raise ValueError("%s: output sizes must be positive (and below 2^31 pixels), got %r" % (what, sizes))
+    rows, off, soff = [], 0, 0
+    for b, (H, W) in enumerate(sizes):
+        rows.append((b * records.width, h8[b], w8[b], offm[b], offd2[b], hd2[b], wd2[b], H, W, off, soff, cc_max_area(H * W, cc_th)))
+        off += H * W
+        soff += records.max_h * H * W
+    return rows, max(H * W for H, W in sizes), off
+
+
+def _kitti_plan(rows, max_h, cc_th, ws_bytes):
+    if ws_bytes is None:
+        ws_bytes = KITTI_WS_BYTES
+    if isinstance(ws_bytes, bool) or not isinstance(ws_bytes, int) or ws_bytes <= 0:
+        raise ValueError("assemble_kitti_records: ws_bytes must be a positive int, got %r" % (ws_bytes,))
+    if max_h > 65535:
+        raise ValueError("assemble_kitti_records: max_h above 65535")
+    max_pairs = 65535 // max_h                                # blockIdx.y of the score kernel = (pair, homography)
+    plan, lo, elems = [], 0, 0
+    for b, r in enumerate(rows):
+        need = max_h * r[7] * r[8] if cc_th > 0 else 0        # floats of scores; 16 bytes each with the filter's three int32
+        if need > 0x7fffffff:
+            raise ValueError("assemble_kitti_records: the %d score maps of pair %d exceed 2^31 - 1 elements" % (max_h, b))
+        if b > lo and (b - lo >= max_pairs or 16 * (elems + need) > ws_bytes or elems + need > 0x7fffffff):
+            plan.append((lo, b))
+            lo, elems = b, 0
+        elems += need
+    plan.append((lo, len(rows)))
+    return plan
+
+
+def assemble_kitti_records_plan(records, out_hw=None, cc_th=0.0, ws_bytes=None):
+    """The chunks assemble_kitti_records processes one after the other: [(lo, hi), ...], consecutive, covering every pair once.  With
+    cc_th > 0 a chunk's workspace -- 4 bytes of scores and 12 bytes of component-filter workspace per pixel and homography, sized by
+    max_h because nbH is known to the device only -- stays within ``ws_bytes`` (default 1 GiB) unless a single pair needs more (at least
+    one pair per chunk).  A chunk also holds at most 65535 // max_h pairs and 2^31 - 1 score elements.  A pure host function."""
+    rows, _, _ = assemble_kitti_records_table(records, out_hw, cc_th)
+    return _kitti_plan(rows, records.max_h, float(cc_th), ws_bytes)
+
+
+def assemble_kitti_records(records, th, multiH, cc_th=0.0, interpolate=False, out_hw=None, out=None, ws_bytes=None):
+    """The KITTI flow assembly (rfx.assemble.assemble_kitti: evalKITTI/getResults.py:95-141) of EVERY pair of a batch from the KITTI
+    drivers' records (built with the d2 lists), per pair bit for bit what assemble_kitti(..., fill="device") gives on the first nbH
+    entries of its record: nbH is read on the device and nothing syncs with the host.  cc_th == 0: ONE launch
+    (rfx_assemble_kitti_records_f32).  cc_th > 0: per chunk of pairs (assemble_kitti_records_plan; the result does not depend on the
+    plan) the scores of all homographies (rfx_kitti_scores_records_f32), the component filter in place on them
+    (rfx_remove_small_cc_ragged_f32) and the merge on the filtered scores -- six launches; the score buffer and the filter's workspace
+    are the only (n,H,W) memory.  interpolate: ops.nearest_fill of the flow with ``binary``, one call for dense records, one per run
+    of consecutive same-size pairs for ragged ones.  out_hw, out and the result: as for assemble_records."""
+    what = "assemble_kitti_records"
+    rows, max_hw, total = assemble_kitti_records_table(records, out_hw, cc_th)
+    ragged = isinstance(records, MultiHRecordsRagged)
+    cc_th = float(cc_th)
+    B, dev, max_h = records.B, records.rec.device, records.max_h
+    plan = _kitti_plan(rows, max_h, cc_th, ws_bytes)
+    if total > 0x7fffffff:
+        raise ValueError("%s: the batch has more than 2^31 - 1 output pixels" % what)
+    if out is not None:
+        fg, mg, binary = out
+        for t, shape, dts, name in ((fg, (total, 2), (torch.float32,), "flow"), (mg, (total,), (torch.float32,), "match"),
+                                    (binary, (total,), (torch.bool,), "binary")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype not in dts or not t.is_contiguous() or t.device != dev:
+                raise ValueError("%s: out %s must be a contiguous %s %s tensor on %s" % (what, name, shape, dts[0], dev))
+        if fg.data_ptr() % 8:
+            raise ValueError("%s: the flow output is accessed as float2 and must be 8-byte aligned" % what)
+    rec = _dev(records.rec, "records")
+    if out is None:
+        fg = torch.empty((total, 2), dtype=torch.float32, device=dev)
+        mg = torch.empty(total, dtype=torch.float32, device=dev)
+        binary = torch.empty(total, dtype=torch.bool, device=dev)
+    hws = [r[7] * r[8] for r in rows]
+    host = [v for r in rows for v in r]
+    if cc_th > 0:                                            # the filter's match_off: the map's offset inside its chunk's score buffer
+        for lo, hi in plan:
+            host += [rows[b][10] - rows[lo][10] + i * hws[b] for b in range(lo, hi) for i in range(max_h)]
+    up = torch.tensor(host, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    table, moff = up[:B * KITTI_TABLE_COLS].view(B, KITTI_TABLE_COLS), up[B * KITTI_TABLE_COLS:]
+    scores = ws = dims = None
+    if cc_th > 0:
+        cap = max(max_h * sum(hws[lo:hi]) for lo, hi in plan)
+        scores = torch.empty(cap, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().rfx_remove_small_cc_ragged_ws_bytes(cap), dtype=torch.uint8, device=dev)
+        dims = torch.empty((max(hi - lo for lo, hi in plan) * max_h, 3), dtype=torch.int32, device=dev)
+    one = _one_device(rec, fg, mg, binary)
+    head = (_p(rec), rec.numel(), records.width, max_h, records.off_H, records.off_flow)
+    for lo, hi in plan:
+        Bc, mhw, base, elems = hi - lo, max(hws[lo:hi]), rows[lo][10], max_h * sum(hws[lo:hi])
+        if cc_th > 0:
+            _call("rfx_kitti_scores_records_f32", one, *head, _p(table[lo:hi]), Bc, mhw, 1 if multiH else 0, _p(scores), base, elems,
+                  _p(dims), total)
+            _call("rfx_remove_small_cc_ragged_f32", one, _p(scores), _p(scores), _p(moff[lo * max_h:hi * max_h]), _p(dims), Bc * max_h,
+                  elems, mhw, 0.99, _p(ws))
+        _call("rfx_assemble_kitti_records_f32", one, *head, _p(table[lo:hi]), Bc, mhw, float(th), 1 if multiH else 0, _p(scores), base,
+              elems, _p(fg), _p(mg), _p(binary), total)
+    valid = rec[:, 0] >= 1                                    # the kernel's own test of nbH
+    if interpolate:
+        # runs of consecutive pairs of one size: a pair without explained pixel (nbH == 0 among them) takes its pixel (H-1, 0), zero
+        b = 0
+        while b < B:
+            e = b + 1
+            while e < B and rows[e][7:9] == rows[b][7:9]:
+                e += 1
+            (H, W), o, n = rows[b][7:9], rows[b][9], (e - b) * hws[b]
+            filled = nearest_fill(fg[o:o + n].view(e - b, H, W, 2), binary[o:o + n].view(e - b, H, W))
+            if out is None and e - b == B:
+                fg = filled.view(total, 2)
+            else:
+                fg[o:o + n].copy_(filled.view(n, 2))
+            b = e
+    if not ragged:
+        H, W = rows[0][7:9]
+        return fg.view(B, H, W, 2), mg.view(B, H, W), binary.view(B, H, W), valid
+    views = [(r[9], r[7], r[8]) for r in rows]
+    return ([fg[o:o + H * W].view(H, W, 2) for o, H, W in views], [mg[o:o + H * W].view(H, W) for o, H, W in views],
+            [binary[o:o + H * W].view(H, W) for o, H, W in views], valid)
+
+
 def multih_accept(match, mask, bg, active, ransac_result, n_match, nbH, th, mode, bestH=None, flowDown8=None, match12Down8=None,
                   match21Down8=None, flowD2=None, records=None):
     """Accept rule + mask update + record store of one round (rfx_multih_accept_f32) -> (accept (a,) int32, gain (a,) f32),
