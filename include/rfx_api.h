@@ -469,6 +469,32 @@ size_t rfx_flow_points_ws_bytes(int N, int H, int W);
 int rfx_flow_points_f32(const float* flow, const unsigned char* keep, const unsigned char* bg, int N, int H, int W, int k, int wA,
                         int hA, int wB, int hB, float* pts1, long long* pts2, long long* offsets, void* ws, void* stream);
 
+/* rfx_flow_points_f32 for B maps of DIFFERENT sizes, each with its own quarter turn and its own source size, in one chain (ADDED
+ * under ABI 17, like rfx_keep_mask_ragged_f32: nothing existing moves): evaluation/evalYFCC/getResults.py:53-71 (matches_from_flow)
+ * as the script's loop :298-318 calls it once per pair, for a whole batch.
+ * flow (total_px,2) float32, keep (total_px) bytes, bg (total_px) bytes or NULL: the packed buffers rfx_assemble_records_f32 fills
+ * for a ragged batch -- map b's pixels at its pixel offset, row-major.  table (B,8) int64 on the device, row b:
+ *     pixel offset | H | W | k | wA | hA | index of the map's first tile | 0
+ * a pure function of the size lists: a map of H*W pixels has ceil(H*W / 1024) tiles, the first-tile column is their exclusive
+ * prefix, total_tiles their sum.  (wB, hB) follow from (H, W, k): the map is (hB, wB) for even k and (wB, hB) for odd k.
+ * The rule is rfx_flow_points_f32's, applied per map with that map's k, wA, hA, wB, hB; rows come map after map, row-major inside a
+ * map; offsets (B+1) int64 = the rows before each map, offsets[B] = all rows, stays on the device; a map without a kept pixel
+ * contributes no row.  pts1 and pts2 must have room for total_px rows; rows beyond offsets[B] are not written, and no row at or
+ * beyond total_px is ever written, whatever ws holds.  Deterministic: three stream-ordered launches (count per tile, the map of a
+ * tile found by a binary search over the first-tile column; one-workgroup scan; scatter by recomputed ballots), no atomics, no
+ * workgroup waits on another; both tiled grids are capped at 8192 workgroups and stride.
+ * ws: rfx_flow_points_ragged_ws_bytes(total_tiles) bytes = one int32 per tile (0 for a non-positive count).
+ * A table row that does not describe a map inside the buffers (a negative offset, a non-positive size, offset + H*W > total_px, k
+ * outside 0..3, wA or hA outside 1..2^31-1, a first tile that is negative or behind the tile looked up) is skipped: none of its
+ * pixels is read, it contributes no row.
+ * RFX_E_ARG: a null pointer other than bg, a non-positive B, total_px or total_tiles, total_tiles > total_px, flow / table / pts1 /
+ * offsets not 8-byte or pts2 not 16-byte aligned.  RFX_E_LIMIT: total_px > 2^31 - 1, B > 65535.  All of these are checked before
+ * any HIP call. */
+size_t rfx_flow_points_ragged_ws_bytes(long long total_tiles);
+int rfx_flow_points_ragged_f32(const float* flow, const unsigned char* keep, const unsigned char* bg, const long long* table, int B,
+                               long long total_px, long long total_tiles, float* pts1, long long* pts2, long long* offsets, void* ws,
+                               void* stream);
+
 /* The keypoint transfer of evaluation/evalCorr/getResults.py:15-31 (alignmentError: the whole maps go to the host there): for K
  * target pixels (xb[q], yb[q]) (int32, device) of ONE map, flow (H,W,2), match (H,W) float32,
  *     xa[q] = ((flow[yb,xb,0] + 1) * 0.5f) * (float)(wA - 1),  ya[q] with channel 1 and hA - 1 (float32, in that order),

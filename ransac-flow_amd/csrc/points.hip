@@ -13,17 +13,9 @@
 // (b) rfx_sample_points_f32: the keypoint transfer of evaluation/evalCorr/getResults.py:15-31 (alignmentError), one thread per point.
 // Built with -ffp-contract=off: every float32 step below is rounded on its own, in the order written.
 #include "common.h"
+#include "points_tile.h"
 
 namespace {
-
-constexpr int POINTS_BLOCK = 256;                // 4 wavefronts
-constexpr int POINTS_PASSES = 4;
-constexpr int POINTS_TILE = POINTS_BLOCK * POINTS_PASSES;
-constexpr int POINTS_WAVES = POINTS_BLOCK / 64;
-constexpr int POINTS_GRID_CAP = 8192;            // workgroups stride over the tiles beyond it
-constexpr int POINTS_SCAN_BLOCK = 1024;          // 16 wavefronts
-
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
 
 struct PointsTiling {
     long long tiles;     // N * per_map
@@ -171,8 +163,6 @@ PointsTiling points_tiling(int N, int H, int W) {
     tl.rows = (long long)N * tl.HW;
     return tl;
 }
-
-bool points_aligned(const void* p, size_t a) { return ((size_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

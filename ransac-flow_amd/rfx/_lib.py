@@ -83,6 +83,8 @@ SIGNATURES = {
     "rfx_nearest_fill_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
     "rfx_flow_points_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_flow_points_f32": (c_int, [c_void_p] * 3 + [c_int] * 8 + [c_void_p] * 5),
+    "rfx_flow_points_ragged_ws_bytes": (c_size_t, [c_longlong]),
+    "rfx_flow_points_ragged_f32": (c_int, [c_void_p] * 4 + [c_int, c_longlong, c_longlong] + [c_void_p] * 5),
     "rfx_sample_points_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4),
     "rfx_epe_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_epe_homography_f32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 5),

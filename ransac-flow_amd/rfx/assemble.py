@@ -24,6 +24,9 @@ assemble_yfcc give on the record's first nbH entries, with nbH read on the devic
 HPatches, Corr and YFCC forms.  KITTI's records (with flowD2) go through assemble_kitti_records (rfx_assemble_kitti_records_f32, with
 cc_th > 0 also rfx_kitti_scores_records_f32 and the ragged component filter): the two-level composition is evaluated per pixel, the
 filter runs on one packed score buffer per chunk of pairs, and the --interpolate fill is ops.nearest_fill on the batch.
+The YFCC results step has its batch form as well: yfcc_matches_records takes the records multi_h_variant_c(..., want_records=True)
+builds for pairs of any sizes to the correspondences of every pair -- one assembly launch, the three launches of
+rfx_flow_points_ragged_f32 and ONE host read for the batch; yfcc_norm_kp is the script's norm_kp on the host.
 
 On-disk formats (written by evaluation/evalHpatch/evaluation.py:254-260 and friends):
     <fine>/flow_{id}_{n}H.npy   (n,2,h/8,w/8) float   fine flow, stride 8
@@ -111,6 +114,62 @@ def yfcc_matches(flowGlobal, binary, sizeA, sizeB, angle):
     if f.dim() == 4 and f.shape[0] == 1:
         f, b = f[0], b.reshape(f.shape[1], f.shape[2])
     return ops.matches_from_flow(f, b, sizeA, sizeB, angle)[:2]
+
+
+def yfcc_matches_records(records, th, multiH, sizesA=None, sizesB=None, angles=None, bg="records", return_maps=False):
+    """The YFCC results step (evalYFCC/getResults.py:304-318: getFlow, then matches_from_flow) for EVERY pair of a batch of device
+    records at once: ops.assemble_records (cycle=True at 8h x 8w, the background ANDed in) into packed buffers allocated here, then
+    ops.matches_from_flow_ragged on those buffers -- one assembly launch, three points launches and ONE host read (the offsets) for
+    the whole batch, whatever the pairs' sizes.  Per pair bit for bit assemble_yfcc on the record's first nbH entries followed by
+    yfcc_matches.  ``sizesA[b]`` = (wA, hA) of the resized source, ``sizesB[b]`` = (wB, hB) of the resized target BEFORE its rotation
+    by ``angles[b]``; the defaults are what multi_h_variant_c(_pairs)(..., want_records=True) left on the records: size_src, size_tgt
+    turned back by the angle, angle.  ``bg``: "records" (records.bg, possibly None), None, or what ops.assemble_records takes.
+    -> (pts1 (n,2) float32, pts2 (n,2) int64, offsets (B+1,) int64 on the HOST, valid (B,) bool on the device); pair b's points are
+    rows offsets[b]:offsets[b+1], a pair without a homography (valid False) has none.  ``return_maps``: also the per-pair
+    flowGlobal / binary views of the packed buffers."""
+    rows, _, total = ops.assemble_records_table(records)
+    B, dev = records.B, records.rec.device
+    sizes = [(r[4], r[5]) for r in rows]
+    sizesA = getattr(records, "size_src", None) if sizesA is None else sizesA
+    if sizesA is None:
+        raise ValueError("yfcc_matches_records: these records carry no size_src; pass sizesA = one (wA, hA) per pair")
+    angles = getattr(records, "angle", None) if angles is None else angles
+    if angles is None:
+        raise ValueError("yfcc_matches_records: these records carry no angle (multi_h_variant_c_pairs sets it); pass angles")
+    ptab = ops.flow_points_ragged_table(sizes, sizesA, angles)[0]                # checks lengths, angles and sizes on the host
+    if sizesB is None:
+        tgt = getattr(records, "size_tgt", None)
+        if tgt is None:
+            raise ValueError("yfcc_matches_records: these records carry no size_tgt; pass sizesB = one (wB, hB) per pair")
+        sizesB = [(h, w) if r[3] & 1 else (w, h) for (w, h), r in zip(tgt, ptab)]
+    if len(sizesB) != B:
+        raise ValueError("yfcc_matches_records: %d sizesB for %d pairs" % (len(sizesB), B))
+    for b, ((wB, hB), r) in enumerate(zip(sizesB, ptab)):
+        want = (int(wB), int(hB)) if r[3] & 1 else (int(hB), int(wB))
+        if (r[1], r[2]) != want:
+            raise ValueError("yfcc_matches_records: pair %d's map of shape %s does not fit sizeB = %s at angle %s (%s expected)"
+                             % (b, (r[1], r[2]), (wB, hB), 90 * r[3], want))
+    if isinstance(bg, str):
+        if bg != "records":
+            raise ValueError("yfcc_matches_records: bg is \"records\", None or background maps, got %r" % bg)
+        bg = getattr(records, "bg", None)
+    out = (torch.empty((total, 2), dtype=torch.float32, device=dev), torch.empty(total, dtype=torch.float32, device=dev),
+           torch.empty(total, dtype=torch.bool, device=dev))
+    flows, _, binaries, valid = ops.assemble_records(records, th, multiH, True, bg=bg, out=out)
+    pts1, pts2, off = ops.matches_from_flow_ragged(out[0], out[2], sizes, sizesA, [90 * r[3] for r in ptab])
+    return (pts1, pts2, off, valid, flows, binaries) if return_maps else (pts1, pts2, off, valid)
+
+
+def yfcc_norm_kp(org_size, new_size, K, kp):
+    """evalYFCC/getResults.py:29-50 (norm_kp): pixel coordinates ``kp`` (n,2) of an image resized from ``org_size`` = (w, h) to
+    ``new_size`` = (w_n, h_n) -> image-plane coordinates under the calibration K (3,3), whose principal point is given relative to
+    the image centre.  numpy float64 on host arrays, the script's own operations in its order (the points have to cross the bus for
+    cv2's pose solver anyway): not a device op."""
+    (w, h), (w_n, h_n) = org_size, new_size
+    sx, sy = w_n / w, h_n / h                                      # the resize, per axis
+    centre = np.array([[((w - 1.0) * 0.5 + K[0, 2]) * sx, ((h - 1.0) * 0.5 + K[1, 2]) * sy]])
+    focal = np.array([[K[0, 0] * sx, K[1, 1] * sy]])
+    return (kp - centre) / focal
 
 
 def corr_alignment_error(wB, hB, wA, hA, XA, YA, XB, YB, flow, match2, pixelGrid, device="cuda"):

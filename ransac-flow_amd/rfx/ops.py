@@ -1275,6 +1275,97 @@ def matches_from_flow(flow, keep, sizeA, sizeB, angle=0, bg=None):
     return pts1[:total], pts2[:total], off
 
 
+POINTS_TILE = 1024             # pixels of one workgroup's tile (csrc/points_tile.h)
+
+
+def flow_points_ragged_table(sizes, sizesA, angles):
+    """The table of rfx_flow_points_ragged_f32 for B maps of different sizes, on the host: a pure function of ``sizes[b]`` = (H, W) of
+    map b as it lies in the packed buffers, ``sizesA[b]`` = (wA, hA) of its source and ``angles[b]`` (a multiple of 90 degrees; one
+    int = the same for all).  -> (rows, total_px, total_tiles): row b = (pixel offset | H | W | k | wA | hA | index of the map's first
+    tile | 0) with k = (angle // 90) % 4; a map has ceil(H * W / 1024) tiles.  The unrotated target size follows from (H, W, k):
+    (wB, hB) = (W, H) for even k, (H, W) for odd k."""
+    B = len(sizes)
+    angles = [angles] * B if isinstance(angles, int) else list(angles)
+    if B == 0 or len(sizesA) != B or len(angles) != B:
+        raise ValueError("flow_points_ragged: one (H, W), one (wA, hA) and one angle per map, got %d, %d and %d"
+                         % (B, len(sizesA), len(angles)))
+    rows, off, tile = [], 0, 0
+    for (H, W), (wA, hA), a in zip(sizes, sizesA, angles):
+        H, W, wA, hA = int(H), int(W), int(wA), int(hA)
+        if int(a) != a or int(a) % 90:
+            raise ValueError("flow_points_ragged: angles are multiples of 90 degrees, got %r" % (a,))
+        if H < 1 or W < 1:
+            raise ValueError("flow_points_ragged: a map of shape %s" % ((H, W),))
+        if wA < 1 or hA < 1:
+            raise ValueError("flow_points_ragged: sizeA = %s" % ((wA, hA),))
+        rows.append((off, H, W, int(a) // 90 % 4, wA, hA, tile, 0))
+        off += H * W
+        tile += (H * W + POINTS_TILE - 1) // POINTS_TILE
+    return rows, off, tile
+
+
+def _packed_maps(x, name):
+    """A packed buffer from ``x`` (shapes checked by the caller): a tensor as it is; a list of one map per pair taken as ONE view
+    where the maps already lie one behind the other in one buffer (what assemble_records returns), concatenated otherwise."""
+    if isinstance(x, torch.Tensor):
+        return x
+    parts, trailing = list(x), tuple(x[0].shape[2:])
+    total = sum(t.shape[0] * t.shape[1] for t in parts)
+    if any(not t.is_cuda for t in parts):
+        raise RuntimeError("%s is on %s: rfx ops run only on a HIP device (no CPU fallback)" % (name, parts[0].device))
+    if any(t.dtype != parts[0].dtype for t in parts):
+        raise TypeError("flow_points_ragged: the maps of %s differ in dtype" % name)
+    first, size = parts[0], parts[0].element_size()
+    ptr, consecutive = first.data_ptr(), True
+    for t in parts:
+        consecutive = consecutive and t.is_contiguous() and t.data_ptr() == ptr and \
+            t.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+        ptr += t.numel() * size
+    if consecutive:
+        return first.new_empty(0).set_(first.untyped_storage(), first.storage_offset(), (total,) + trailing)
+    return torch.cat([t.reshape((-1,) + trailing) for t in parts])
+
+
+def flow_points_ragged(flow, keep, sizes, sizesA, angles, bg=None):
+    """flow_points for B maps of DIFFERENT sizes, each with its own angle and source size, in one chain (rfx_flow_points_ragged_f32:
+    three launches for the whole batch): evaluation/evalYFCC/getResults.py:53-71 as the script calls it per pair (:318).
+    ``sizes[b]`` = (H, W) of map b, ``sizesA[b]`` = (wA, hA), ``angles[b]`` a multiple of 90 (or one int for all); the unrotated
+    target size is (W, H) for even k = angle // 90, (H, W) for odd k.  flow / keep / bg (optional): the packed buffers of
+    assemble_records on ragged records -- (total_px,2) float32, (total_px,) bool or uint8 -- or lists of per-pair maps (H_b,W_b,2) /
+    (H_b,W_b), which are concatenated only when they are not already consecutive views of one buffer.  No host sync: returns
+    (pts1_buf (total_px,2) float32, pts2_buf (total_px,2) int64, offsets (B+1,) int64), all on the device; pair b's rows are
+    offsets[b]:offsets[b+1], a pair without a kept pixel has none, only the first offsets[-1] rows are written."""
+    rows, total, tiles = flow_points_ragged_table(sizes, sizesA, angles)
+    sizes = [(r[1], r[2]) for r in rows]
+    for name, x, trailing in (("flow", flow, (2,)), ("keep", keep, ()), ("bg", bg, ())):     # every shape before any device
+        shapes = [tuple(x.shape)] if isinstance(x, torch.Tensor) else None if x is None else [tuple(getattr(t, "shape", ())) for t in x]
+        if shapes is not None and shapes != [(total,) + trailing] and shapes != [s + trailing for s in sizes]:
+            raise ValueError("flow_points_ragged: %s is a packed %s buffer or one map per pair of the shapes %r, got %r"
+                             % (name, (total,) + trailing, sizes, shapes))
+    f = _dev(_packed_maps(flow, "flow"), "flow")
+    m = _mask_bytes(_packed_maps(keep, "keep"), "keep")
+    b = _mask_bytes(_packed_maps(bg, "bg"), "bg") if bg is not None else None
+    B, dev = len(rows), f.device
+    pts1 = torch.empty((total, 2), dtype=torch.float32, device=dev)
+    pts2 = torch.empty((total, 2), dtype=torch.int64, device=dev)
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(_lib.load().rfx_flow_points_ragged_ws_bytes(tiles), dtype=torch.uint8, device=dev)
+    table = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    _call("rfx_flow_points_ragged_f32", _one_device(f, m, b), _p(f), _p(m), _p(b), _p(table), B, total, tiles, _p(pts1), _p(pts2),
+          _p(offsets), _p(ws))
+    return pts1, pts2, offsets
+
+
+def matches_from_flow_ragged(flow, keep, sizes, sizesA, angles, bg=None):
+    """flow_points_ragged, exactly sized: ONE read of the offsets (the only host sync of the batch), then views of the first
+    offsets[-1] rows -> (pts1 (n,2) float32, pts2 (n,2) int64, offsets (B+1,) int64 HOST copy): pair b's points are rows
+    offsets[b]:offsets[b+1].  Views of flow_points_ragged's buffers (no copy); ``.clone()`` them to let the buffers go."""
+    pts1, pts2, offsets = flow_points_ragged(flow, keep, sizes, sizesA, angles, bg)
+    off = offsets.cpu()
+    total = int(off[-1])
+    return pts1[:total], pts2[:total], off
+
+
 def sample_points(flow, match, xb, yb, sizeA):
     """evaluation/evalCorr/getResults.py:15-31 (alignmentError's reads of the assembled maps) on the device (rfx_sample_points_f32):
     for K target pixels (xb, yb) -- host integers, or floats truncated toward zero like ``astype(np.int64)`` -- of ONE map,
@@ -1929,7 +2020,14 @@ class MultiHRecordsRagged:
     is zero.  With ``hd2_list`` / ``wd2_list`` (the KITTI driver: the half-resolution /8 sizes per pair) row b gains flowD2
     (max_h,2,hd2,wd2) from off_d2[b] = off_match[b] + 2 h8 w8 max_h, again the dense row of MultiHRecords(1, h8, w8, hd2=, wd2=);
     without them width, offsets and views are unchanged.  A pure function of the size lists.  Filled on the device by
-    multih_accept_ragged."""
+    multih_accept_ragged.
+    What the YFCC driver's candidate search decided rides on the object as plain attributes (None unless
+    multi_h_variant_c(..., want_records=True) built the records; ``rows`` slices them): ``candidate`` the chosen k per pair (host
+    list) and ``candidate_dev`` the same as an int32 device tensor; ``size_src`` (w, h) of each resized source; ``size_tgt`` (w, h)
+    of each CHOSEN candidate as resized -- the assembled maps are 8 h8 x 8 w8 = (h, w) of it; ``bg`` the chosen candidates'
+    background maps (the script's maskBG) as ONE packed byte buffer in assemble_records' output layout, or None when no It_bg was
+    given; ``angle`` (multi_h_variant_c_pairs only) angles[candidate] per pair."""
+    candidate = candidate_dev = size_src = size_tgt = bg = angle = None
 
     def __init__(self, h8_list, w8_list, device, max_h=11, hd2_list=None, wd2_list=None):
         if len(h8_list) != len(w8_list) or not h8_list:
@@ -1961,6 +2059,12 @@ class MultiHRecordsRagged:
         r = copy.copy(self)
         r.B, r.rec = hi - lo, self.rec[lo:hi]
         r.h8, r.w8, r.off_match = self.h8[lo:hi], self.w8[lo:hi], self.off_match[lo:hi]
+        cut = lambda x: None if x is None else x[lo:hi]
+        r.candidate, r.candidate_dev, r.size_src, r.size_tgt, r.angle = (cut(x) for x in (self.candidate, self.candidate_dev, self.size_src,
+                                                                                           self.size_tgt, self.angle))
+        if self.bg is not None:                                  # packed like the assembled maps: 64 h8 w8 bytes per pair
+            px = [64 * sum(a * b for a, b in zip(self.h8[:n], self.w8[:n])) for n in (lo, hi)]
+            r.bg = self.bg[px[0]:px[1]]
         if self.hd2 is not None:
             r.hd2, r.wd2, r.off_d2, r.d2dims = self.hd2[lo:hi], self.wd2[lo:hi], self.off_d2[lo:hi], self.d2dims[lo:hi]
         return r

@@ -839,7 +839,7 @@ class AlignPipeline:
         return self._pred_flow_mask_cycle_lists(self._sampled_features(Is_list, fcs), featt_list, fcs, out=out)
 
     def multi_h_variant_c(self, src_u8, tgt_candidates_u8, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None,
-                          want_lists=True, pair_ids=None, draw_epoch=0, split=None):
+                          want_lists=True, pair_ids=None, draw_epoch=0, split=None, want_records=False):
         """The driver of evaluation/evalYFCC/evaluation.py:176-292 for a batch of B pairs in lock-step, everything on the device.
 
         ``src_u8`` (B,H,W,3) uint8: the sources; ``tgt_candidates_u8``: K tensors (B,Hk,Wk,3) -- candidate k of every pair (the
@@ -862,13 +862,22 @@ class AlignPipeline:
         candidate, all targets of one shape are stacked and take the dense path unchanged; otherwise the ragged path
         (_multi_h_variant_c_ragged) -- per pair the results are, bit for bit, the pair's alone.  ``It_bg`` is then K lists (or None)
         of B per-pair (h,w) tensors at the candidates' resized sizes (None entries = all ones); ``split``: lock-step groups of the
-        rounds as in multi_h_batched (default 1; the dense path runs its shape groups one after the other).  The ragged path fills
-        no ``records`` (their geometry depends on the chosen candidate, known only after the search) and always returns the lists.
+        rounds as in multi_h_batched (default 1; the dense path runs its shape groups one after the other).  The geometry of a
+        ragged batch's records depends on the chosen candidates, known only after the search, so the ragged path takes no
+        ``records=``; it BUILDS them: ``want_records=True`` (list inputs only; such a call always takes the ragged path, also when all
+        sizes agree -- per pair it is bit-identical) makes an ops.MultiHRecordsRagged over the chosen candidates' /8 sizes with
+        max_h = maxCoarse + 1 after the search, has the rounds' accept kernel fill it, hangs the search's decisions on it (candidate,
+        candidate_dev, size_src, size_tgt, bg: see the class) and returns (outs, records); ``want_lists=False`` is allowed with it.
         Returns a list of B dicts: H / flowDown8 / matchDown8 lists, mask, nbH, candidate (the chosen k), nbInlier (K counts)."""
-        if isinstance(src_u8, (list, tuple)) or any(isinstance(c, (list, tuple)) for c in tgt_candidates_u8):
-            src_l, cands, It_bg, mixed = self._variant_c_lists(src_u8, tgt_candidates_u8, It_bg, records, want_lists)
+        lists = isinstance(src_u8, (list, tuple)) or any(isinstance(c, (list, tuple)) for c in tgt_candidates_u8)
+        if want_records and not lists:
+            raise ValueError("multi_h_variant_c: want_records=True builds the records of a LIST of pairs; a batch of stacked tensors "
+                             "fills the ops.MultiHRecords handed in as records=")
+        if lists:
+            src_l, cands, It_bg, mixed = self._variant_c_lists(src_u8, tgt_candidates_u8, It_bg, records, want_lists, want_records)
             if mixed:
-                return self._multi_h_variant_c_ragged(src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split)
+                return self._multi_h_variant_c_ragged(src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split,
+                                                      want_lists, want_records)
             src_u8, tgt_candidates_u8 = src_l, cands
         dev = self.dev
         B, K = src_u8.shape[0], len(tgt_candidates_u8)
@@ -950,9 +959,10 @@ class AlignPipeline:
         return chosen, table, outs
 
     # ---------------------------------------------------------------- the YFCC driver on pairs of different sizes
-    def _variant_c_lists(self, src, cands, It_bg, records, want_lists):
+    def _variant_c_lists(self, src, cands, It_bg, records, want_lists, want_records=False):
         """The list inputs of multi_h_variant_c, checked -> (src, cands, It_bg, mixed).  Same shapes throughout (``mixed`` False):
-        everything stacked into the dense driver's tensors.  Otherwise per-pair lists, It_bg as K lists of B entries or None."""
+        everything stacked into the dense driver's tensors.  Otherwise -- and always with ``want_records`` -- per-pair lists, It_bg
+        as K lists of B entries or None."""
         dev = self.dev
         src_l = list(src)
         cands = [list(c) for c in cands]
@@ -965,7 +975,7 @@ class AlignPipeline:
         imgs = src_l + [x for c in cands for x in c]
         if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 for x in imgs):
             raise ValueError("sources and candidate targets are uint8 (H,W,3) tensors, one per pair")
-        mixed = ragged.mixed(*([tuple(x.shape) for x in lst] for lst in [src_l] + cands))
+        mixed = want_records or ragged.mixed(*([tuple(x.shape) for x in lst] for lst in [src_l] + cands))
         if It_bg is not None:
             if len(It_bg) != K or any(g is not None and len(g) != B for g in It_bg):
                 raise ValueError("It_bg: one entry per candidate (K = %d), each None or B = %d per-pair maps" % (K, B))
@@ -976,11 +986,11 @@ class AlignPipeline:
                     if x is not None and tuple(x.shape) != (nh, nw):
                         raise ValueError("It_bg[%d][%d] of shape %s for a candidate resized to %s" % (k, b, tuple(x.shape), (nh, nw)))
         if mixed and records is not None:
-            raise ValueError("multi_h_variant_c on pairs of different sizes fills no records: their geometry depends on the chosen "
-                             "candidate, which is known only after the search")
-        if mixed and not want_lists:
-            raise ValueError("multi_h_variant_c on pairs of different sizes has no records to fill, so want_lists=False would return "
-                             "nothing")
+            raise ValueError("multi_h_variant_c on pairs of different sizes fills no records= handed in: their geometry depends on the "
+                             "chosen candidate, which is known only after the search (want_records=True builds and returns them)")
+        if mixed and not want_lists and not want_records:
+            raise ValueError("multi_h_variant_c on pairs of different sizes without want_records=True has no records to fill, so "
+                             "want_lists=False would return nothing")
         if any(not x.is_cuda or x.device != imgs[0].device for x in imgs):
             raise ValueError("sources and candidate targets must live on one HIP device (no CPU fallback)")
         if mixed:
@@ -996,13 +1006,15 @@ class AlignPipeline:
             It_bg = dense_bg
         return torch.stack(src_l), [torch.stack(c) for c in cands], It_bg, False
 
-    def _multi_h_variant_c_ragged(self, src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split):
+    def _multi_h_variant_c_ragged(self, src_l, cands, maxCoarse, maskRegionTh, It_bg, sample_fn, pair_ids, draw_epoch, split,
+                                  want_lists=True, want_records=False):
         """multi_h_variant_c for pairs of different sizes (src_l[b], cands[k][b]: uint8 (H,W,3) device tensors).
         *Search*: the source pyramids and all B * K candidate targets through ONE grouped trunk pass (_features_ragged); per
         candidate index k, for all pairs at once: keep map of the candidate's background (rfx_keep_mask_ragged_f32, mask null) ->
         masked ragged mutual matching -> match gather -> draws (tag variant_c_select, round k) -> RANSAC search; ONE host sync, the
         (B,K) inlier-count table.  *Rounds*: rounds.RaggedVariantCGroup on the CHOSEN candidates' features and packed masks
-        (ragged_variant_c_tables) under the lock-step machinery of the other ragged drivers."""
+        (ragged_variant_c_tables) under the lock-step machinery of the other ragged drivers.  ``want_records``: an
+        ops.MultiHRecordsRagged over the chosen candidates' /8 sizes, filled by the rounds' accept kernel; -> (outs, records)."""
         dev, B, K = self.dev, len(src_l), len(cands)
         prep = self.prepare_candidates_device(src_l, cands)
         plan, feats = prep["plan"], self.features(prep)
@@ -1020,26 +1032,39 @@ class AlignPipeline:
             return M1, M2, n_k
         chosen, _, outs = self._variant_c_select(K, B, matches_of, sample_fn, pair_ids, draw_epoch)
         # the rounds: the chosen candidates' features, sizes and tables as ONE ragged batch
-        pb = ragged.PackedBatch(ragged_variant_c_tables(plan, chosen),
-                                None if It_bg is None else [None if It_bg[c] is None else It_bg[c][b] for b, c in enumerate(chosen)], dev)
+        tabs = ragged_variant_c_tables(plan, chosen)
+        pb = ragged.PackedBatch(tabs, None if It_bg is None else [None if It_bg[c] is None else It_bg[c][b] for b, c in enumerate(chosen)], dev)
+        records = None
+        if want_records:
+            sizes8 = [tuple(g[4:6]) for g in tabs["geom"]]
+            records = ops.MultiHRecordsRagged([s[0] for s in sizes8], [s[1] for s in sizes8], dev, max_h=maxCoarse + 1)
+            ops.MultiHRecordsRagged.require(records, sizes8)
+            records.candidate = list(chosen)
+            records.candidate_dev = torch.tensor(chosen, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            records.size_src = [(int(x.shape[3]), int(x.shape[2])) for x in prep["IsTensor"]]
+            records.size_tgt = [(g[1], g[0]) for g in tabs["geom"]]           # (h, w) = (8 h8, 8 w8): a packed mask IS a packed map
+            records.bg = None if pb.bg is None else (pb.bg != 0).to(torch.uint8)
         pick = torch.tensor([c * B + b for b, c in enumerate(chosen)], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         rf = dict(feats, featB=feats["featB"].view(K * B, 1024, ldB).index_select(0, pick), nB=[plan["nB"][c][b] for b, c in enumerate(chosen)],
                   nB_dev=feats["nB_dev"].reshape(-1).index_select(0, pick), offB=feats["offB"].reshape(-1).index_select(0, pick))
-        st = rounds.RoundState(self, outs, "variant_c", (), split, sample_fn, None, True, None, pair_ids, draw_epoch, maskRegionTh, maxCoarse)
+        st = rounds.RoundState(self, outs, "variant_c", (), split, sample_fn, records, want_lists, None, pair_ids, draw_epoch, maskRegionTh,
+                               maxCoarse)
         batch = dict(pb.fields(), prep=dict(IsTensor=prep["IsTensor"], ItTensor=[prep["ItTensor"][c][b] for b, c in enumerate(chosen)]),
                      feats=rf, idx1=None, idx2=None, cnt=None)
         rounds.drive_rounds(self, [rounds.lockstep_rounds(rounds.RaggedVariantCGroup(st, batch, lo, hi)) for lo, hi in st.bounds])
-        return st.close(pb.mask_of)
+        outs = st.close(pb.mask_of)
+        return (outs, records) if want_records else outs
 
     def multi_h_variant_c_pairs(self, pairs, angles=(0, 90, 180, 270), maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None,
-                                records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None, seg=None):
+                                records=None, want_lists=True, pair_ids=None, draw_epoch=0, split=None, seg=None, want_records=False):
         """multi_h_variant_c on pairs of PIL images, the candidates being the target turned by ``angles`` (multiples of 90 degrees,
         counter-clockwise: evaluation/evalYFCC/evaluation.py:189).  Every image is uploaded once; a candidate is torch.rot90 of the
         uploaded target, byte-identical to PIL's rotate(angle, expand=True) for right angles.  All sources of one size and all targets
         of one size: the dense path on stacked tensors (``It_bg``: K tensors (B,h,w), ``records`` an ops.MultiHRecords).  Otherwise the
-        ragged path on lists (``It_bg``: K lists of per-pair maps; no records).  ``seg`` instead of ``It_bg``: one sky mask per target
-        (get_sky_batch), and candidate k gets it turned like the candidate, at that candidate's resized size
-        (evaluation/evalYFCC/evaluation.py:193-200)."""
+        ragged path on lists (``It_bg``: K lists of per-pair maps; no ``records=``).  ``seg`` instead of ``It_bg``: one sky mask per
+        target (get_sky_batch), and candidate k gets it turned like the candidate, at that candidate's resized size
+        (evaluation/evalYFCC/evaluation.py:193-200).  ``want_records=True``: always the ragged path on lists, -> (outs, records) as
+        multi_h_variant_c builds them, with ``records.angle`` = angles[candidate] per pair (the script's rotation.json)."""
         if any(int(a) % 90 for a in angles):
             raise ValueError("candidate angles are multiples of 90 degrees, got %s" % (tuple(angles),))
         use_seg = self._seg_or_bg(seg, It_bg)
@@ -1049,12 +1074,16 @@ class AlignPipeline:
             masks = seg.get_sky_batch(tgt)
             It_bg = [self._backgrounds_of_masks(masks, [self._target_resized_hw(int(x.shape[0]), int(x.shape[1])) for x in c],
                                                 [int(a) // 90] * len(tgt)) for a, c in zip(angles, cands)]
-        if not self._mixed_sizes(pairs):
+        if not self._mixed_sizes(pairs) and not want_records:
             src, cands = torch.stack(src), [torch.stack(c) for c in cands]
             if use_seg:
                 It_bg = [torch.stack(g) for g in It_bg]
-        return self.multi_h_variant_c(src, cands, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
-                                      records=records, want_lists=want_lists, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
+        res = self.multi_h_variant_c(src, cands, maxCoarse=maxCoarse, maskRegionTh=maskRegionTh, It_bg=It_bg, sample_fn=sample_fn,
+                                     records=records, want_lists=want_lists, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split,
+                                     want_records=want_records)
+        if want_records:
+            res[1].angle = [int(angles[c]) for c in res[1].candidate]
+        return res
 
     # ---------------------------------------------------------------- KITTI two-resolution driver (BASELINE config 5)
     resize_img_dims = staticmethod(resize_img_dims)     # outil.resizeImg's sizes (module level: ragged_kitti_tables uses it too)
