@@ -48,7 +48,7 @@ const char* rfx_version(void);
  * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
  * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17,
  * and so were rfx_epe_ws_bytes, rfx_epe_homography_f32, rfx_epe_flow_f32, rfx_assemble_records_f32, rfx_assemble_kitti_records_f32
- * and rfx_kitti_scores_records_f32: no existing entry point moved, and a binding that knows
+ * and rfx_kitti_scores_records_f32, then rfx_records_keypoints_f32 and rfx_pck_tally_f64: no existing entry point moved, and a binding that knows
  * a new name refuses a library without it).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
 #define RFX_ABI_VERSION 17
@@ -503,6 +503,44 @@ int rfx_flow_points_ragged_f32(const float* flow, const unsigned char* keep, con
  * RFX_E_ARG: a null pointer, a non-positive K, H or W, wA or hA < 1, flow not 8-byte aligned; RFX_E_LIMIT: H*W > 2^31 - 1. */
 int rfx_sample_points_f32(const float* flow, const float* match, const int32_t* xb, const int32_t* yb, int K, int H, int W, int wA,
                           int hA, float* xa, float* ya, unsigned char* keep, void* stream);
+
+/* The sparse-correspondence results step of a whole batch from the drivers' records, without the dense maps (both ADDED under ABI 17,
+ * like rfx_keep_mask_ragged_f32: nothing existing moves).
+ *
+ * rfx_records_keypoints_f32: evaluation/evalCorr/getResults.py:78-136 (getFlow) read at the annotated pixels as :15-31
+ * (alignmentError) and :281-282 (the threshold loop) read it.  rec, rec_elems, width, max_h, off_H, off_flow, table (B,8), th, multiH,
+ * cycle, bg: as rfx_assemble_records_f32 takes them, with the same row checks; total_px = the pixels of all pairs' maps in that
+ * layout (what bg holds; a row's map must lie inside it).  ktable (B,4) int64 on the device, row b:
+ *     first keypoint | number of keypoints | wA | hA
+ * the first-keypoint column the exclusive prefix of the counts; xb, yb (K_total) int32: the target pixels, pair after pair.  One
+ * thread per keypoint finds its pair by a binary search over the first-keypoint column and evaluates the pixel from the record alone:
+ *     xa[q] = ((flowGlobal[yb,xb,0] + 1) * 0.5f) * (float)(wA - 1), ya[q] with channel 1 and hA - 1 (float32, in that order);
+ *     m[q] = matchGlobal[yb,xb];  flag[q] bit 0 = binary[yb,xb] (ANDed with bg when given), bit 1 = both flow channels in [-1, 1]
+ *     (the flow is clamped: clear only for a NaN).
+ * Per pair bit for bit what rfx_assemble_records_f32 followed by rfx_sample_points_f32 gives at the same pixels.  A keypoint outside
+ * its map, or of a row that is refused, reads nothing and gives 0, 0, 0, 0; a pair with nbH < 1 gives what its zero maps give.  No
+ * atomics, no LDS.
+ * RFX_E_ARG: a null pointer other than bg, a non-positive B, width, max_h, total_px or K_total, offsets that do not describe a
+ * record, rec_elems < B * width, a table not 8-byte aligned.  RFX_E_LIMIT: B > 65535, total_px or K_total > 2^31 - 1.
+ *
+ * rfx_pck_tally_f64: evaluation/evalCorr/getResults.py:281-282 (which keypoints a matchability threshold keeps), :25-36 (distances
+ * and their tally under the pixel grid) and :273-277 (a pair without a flow).  xa, ya, m, flag: the outputs above; xs, ys (K_total)
+ * int32 the source keypoints; ktable as above; match_th (M) float32; grid (T) float64, T <= 16; valid (B) bytes or NULL.
+ * For threshold t: keep = (m >= t) && flag bit 1 when t > 0, every keypoint (a NaN included) when t <= 0;
+ *     d = sqrt((double(xa) - xs)^2 + (double(ya) - ys)^2), every float64 step rounded on its own (no fused multiply-add);
+ *     counts[t,b,j] = kept keypoints of pair b with d <= grid[j] (int64, (M,B,T));  nb[t,b] = kept keypoints (int64, (M,B));
+ *     dist (M,K_total) float64 or NULL: d, NaN where the keypoint is not kept.
+ * A pair with valid[b] == 0: nb = its number of keypoints, counts zero, dist NaN.  One workgroup per (threshold, pair): ballots and
+ * popcounts per wavefront, one LDS pass, thread 0 writes; no atomics; integer sums, the same bits every run.  K_total may be 0.
+ * RFX_E_ARG: a null ktable, match_th, grid, counts or nb, a null keypoint array with K_total > 0, a non-positive B, M or T, T > 16,
+ * K_total < 0, ktable / grid / counts / nb / dist not 8-byte aligned.  RFX_E_LIMIT: B > 65535, K_total > 2^31 - 1. */
+int rfx_records_keypoints_f32(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow,
+                              const long long* table, int B, long long total_px, float th, int multiH, int cycle, const uint8_t* bg,
+                              const long long* ktable, const int32_t* xb, const int32_t* yb, long long K_total, float* xa, float* ya,
+                              float* m, uint8_t* flag, void* stream);
+int rfx_pck_tally_f64(const float* xa, const float* ya, const float* m, const uint8_t* flag, const int32_t* xs, const int32_t* ys,
+                      const long long* ktable, int B, long long K_total, const float* match_th, int M, const double* grid, int T,
+                      const uint8_t* valid, long long* counts, long long* nb, double* dist, void* stream);
 
 /* The end-point error of an assembled flow, reduced on the device to one float64 sum and one count per map (ADDED under ABI 17, like
  * rfx_keep_mask_ragged_f32: nothing existing moves).  Both entry points below share the outputs and the reduction:

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "group.h"
 #include "linspace.h"
+#include "assemble_pixel.h"
 #include <math.h>
 
 namespace {
@@ -18,34 +19,6 @@ inline int grid_for(long long total, int block) {
     long long g = (total + block - 1) / block;
     const long long cap = 256LL * 32;
     return (int)(g < cap ? g : cap);
-}
-
-__device__ __forceinline__ float unnormalize(float g, int size, int align) {
-    return align ? (g + 1.0f) * 0.5f * (float)(size - 1) : ((g + 1.0f) * (float)size - 1.0f) * 0.5f;
-}
-
-struct Corners {
-    int x0, y0;
-    float nw, ne, sw, se;
-    bool m_nw, m_ne, m_sw, m_se;
-};
-
-// ATen grid_sampler_2d (bilinear, zeros): weights from the fractional parts, out-of-image corners contribute 0.
-__device__ __forceinline__ Corners corners(float gx, float gy, int Hi, int Wi, int align) {
-    Corners c;
-    const float ix = unnormalize(gx, Wi, align), iy = unnormalize(gy, Hi, align);
-    const float xw = floorf(ix), yn = floorf(iy);
-    const float w = ix - xw, e = 1.0f - w, n = iy - yn, s = 1.0f - n;
-    c.nw = s * e; c.ne = s * w; c.sw = n * e; c.se = n * w;
-    // NaN / +-inf / huge coordinates: the comparisons below are all false -> the pixel is 0, as in ATen's CUDA grid_sampler (its
-    // within-bounds masks); ATen's CPU kernel returns NaN for NaN / +-inf coordinates and is not followed.  The (int) conversion
-    // further down is applied only to a floor that passed a range test (tests/test_gpu_pointwise_exact.py pins all of this).
-    const bool xin0 = xw >= 0.0f && xw <= (float)(Wi - 1), xin1 = xw + 1.0f >= 0.0f && xw + 1.0f <= (float)(Wi - 1);
-    const bool yin0 = yn >= 0.0f && yn <= (float)(Hi - 1), yin1 = yn + 1.0f >= 0.0f && yn + 1.0f <= (float)(Hi - 1);
-    c.m_nw = xin0 && yin0; c.m_ne = xin1 && yin0; c.m_sw = xin0 && yin1; c.m_se = xin1 && yin1;
-    c.x0 = (xin0 || xin1) ? (int)xw : 0;
-    c.y0 = (yin0 || yin1) ? (int)yn : 0;
-    return c;
 }
 
 // Argument blocks of the three fine-stage kernels.  Each kernel body is a typed device function of (arguments, the problem's own
@@ -58,19 +31,6 @@ struct ComposeFlowArgs {
     const float* flowDown; const float* coarse; float* flow12; float* inb; float* flowUp;
     long long NP; int hd, wd, Hc, Wc, H, W; float sh, sw; int clampf;
 };
-
-// kornia's warp_grid at integer pixel (x, y) of an h x w grid: M (px, py, 1) divided by its third component
-__device__ __forceinline__ float2 warp_point(const float* __restrict__ M, int x, int y, int h, int w) {
-    const float px = rfx_lin(x, w), py = rfx_lin(y, h);
-    // (x', y', z') = M (px, py, 1): k-ordered fma chain like a K=3 sgemm
-    const float xs = fmaf(1.0f, M[2], fmaf(py, M[1], __fmul_rn(px, M[0])));
-    const float ys = fmaf(1.0f, M[5], fmaf(py, M[4], __fmul_rn(px, M[3])));
-    const float zs = fmaf(1.0f, M[8], fmaf(py, M[7], __fmul_rn(px, M[6])));
-    float2 o;
-    o.x = xs / zs;
-    o.y = ys / zs;
-    return o;
-}
 
 __device__ __forceinline__ void warp_grid_body(const WarpGridArgs& a, const unsigned bx, const unsigned gx) {
     const float* __restrict__ Hm = a.Hm;
@@ -122,11 +82,6 @@ __device__ __forceinline__ void grid_sample_body(const GridSampleArgs& a, const 
 
 using GridSample = RfxFamily<GridSampleArgs, grid_sample_body, 256>;
 __global__ __launch_bounds__(GridSample::BLOCK) void grid_sample_kernel(GridSampleArgs a) { grid_sample_body(a, blockIdx.x, gridDim.x); }
-
-__device__ __forceinline__ float src_index(float scale, int dst) {  // align_corners=False
-    const float s = scale * ((float)dst + 0.5f) - 0.5f;
-    return s < 0.f ? 0.f : s;
-}
 
 __device__ __forceinline__ void compose_flow_body(const ComposeFlowArgs& a, const unsigned bx, const unsigned gx) {
     const float* __restrict__ flowDown = a.flowDown;
@@ -250,45 +205,6 @@ struct CycleTailArgs {
     int hd, wd, Hc, Wc, H, W; float sh, sw;
 };
 
-// the taps of resize_bilinear_body (align_corners = 0) at one output pixel: the upper left tap's offset inside a plane, the steps to
-// the clamped right and lower neighbours and the two fractions
-struct UpTap { int o00, dx, dy; float lx, ly; };
-
-__device__ __forceinline__ UpTap up_tap(float sh, float sw, int y, int x, int hd, int wd) {
-    UpTap t;
-    const float fy = src_index(sh, y), fx = src_index(sw, x);
-    int y0 = (int)fy, x0 = (int)fx;
-    y0 = y0 < hd - 1 ? y0 : hd - 1;          // (never taken by an index the rule above produces: keeps every read inside the plane)
-    x0 = x0 < wd - 1 ? x0 : wd - 1;
-    t.ly = fy - (float)y0;
-    t.lx = fx - (float)x0;
-    t.o00 = y0 * wd + x0;
-    t.dx = x0 < wd - 1 ? 1 : 0;
-    t.dy = y0 < hd - 1 ? wd : 0;
-    return t;
-}
-
-// resize_bilinear_body's per-sample expression, operation for operation
-__device__ __forceinline__ float up_resize(const float* __restrict__ plane, const UpTap& t) {
-    const float* q = plane + t.o00;
-    const float v00 = q[0], v01 = q[t.dx], v10 = q[t.dy], v11 = q[t.dy + t.dx];
-    const float hy = 1.f - t.ly, hx = 1.f - t.lx;
-    const float r0 = fmaf(v01, t.lx, __fmul_rn(v00, hx));
-    const float r1 = fmaf(v11, t.lx, __fmul_rn(v10, hx));
-    return fmaf(r1, t.ly, __fmul_rn(r0, hy));
-}
-
-// compose_flow_body's up-sampling of one residual-flow channel: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11), contracted
-// as compose_flow_kernel is (the second product of every sum fused)
-__device__ __forceinline__ float up_flow(const float* __restrict__ plane, const UpTap& t) {
-    const float* q = plane + t.o00;
-    const float v00 = q[0], v01 = q[t.dx], v10 = q[t.dy], v11 = q[t.dy + t.dx];
-    const float hy = 1.f - t.ly, hx = 1.f - t.lx;
-    const float top = fmaf(t.lx, v01, __fmul_rn(hx, v00));
-    const float bot = fmaf(t.lx, v11, __fmul_rn(hx, v10));
-    return fmaf(hy, top, __fmul_rn(t.ly, bot));
-}
-
 __device__ __forceinline__ void cycle_tail_body(const CycleTailArgs& a, const unsigned bx, const unsigned gx_) {
     const float* __restrict__ flowDown = a.flowDown;
     const float* __restrict__ m12 = a.m12;
@@ -354,79 +270,22 @@ struct AssembleRecArgs {
 };
 
 __global__ __launch_bounds__(256) void assemble_records_kernel(AssembleRecArgs a) {
-    // row blockIdx.y of the table: row offset in rec | h8 | w8 | off_match | H | W | offset of the pair's pixels in the outputs | 0
-    const long long* __restrict__ T = a.table + (long long)blockIdx.y * 8;
-    const long long row_off = T[0], h8l = T[1], w8l = T[2], off_match = T[3], Hl = T[4], Wl = T[5], out_off = T[6];
-    // a row that does not describe a record inside rec and a map inside the outputs is skipped: no read or write leaves the buffers
-    if (row_off < 0 || row_off + a.width > a.rec_elems || h8l <= 0 || w8l <= 0 || h8l > a.width || w8l > a.width || Hl <= 0 ||
-        Wl <= 0 || Hl > 0x7fffffffLL || Wl > 0x7fffffffLL || Hl * Wl > 0x7fffffffLL)
-        return;
-    const long long n8 = 2 * h8l * w8l * a.max_h, HWl = Hl * Wl;
-    if (off_match < a.off_flow + n8 || off_match + n8 > a.width || out_off < 0 || out_off + HWl > a.total_px) return;
-    const int hd = (int)h8l, wd = (int)w8l, H = (int)Hl, W = (int)Wl, HW = (int)HWl, hw = hd * wd;
-    const float* __restrict__ row = a.rec + row_off;
-    const float* __restrict__ Hm = row + a.off_H;
-    const float* __restrict__ flowDown = row + a.off_flow;
-    const float* __restrict__ matchDown = row + off_match;
-    const uint8_t* __restrict__ bg = a.bg ? a.bg + out_off : nullptr;
-    float2* __restrict__ flowG = reinterpret_cast<float2*>(a.flowG) + out_off;
-    float* __restrict__ matchG = a.matchG + out_off;
-    uint8_t* __restrict__ binary = a.binary + out_off;
-    const float nf = row[0];                                   // nbH, a small integer held as a float
-    const int nb = nf >= 1.0f ? (nf < (float)a.max_h ? (int)nf : a.max_h) : 0;
-    const int last = a.multiH ? nb : (nb < 1 ? nb : 1);
-    const float sh = (float)hd / (float)H, sw = (float)wd / (float)W, th = a.th;
+    // row blockIdx.y of the table, checked (assemble_pixel.h): a row that does not describe a record inside rec and a map inside the
+    // outputs is skipped, no read or write leaves the buffers
+    const RecPair k = rec_pair(a.rec, a.rec_elems, a.table, blockIdx.y, a.width, a.max_h, a.off_H, a.off_flow, a.multiH, a.total_px);
+    if (!k.ok) return;
+    const int W = k.W, HW = k.HW;
+    const uint8_t* __restrict__ bg = a.bg ? a.bg + k.out_off : nullptr;
+    float2* __restrict__ flowG = reinterpret_cast<float2*>(a.flowG) + k.out_off;
+    float* __restrict__ matchG = a.matchG + k.out_off;
+    uint8_t* __restrict__ binary = a.binary + k.out_off;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < HW; q += (long long)gridDim.x * blockDim.x) {
         const int p = (int)q;
         const int y = p / W, x = p - y * W;
-        const UpTap t = up_tap(sh, sw, y, x, hd, wd);
-        float2 fbest;
-        fbest.x = 0.0f; fbest.y = 0.0f;
-        float mbest = 0.0f;
-        bool found = false;
-        for (int i = 0; i < last; ++i) {
-            // compose_flow (clamp = 1) on homography i's grid: the sampling point, flow_i, the in-bounds mask
-            const float* f = flowDown + (size_t)i * 2 * hw;
-            float gx = __fadd_rn(up_flow(f, t), rfx_lin(x, W)), gy = __fadd_rn(up_flow(f + hw, t), rfx_lin(y, H));
-            gx = fminf(fmaxf(gx, -1.0f), 1.0f);
-            gy = fminf(fmaxf(gy, -1.0f), 1.0f);
-            const Corners c = corners(gx, gy, H, W, 0);
-            const float* M = Hm + i * 9;
-            float ox = 0.f, oy = 0.f;
-            if (c.m_nw) { const float2 v = warp_point(M, c.x0, c.y0, H, W); ox = fmaf(v.x, c.nw, ox); oy = fmaf(v.y, c.nw, oy); }
-            if (c.m_ne) { const float2 v = warp_point(M, c.x0 + 1, c.y0, H, W); ox = fmaf(v.x, c.ne, ox); oy = fmaf(v.y, c.ne, oy); }
-            if (c.m_sw) { const float2 v = warp_point(M, c.x0, c.y0 + 1, H, W); ox = fmaf(v.x, c.sw, ox); oy = fmaf(v.y, c.sw, oy); }
-            if (c.m_se) { const float2 v = warp_point(M, c.x0 + 1, c.y0 + 1, H, W); ox = fmaf(v.x, c.se, ox); oy = fmaf(v.y, c.se, oy); }
-            const float inb = (ox >= -1.0f && ox <= 1.0f && oy >= -1.0f && oy <= 1.0f) ? 1.0f : 0.0f;
-            // resize_bilinear of match12Down8 at the pixel; with the cycle check, grid_sample of the up-sampled match21 at (gx, gy):
-            // the map has the grid's size, so the taps and weights are c's, each tap the resize expression at its integer pixel
-            const float* m12 = matchDown + (size_t)i * 2 * hw;
-            float v = up_resize(m12, t);
-            if (a.cycle) {
-                const float* s21 = m12 + hw;
-                float cyc = 0.0f;
-                if (c.m_nw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0, c.x0, hd, wd)), c.nw, cyc);
-                if (c.m_ne) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0, c.x0 + 1, hd, wd)), c.ne, cyc);
-                if (c.m_sw) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0 + 1, c.x0, hd, wd)), c.sw, cyc);
-                if (c.m_se) cyc = fmaf(up_resize(s21, up_tap(sh, sw, c.y0 + 1, c.x0 + 1, hd, wd)), c.se, cyc);
-                v = __fmul_rn(v, cyc);
-            }
-            v = __fmul_rn(v, inb);                             // score_i = match12 (* cycle) * in-bounds, left to right
-            // merge_multi_h_kernel's rule: 0 owns the pixel unless a later homography is the first to reach th
-            if (i == 0) { mbest = v; fbest.x = ox; fbest.y = oy; }
-            if (v >= th) {
-                mbest = v; fbest.x = ox; fbest.y = oy;
-                found = true;
-                break;
-            }
-        }
-        // torch.clamp: a NaN stays a NaN (merge_multi_h_kernel)
-        float2 o;
-        o.x = fbest.x < -1.0f ? -1.0f : (fbest.x > 1.0f ? 1.0f : fbest.x);
-        o.y = fbest.y < -1.0f ? -1.0f : (fbest.y > 1.0f ? 1.0f : fbest.y);
-        flowG[p] = o;
-        matchG[p] = mbest;
-        binary[p] = (found && (!bg || bg[p] != 0)) ? 1 : 0;
+        const PixelResult r = assemble_pixel(k, y, x, a.cycle, a.th);
+        flowG[p] = r.flow;
+        matchG[p] = r.match;
+        binary[p] = (r.found && (!bg || bg[p] != 0)) ? 1 : 0;
     }
 }
 

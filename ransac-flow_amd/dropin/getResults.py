@@ -7,6 +7,8 @@ and return conventions (CPU tensors, ``[]`` sentinels); the arithmetic runs in l
     flow, match = corr.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)
     flow = kitti.getFlow_all(pairID, predDir, nbH, res_name, warper_org, multiH, grid_org, th, cc_th, interpolate)
     counts, nbAlign = corr.alignmentError(wB, hB, wA, hA, XA, YA, XB, YB, flow, match, pixelGrid)
+    counts, nbAlign, valid = corr.keypoints_records(records, th, multiH, XA, YA, XB, YB, matchability_ths)   # a whole batch, on the device
+    precision, total = corr.precision(counts, nbAlign)                                                    # the one host read
     flow, binary = yfcc.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)        # numpy, like the script
     pts1, pts2 = yfcc.matches_from_flow(flow, binary, sizeA, sizeB, angle)                             # numpy float32 / int64
     aepe = hpatch.epe_from_homography(flow_est, Hinv)                  # a float; Hinv: rfx.assemble.hpatch_gt_homography(...)[1]
@@ -73,7 +75,8 @@ def _yfcc_matches_from_flow(flowFine, matchBinary, sizeA, sizeB, angle):
 hpatch = types.SimpleNamespace(getFlow_all=_wrap(_a.hpatch_getFlow_all),
                                getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse), epe_from_homography=_a.hpatch_epe)
 corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse),
-                             alignmentError=_a.corr_alignment_error)
+                             alignmentError=_a.corr_alignment_error, keypoints_records=_a.corr_keypoints_records,
+                             precision=_a.corr_precision)
 kitti = types.SimpleNamespace(getFlow_all=_wrap(_kitti_getFlow_all),
                               getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse), epe=_a.kitti_epe)
 yfcc = types.SimpleNamespace(getFlow=_yfcc_getFlow, _getFlow=_yfcc__getFlow, matches_from_flow=_yfcc_matches_from_flow)

@@ -191,6 +191,48 @@ def corr_alignment_error(wB, hB, wA, hA, XA, YA, XB, YB, flow, match2, pixelGrid
     return np.sum(pixelDiff.reshape((-1, 1)) <= pixelGrid, axis=0), nbAlign
 
 
+def corr_keypoints_records(records, th, multiH, XA, YA, XB, YB, matchability_ths=(0,), pixelGrid=None, sizesA=None, bg=None):
+    """The Corr results step (evalCorr/getResults.py:271-285: getFlow, then alignmentError per matchability threshold) for EVERY pair
+    of a batch of device records at once, without the dense maps: ops.records_keypoints (cycle=True at the 8x size) reads the
+    assembly at the target keypoints only, ops.pck_tally forms the float64 distances and the per-pair tally -- two launches, two
+    pinned uploads, no host sync.  XA, YA (source) and XB, YB (target): one host array per pair, floats truncated toward zero like
+    the script's astype(np.int64); ``sizesA[b]`` = (wA, hA) of the resized source, by default records.size_src (what
+    multi_h_variant_c(..., want_records=True) leaves there).  A pair without a homography follows the script's ``continue`` branch.
+    -> (counts (M,B,T) int64, nbAlign (M,B) int64, valid (B,) bool) on the device; corr_precision reads them."""
+    xa, ya, m, flag, koff = ops.records_keypoints(records, th, multiH, True, XB, YB, sizesA=sizesA, bg=bg)
+    valid = records.rec[:, 0] >= 1                             # the kernels' own test of nbH
+    grid = None if pixelGrid is None else np.asarray(pixelGrid, dtype=np.float64).reshape(-1)
+    counts, nb = ops.pck_tally(xa, ya, m, flag, XA, YA, koff, match_ths=matchability_ths, pixel_grid=grid, valid=valid)
+    return counts, nb, valid
+
+
+def corr_precision(counts, nbAlign):
+    """The table the script prints (evalCorr/getResults.py:287-289) from corr_keypoints_records' device tallies -- the one host read
+    of the batch: -> (precision (M,T) float64 = counts summed over the pairs / nbAlign summed over the pairs, total (M,) int64)."""
+    c = (counts.cpu() if torch.is_tensor(counts) else torch.as_tensor(np.asarray(counts))).numpy().sum(axis=1)
+    n = (nbAlign.cpu() if torch.is_tensor(nbAlign) else torch.as_tensor(np.asarray(nbAlign))).numpy().sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):       # no kept keypoint: the script's 0 / 0
+        return c.astype(np.float64) / n[:, None], n
+
+
+def corr_resize_keypoints(minSize, size, x, y, strideNet=16, megadepth=False):
+    """The coordinate half of evalCorr/getResults.py:41-56 (ResizeMinResolution) and :60-76 (ResizeMinResolution_megadepth): an image
+    of ``size`` = (w, h) is resized so that its shorter side is about ``minSize``, both sides rounded down to multiples of
+    ``strideNet``, and the keypoints move with it.  x, y: arrays, or the CSV's ';'-separated strings; float32 like the script's.
+    -> ((new_w, new_h), x, y[, index_valid: megadepth -- the keypoints strictly inside the resized image])."""
+    parse = lambda v: np.array([float(t) for t in v.split(";")] if isinstance(v, str) else v).astype(np.float32)
+    x, y = parse(x), parse(y)
+    w, h = size
+    ratio = min(w / float(minSize), h / float(minSize))
+    new_w, new_h = round(w / ratio), round(h / ratio)
+    new_w, new_h = new_w // strideNet * strideNet, new_h // strideNet * strideNet
+    ratioW, ratioH = new_w / float(w), new_h / float(h)
+    x, y = x * ratioW, y * ratioH
+    if megadepth:
+        return (new_w, new_h), x, y, (x > 0) * (x < new_w) * (y > 0) * (y < new_h)
+    return (new_w, new_h), x, y
+
+
 def identity_grid(h, w, device="cuda"):
     """The grid the scripts fall back to when a pair has no saved flow (evalHpatch/getResults.py:191-193,218;
     evalKITTI/getResults.py:209-214): torch.linspace(-1, 1, w) along x and (-1, 1, h) along y, (1,h,w,2).  ops.warp_grid of the

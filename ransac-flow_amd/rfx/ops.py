@@ -2185,6 +2185,168 @@ def assemble_records(records, th, multiH, cycle, out_hw=None, bg=None, out=None)
             [binary[o:o + H * W].view(H, W) for o, H, W in views], valid)
 
 
+def _host_pixels(v, what):
+    """A host keypoint coordinate array as int64, floats truncated toward zero like the scripts' ``astype(np.int64)``."""
+    import numpy as np
+    a = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+    if a.dtype.kind not in "iuf":
+        raise TypeError("%s: keypoint coordinates are integers or floats, got %s" % (what, a.dtype))
+    return a.astype(np.int64).reshape(-1)
+
+
+def records_keypoints_table(records, xb, yb, sizesA=None, out_hw=None):
+    """The host part of records_keypoints, a pure function of the records' size lists and the keypoints: -> (rows, total_px, krows,
+    x, y, koff).  rows / total_px: assemble_records_table's; krows[b] = (first keypoint | number of keypoints | wA | hA), the
+    keypoint table of rfx_records_keypoints_f32; x, y the target pixels of all pairs, pair after pair, as int32 arrays (floats
+    truncated toward zero); koff (B+1,) the host offset list, pair b's keypoints are koff[b]:koff[b+1].  ``xb`` / ``yb``: one host
+    array per pair (empty arrays allowed); ``sizesA[b]`` = (wA, hA), by default records.size_src.  A keypoint outside its pair's
+    map is refused here (RfxError), as sample_points refuses it."""
+    import numpy as np
+    if not isinstance(records, (MultiHRecords, MultiHRecordsRagged)):
+        raise TypeError("records must be an ops.MultiHRecords or ops.MultiHRecordsRagged")
+    rows, _, total = assemble_records_table(records, out_hw)       # refuses records with a flowD2 part (the KITTI drivers')
+    B = records.B
+    sizesA = getattr(records, "size_src", None) if sizesA is None else sizesA
+    if sizesA is None:
+        raise ValueError("records_keypoints: these records carry no size_src; pass sizesA = one (wA, hA) per pair")
+    if len(xb) != B or len(yb) != B or len(sizesA) != B:
+        raise ValueError("records_keypoints: one xb, one yb and one (wA, hA) per pair (%d pairs), got %d, %d and %d"
+                         % (B, len(xb), len(yb), len(sizesA)))
+    krows, xs, ys, off = [], [], [], 0
+    for b in range(B):
+        x, y = _host_pixels(xb[b], "records_keypoints"), _host_pixels(yb[b], "records_keypoints")
+        if x.shape != y.shape:
+            raise ValueError("records_keypoints: pair %d has %d xb for %d yb" % (b, x.size, y.size))
+        wA, hA = int(sizesA[b][0]), int(sizesA[b][1])
+        H, W = rows[b][4], rows[b][5]
+        if wA < 1 or hA < 1 or wA > 0x7fffffff or hA > 0x7fffffff or \
+                (x.size and (x.min() < 0 or x.max() >= W or y.min() < 0 or y.max() >= H)):
+            _lib.check(-1, "rfx_records_keypoints_f32 (pair %d: a keypoint outside the %d x %d map, or sizeA = %s)" % (b, W, H, (wA, hA)))
+        krows.append((off, int(x.size), wA, hA))
+        xs.append(x)
+        ys.append(y)
+        off += int(x.size)
+    if off > 0x7fffffff:
+        _lib.check(-2, "rfx_records_keypoints_f32 (%d keypoints)" % off)
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return rows, total, krows, cat(xs), cat(ys), [r[0] for r in krows] + [off]
+
+
+def _upload_i64(parts, dev):
+    """Host int64 arrays -> device tensors through ONE pinned, non-blocking copy (no sync)."""
+    import numpy as np
+    flat = np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in parts])
+    buf = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)
+    out, o = [], 0
+    for p in parts:
+        n = int(np.asarray(p).size)
+        out.append(buf[o:o + n])
+        o += n
+    return out
+
+
+def records_keypoints(records, th, multiH, cycle, xb, yb, sizesA=None, out_hw=None, bg=None):
+    """The assembled maps of EVERY pair of a batch of device records, read at annotated target pixels only
+    (rfx_records_keypoints_f32; evaluation/evalCorr/getResults.py:78-136 as :15-31 and :281-282 read it): per pair bit for bit what
+    assemble_records followed by sample_points gives at the same pixels, without the maps -- one thread per keypoint walks the
+    record's homographies at its pixel.  records, th, multiH, cycle, out_hw: as assemble_records takes them; xb, yb, sizesA: see
+    records_keypoints_table; bg: a packed (total_px,) bool / uint8 buffer in assemble_records' output layout, a (B,H,W) tensor for
+    dense records, or a list of one (H_b,W_b) map per pair.
+    -> (xa, ya float32, m float32 = matchGlobal at the pixel, flag uint8: bit 0 = binary at the pixel (ANDed with bg), bit 1 = both
+    flow channels in [-1, 1] (clear only for a NaN), koff): device tensors of K_total = koff[-1] entries, pair b's at
+    koff[b]:koff[b+1]; koff is the host list.  The tables and keypoints go up in one pinned, non-blocking copy; nothing syncs."""
+    import numpy as np
+    rows, total, krows, x, y, koff = records_keypoints_table(records, xb, yb, sizesA, out_hw)
+    B, dev, K = records.B, records.rec.device, koff[-1]
+    if bg is not None:
+        parts = list(bg) if isinstance(bg, (list, tuple)) else [bg]
+        shapes = [tuple(getattr(t, "shape", ())) for t in parts]
+        sizes = [(r[4], r[5]) for r in rows]
+        dense = [(B,) + sizes[0]] if not isinstance(records, MultiHRecordsRagged) else None
+        if not isinstance(bg, (list, tuple)) and shapes not in ([(total,)], dense) or isinstance(bg, (list, tuple)) and shapes != sizes:
+            raise ValueError("records_keypoints: bg is a packed (%d,) buffer%s or one map per pair of the shapes %r, got %r"
+                             % (total, "" if dense is None else ", a %r tensor" % (dense[0],), sizes, shapes))
+        if any(not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8) for t in parts):
+            raise ValueError("records_keypoints: bg must be bool or uint8 tensors")
+        if any(t.device != dev for t in parts):
+            raise ValueError("records_keypoints: bg must live on the records' device %s" % dev)
+        bg = _mask_bytes(_packed_maps(parts if len(parts) > 1 else parts[0], "bg").reshape(-1), "bg")
+    rec = _dev(records.rec, "records")
+    xa = torch.empty(K, dtype=torch.float32, device=dev)
+    ya = torch.empty(K, dtype=torch.float32, device=dev)
+    m = torch.empty(K, dtype=torch.float32, device=dev)
+    flag = torch.empty(K, dtype=torch.uint8, device=dev)
+    if K:
+        xy = np.concatenate((x, y)).view(np.int64)                # 2 K int32 pixels ride in the int64 upload two to a word
+        table, ktable, xyd = _upload_i64([np.asarray(rows, np.int64), np.asarray(krows, np.int64), xy], dev)
+        xyd = xyd.view(torch.int32)
+        _call("rfx_records_keypoints_f32", _one_device(rec, bg, xa), _p(rec), rec.numel(), records.width, records.max_h, records.off_H,
+              records.off_flow, _p(table), B, total, float(th), 1 if multiH else 0, 1 if cycle else 0, _p(bg), _p(ktable),
+              _p(xyd[:K]), _p(xyd[K:]), K, _p(xa), _p(ya), _p(m), _p(flag))
+    return xa, ya, m, flag, koff
+
+
+PCK_MAX_GRID = 16              # thresholds of the pixel grid rfx_pck_tally_f64 takes
+
+
+def pck_pixel_grid():
+    """The pixel grid of evaluation/evalCorr/getResults.py:230: 1, 2, 3, 5, 8, 13, 22, 36."""
+    import numpy as np
+    return np.around(np.logspace(0, np.log10(36), 8))
+
+
+def pck_tally(xa, ya, m, flag, xs, ys, koff, match_ths=(0.0,), pixel_grid=None, valid=None, want_dist=False):
+    """evaluation/evalCorr/getResults.py:279-285 with alignmentError (:25-36) on the outputs of records_keypoints, for every pair and
+    every matchability threshold at once (rfx_pck_tally_f64): threshold t > 0 keeps a keypoint with m >= t whose flow is inside
+    [-1, 1], t <= 0 keeps every keypoint; d = sqrt((double(xa) - xs)^2 + (double(ya) - ys)^2) in float64 steps like numpy's.
+    xs, ys: the source keypoints, one host array per pair (floats truncated toward zero) in koff's order; match_ths (M); pixel_grid
+    (T <= 16 values, default the script's 1..36 grid); valid: (B,) bool / uint8 on the device or None -- a pair with valid 0 follows
+    the script's ``continue`` branch (:273-277): nb = its keypoints, counts zero.
+    -> (counts (M,B,T) int64, nb (M,B) int64[, dist (M,K_total) float64, NaN where a keypoint is not kept]) on the device.  No sync."""
+    import numpy as np
+    B, K = len(koff) - 1, int(koff[-1])
+    if B < 1 or len(xs) != B or len(ys) != B:
+        raise ValueError("pck_tally: one xs and one ys per pair (%d pairs), got %d and %d" % (B, len(xs), len(ys)))
+    grid = pck_pixel_grid() if pixel_grid is None else np.asarray(pixel_grid, dtype=np.float64).reshape(-1)
+    ths = np.asarray(match_ths, dtype=np.float32).reshape(-1)
+    T, M = int(grid.size), int(ths.size)
+    if T < 1 or T > PCK_MAX_GRID or M < 1:
+        raise ValueError("pck_tally: 1 to %d pixel thresholds and at least one matchability threshold, got %d and %d" % (PCK_MAX_GRID, T, M))
+    outs = ((xa, torch.float32, "xa"), (ya, torch.float32, "ya"), (m, torch.float32, "m"), (flag, torch.uint8, "flag"))
+    for t, dt, name in outs:                                      # every host-side check before any device
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != K or not t.is_contiguous():
+            raise ValueError("pck_tally: %s must be a contiguous %s tensor of koff[-1] = %d entries" % (name, dt, K))
+    hx, hy = [], []
+    for b in range(B):
+        sx, sy = _host_pixels(xs[b], "pck_tally"), _host_pixels(ys[b], "pck_tally")
+        n = int(koff[b + 1]) - int(koff[b])
+        if sx.size != n or sy.size != n:
+            raise ValueError("pck_tally: pair %d has %d keypoints, got %d xs and %d ys" % (b, n, sx.size, sy.size))
+        if n and max(np.abs(sx).max(), np.abs(sy).max()) > 0x7fffffff:
+            _lib.check(-2, "rfx_pck_tally_f64 (a source keypoint beyond int32)")
+        hx.append(sx)
+        hy.append(sy)
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.numel() != B or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("pck_tally: valid is a (B,) bool or uint8 tensor")
+    for t, dt, name in outs:
+        _dev(t, name, dt)
+    if valid is not None:
+        valid = _mask_bytes(valid.reshape(-1), "valid")
+    dev = xa.device
+    xy = np.concatenate(hx + hy).astype(np.int32)
+    xy = np.concatenate((xy, np.zeros(xy.size % 2, np.int32))).view(np.int64)      # int32 pixels, two to a word
+    krows = np.asarray([(int(koff[b]), int(koff[b + 1]) - int(koff[b]), 1, 1) for b in range(B)], np.int64)
+    ktable, gd, td, xyd = _upload_i64([krows, grid.view(np.int64), np.concatenate((ths, np.zeros(M % 2, np.float32))).view(np.int64), xy],
+                                      dev)
+    gd, td, xyd = gd.view(torch.float64), td.view(torch.float32), xyd.view(torch.int32)
+    counts = torch.empty((M, B, T), dtype=torch.int64, device=dev)
+    nb = torch.empty((M, B), dtype=torch.int64, device=dev)
+    dist = torch.empty((M, K), dtype=torch.float64, device=dev) if want_dist else None
+    _call("rfx_pck_tally_f64", _one_device(xa, ya, m, flag, valid, counts), _p(xa), _p(ya), _p(m), _p(flag), _p(xyd[:K]), _p(xyd[K:]),
+          _p(ktable), B, K, _p(td), M, _p(gd), T, _p(valid), _p(counts), _p(nb), _p(dist))
+    return (counts, nb, dist) if want_dist else (counts, nb)
+
+
 KITTI_WS_BYTES = 1 << 30       # default workspace bound of assemble_kitti_records (scores + component-filter workspace of one chunk)
 KITTI_TABLE_COLS = 12
 
