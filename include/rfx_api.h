@@ -48,7 +48,8 @@ const char* rfx_version(void);
  * rfx_group_stats, and the fine-stage entry points record inside a group; 17: rfx_ransac_degenerate_list and rfx_ransac_patch_h
  * removed, superseded since 9 by rfx_ransac_degenerate_gather / rfx_ransac_patch_h_rows; rfx_keep_mask_ragged_f32 was ADDED under 17,
  * and so were rfx_epe_ws_bytes, rfx_epe_homography_f32, rfx_epe_flow_f32, rfx_assemble_records_f32, rfx_assemble_kitti_records_f32
- * and rfx_kitti_scores_records_f32, then rfx_records_keypoints_f32 and rfx_pck_tally_f64: no existing entry point moved, and a binding that knows
+ * and rfx_kitti_scores_records_f32, then rfx_records_keypoints_f32 and rfx_pck_tally_f64, then
+ * rfx_warp_records_u8 and rfx_warp_flow_u8: no existing entry point moved, and a binding that knows
  * a new name refuses a library without it).  A binding
  * compares rfx_abi_version() with the RFX_ABI_VERSION it was written against and refuses a mismatch. */
 #define RFX_ABI_VERSION 17
@@ -952,6 +953,43 @@ int rfx_sky_bytes_u8(const float* mask, int N, int H, int W, int k, uint8_t* out
 /* out[i] = in[i] < threshold ? 1.0f : 0.0f -- the scripts' ``(imresize(It_bg, (Ith, Itw)) < 128).astype(np.float32)``
  * (evalHpatch/evaluation.py:180) on the resized bytes.  RFX_E_ARG: a null pointer or total <= 0. */
 int rfx_less_than_u8_f32(const uint8_t* in, long long total, int threshold, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Aligned source images of a batch (both ADDED under ABI 17: no existing entry point moved).
+ * ------------------------------------------------------------------------------------------ */
+/* quick_start/align2images.py:97-98,117 (F.grid_sample(IsTensor, flow12), ToPILImage, fine_aligned_source.png) and :25-28,112
+ * (get_Avg_Image, the 50 % overlay with the target) for EVERY pair of a batch, as uint8 HWC images, in one launch each.
+ *
+ * rfx_warp_records_u8: from the drivers' records.  rec, rec_elems, width, max_h, off_H, off_flow, table (B,8), B, max_hw, th, multiH,
+ * cycle, bg, total_px: as rfx_assemble_records_f32 takes them, with the same row checks (records with a flowD2 part, the KITTI
+ * drivers', are not covered: their flow goes through rfx_warp_flow_u8).  itable (B,4) int64 on the device, row b:
+ *     address of the pair's source (Hs,Ws,3) uint8 | Hs | Ws | address of its target (H,W,3) uint8 at the OUTPUT size, or 0
+ * so that sources of any sizes are read where they lie.  Outputs in the packed layout of the table's pixel offsets:
+ * img (total_px,3) uint8; overlay (total_px,3) uint8 or NULL; mask (total_px) uint8 or NULL.  Per pixel of pair b:
+ *     (fx, fy), found = flowGlobal and the explained bit of rfx_assemble_records_f32 at the pixel, from the record alone;
+ *     per channel v = 0, then for each corner of ATen's bilinear sample of the SOURCE (zeros padding, align_corners = 0) that lies
+ *     inside it, in the order nw, ne, sw, se: v = fma(float(byte) / 255.0f, weight, v) -- rfx_u8_to_f32_chw's x / 255 followed by
+ *     rfx_grid_sample_f32, bit for bit;
+ *     img = (uint8)(clamp(v, 0, 1) * 255.0f), the product rounded to float32, then truncated (mul(255).byte());
+ *     overlay = (img + target) >> 1 per channel, where the pair has a target (a pair with target 0 leaves its overlay bytes alone);
+ *     mask = 255 where found && (bg == NULL || bg[pixel] != 0), else 0  (binary of rfx_assemble_records_f32).
+ * A NaN flow has no in-image corner: the pixel is 0.  A pair with nbH < 1 has the zero flow: every pixel samples the source's centre.
+ * A table row that is refused, or an itable row without a source (address 0) or with a size that is not positive or whose Hs*Ws
+ * leaves int32, is skipped: nothing of it is read or written.  One thread per pixel stores its own bytes; no LDS, no atomics, no
+ * workgroup waits on another; blockIdx.y = the pair, the grid over a pair's pixels is capped at 8192 workgroups and strides.
+ * RFX_E_ARG: a null rec, table, itable or img, a non-positive B, width, max_h or max_hw, offsets that do not describe a record,
+ * rec_elems < B * width, total_px < max_hw, a table not 8-byte aligned.  RFX_E_LIMIT: B > 65535, max_hw > 2^31 - 1.
+ *
+ * rfx_warp_flow_u8: the same image tail on a stored flow (total_px,2) float32 in the packed layout -- what
+ * rfx_assemble_records_f32 / rfx_assemble_kitti_records_f32 fill, or quick-start's flow12 (B = 1).  table (B,8): only columns 4..6
+ * (H | W | pixel offset) are read; binary (total_px) bytes or NULL is passed through to mask (255 where non-zero).
+ * RFX_E_ARG: a null flow, table, itable or img, a mask without binary, a non-positive B or max_hw, total_px < max_hw, flow or a table
+ * not 8-byte aligned.  RFX_E_LIMIT as above.  All of these are checked before any HIP call. */
+int rfx_warp_records_u8(const float* rec, long long rec_elems, int width, int max_h, int off_H, int off_flow, const long long* table,
+                        int B, long long max_hw, float th, int multiH, int cycle, const uint8_t* bg, const long long* itable,
+                        uint8_t* img, uint8_t* overlay, uint8_t* mask, long long total_px, void* stream);
+int rfx_warp_flow_u8(const float* flow, const long long* table, int B, long long max_hw, const uint8_t* binary, const long long* itable,
+                     uint8_t* img, uint8_t* overlay, uint8_t* mask, long long total_px, void* stream);
 
 #ifdef __cplusplus
 }

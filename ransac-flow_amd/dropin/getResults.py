@@ -9,6 +9,8 @@ and return conventions (CPU tensors, ``[]`` sentinels); the arithmetic runs in l
     counts, nbAlign = corr.alignmentError(wB, hB, wA, hA, XA, YA, XB, YB, flow, match, pixelGrid)
     counts, nbAlign, valid = corr.keypoints_records(records, th, multiH, XA, YA, XB, YB, matchability_ths)   # a whole batch, on the device
     precision, total = corr.precision(counts, nbAlign)                                                    # the one host read
+    img, overlay, mask, valid = corr.aligned_images_records(records, src_u8, th, multiH, cycle)     # uint8 HWC, a whole batch, on the device
+    img = aligned_image(flow, src_u8)                              # the same image from a flow the caller holds (KITTI, quick start)
     flow, binary = yfcc.getFlow(pairID, finePath, flowList, coarsePath, maskPath, multiH, th)        # numpy, like the script
     pts1, pts2 = yfcc.matches_from_flow(flow, binary, sizeA, sizeB, angle)                             # numpy float32 / int64
     aepe = hpatch.epe_from_homography(flow_est, Hinv)                  # a float; Hinv: rfx.assemble.hpatch_gt_homography(...)[1]
@@ -76,7 +78,11 @@ hpatch = types.SimpleNamespace(getFlow_all=_wrap(_a.hpatch_getFlow_all),
                                getFlow_onlyCoarse=_wrap(_a.hpatch_getFlow_onlyCoarse), epe_from_homography=_a.hpatch_epe)
 corr = types.SimpleNamespace(getFlow=_wrap(_a.corr_getFlow), getFlow_Coarse=_wrap(_a.corr_getFlow_Coarse),
                              alignmentError=_a.corr_alignment_error, keypoints_records=_a.corr_keypoints_records,
-                             precision=_a.corr_precision)
+                             precision=_a.corr_precision, aligned_images_records=_a.aligned_images_records,
+                             aligned_image=_a.aligned_image)
 kitti = types.SimpleNamespace(getFlow_all=_wrap(_kitti_getFlow_all),
                               getFlow_onlyCoarse=_wrap(_a.kitti_getFlow_onlyCoarse), epe=_a.kitti_epe)
 yfcc = types.SimpleNamespace(getFlow=_yfcc_getFlow, _getFlow=_yfcc__getFlow, matches_from_flow=_yfcc_matches_from_flow)
+# the aligned source images (quick_start/align2images.py:97-98,117 and :25-28,112) of a batch of any driver's records, or of a flow the
+# caller holds -- the same two functions whichever protocol the records come from
+aligned_images_records, aligned_image = _a.aligned_images_records, _a.aligned_image

@@ -88,6 +88,9 @@ SIGNATURES = {
     "rfx_sample_points_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 4),
     "rfx_records_keypoints_f32": (c_int, [c_void_p, c_longlong] + [c_int] * 4 + [c_void_p, c_int, c_longlong, c_float, c_int, c_int] +
                                   [c_void_p] * 4 + [c_longlong] + [c_void_p] * 5),
+    "rfx_warp_records_u8": (c_int, [c_void_p, c_longlong] + [c_int] * 4 + [c_void_p, c_int, c_longlong, c_float, c_int, c_int] +
+                            [c_void_p] * 5 + [c_longlong, c_void_p]),
+    "rfx_warp_flow_u8": (c_int, [c_void_p, c_void_p, c_int, c_longlong] + [c_void_p] * 5 + [c_longlong, c_void_p]),
     "rfx_pck_tally_f64": (c_int, [c_void_p] * 7 + [c_int, c_longlong, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5),
     "rfx_epe_ws_bytes": (c_size_t, [c_int] * 3),
     "rfx_epe_homography_f32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 5),

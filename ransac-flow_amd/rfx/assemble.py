@@ -103,6 +103,23 @@ def assemble_yfcc_records(records, bg, th, multiH):
     return fg, binary, valid
 
 
+def aligned_images_records(records, src_u8, th, multiH, cycle, out_hw=None, bg=None, tgt_u8=None, want_mask=False):
+    """The aligned source image of every pair of a batch of device records, as uint8 HWC (ops.warp_records_u8;
+    quick_start/align2images.py:97-98,117: F.grid_sample(IsTensor, flow12) -> ToPILImage, and with ``tgt_u8`` get_Avg_Image of
+    :25-28,112), in one launch: what assemble_records -> grid_sample -> mul(255).byte() gives per pair, without the flow or any float
+    image.  src_u8 / tgt_u8: a (B,H,W,3) uint8 tensor or one (H_b,W_b,3) uint8 device tensor per pair -- sources of any sizes, each
+    target at its pair's output size.  -> (img, overlay | None, mask | None, valid): (B,H,W,3) for dense records, lists of per-pair
+    images for ragged ones; valid (B,) bool on the device."""
+    return ops.warp_records_u8(records, src_u8, th, multiH, cycle, out_hw=out_hw, bg=bg, tgt=tgt_u8, want_mask=want_mask)
+
+
+def aligned_image(flow, src_u8, tgt_u8=None):
+    """The same image from a flow the caller holds (ops.warp_flow_u8): ``flow`` (H,W,2) / (B,H,W,2) float32 or a list of per-pair
+    maps -- quick-start's flow12, assemble_kitti_records' flow.  -> img, or (img, overlay) with ``tgt_u8``."""
+    img, overlay, _ = ops.warp_flow_u8(flow, src_u8, tgt=tgt_u8)
+    return img if tgt_u8 is None else (img, overlay)
+
+
 def yfcc_matches(flowGlobal, binary, sizeA, sizeB, angle):
     """evalYFCC/getResults.py:53-71 (matches_from_flow) on the maps assemble_yfcc returns, (1,H,W,2) and (1,H,W), or on single
     (H,W,2) / (H,W) maps; numpy arrays are uploaded.  sizeA = (wA, hA), sizeB = (wB, hB) before the rotation by ``angle``.

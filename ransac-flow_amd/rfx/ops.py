@@ -2185,6 +2185,184 @@ def assemble_records(records, th, multiH, cycle, out_hw=None, bg=None, out=None)
             [binary[o:o + H * W].view(H, W) for o, H, W in views], valid)
 
 
+def warp_image_table(sizes, src, tgt=None, device=None):
+    """The image table of rfx_warp_records_u8 / rfx_warp_flow_u8, on the host: ``sizes[b]`` = (H, W) of pair b's OUTPUT map; ``src`` a
+    (B,Hs,Ws,3) uint8 tensor or a list of one (Hs_b,Ws_b,3) uint8 tensor per pair (any sizes, read where they lie); ``tgt`` None, or
+    the targets in the same two forms, each (H_b,W_b,3) -- the pair's output size.  ``device``: the device every image must live on
+    (None: not checked, for a host-only look at the table).  -> (rows, keep): row b = (source address | Hs | Ws | target address or
+    0); keep = the tensors whose addresses the rows carry, to be held until the launch is enqueued.  ValueError for a wrong count,
+    dtype, shape, contiguity or target size, RuntimeError for a wrong device."""
+    B = len(sizes)
+
+    def images(x, name):
+        if isinstance(x, torch.Tensor):
+            if x.dim() != 4 or x.shape[0] != B:
+                raise ValueError("warp_image: %s is a (B,H,W,3) uint8 tensor or a list of one (H,W,3) uint8 tensor per pair (%d pairs), "
+                                 "got the shape %r" % (name, B, tuple(x.shape)))
+            return [x[b] for b in range(B)]
+        if not isinstance(x, (list, tuple)) or len(x) != B or any(not isinstance(t, torch.Tensor) for t in x):
+            raise ValueError("warp_image: %s is a (B,H,W,3) uint8 tensor or a list of one (H,W,3) uint8 tensor per pair (%d pairs)"
+                             % (name, B))
+        return list(x)
+
+    def check(t, name, b, want=None):
+        if t.dtype != torch.uint8:
+            raise ValueError("warp_image: %s of pair %d must be uint8, got %s" % (name, b, t.dtype))
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1 or t.shape[0] * t.shape[1] > 0x7fffffff:
+            raise ValueError("warp_image: %s of pair %d must be (H,W,3) with 1 <= H*W < 2^31, got %r" % (name, b, tuple(t.shape)))
+        if want is not None and tuple(t.shape[:2]) != tuple(want):
+            raise ValueError("warp_image: %s of pair %d must have the pair's output size %r, got %r" % (name, b, tuple(want), tuple(t.shape[:2])))
+        if not t.is_contiguous():
+            raise ValueError("warp_image: %s of pair %d must be contiguous (it is read where it lies)" % (name, b))
+        if device is not None and t.device != torch.device(device):
+            raise RuntimeError("warp_image: %s of pair %d is on %s, the call runs on %s" % (name, b, t.device, device))
+
+    srcs = images(src, "src")
+    tgts = images(tgt, "tgt") if tgt is not None else [None] * B
+    rows = []
+    for b, (s, t) in enumerate(zip(srcs, tgts)):
+        check(s, "src", b)
+        if t is not None:
+            check(t, "tgt", b, want=sizes[b])
+        rows.append((s.data_ptr(), int(s.shape[0]), int(s.shape[1]), t.data_ptr() if t is not None else 0))
+    return rows, srcs + [t for t in tgts if t is not None]
+
+
+def _warp_u8_outputs(out, total, dev, overlay, mask, what):
+    """(img, overlay | None, mask | None) packed uint8 buffers: new ones, or ``out`` = (img (total,3), overlay (total,3) | None,
+    mask (total,) | None) checked."""
+    if out is None:
+        return (torch.empty((total, 3), dtype=torch.uint8, device=dev),
+                torch.empty((total, 3), dtype=torch.uint8, device=dev) if overlay else None,
+                torch.empty(total, dtype=torch.uint8, device=dev) if mask else None)
+    if len(out) != 3:
+        raise ValueError("%s: out is (img, overlay or None, mask or None)" % what)
+    for t, shape, name, need in ((out[0], (total, 3), "img", True), (out[1], (total, 3), "overlay", overlay), (out[2], (total,), "mask", mask)):
+        if t is None and not need:
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: out %s must be a contiguous %s uint8 tensor on %s" % (what, name, shape, dev))
+    return out[0], out[1] if overlay else None, out[2] if mask else None
+
+
+def _warp_u8_views(bufs, rows, dense):
+    """The packed outputs as the caller sees them: (B,H,W[,3]) tensors for a dense batch, lists of per-pair views for a ragged one."""
+    def view(t):
+        if t is None:
+            return None
+        tail = tuple(t.shape[1:])
+        if dense:
+            return t.view((len(rows), rows[0][4], rows[0][5]) + tail)
+        return [t[r[6]:r[6] + r[4] * r[5]].view((r[4], r[5]) + tail) for r in rows]
+    return tuple(view(t) for t in bufs)
+
+
+def warp_records_u8(records, src, th, multiH, cycle, out_hw=None, bg=None, tgt=None, want_mask=False, out=None):
+    """The aligned source image of EVERY pair of a batch from the drivers' records, as uint8 HWC, in one launch
+    (rfx_warp_records_u8; quick_start/align2images.py:97-98,117 and, with ``tgt``, the 50 % overlay of :25-28,112): per pair bit
+    for bit what assemble_records -> grid_sample(u8_to_f32(src) raw, flow) -> clamp(0,1).mul(255).byte() -> HWC gives, without the
+    flow, the float source or the float image.  records, th, multiH, cycle, out_hw, bg: as assemble_records takes them (KITTI
+    records are refused: warp_flow_u8 takes their assembled flow).  src / tgt: see warp_image_table -- sources of any sizes, read
+    where they lie; a target has its pair's output size.  want_mask: also ``binary`` of assemble_records as a 0 / 255 byte map.
+    out: (img (total_px,3), overlay (total_px,3) or None, mask (total_px,) or None) packed uint8 buffers to fill.
+    -> (img, overlay | None, mask | None, valid): dense records (B,H,W,3), (B,H,W,3), (B,H,W) uint8; ragged records lists of
+    per-pair views of packed buffers; valid (B,) bool = nbH > 0 on the device (a pair without a homography has the zero flow: its
+    image is the source's centre colour).  Everything is checked on the host before any HIP call; nothing syncs."""
+    if not isinstance(records, (MultiHRecords, MultiHRecordsRagged)):
+        raise TypeError("records must be an ops.MultiHRecords or ops.MultiHRecordsRagged")
+    ragged = isinstance(records, MultiHRecordsRagged)
+    rows, max_hw, total = assemble_records_table(records, out_hw)          # refuses records with a flowD2 part
+    B, dev = records.B, records.rec.device
+    sizes = [(r[4], r[5]) for r in rows]
+    irows, keep = warp_image_table(sizes, src, tgt, device=dev)
+    if bg is not None:
+        parts = list(bg) if isinstance(bg, (list, tuple)) else [bg]
+        shapes = [tuple(getattr(t, "shape", ())) for t in parts]
+        dense_shape = None if ragged else [(B,) + sizes[0]]
+        if (shapes != sizes) if isinstance(bg, (list, tuple)) else (shapes not in ([(total,)], dense_shape)):
+            raise ValueError("warp_records_u8: bg is a packed (%d,) buffer%s or one map per pair of the shapes %r, got %r"
+                             % (total, "" if ragged else ", a %r tensor" % (dense_shape[0],), sizes, shapes))
+        if any(not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8) for t in parts):
+            raise ValueError("warp_records_u8: bg must be bool or uint8 tensors")
+        if any(t.device != dev for t in parts):
+            raise RuntimeError("warp_records_u8: bg must live on the records' device %s" % dev)
+    img, overlay, mask = _warp_u8_outputs(out, total, dev, tgt is not None, want_mask, "warp_records_u8")
+    rec = _dev(records.rec, "records")
+    if bg is not None:
+        bg = _mask_bytes(_packed_maps(parts if len(parts) > 1 else parts[0], "bg").reshape(-1), "bg")
+    import numpy as np
+    table, itable = _upload_i64([np.asarray(rows, np.int64), np.asarray(irows, np.int64)], dev)
+    _call("rfx_warp_records_u8", _one_device(rec, bg, img, overlay, mask), _p(rec), rec.numel(), records.width, records.max_h,
+          records.off_H, records.off_flow, _p(table), B, max_hw, float(th), 1 if multiH else 0, 1 if cycle else 0, _p(bg), _p(itable),
+          _p(img), _p(overlay), _p(mask), total)
+    del keep                                                   # the images were referenced until the launch was enqueued
+    valid = rec[:, 0] >= 1
+    return _warp_u8_views((img, overlay, mask), rows, not ragged) + (valid,)
+
+
+def warp_flow_u8(flow, src, tgt=None, binary=None, out=None):
+    """The image tail of warp_records_u8 on a stored flow (rfx_warp_flow_u8): quick-start's flow12, assemble_kitti_records' flow, any
+    flow a caller holds.  flow: (H,W,2) or (B,H,W,2) float32, or a list of one (H_b,W_b,2) map per pair (the views assemble_records
+    returns for a ragged batch are taken as the one packed buffer they are; other lists are concatenated).  src / tgt: see
+    warp_image_table.  binary: None, or bool / uint8 maps in flow's form without the last axis, passed through as a 0 / 255 byte map.
+    -> (img, overlay | None, mask | None) in flow's form: (H,W,3) / (B,H,W,3) uint8 or lists of per-pair views.  No sync."""
+    single = isinstance(flow, torch.Tensor) and flow.dim() == 3
+    listed = isinstance(flow, (list, tuple))
+    parts = list(flow) if listed else [flow]
+    if not parts or any(not isinstance(t, torch.Tensor) for t in parts) or \
+            (listed and any(t.dim() != 3 or t.shape[2] != 2 for t in parts)) or \
+            (not listed and (flow.dim() not in (3, 4) or flow.shape[-1] != 2)):
+        raise ValueError("warp_flow_u8: flow is (H,W,2), (B,H,W,2) or a list of (H,W,2) float32 maps")
+    if any(t.dtype != torch.float32 for t in parts):
+        raise ValueError("warp_flow_u8: flow must be float32, got %s" % parts[0].dtype)
+    if not listed and not flow.is_contiguous():
+        raise ValueError("warp_flow_u8: flow must be contiguous")
+    if parts[0].data_ptr() % 8:
+        raise ValueError("warp_flow_u8: the flow is read as float2 and must be 8-byte aligned")
+    if any(t.numel() == 0 for t in parts):
+        raise ValueError("warp_flow_u8: an empty flow map")
+    if listed:
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in parts]
+    else:
+        sizes = [(int(flow.shape[-3]), int(flow.shape[-2]))] * (1 if single else int(flow.shape[0]))
+    if any(H * W > 0x7fffffff for H, W in sizes):
+        raise ValueError("warp_flow_u8: maps have fewer than 2^31 pixels, got %r" % (sizes,))
+    B, dev = len(sizes), parts[0].device
+    rows, off = [], 0
+    for H, W in sizes:
+        rows.append((0, 0, 0, 0, H, W, off, 0))
+        off += H * W
+    total, max_hw = off, max(H * W for H, W in sizes)
+    if single:                                                 # one map: its images may come without the batch axis
+        src = [src] if isinstance(src, torch.Tensor) and src.dim() == 3 else src
+        tgt = [tgt] if isinstance(tgt, torch.Tensor) and tgt.dim() == 3 else tgt
+    irows, keep = warp_image_table(sizes, src, tgt, device=dev)
+    if binary is not None:
+        bparts = list(binary) if isinstance(binary, (list, tuple)) else [binary]
+        want = sizes if listed else [tuple(flow.shape[:-1])]
+        if [tuple(getattr(t, "shape", ())) for t in bparts] != want:
+            raise ValueError("warp_flow_u8: binary has flow's form without the last axis %r" % (want,))
+        if any(not isinstance(t, torch.Tensor) or t.dtype not in (torch.bool, torch.uint8) for t in bparts):
+            raise ValueError("warp_flow_u8: binary must be bool or uint8")
+        if any(t.device != dev for t in bparts):
+            raise RuntimeError("warp_flow_u8: binary must live on the flow's device %s" % dev)
+    img, overlay, mask = _warp_u8_outputs(out, total, dev, tgt is not None, binary is not None, "warp_flow_u8")
+    f = _dev(_packed_maps(parts if listed else flow, "flow").reshape(-1, 2), "flow")
+    if f.data_ptr() % 8:
+        raise ValueError("warp_flow_u8: the flow is read as float2 and must be 8-byte aligned")
+    if binary is not None:
+        binary = _mask_bytes(_packed_maps(bparts if listed else binary, "binary").reshape(-1), "binary")
+    import numpy as np
+    table, itable = _upload_i64([np.asarray(rows, np.int64), np.asarray(irows, np.int64)], dev)
+    _call("rfx_warp_flow_u8", _one_device(f, binary, img, overlay, mask), _p(f), _p(table), B, max_hw, _p(binary), _p(itable), _p(img),
+          _p(overlay), _p(mask), total)
+    del keep                                                   # the images were referenced until the launch was enqueued
+    if listed:
+        return _warp_u8_views((img, overlay, mask), rows, False)
+    shape = tuple(flow.shape[:-1])
+    return tuple(None if t is None else t.view(shape + tuple(t.shape[1:])) for t in (img, overlay, mask))
+
+
 def _host_pixels(v, what):
     """A host keypoint coordinate array as int64, floats truncated toward zero like the scripts' ``astype(np.int64)``."""
     import numpy as np

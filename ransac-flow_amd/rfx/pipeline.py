@@ -186,21 +186,24 @@ class AlignPipeline:
         nw, nh = resize_dims(w, h, size, "max" if self.variant == "A" else "min")
         return I.resize((nw, nh), resample=Image.LANCZOS)
 
-    def prepare(self, pairs):
-        """pairs: list of (Is, It) PIL images, all of one size.  Returns device-resident inputs."""
+    def prepare(self, pairs, want_u8=False):
+        """pairs: list of (Is, It) PIL images, all of one size.  Returns device-resident inputs.  ``want_u8``: also ``Is_u8``
+        (B,h,w,3), the bytes IsTensor is x / 255 of (align_prepared(want_u8=True) samples them)."""
         nS = len(self.scaleList)
         src = [[] for _ in range(nS)]
-        tgt, IsT, ItT = [], [], []
+        tgt, IsT, ItT, Is8 = [], [], [], []
         for Is_org, It_org in pairs:
             pyr = [self._resize(Is_org, int(self.minSize * s)) for s in self.scaleList]
             for i, im in enumerate(pyr):
                 src[i].append(pil_to_tensor(im))
             IsT.append(src[nS // 2][-1])
+            if want_u8:
+                Is8.append(torch.from_numpy(np.asarray(pyr[nS // 2], dtype=np.uint8).copy()))
             It = self._resize(It_org, self.minSize)
             tgt.append(pil_to_tensor(It))
         norm = lambda lst: ((torch.stack(lst) - self.mean) / self.std).to(self.dev)
         return dict(src=[norm(s) for s in src], tgt=norm(tgt), IsTensor=torch.stack(IsT).to(self.dev),
-                    ItTensor=torch.stack(tgt).to(self.dev), B=len(pairs))
+                    ItTensor=torch.stack(tgt).to(self.dev), B=len(pairs), Is_u8=torch.stack(Is8).to(self.dev) if want_u8 else None)
 
     @staticmethod
     def _mixed_sizes(pairs):
@@ -224,7 +227,7 @@ class AlignPipeline:
         conversions are reproduced exactly by rfx_lanczos_pass_u8 / rfx_u8_to_f32_chw."""
         mode = "max" if self.variant == "A" else "min"
         B, h, w, _ = src_u8.shape
-        srcs, IsT = [], None
+        srcs, IsT, Is8 = [], None, None
         mid = len(self.scaleList) // 2
         for i, sc in enumerate(self.scaleList):
             nw, nh = resize_dims(w, h, int(self.minSize * sc), mode)
@@ -232,9 +235,9 @@ class AlignPipeline:
             raw, norm = ops.u8_to_f32(im, IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid))
             srcs.append(norm)
             if i == mid:
-                IsT = raw
+                IsT, Is8 = raw, im
         ItT, tnorm = self.prepare_target_device(tgt_u8)
-        return dict(src=srcs, tgt=tnorm, IsTensor=IsT, ItTensor=ItT, B=B)
+        return dict(src=srcs, tgt=tnorm, IsTensor=IsT, ItTensor=ItT, B=B, Is_u8=Is8)
 
     def prepare_target_device(self, tgt_u8):
         """The target half of prepare_device: raw uint8 (N,H,W,3) -> (ItTensor raw, normalised), resized like setTarget does."""
@@ -271,30 +274,34 @@ class AlignPipeline:
     def _ragged_plan(self, src_sizes, tgt_sizes):
         return ragged_plan(src_sizes, tgt_sizes, self.minSize, self.scaleList, "max" if self.variant == "A" else "min")
 
-    def prepare_ragged(self, pairs):
+    def prepare_ragged(self, pairs, want_u8=False):
         """prepare() for pairs of different sizes (PIL path).  Every image is resized, converted and normalised exactly as prepare()
         does it for its pair alone; images of one shape are stacked into one bucket (ragged_plan).  Returns a ragged prep, which
         features / coarse / fine_quickstart / align_prepared accept."""
         plan = self._ragged_plan([p[0].size for p in pairs], [p[1].size for p in pairs])
         nS, mid = plan["nS"], plan["nS"] // 2
         mean, std = self.mean, self.std
-        norm, IsT, ItT = {}, [], []
+        norm, IsT, ItT, Is8 = {}, [], [], []
         for b, (Is_org, It_org) in enumerate(pairs):
             for i, s in enumerate(self.scaleList):
-                t = pil_to_tensor(self._resize(Is_org, int(self.minSize * s)))[None]
+                im = self._resize(Is_org, int(self.minSize * s))
+                t = pil_to_tensor(im)[None]
                 norm[(b, i)] = ((t - mean) / std).to(self.dev)
                 if i == mid:
                     IsT.append(t.to(self.dev))
+                    if want_u8:                                  # the bytes IsTensor is x / 255 of, one (h,w,3) tensor per pair
+                        Is8.append(torch.from_numpy(np.asarray(im, dtype=np.uint8).copy()).to(self.dev))
             t = pil_to_tensor(self._resize(It_org, self.minSize))[None]
             norm[(b, nS)] = ((t - mean) / std).to(self.dev)
             ItT.append(t.to(self.dev))
-        return self._ragged_prep(plan, norm, IsT, ItT)
+        return dict(self._ragged_prep(plan, norm, IsT, ItT), Is_u8=Is8 if want_u8 else None)
 
-    def _prepare_lists_device(self, plan, src_list, cands):
+    def _prepare_lists_device(self, plan, src_list, cands, u8_out=None):
         """The device pre-processing of B sources and K lists of B targets (uint8 (H,W,3) device tensors) over ``plan`` (image nS + k
         of a pair = its target k): the LANCZOS pyramid and the float conversions run once per input shape and level -- one
         rfx_lanczos_pass_u8 / rfx_u8_to_f32_chw chain for all images that share both, whatever pair or list they belong to.
-        Returns (norm[(b, i)], IsTensor[b], ItTensor[k][b]): the normalised images and the raw ones of the fine stage, (1,3,h,w)."""
+        Returns (norm[(b, i)], IsTensor[b], ItTensor[k][b]): the normalised images and the raw ones of the fine stage, (1,3,h,w).
+        ``u8_out``: a list of B entries that receives each source's resized mid-level bytes (h,w,3), which the pass forms anyway."""
         nS, mid, B = plan["nS"], plan["nS"] // 2, plan["B"]
         norm, IsT, ItT = {}, [None] * B, [[None] * B for _ in cands]
         imgs = [(x, b, None) for b, x in enumerate(src_list)] + [(x, b, k) for k, c in enumerate(cands) for b, x in enumerate(c)]
@@ -303,21 +310,26 @@ class AlignPipeline:
             who = [imgs[j][1:] for j in mem]
             for i in ([nS + who[0][1]] if is_tgt else range(nS)):
                 nh, nw = plan["levels"][who[0][0]][i]
-                raw, nrm = ops.u8_to_f32(ops.lanczos_resize_u8(u8, nw, nh), IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid or is_tgt))
+                small = ops.lanczos_resize_u8(u8, nw, nh)
+                raw, nrm = ops.u8_to_f32(small, IMAGENET_MEAN, IMAGENET_STD, want_raw=(i == mid or is_tgt))
                 ragged.hand_back(norm, [(b, i if k is None else nS + k) for b, k in who], nrm)
                 if is_tgt:
                     for j, (b, k) in enumerate(who):
                         ItT[k][b] = raw[j:j + 1]
                 elif i == mid:
                     ragged.hand_back(IsT, [b for b, _ in who], raw)
+                    if u8_out is not None:
+                        for j, (b, _) in enumerate(who):
+                            u8_out[b] = small[j]
         return norm, IsT, ItT
 
     def prepare_ragged_device(self, src_list, tgt_list):
         """prepare_device() for pairs of different sizes: src_list / tgt_list = uint8 (H,W,3) device tensors, one per pair
         (_prepare_lists_device with one list of targets); equals prepare_ragged() bit for bit."""
         plan = self._ragged_plan([(x.shape[1], x.shape[0]) for x in src_list], [(x.shape[1], x.shape[0]) for x in tgt_list])
-        norm, IsT, ItT = self._prepare_lists_device(plan, src_list, [tgt_list])
-        return self._ragged_prep(plan, norm, IsT, ItT[0])
+        Is8 = [None] * len(src_list)
+        norm, IsT, ItT = self._prepare_lists_device(plan, src_list, [tgt_list], u8_out=Is8)
+        return dict(self._ragged_prep(plan, norm, IsT, ItT[0]), Is_u8=Is8)
 
     def prepare_candidates_device(self, src_list, cands):
         """prepare_ragged_device for pairs with K candidate targets each (cands[k][b]: uint8 (H,W,3) device tensors).  Returns a
@@ -1304,12 +1316,21 @@ class AlignPipeline:
                                           trace=trace, pair_ids=pair_ids, draw_epoch=draw_epoch, split=split)
 
     # ---------------------------------------------------------------- whole path
-    def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0):
+    def align_prepared(self, prep, fine=True, samples=None, feats=None, pair_ids=None, draw_epoch=0, want_u8=False):
         """coarse() + fine_quickstart() of a prep from prepare / prepare_device or, for pairs of different sizes, prepare_ragged /
         prepare_ragged_device.  A ragged batch gives every pair, bit for bit, what it gives alone (same ``pair_ids`` / draws); it
         runs eagerly (no HIP-graph capture).  multi_h_batched takes ragged preps too (multi_h_pairs), and multi_h_kitti_batched takes
         lists of images of different sizes (multi_h_kitti_pairs), and so does multi_h_variant_c (multi_h_variant_c_pairs; without
-        records).  Not covered for ragged batches: the drop-in modules."""
+        records).  Not covered for ragged batches: the drop-in modules.
+        ``want_u8`` (with ``fine``): every result also carries ``img1_fine_u8`` (1,H,W,3) uint8, the aligned source as an image
+        (quick_start/align2images.py:97-98: ToPILImage of img1_fine), made in one launch for the batch by ops.warp_flow_u8 from
+        flow12 and the prep's uint8 source ``Is_u8``; equal to (img1_fine.clamp(0, 1) * 255).byte() as HWC.  Nothing else changes.
+        Preps with ``Is_u8``: prepare_device, prepare_and_features and prepare_ragged_device always (they hold the bytes anyway, at
+        no cost), prepare / prepare_ragged when called with want_u8=True (align_pairs does that).  Preps without: prepare /
+        prepare_ragged by default, prepare_candidates_device (its fine stage belongs to the multi-homography drivers)."""
+        if want_u8 and fine and prep.get("Is_u8") is None:
+            raise ValueError("align_prepared: want_u8 needs the prep's uint8 source Is_u8: prepare(pairs, want_u8=True) / "
+                             "prepare_ragged(pairs, want_u8=True), or a prep of prepare_device / prepare_ragged_device")
         res = self.coarse(prep, feats=feats, samples=samples, pair_ids=pair_ids, draw_epoch=draw_epoch)
         if fine:
             eye = torch.eye(3, device=self.dev)
@@ -1317,19 +1338,26 @@ class AlignPipeline:
             if prep.get("ragged"):
                 for r, f in zip(res, self._fine_ragged(prep, Hs)):
                     r["flow12"], r["img1_fine"], r["flowDown"] = f["flow12"], f["img1_fine"], f["flowDown"]
+                if want_u8:
+                    imgs = ops.warp_flow_u8([r["flow12"][0] for r in res], list(prep["Is_u8"]))[0]
+                    for r, im in zip(res, imgs):
+                        r["img1_fine_u8"] = im[None]
                 return res
             f = self.fine_quickstart(prep, Hs)
+            u8 = ops.warp_flow_u8(f["flow12"], prep["Is_u8"])[0] if want_u8 else None
             for b, r in enumerate(res):
                 r["flow12"] = f["flow12"][b:b + 1]
                 r["img1_fine"] = f["img1_fine"][b:b + 1]
                 r["flowDown"] = f["flowDown"][b:b + 1]
+                if want_u8:
+                    r["img1_fine_u8"] = u8[b:b + 1]
         return res
 
-    def align_pairs(self, pairs, fine=True, samples=None, pair_ids=None):
+    def align_pairs(self, pairs, fine=True, samples=None, pair_ids=None, want_u8=False):
         """Pairs of PIL images.  All sources of one size and all targets of one size: prepare(), today's dense path.  Otherwise the
-        ragged path (prepare_ragged)."""
-        prep = self.prepare_ragged(pairs) if self._mixed_sizes(pairs) else self.prepare(pairs)
-        return self.align_prepared(prep, fine=fine, samples=samples, pair_ids=pair_ids)
+        ragged path (prepare_ragged).  ``want_u8``: see align_prepared."""
+        prep = self.prepare_ragged(pairs, want_u8) if self._mixed_sizes(pairs) else self.prepare(pairs, want_u8)
+        return self.align_prepared(prep, fine=fine, samples=samples, pair_ids=pair_ids, want_u8=want_u8)
 
     def multi_h_pairs(self, pairs, maxCoarse=10, maskRegionTh=0.01, It_bg=None, sample_fn=None, records=None, want_lists=True,
                       trace=None, pair_ids=None, draw_epoch=0, split=None, seg=None):
